@@ -7,6 +7,7 @@ Rd=-10n) of the synthetic dense SDP, inputs resident in HBM:
 (the Phase-A sequence interface/hdsdp_algo.c:1082-1101).
 
     python bench.py                         # 1 GPU, n=m=2000
+    python bench.py --dump-outputs DIR      # also write the last timed step's outputs as DIR/<name>.npy (dump_outputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -161,6 +162,35 @@ def golden_check(n, m, kkt, sol, rhs):
               d["max_residual_rows"] < 1e-8)
         return d, bool(ok)
     return None, None
+
+
+DUMP_LIMIT_BYTES = 64_000_000    # --dump-outputs writes at most this much in all
+DUMP_M_BYTES = 48_000_000        # of which the rows of M: all of them where they fit, else a fixed seeded sample
+DUMP_SEED = 20260101
+
+
+def dump_outputs(path, kkt, sol, m):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, one float64 DIR/<name>.npy per
+    array -- the three solutions d1, d2, d3 (HKKTSolve on b, ASinv, ASinvRdSinv), the vectors and scalars of HKKTExport, and
+    M_rows: full symmetric rows of the Schur matrix M (device copy), every row where they fit in DUMP_M_BYTES, else a fixed
+    seeded sample of rows; M_rows_index holds which.  The inputs are the same from run to run, so that the dumps of two
+    builds can be compared array for array.  Returns the names written."""
+    arrays = {"d1": sol[0], "d2": sol[1], "d3": sol[2]}
+    arrays.update({k: np.atleast_1d(v) for k, v in kkt.export().items()})
+    if m * m * 8 <= DUMP_M_BYTES:
+        rows = np.arange(m)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(m, DUMP_M_BYTES // (8 * m), replace=False))
+    arrays["M_rows_index"] = rows
+    arrays["M_rows"] = kkt.rows(rows)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def cpu_baseline(n, m, budget_cols=16):
@@ -429,7 +459,11 @@ def main():
     ap.add_argument("--loopback", action="store_true",
                     help="--gpus N on fewer than N devices: shards share devices (a rehearsal; n_gpus then reports the devices "
                          "really used, never N)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     from hdsdp_amd import api, dist as hdist
@@ -567,6 +601,9 @@ def main():
             torch.distributed.barrier()
             torch.distributed.destroy_process_group()
         return
+    if args.dump_outputs:
+        names = dump_outputs(args.dump_outputs, kkt, sol, m)
+        print(f"bench.py: last timed step's outputs written to {args.dump_outputs}: {', '.join(names)}", file=sys.stderr)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = args.steps / elapsed

@@ -10,11 +10,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from util import load_golden
+from util import GOLDEN, load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "hdsdp_mi355x.h")
-REFERENCE = "/root/reference"
+# optional: a reference source tree to check the stored reference figures against (as oracle/gen_golden.py reads it)
+REFERENCE = os.environ.get("HDSDP_REFERENCE")
 
 
 def _declared_functions():
@@ -51,9 +52,15 @@ def test_no_cpu_fallback_without_gpu():
         api.SDPCone.synthetic(8, 4)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE) or shutil.which("gcc") is None, reason="reference headers absent")
+def _layout_lines(text):
+    return [l for l in text.splitlines() if l.strip() and not l.startswith("#")]
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
 def test_struct_layout_matches_reference(tmp_path):
-    """offsetof/sizeof of hdsdp_kkt, hdsdp_linsys_fp and hdsdp_cone: our header vs the reference's"""
+    """offsetof/sizeof of hdsdp_kkt, hdsdp_linsys_fp and hdsdp_cone: our header vs the reference's.  The reference's figures
+    are stored in tests/golden/struct_layout_ref.txt (this probe compiled against its interface/hdsdp_schur.h); with
+    HDSDP_REFERENCE naming a reference source tree the probe is also compiled against it and must give the stored figures."""
     fields = {
         "hdsdp_kkt": ["nRow", "nCones", "maxConeDim", "cones", "isKKTSparse", "kktM", "invBuffer", "kktBuffer",
                       "kktBuffer2", "kktMatBeg", "kktMatIdx", "kktMatElem", "kktDiag", "dASinvVec", "dASinvCSinvVec",
@@ -73,15 +80,18 @@ def test_struct_layout_matches_reference(tmp_path):
         f'printf("{s} %zu\\n", sizeof({s}));\n' + "".join(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));\n' for f in fl)
         for s, fl in fields.items())
     head, tail = "#include <stdio.h>\n#include <stddef.h>\n", "\nint main(void){\n" + body + "return 0;}\n"
-    outs = []
-    for tag, inc, flags in (("ours", f'#include "{HEADER}"', []),
-                            ("ref", '#include "interface/hdsdp_schur.h"', ["-DHEADERPATH", f"-I{REFERENCE}"])):
+    probes = [("ours", f'#include "{HEADER}"', [])]
+    if REFERENCE and os.path.isdir(os.path.join(REFERENCE, "interface")):
+        probes.append(("ref", '#include "interface/hdsdp_schur.h"', ["-DHEADERPATH", f"-I{REFERENCE}"]))
+    with open(os.path.join(GOLDEN, "struct_layout_ref.txt")) as f:
+        want = _layout_lines(f.read())
+    assert len(want) == sum(1 + len(fl) for fl in fields.values())
+    for tag, inc, flags in probes:
         src = tmp_path / f"{tag}.c"
         src.write_text(head + inc + tail)
         exe = tmp_path / tag
         subprocess.check_call(["gcc", "-w", "-std=gnu99"] + flags + ["-o", str(exe), str(src)])
-        outs.append(subprocess.check_output([str(exe)], text=True))
-    assert outs[0] == outs[1]
+        assert _layout_lines(subprocess.check_output([str(exe)], text=True)) == want, tag
 
 
 @pytest.mark.parametrize("name", ["theta1_A", "mcp100_A", "gpp100_A", "mix40_A", "mix40_B"])
@@ -187,18 +197,23 @@ def test_lanczos_start_vector_matches_libc():
 def test_reference_minus_two_files_links_against_the_library():
     """the drop-in claim at link level: the reference without interface/hdsdp_schur.c and linalg/hdsdp_linsolver.c,
     linked with --no-undefined against the product library (make -C oracle drop), takes every HKKT* / HFpLinsys* symbol
-    it calls from the library and has no unresolved symbol left"""
+    it calls from the library and has no unresolved symbol left.  The HKKT* / HFpLinsys* symbols that library imports are
+    stored in tests/golden/ref_minus_imports.txt (`nm -D --undefined-only` of it); the library is checked against that
+    list everywhere, and where the drop-in library was built (it needs the reference's sources at build time) the list
+    is checked against it and the whole link is resolved."""
     import subprocess
-    so = os.path.join(ROOT, "oracle", "_ref", "libhdsdp_ref_minus.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref/libhdsdp_ref_minus.so not built (needs /root/reference: make -C oracle drop)")
-    nm = subprocess.run(["nm", "-D", "--undefined-only", so], capture_output=True, text=True).stdout
-    wanted = sorted({ln.split()[-1] for ln in nm.splitlines() if ln.split() and ln.split()[-1].startswith(("HKKT", "HFpLinsys"))})
+    with open(os.path.join(GOLDEN, "ref_minus_imports.txt")) as f:
+        wanted = [ln.strip() for ln in f if ln.strip() and not ln.startswith("#")]
     assert len(wanted) >= 20, wanted          # the driver and the cones really call into the replaced files
     lib = os.path.join(ROOT, "hdsdp_amd", "libhdsdp_mi355x.so")
     ours = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True).stdout
     have = {ln.split()[-1] for ln in ours.splitlines() if ln.split()}
     assert not [w for w in wanted if w not in have]
+    so = os.path.join(ROOT, "oracle", "_ref", "libhdsdp_ref_minus.so")
+    if not os.path.exists(so):
+        return
+    nm = subprocess.run(["nm", "-D", "--undefined-only", so], capture_output=True, text=True).stdout
+    assert sorted({ln.split()[-1] for ln in nm.splitlines() if ln.split() and ln.split()[-1].startswith(("HKKT", "HFpLinsys"))}) == wanted
     r = subprocess.run(["ldd", "-r", so], capture_output=True, text=True)
     assert "undefined symbol" not in (r.stdout + r.stderr), (r.stdout + r.stderr)[-2000:]
 
@@ -333,6 +348,61 @@ def test_a_multi_gpu_bench_line_says_where_its_step_went():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'out["sharded_step"] = shard_prof' in src and "all_gather_object" in src and "cone.build_profile(r) for r in range(shards)" in src
     assert "HMiConeGetBuildProfile" in open(HEADER).read()
+
+
+def test_bench_dump_outputs_writes_the_callers_arrays_within_the_limit(tmp_path):
+    """bench.dump_outputs (pure given the operator; here a fake one): the three solutions, HKKTExport's vectors and scalars and
+    rows of M as float64 .npy files -- every row where M fits, else the same seeded sample of rows on every call -- and never
+    more than 64 MB in all"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class FakeKKT:
+        def __init__(self, m):
+            self.m = m
+
+        def export(self):
+            v = np.arange(self.m, dtype=np.float64)
+            return {"ASinv": v, "ASinvRdSinv": 2 * v, "ASinvCSinv": 3 * v, "CSinvCSinv": 1.5, "CSinv": 2.5,
+                    "CSinvRdSinv": 3.5, "TraceSinv": 4.5}
+
+        def rows(self, rows):
+            rows = np.asarray(rows)
+            return rows[:, None] * 1e4 + np.arange(self.m)[None, :]
+
+    for m in (50, 8000):
+        sol = tuple(np.full(m, k, dtype=np.float32) for k in (1.0, 2.0, 3.0))
+        dirs = [tmp_path / f"m{m}_a", tmp_path / f"m{m}_b"]
+        for d in dirs:
+            names = bench.dump_outputs(str(d), FakeKKT(m), sol, m)
+        assert names == sorted(["d1", "d2", "d3", "ASinv", "ASinvRdSinv", "ASinvCSinv", "CSinvCSinv", "CSinv", "CSinvRdSinv",
+                                "TraceSinv", "M_rows_index", "M_rows"])
+        assert sorted(os.listdir(dirs[0])) == sorted(k + ".npy" for k in names)
+        got = [{k: np.load(os.path.join(d, k + ".npy")) for k in names} for d in dirs]
+        assert all(a.dtype == np.float64 for a in got[0].values())
+        assert sum(os.path.getsize(os.path.join(dirs[0], k + ".npy")) for k in names) <= 64_000_000
+        for k in names:
+            assert np.array_equal(got[0][k], got[1][k]), k
+        assert np.array_equal(got[0]["d3"], np.full(m, 3.0)) and got[0]["TraceSinv"].tolist() == [4.5]
+        idx = got[0]["M_rows_index"].astype(np.int64)
+        assert np.array_equal(got[0]["M_rows"], FakeKKT(m).rows(idx))
+        if m == 50:
+            assert np.array_equal(idx, np.arange(m))
+        else:
+            assert 0 < idx.size < m and np.all(np.diff(idx) > 0) and idx[-1] < m
+
+
+def test_bench_refuses_a_step_count_it_cannot_time():
+    """--steps sets the number of timed steps: zero or negative is an argument error, before any GPU work"""
+    import subprocess
+    import sys
+    for args in (["--steps", "0"], ["--steps", "-2"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu"] + args, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, (args, r.stderr[-500:])
+        assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
 def test_library_exports_nothing_but_the_declared_surface():

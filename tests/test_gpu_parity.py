@@ -1389,3 +1389,39 @@ def test_sparse_operator_with_a_banded_pattern_over_several_blocks_of_M(scramble
     finally:
         for c in cones:
             c.destroy()
+
+
+def test_bench_dump_outputs_is_the_last_timed_steps_answer(tmp_path):
+    """bench.py --dump-outputs on a small synthetic instance, twice: the line reports the steps asked for, the dumped d1 / d2 are
+    the ones its checksum was taken from, the dumped rows of M are M (symmetric, and M d2 = ASinv, M d3 = ASinvRdSinv with the
+    dumped vectors), and the second run writes the same arrays as the first"""
+    import json
+    import subprocess
+    import sys
+    from util import rel_err
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["HDM_BENCH_NO_PROBE"] = "1"
+    n, m, steps = 128, 96, 3
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", str(n), "--m", str(m), "--steps", str(steps),
+                            "--warmup", "1", "--no-cpu", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600,
+                           env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["warmup"] == 1
+        d = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+        assert all(a.dtype == np.float64 for a in d.values())
+        assert line["checksum"]["sum_d2"] == float(np.sum(d["d2"]))
+        assert line["checksum"]["sum_d1w"] == float(np.dot(np.arange(1, m + 1), d["d1"]))
+        assert np.array_equal(d["M_rows_index"], np.arange(m))
+        M = d["M_rows"]
+        assert M.shape == (m, m) and np.array_equal(M, M.T)
+        for x, rhs in ((d["d2"], d["ASinv"]), (d["d3"], d["ASinvRdSinv"])):
+            assert np.linalg.norm(M @ x - rhs) <= 1e-8 * np.linalg.norm(rhs)
+        dumps.append(d)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for k in dumps[0]:
+        assert rel_err(dumps[1][k], dumps[0][k]) <= 1e-13, k
