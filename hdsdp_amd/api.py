@@ -30,7 +30,7 @@ EXPORTS = [
     "HFpLinsysCreate", "HFpLinsysSetParam", "HFpLinsysSymbolic", "HFpLinsysNumeric", "HFpLinsysSwitchToBackUp",
     "HFpLinsysPsdCheck", "HFpLinsysFSolve", "HFpLinsysBSolve", "HFpLinsysSolve", "HFpLinsysGetDiag",
     "HFpLinsysInvert", "HFpLinsysClear", "HFpLinsysDestroy",
-    "HMiConeCreateSDP", "HMiConeCreateSDP64", "HMiConeBuilderBegin", "HMiConeBuilderAddColumn", "HMiConeBuilderStored", "HMiConeBuilderFinish", "HMiConeBuilderAbort", "HMiConeCreateSynthetic", "HMiConeDestroy", "HMiConeSetStart", "HMiConeUpdate",
+    "HMiConeCreateSDP", "HMiConeCreateSDP64", "HMiConeCreateLP", "HMiConeLPSetSchurPath", "HMiConeLPGetSchurPath", "HMiConeBuilderBegin", "HMiConeBuilderAddColumn", "HMiConeBuilderStored", "HMiConeBuilderFinish", "HMiConeBuilderAbort", "HMiConeCreateSynthetic", "HMiConeDestroy", "HMiConeSetStart", "HMiConeUpdate",
     "HMiConeCheckIsInterior", "HMiConeGetLogBarrier", "HMiConeRatioTest", "HMiLanczosStartVector", "HMiConeGetPrimal", "HMiConeCheckIsInteriorExpert",
     "HMiConeAddStepToBufferAndCheck", "HMiConeReduceResi", "HMiConeSetPerturb", "HMiConeGetCoeffNorm", "HMiConeGetObjNorm",
     "HMiConeScalByConstant", "HMiConeComputeATimesXpy", "HMiConeComputeXDotS", "HMiConeComputeTraceCX", "HMiConeGetDual", "HMiConeGetPresolve", "HMiConeDetectFeature", "HMiConeGetDualMatrix",
@@ -39,7 +39,7 @@ EXPORTS = [
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
-    "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetRHS", "HMiSDPAFree",
+    "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
 ]
 
 
@@ -121,6 +121,9 @@ def load_library():
         "HFpLinsysClear": (None, [vp]),
         "HFpLinsysDestroy": (None, [C.POINTER(vp)]),
         "HMiConeCreateSDP": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, ip, ip, dp, C.c_int, C.c_int]),
+        "HMiConeCreateLP": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, ip, ip, dp]),
+        "HMiConeLPSetSchurPath": (C.c_int, [vp, C.c_int]),
+        "HMiConeLPGetSchurPath": (C.c_int, [vp, dp, dp, C.POINTER(C.c_int64)]),
         "HMiConeCreateSynthetic": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "HMiConeDestroy": (None, [C.POINTER(vp)]),
         "HMiConeSetStart": (None, [vp, C.c_double]),
@@ -193,6 +196,7 @@ def load_library():
         "HMiReadSDPA": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "HMiSDPAGetDims": (None, [vp, ip, ip, ip]),
         "HMiSDPAGetBlock": (C.c_int, [vp, C.c_int, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(dp)]),
+        "HMiSDPAGetLPBlock": (C.c_int, [vp, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(dp)]),
         "HMiSDPAGetBlock64": (C.c_int, [vp, C.c_int, ip, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(ip), C.POINTER(dp)]),
         "HMiSDPAGetRHS": (dp, [vp]),
         "HMiConeCreateSDP64": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), ip, dp, C.c_int, C.c_int]),
@@ -280,7 +284,8 @@ def lanczos_start_vector(n):
 
 
 def read_sdpa(fname):
-    """SDPA sparse file -> dict(m, b, blocks=[dict(n, beg, idx, val)], n_lp) in the reference's CSC layout"""
+    """SDPA sparse file -> dict(m, b, blocks=[dict(n, beg, idx, val)], n_lp, lp) in the reference's CSC layout; lp = the LP
+    block as dict(n, beg, idx, val) (CSC of n rows and m + 1 columns, column 0 = the objective), or None"""
     lib = load_library()
     h = C.c_void_p()
     _check(lib.HMiReadSDPA(os.fsencode(fname), C.byref(h)), f"HMiReadSDPA({fname})")
@@ -298,7 +303,17 @@ def read_sdpa(fname):
             idx = np.ctypeslib.as_array(pi, shape=(max(nnz, 1),))[:nnz].copy()
             val = np.ctypeslib.as_array(pv, shape=(max(nnz, 1),))[:nnz].copy()
             blocks.append({"n": dim.value, "beg": beg, "idx": idx, "val": val})
-        return {"m": m.value, "b": b, "blocks": blocks, "n_lp": nlp.value}
+        lp = None
+        if nlp.value > 0:
+            ncol = C.c_int()
+            pb, pi, pv = C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.POINTER(C.c_double)()
+            _check(lib.HMiSDPAGetLPBlock(h, C.byref(ncol), C.byref(pb), C.byref(pi), C.byref(pv)), "HMiSDPAGetLPBlock")
+            beg = np.ctypeslib.as_array(pb, shape=(m.value + 2,)).copy()
+            nnz = int(beg[-1])
+            idx = np.ctypeslib.as_array(pi, shape=(max(nnz, 1),))[:nnz].copy()
+            val = np.ctypeslib.as_array(pv, shape=(max(nnz, 1),))[:nnz].copy()
+            lp = {"n": ncol.value, "beg": beg, "idx": idx, "val": val}
+        return {"m": m.value, "b": b, "blocks": blocks, "n_lp": nlp.value, "lp": lp}
     finally:
         lib.HMiSDPAFree(C.byref(h))
 
@@ -540,6 +555,90 @@ class SDPCone:
             self._h = None
 
 
+class LPCone:
+    """The LP (diagonal) block of an SDPA problem living in HBM: the reference's hdsdp_cone with the LP slots
+    (interface/hdsdp_conic_lp.c), its Schur build on the device.  Vectors (duals, primals) are 1-D arrays of n = nCol."""
+
+    DENSE, SPARSE = 1, 2
+
+    def __init__(self, handle, n, m):
+        self._h, self.n, self.m = handle, n, m
+
+    @classmethod
+    def from_csc(cls, m, n, beg, idx, val, iCone=0):
+        """CSC of n rows (LP columns) and m + 1 columns, column 0 = the objective (LPConeProcDataImpl's input)"""
+        lib = load_library()
+        beg = np.ascontiguousarray(beg, dtype=np.int32)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        assert beg.shape[0] == m + 2
+        h = C.c_void_p()
+        _check(lib.HMiConeCreateLP(C.byref(h), iCone, m, n, _iptr(beg), _iptr(idx), _dptr(val)), "HMiConeCreateLP")
+        return cls(h, n, m)
+
+    @classmethod
+    def from_sdpa(cls, fname, iCone=0):
+        """the LP block of an SDPA file (read_sdpa(fname)["lp"])"""
+        p = read_sdpa(fname)
+        if p["lp"] is None:
+            raise HDSDPError(f"{fname} has no LP block")
+        lp = p["lp"]
+        return cls.from_csc(p["m"], lp["n"], lp["beg"], lp["idx"], lp["val"], iCone=iCone)
+
+    def set_schur_path(self, path):
+        """0 = by the cost rule, LPCone.DENSE, LPCone.SPARSE (HMiConeLPSetSchurPath)"""
+        if load_library().HMiConeLPSetSchurPath(self._h, int(path)) != 0:
+            raise HDSDPError(f"HMiConeLPSetSchurPath({path}) failed")
+
+    def schur_path(self):
+        """(path, modelled dense seconds, modelled sparse seconds, pair-list bytes)"""
+        a, b, n = C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
+        p = load_library().HMiConeLPGetSchurPath(self._h, C.byref(a), C.byref(b), C.byref(n))
+        return p, a.value, b.value, n.value
+
+    set_start = SDPCone.set_start
+    check_is_interior = SDPCone.check_is_interior
+    ratio_test = SDPCone.ratio_test
+    check_is_interior_expert = SDPCone.check_is_interior_expert
+    axpy_buffer_and_check = SDPCone.axpy_buffer_and_check
+    log_barrier_of = SDPCone.log_barrier_of
+    log_barrier = SDPCone.log_barrier
+    coeff_norm = SDPCone.coeff_norm
+    obj_norm = SDPCone.obj_norm
+    scal_by_constant = SDPCone.scal_by_constant
+    a_times_x = SDPCone.a_times_x
+    x_dot_s = SDPCone.x_dot_s
+    trace_cx = SDPCone.trace_cx
+    reduce_resi = SDPCone.reduce_resi
+    set_perturb = SDPCone.set_perturb
+    detect_feature = SDPCone.detect_feature
+    destroy = SDPCone.destroy
+
+    def update(self, tau, y):
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        load_library().HMiConeUpdate(self._h, float(tau), _dptr(y))
+
+    def get_dual(self):
+        s = np.zeros(self.n)
+        load_library().HMiConeGetDual(self._h, _dptr(s), None)
+        return s
+
+    def get_primal(self, mu, y, dy):
+        """HConeGetPrimal: the nCol primal values, or None if the recovery point is not interior"""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        dy = np.ascontiguousarray(dy, dtype=np.float64)
+        X = np.full(self.n, np.nan)
+        load_library().HMiConeGetPrimal(self._h, float(mu), _dptr(y), _dptr(dy), _dptr(X), None)
+        return None if np.isnan(X[0]) else X
+
+    def build_primal_xsx(self, X, XSX, dual_matrix=True):
+        """XSX = X * X * s with s = the dual (dual_matrix) or the dual step of the last ratio test"""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        assert XSX.flags.c_contiguous and XSX.dtype == np.float64 and XSX.shape == (self.n,)
+        load_library().HMiConeBuildPrimalXSXDirection(self._h, _dptr(X), _dptr(XSX), 1 if dual_matrix else 0)
+        return XSX
+
+
 class KKT:
     """hdsdp_kkt: the Schur operator (interface/hdsdp_schur.c)."""
 
@@ -561,9 +660,15 @@ class KKT:
         _check(load_library().HKKTBuildUpFixed(self._k, typeKKT, strategy), "HKKTBuildUpFixed")
 
     def register_psdp(self, primal_mats):
-        """HKKTRegisterPSDP (interface/hdsdp_schur.c:375-380): borrow one n x n column-major primal matrix per cone;
-        build_up(KKT_TYPE_PRIMAL) then runs the builder on them instead of S^-1"""
-        self._psdp = [np.ascontiguousarray(x, dtype=np.float64) for x in primal_mats]
+        """HKKTRegisterPSDP (interface/hdsdp_schur.c:375-380): borrow one primal per cone -- an n x n column-major matrix for
+        an SDP cone, a 1-D array of nCol entries for an LP cone; build_up(KKT_TYPE_PRIMAL) then runs the builder on them
+        instead of S^-1"""
+        self._psdp = []
+        for c, x in zip(self.cones, primal_mats):
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if isinstance(c, LPCone) and x.shape != (c.n,):
+                raise ValueError(f"LP cone of {c.n} columns: the primal is a 1-D array of {c.n} entries, not {x.shape}")
+            self._psdp.append(x)
         self._psdp_arr = (C.POINTER(C.c_double) * len(self._psdp))(*[_dptr(x) for x in self._psdp])
         load_library().HKKTRegisterPSDP(self._k, C.cast(self._psdp_arr, C.c_void_p))
 

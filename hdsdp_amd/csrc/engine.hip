@@ -1,7 +1,8 @@
 // engine.hip -- host side of the MI355X Schur engine: the HKKT* / HFpLinsys* operator surface of the
 // reference (interface/hdsdp_schur.c, linalg/hdsdp_linsolver.c) re-implemented over device-resident
 // state, plus the MI355X SDP cone whose `coneBuildSchur` slot is the GPU builder that replaces
-// sdpDenseConeGetKKT (interface/hdsdp_conic_sdp.c:1726-1812).
+// sdpDenseConeGetKKT (interface/hdsdp_conic_sdp.c:1726-1812), and the LP cone whose slot replaces LPConeGetKKT
+// (interface/hdsdp_conic_lp.c:266-348; engine_lp.h).
 //
 // Mathematical formulation.  With S = L L^T and At_i = L^-1 A_i L^-T:
 //     M_ij               = tr(A_i S^-1 A_j S^-1)        = <At_i, At_j>
@@ -47,6 +48,7 @@ __global__ void mi_csc_gather_kernel(HdmMatView Mv, const int *__restrict__ rows
 __global__ void mi_csc_scatter_kernel(HdmMatView Mv, const int *__restrict__ rows, const int *__restrict__ cols, long nnz,
                                       const double *__restrict__ vals);
 __global__ void mi_get_row_kernel(HdmMatView Mv, int i, int m, double *__restrict__ out);
+#include "lp_kernels.h"   // the LP cone's kernels (engine_lp.h)
 
 namespace {
 
@@ -119,6 +121,7 @@ int ensure_ctx() {
 #include "engine_linsys.h"
 #include "engine_cone.h"
 #include "engine_build.h"
+#include "engine_lp.h"
 
 }  // namespace
 

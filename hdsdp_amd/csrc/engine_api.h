@@ -10,6 +10,30 @@ hdsdp_retcode HMiConeCreateSDP64(hdsdp_cone **pCone, int iCone, int nRow, int nC
     return cone_create_csc(pCone, iCone, nRow, nCol, coneMatBeg, coneMatIdx, coneMatElem, rank, world);
 }
 
+// ---------------------------------------------------------------- LP cone (engine_lp.h)
+hdsdp_retcode HMiConeCreateLP(hdsdp_cone **pCone, int iCone, int nRow, int nCol, const int *coneMatBeg, const int *coneMatIdx,
+                              const double *coneMatElem) {
+    return lp_cone_create(pCone, iCone, nRow, nCol, coneMatBeg, coneMatIdx, coneMatElem);
+}
+int HMiConeLPSetSchurPath(hdsdp_cone *cone, int path) {
+    if (!cone || cone->coneBuildSchur != lp_build_schur || path < 0 || path > 2) return 1;
+    MiLPCone *c = (MiLPCone *) cone->coneData;
+    if (lp_set_path(c, path)) {
+        fprintf(stderr, "[hdsdp_mi355x] HMiConeLPSetSchurPath(%d): the %s path cannot be set up (pair list of %.2f GiB, cap %.2f)\n", path,
+                path == 2 ? "sparse" : "dense", (double) lp_sparse_bytes(c) / LP_PAIR_CAP, 1.0);
+        return 1;
+    }
+    return 0;
+}
+int HMiConeLPGetSchurPath(hdsdp_cone *cone, double *costDense, double *costSparse, int64_t *pairBytes) {
+    if (!cone || cone->coneBuildSchur != lp_build_schur) return -1;
+    const MiLPCone *c = (const MiLPCone *) cone->coneData;
+    if (costDense) *costDense = c->cost_dense;
+    if (costSparse) *costSparse = c->cost_sparse;
+    if (pairBytes) *pairBytes = lp_sparse_bytes(c);
+    return c->path;
+}
+
 // ---------------------------------------------------------------- column-by-column ingest (64-bit totals)
 struct HMiConeBuilder_s : MiConeBuilder {};
 hdsdp_retcode HMiConeBuilderBegin(HMiConeBuilder **pBuilder, int iCone, int nRow, int nCol, int rank, int world) {
@@ -114,6 +138,7 @@ void HMiConeGetPrimal(hdsdp_cone *cone, double dBarrierMu, double *dRowDual, dou
 void HMiConeGetPresolve(hdsdp_cone *cone, int *coefType, int *coefRank, int *coefNnz, int *kktPerm, int *kktStrategy,
                         int *objType) {
     MiCone *c = cone_data(cone);
+    if (!c) return;                   // (not an SDP cone of the engine: no presolve)
     for (int i = 0; i < c->m && !c->synthetic; ++i) {
         if (coefType) coefType[i] = c->blk.rows[i].type;
         if (coefRank) coefRank[i] = c->blk.rows[i].rank;
@@ -141,20 +166,21 @@ hdsdp_retcode HMiPresolveCSC(int nRow, int nCol, const int *coneMatBeg, const in
 }
 hdsdp_retcode HMiConeGetDualMatrix(hdsdp_cone *cone, double *S) {
     MiCone *c = cone_data(cone);
+    if (!c) return HDSDP_RETCODE_FAILED;
     if (hipMemcpy2DAsync(S, sizeof(double) * c->n, c->S, sizeof(double) * c->n16, sizeof(double) * c->n, c->n,
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     return hipStreamSynchronize(g.stream) == hipSuccess ? HDSDP_RETCODE_OK : HDSDP_RETCODE_FAILED;
 }
 hdsdp_retcode HMiConeGetTraces(hdsdp_cone *cone, double *trA) {
     MiCone *c = cone_data(cone);
-    if (!c->trA) return HDSDP_RETCODE_FAILED;
+    if (!c || !c->trA) return HDSDP_RETCODE_FAILED;
     memcpy(trA, c->trA, sizeof(double) * c->m);
     return HDSDP_RETCODE_OK;
 }
-int HMiConeGetPath(hdsdp_cone *cone) { return cone_data(cone)->path; }
+int HMiConeGetPath(hdsdp_cone *cone) { const MiCone *c = cone_data(cone); return c ? c->path : -1; }
 int HMiConeUseSweepCopy(hdsdp_cone *cone, int on) {
     MiCone *c = cone_data(cone);
-    if (ensure_ctx()) return 1;
+    if (!c || ensure_ctx()) return 1;
     c->pS_ok = c->pD_ok = false;     // the next request is assembled, not short-cut
     if (!on) { c->zs_state = -1; return 0; }
     if (!c->zs.val && cone_has_rows(c) && c->mloc > 0 &&
@@ -165,12 +191,12 @@ int HMiConeUseSweepCopy(hdsdp_cone *cone, int on) {
 }
 int HMiConeGetStreaming(hdsdp_cone *cone, int *batchRows) {
     const MiCone *c = cone_data(cone);
-    if (batchRows) *batchRows = c->streamed ? c->Bs : 0;
-    return c->streamed ? 1 : 0;
+    if (batchRows) *batchRows = (c && c->streamed) ? c->Bs : 0;
+    return (c && c->streamed) ? 1 : 0;
 }
 int HMiConeSweepInfo(hdsdp_cone *cone, int64_t *values, int64_t *positions) {
     const MiCone *c = cone_data(cone);
-    const bool on = (c->zs_state == 1);
+    const bool on = c && (c->zs_state == 1);
     if (values) *values = on ? (int64_t) c->zs.nnz : 0;
     if (positions) *positions = on ? (int64_t) c->zs.sky * c->zs.m : 0;
     return on ? 1 : 0;
@@ -202,7 +228,7 @@ int HMiConeGetBuildProfile(hdsdp_cone *cone, int shard, double *out, int cap) {
         if (shard < 0 || shard >= (int) cg->shard.size()) return -1;
         c = cg->shard[shard];
     } else {
-        if (shard != 0) return -1;
+        if (shard != 0 || cone->coneBuildSchur != cone_build_schur) return -1;
         c = (MiCone *) cone->coneData;
     }
     const MiCone::BuildProfile &pf = c->prof;

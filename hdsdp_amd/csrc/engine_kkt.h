@@ -168,6 +168,16 @@ static hdsdp_retcode linsys_create_tiles(hdsdp_linsys_fp **pHLin, int nCol, HdmB
 
 hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones) {
     if (ensure_ctx()) return HDSDP_RETCODE_FAILED;
+    {   // An LP cone builds on the caller's device and stream into the operator's matrix; a device-group cone's shards build on
+        // worker threads and devices of their own (group_impl.h: grun), with no ordering against the caller's stream that the LP
+        // cone's accumulation could rely on.  The two are not combined in one operator.
+        bool lp = false, grp = false;
+        for (int i = 0; i < nCones; ++i) { lp = lp || cones[i]->coneBuildSchur == lp_build_schur; grp = grp || cones[i]->coneBuildSchur == gc_build_schur; }
+        if (lp && grp) {
+            fprintf(stderr, "[hdsdp_mi355x] HKKTInit: an LP cone cannot share an operator with a device-group (sharded) cone\n");
+            return HDSDP_RETCODE_FAILED;
+        }
+    }
     HKKT->nRow = nRow;
     HKKT->nCones = nCones;
     HKKT->cones = cones;
@@ -340,7 +350,8 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     if (hipMalloc((void **) &pv->vecs, sizeof(double) * (3 * (size_t) nRow + 4)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
     pv->n_engine = pv->n_foreign = 0;
     for (int i = 0; i < nCones; ++i) {
-        if (cones[i]->coneBuildSchur == cone_build_schur || cones[i]->coneBuildSchur == gc_build_schur) pv->n_engine += 1;
+        if (cones[i]->coneBuildSchur == cone_build_schur || cones[i]->coneBuildSchur == gc_build_schur ||
+            cones[i]->coneBuildSchur == lp_build_schur) pv->n_engine += 1;
         else pv->n_foreign += 1;
     }
     HKKT->dPrimalX = nullptr;
@@ -639,6 +650,7 @@ void HMiKKTSetHostMirror(hdsdp_kkt *HKKT, int mirrorM) {
 }
 void HMiConeSetExchangePieces(hdsdp_cone *cone, hmi_alltoall_piece_fn start, hmi_alltoall_wait_fn wait, int npieces) {
     MiCone *c = cone_data(cone);
+    if (!c) return;                   // (not an SDP cone of the engine: nothing to exchange)
     c->a2a_start = start; c->a2a_wait = wait; c->a2a_pieces = std::max(1, npieces);
 }
 void HMiConeBuildPrimalXSXDirection(hdsdp_cone *cone, double *dPrimalScalMatrix, double *dPrimalXSXBuffer, int iDualMat) {
@@ -646,15 +658,18 @@ void HMiConeBuildPrimalXSXDirection(hdsdp_cone *cone, double *dPrimalScalMatrix,
 }
 void HMiConeGetExchangeStats(hdsdp_cone *cone, int *pieces, int *stagedLaunches) {
     MiCone *c = cone_data(cone);
+    if (!c) { if (pieces) *pieces = 0; if (stagedLaunches) *stagedLaunches = 0; return; }
     if (pieces) *pieces = c->last_pieces;
     if (stagedLaunches) *stagedLaunches = c->last_staged;
 }
 void HMiConeSetExchange(hdsdp_cone *cone, hmi_alltoall_fn a2a, hmi_allreduce_fn ar, void *ctx) {
     MiCone *c = cone_data(cone);
+    if (!c) return;
     c->alltoall = a2a; c->allreduce = ar; c->xctx = ctx;
 }
 hdsdp_retcode HMiConeGetExchangeBuffers(hdsdp_cone *cone, void **sendBuf, void **recvBuf, int64_t *chunkCount) {
     MiCone *c = cone_data(cone);
+    if (!c) return HDSDP_RETCODE_FAILED;
     if (chunkCount) *chunkCount = (int64_t) c->npb_loc * c->Lr * 16;
     if (sendBuf) *sendBuf = c->AhatLoc;
     if (recvBuf) *recvBuf = c->AhatAll;
@@ -662,7 +677,7 @@ hdsdp_retcode HMiConeGetExchangeBuffers(hdsdp_cone *cone, void **sendBuf, void *
 }
 hdsdp_retcode HMiConeSetExchangeBuffers(hdsdp_cone *cone, void *sendBuf, void *recvBuf) {
     MiCone *c = cone_data(cone);
-    if (c->work_ready || !sendBuf || !recvBuf) return HDSDP_RETCODE_FAILED;
+    if (!c || c->work_ready || !sendBuf || !recvBuf) return HDSDP_RETCODE_FAILED;
     c->AhatLoc = (double *) sendBuf;
     c->AhatAll = (c->world == 1) ? c->AhatLoc : (double *) recvBuf;
     c->ext_ahat = true;

@@ -521,7 +521,9 @@ void gc_destroy_data(void **pcd) {
 }
 
 MiCone *cone_data(hdsdp_cone *cone) {
+    if (!cone) return nullptr;
     if (cone->coneBuildSchur == gc_build_schur) return ((MiConeGroup *) cone->coneData)->shard[0];
+    if (cone->coneBuildSchur != cone_build_schur) return nullptr;     // an LP cone (engine_lp.h) or a foreign one: no SDP data
     return (MiCone *) cone->coneData;
 }
 

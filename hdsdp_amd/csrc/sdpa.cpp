@@ -24,7 +24,7 @@ struct HMiSDPA_s {
     std::vector<std::vector<int>> beg32, idx;
     std::vector<std::vector<double>> val;
     std::vector<int64_t> lpBeg;
-    std::vector<int> lpIdx;
+    std::vector<int> lpBeg32, lpIdx;
     std::vector<double> lpVal;
 };
 
@@ -125,7 +125,11 @@ hdsdp_retcode HMiReadSDPA(const char *fname, HMiSDPA **out) {
         // the reference-style int column pointers of a block that fits them, made here so that the accessors only read
         if (p->beg[b].back() <= 2147483647LL) p->beg32[b].assign(p->beg[b].begin(), p->beg[b].end());
     }
-    if (p->nlp > 0) bucket(p->m + 1, lpt, p->lpBeg, p->lpIdx, p->lpVal);
+    if (p->nlp > 0) {
+        if (lpt.size() > 2147483647UL) return fail("LP block of more than 2^31 - 1 entries");
+        bucket(p->m + 1, lpt, p->lpBeg, p->lpIdx, p->lpVal);
+        p->lpBeg32.assign(p->lpBeg.begin(), p->lpBeg.end());
+    }
     *out = p;
     return HDSDP_RETCODE_OK;
 }
@@ -154,6 +158,16 @@ hdsdp_retcode HMiSDPAGetBlock(const HMiSDPA *p, int iBlk, int *dim, const int **
     if (beg) *beg = p->beg32[iBlk].data();
     if (idx) *idx = p->idx[iBlk].data();
     if (val) *val = p->val[iBlk].data();
+    return HDSDP_RETCODE_OK;
+}
+// the LP (diagonal) block as the reference's reader leaves it (hdsdp_file_io.c:185-310): CSC of nCol rows and m + 1 columns,
+// column 0 = the objective (sign flipped like every F0 entry), entries in file order inside a column
+hdsdp_retcode HMiSDPAGetLPBlock(const HMiSDPA *p, int *nCol, const int **beg, const int **idx, const double **val) {
+    if (!p || p->nlp <= 0) return HDSDP_RETCODE_FAILED;
+    if (nCol) *nCol = p->nlp;
+    if (beg) *beg = p->lpBeg32.data();
+    if (idx) *idx = p->lpIdx.data();
+    if (val) *val = p->lpVal.data();
     return HDSDP_RETCODE_OK;
 }
 const double *HMiSDPAGetRHS(const HMiSDPA *p) { return p->rhs.data(); }

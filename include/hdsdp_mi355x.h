@@ -231,6 +231,32 @@ hdsdp_retcode HMiConeBuilderAddColumn(HMiConeBuilder *builder, int iCol, int64_t
 int64_t HMiConeBuilderStored(const HMiConeBuilder *builder);          /* entries handed in so far */
 hdsdp_retcode HMiConeBuilderFinish(HMiConeBuilder **pBuilder, hdsdp_cone **pCone);   /* frees the builder either way */
 void HMiConeBuilderAbort(HMiConeBuilder **pBuilder);
+/* ==========  LP cone: the SDPA diagonal block (interface/hdsdp_conic_lp.c)  ==========
+ * HMiConeCreateLP      = HConeCreate/SetData/ProcData for one HDSDP_CONETYPE_LP block (LPConeProcDataImpl :101-160): the CSC
+ *                        input has nCol rows (LP columns) and nRow + 1 columns, column 0 = the objective c (the layout of
+ *                        HMiSDPAGetLPBlock and of the reference's reader, hdsdp_file_io.c:185-310).  The returned cone has
+ *                        cone = HDSDP_CONETYPE_LP and the reference's slots, quirks included (HMiCone* above dispatch to them):
+ *                        updates with dualPerturb on the non-step buffers (:46-83), a ratio test of 100 when no component
+ *                        blocks (:223-259), primal recovery that prints "Recovery step is infeasible" and leaves the output
+ *                        untouched when the recovery point is not interior (:466-487), ScalByConstant dividing (rscl, :205-209),
+ *                        GetSymNnz = nRow^2 (the Schur matrix of an operator with an LP cone is dense), feature detection of
+ *                        implied y bounds and free variables (:567-667).  Its coneBuildSchur slot (LPConeGetKKT, :266-348)
+ *                        runs on the device: the vectors into the operator's device accumulators, M += A diag(d)^2 A^T into
+ *                        the device matrix, d = 1/s (or the registered primal X for KKT_TYPE_PRIMAL).  So an operator of
+ *                        engine SDP cones and LP cones counts no host cone and accepts HMiKKTSetHostMirror(0).  HKKTInit
+ *                        refuses an operator holding an LP cone and a device-group cone (HMiSetDevices).  The SDP-only
+ *                        accessors below (GetDualMatrix, GetTraces, GetPath, GetPresolve, SweepInfo, GetStreaming,
+ *                        UseSweepCopy, GetBuildProfile, the exchange calls) fail or return their neutral value on an LP cone.
+ * HMiConeLPSetSchurPath  how M is built: 0 = by the cost rule, 1 = dense (chunks of W = A diag(d) scattered on the
+ *                        device, M += W W^T on the fp64 matrix pipe), 2 = sparse (a pair list made once at creation: one
+ *                        fixed-order segmented sum per lower entry of M).  0 on success; 1 if the path cannot be set up (the
+ *                        pair list would exceed 1 GiB) or the cone is not an LP cone.
+ * HMiConeLPGetSchurPath  the path builds use (1 dense, 2 sparse; -1: not an LP cone), the two modelled build times in seconds
+ *                        and the pair list's bytes. */
+hdsdp_retcode HMiConeCreateLP(hdsdp_cone **pCone, int iCone, int nRow, int nCol, const int *coneMatBeg, const int *coneMatIdx,
+                              const double *coneMatElem);
+int HMiConeLPSetSchurPath(hdsdp_cone *cone, int path);
+int HMiConeLPGetSchurPath(hdsdp_cone *cone, double *costDense, double *costSparse, int64_t *pairBytes);
 void HMiConeDestroy(hdsdp_cone **pCone);
 void HMiConeSetStart(hdsdp_cone *cone, double dConeStartVal);                   /* HConeSetStart  hdsdp_conic.c:222 */
 void HMiConeUpdate(hdsdp_cone *cone, double barHsdTau, double *rowDual);        /* HConeUpdate    :228 */
@@ -428,6 +454,9 @@ hdsdp_retcode HMiSDPAGetBlock(const HMiSDPA *p, int iBlk, int *dim, const int **
  * refuses such a block): feeds HMiConeCreateSDP64 */
 hdsdp_retcode HMiSDPAGetBlock64(const HMiSDPA *p, int iBlk, int *dim, const int64_t **beg, const int **idx,
                                 const double **val);
+/* the LP (diagonal) block, hdsdp_file_io.c:185-310: CSC of nCol rows and m + 1 columns, column 0 = the objective (-F0's
+ * entries), entries in file order inside a column; RETCODE_FAILED if the file has no LP block.  Feeds HMiConeCreateLP. */
+hdsdp_retcode HMiSDPAGetLPBlock(const HMiSDPA *p, int *nCol, const int **beg, const int **idx, const double **val);
 const double *HMiSDPAGetRHS(const HMiSDPA *p);
 void HMiSDPAFree(HMiSDPA **pp);
 
