@@ -34,7 +34,7 @@ EXPORTS = [
     "HMiConeCheckIsInterior", "HMiConeGetLogBarrier", "HMiConeRatioTest", "HMiLanczosStartVector", "HMiConeGetPrimal", "HMiConeCheckIsInteriorExpert",
     "HMiConeAddStepToBufferAndCheck", "HMiConeReduceResi", "HMiConeSetPerturb", "HMiConeGetCoeffNorm", "HMiConeGetObjNorm",
     "HMiConeScalByConstant", "HMiConeComputeATimesXpy", "HMiConeComputeXDotS", "HMiConeComputeTraceCX", "HMiConeGetDual", "HMiConeGetPresolve", "HMiConeDetectFeature", "HMiConeGetDualMatrix",
-    "HMiConeGetTraces", "HMiConeGetPath", "HMiConeSweepInfo", "HMiConeGetStreaming", "HMiConeUseSweepCopy", "HMiKKTSetHostMirror", "HMiConeSetExchange", "HMiConeSetExchangePieces", "HMiConeGetExchangeStats", "HMiConeGetBuildProfile", "HMiConeBuildPrimalXSXDirection",
+    "HMiConeGetTraces", "HMiConeGetPath", "HMiConeSweepInfo", "HMiConeGetStreaming", "HMiConeUseSweepCopy", "HMiKKTSetHostMirror", "HMiConeSetExchange", "HMiConeSetExchangePieces", "HMiConeGetExchangeStats", "HMiConeGetPrimalRoute", "HMiConeGetPrimalProfile", "HMiConeGetBuildProfile", "HMiConeBuildPrimalXSXDirection",
     "HMiConeGetExchangeBuffers", "HMiConeSetExchangeBuffers", "HMiKKTDeviceMatrix", "HMiKKTGetRows", "HMiDeviceInit",
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
@@ -156,6 +156,8 @@ def load_library():
         "HMiConeSetExchange": (None, [vp, vp, vp, vp]),
         "HMiConeSetExchangePieces": (None, [vp, vp, vp, C.c_int]),
         "HMiConeGetExchangeStats": (None, [vp, ip, ip]),
+        "HMiConeGetPrimalRoute": (C.c_int, [vp, ip, dp]),
+        "HMiConeGetPrimalProfile": (C.c_int, [vp, dp, C.POINTER(C.c_int64)]),
         "HMiConeGetBuildProfile": (C.c_int, [vp, C.c_int, dp, C.c_int]),
         "HMiConeBuildPrimalXSXDirection": (None, [vp, dp, dp, C.c_int]),
         "HMiConeGetExchangeBuffers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]),
@@ -486,6 +488,24 @@ class SDPCone:
         p, s = C.c_int(0), C.c_int(0)
         load_library().HMiConeGetExchangeStats(self._h, C.byref(p), C.byref(s))
         return p.value, s.value
+
+    def primal_route(self):
+        """(route, q, growth) of the last KKT_TYPE_PRIMAL build (HMiConeGetPrimalRoute): route 0 = X positive definite,
+        1 = signed factor + signed Gram correction, 2 = row-by-row fallback or refusal; q = negative pivots of the signed
+        factor, growth = |W|_F^2 / |X|_F.  None before the first such build"""
+        q, gr = C.c_int(0), C.c_double(0.0)
+        r = int(load_library().HMiConeGetPrimalRoute(self._h, C.byref(q), C.byref(gr)))
+        return None if r < 0 else (r, q.value, gr.value)
+
+    def primal_profile(self):
+        """ms of the signed part of the last route-1 KKT_TYPE_PRIMAL build (HMiConeGetPrimalProfile): dict with the signed
+        factor + acceptance test, the gathers, the correction's Gram launches, the combination, and the gathered columns;
+        None when the last KKT_TYPE_PRIMAL build was not on route 1"""
+        ms, cols = np.zeros(4), C.c_int64(0)
+        if load_library().HMiConeGetPrimalProfile(self._h, _dptr(ms), C.byref(cols)):
+            return None
+        return {"factor_check_ms": float(ms[0]), "gather_ms": float(ms[1]), "correction_ms": float(ms[2]),
+                "combine_ms": float(ms[3]), "columns": int(cols.value)}
 
     def build_profile(self, shard=0):
         """where the last SHARDED Schur build of one shard spent its time (HMiConeGetBuildProfile; ms, bytes): None when no

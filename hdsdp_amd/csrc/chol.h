@@ -36,6 +36,9 @@ struct HdmChol {
     // stop at row env_colh[k] and the substitutions skip the blocks outside.  Empty = dense.
     std::vector<int> env_first, env_colh;
     int *env_dev = nullptr;      // device copy: first[nblk], then colh[nblk]
+    // factor_signed (KKT_TYPE_PRIMAL with an indefinite X): the pivot signs and two info words of the last signed factorisation
+    double *sgn = nullptr;       // npad: sign of pivot k (+1 in the identity padding)
+    int *sinfo_dev = nullptr;    // [0] first zero / non-finite pivot + 1, [1] negative pivots
 
     int init(int n);
     int set_envelope(const int *first_blockcol_of_blockrow);   // nblk entries; nullptr = dense.  Before the first factor().
@@ -46,6 +49,11 @@ struct HdmChol {
     int factor(hipStream_t s, int *info_host);          // info = 0 ok, j+1 = first non-positive pivot
     int invert_factor(hipStream_t s);                   // builds Linv (idempotent until the next load)
     int set_reverse_inverse(hipStream_t s);             // primal builds: Linv <- W, W^T W = X, from the factor of J X J
+    // blocked LDL' without pivoting in Cholesky clothing (the SIGNED sweep of sweep128.h per diagonal block): A = F S F^T,
+    // S = diag(sgn), F lower with a positive diagonal.  info = first exactly zero / non-finite pivot + 1 (0: factored),
+    // nneg = negative pivots.  After it, set_reverse_inverse gives W with W^T diag(sigma) W = X, sigma from reverse_signs.
+    int factor_signed(hipStream_t s, int *info_host, int *nneg_host);
+    int reverse_signs(double *sig_dev, hipStream_t s);  // sig[i] = sgn[n - 1 - i] for i < n, +1 in the padding (npad entries)
     int get_diag(double *diag_host, hipStream_t s);
     int solve_device(double *b_dev, double *x_dev, int nrhs, long ldv, int which, hipStream_t s);
     int enqueue_factor(hipStream_t s);

@@ -237,6 +237,12 @@ __global__ __launch_bounds__(SM_T) void hdm_potrf_diag_sweep_kernel(double *__re
                                                                     int *__restrict__ info, int col0, int nv) {
     hdm_potrf_diag_sweep_body(A, ld, Dinv, info, col0, nv);
 }
+// the signed sweep on one diagonal block of the dense blocked factor (HdmChol::factor_signed): block column col0 / 128
+__global__ __launch_bounds__(SM_T) void hdm_potrf_diag_sweep_signed_kernel(double *__restrict__ A, long ld, double *__restrict__ Dinv,
+                                                                           int *__restrict__ info, int col0, int nv,
+                                                                           double *__restrict__ sgn) {
+    hdm_potrf_diag_sweep_body<true>(A, ld, Dinv, info, col0, nv, sgn, info + 1);
+}
 // the same for a list of independent diagonal tiles of a block-sparse matrix (bsparse.hip): workgroup b factors the diagonal
 // tile of block column cols[b]; a non-positive pivot is reported as the smallest failing row + 1 over the launch
 // sgn != nullptr: the signed (LDL') sweep; sgn[128 k ..] receives block column k's pivot signs, info[1] counts negative pivots
@@ -303,6 +309,23 @@ __global__ void hdm_reverse_factor_kernel(const double *__restrict__ F, double *
     else v = (i >= j) ? F[(n - 1 - j) + (long) (n - 1 - i) * ld] : 0.0;
     W[i + (long) j * ld] = v;
 }
+
+// signed panel (HdmChol::factor_signed): P holds Q = A_ik inv(F_kk)^T; Z <- Q, P <- Q S_k = F_ik (column j scaled by the
+// sign of pivot j of block k), so that the trailing update A22 -= F_ik S_k F_jk^T = P Z^T is the unsigned update's product
+__global__ void hdm_signed_panel_kernel(double *__restrict__ P, long ld, double *__restrict__ Z, long ldz,
+                                        const double *__restrict__ sg, int rows) {
+    const long e = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long) rows * NB) return;
+    const int i = (int) (e % rows), j = (int) (e / rows);
+    const double q = P[i + (long) j * ld];
+    Z[i + (long) j * ldz] = q;
+    P[i + (long) j * ld] = q * sg[j];
+}
+__global__ void hdm_reverse_signs_kernel(const double *__restrict__ sgn, double *__restrict__ sig, int n, int npad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < npad) sig[i] = (i < n) ? sgn[n - 1 - i] : 1.0;
+}
+__global__ void hdm_zero_words_kernel(int *p, int count) { if ((int) threadIdx.x < count) p[threadIdx.x] = 0; }
 
 // Linv diagonal blocks <- the inverted 128 x 128 diagonal blocks (blockIdx.y = block)
 __global__ void hdm_copy_diag_blocks_kernel(const double *__restrict__ Dinv, double *__restrict__ Linv, long ld) {
@@ -611,6 +634,9 @@ void HdmChol::destroy() {
     if (Zd) (void) hipFree(Zd);
     if (info_dev) (void) hipFree(info_dev);
     if (vec) (void) hipFree(vec);
+    if (sgn) (void) hipFree(sgn);
+    if (sinfo_dev) (void) hipFree(sinfo_dev);
+    sgn = nullptr; sinfo_dev = nullptr;
     if (flow_flags) (void) hipFree(flow_flags);
     if (flow_err) (void) hipHostFree(flow_err);
     flow_flags = nullptr; flow_err = nullptr;
@@ -656,6 +682,75 @@ int HdmChol::set_reverse_inverse(hipStream_t s) {
                        (long) npad, n, npad);
     HDM_HIP_CHECK(hipGetLastError());
     have_inv = true;
+    return 0;
+}
+
+// Blocked LDL' without pivoting, in the clothing of the blocked Cholesky above (KKT_TYPE_PRIMAL with an indefinite registered
+// matrix, engine_build.h: build_primal).  Per block column k: the SIGNED register sweep factors the diagonal block as
+// F_kk S_k F_kk^T and inverts F_kk (sweep128.h; S_k = the pivots' signs, F_kk with a positive diagonal); the panel is
+// Q = A_ik inv(F_kk)^T (the same product as the Cholesky panel), F_ik = Q S_k; the trailing update is
+// A22 -= F_ik S_k F_jk^T = F_ik Q^T -- the Cholesky update's product with Q kept aside in Z as its second operand.  Same
+// kernels as enqueue_factor apart from the sweep's flavour and one scaling pass per panel; dense only (no envelope), eager only.
+static int hdm_k128_launch(bool update, const double *A, long lda, const double *B, long ldb, double *C, long ldc, int rows,
+                           hipStream_t s);
+int HdmChol::factor_signed(hipStream_t s, int *info_host, int *nneg_host) {
+    if (!sgn) {
+        HDM_HIP_CHECK(hipMalloc((void **) &sgn, sizeof(double) * (size_t) npad));
+        HDM_HIP_CHECK(hipMalloc((void **) &sinfo_dev, sizeof(int) * 2));
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_potrf_diag_sweep_signed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          DIAG_SWEEP_LDS_DOUBLES * (int) sizeof(double)));
+    }
+    if (!Z && nblk > 1) HDM_HIP_CHECK(hipMalloc((void **) &Z, sizeof(double) * (size_t) npad * NB));
+    hipLaunchKernelGGL(hdm_zero_words_kernel, dim3(1), dim3(64), 0, s, sinfo_dev, 2);
+    HDM_HIP_CHECK(hipGetLastError());
+    const long ld = npad;
+    static const bool k128 = [] { const char *e = getenv("HDM_CHOL_K128"); return !(e && atoi(e) == 0); }();
+    for (int k = 0; k < nblk; ++k) {
+        double *Akk = L + (long) k * NB * (ld + 1);
+        hipLaunchKernelGGL(hdm_potrf_diag_sweep_signed_kernel, dim3(1), dim3(SM_T), DIAG_SWEEP_LDS_DOUBLES * sizeof(double), s, Akk, ld,
+                           Dinv + (long) k * NB * NB, sinfo_dev, k * NB, std::max(1, std::min(NB, n - k * NB)), sgn + (long) k * NB);
+        HDM_HIP_CHECK(hipGetLastError());
+        const int rows = npad - (k + 1) * NB;
+        if (rows <= 0) break;
+        double *P = Akk + NB;
+        if (k128 && rows % 64 == 0 && ld < (1L << 20)) {
+            if (hdm_k128_launch(false, P, ld, Dinv + (long) k * NB * NB, NB, P, ld, rows, s)) return 1;
+        } else {
+            HdmGemmArgs g = {};
+            g.A = P; g.lda = ld; g.B = Dinv + (long) k * NB * NB; g.ldb = NB; g.C = P; g.ldc = ld;
+            g.M = rows; g.N = NB; g.K = NB; g.batch = 1; g.alpha = 1.0; g.beta = 0.0; g.epilogue = HDM_EPI_STORE;
+            if (hdm_launch_gemm(g, s)) return 1;
+        }
+        const long tot = (long) rows * NB;
+        hipLaunchKernelGGL(hdm_signed_panel_kernel, dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, s, P, ld, Z, (long) npad,
+                           (const double *) (sgn + (long) k * NB), rows);
+        HDM_HIP_CHECK(hipGetLastError());
+        if (k128 && rows % 64 == 0 && ld < (1L << 20)) {
+            if (hdm_k128_launch(true, P, ld, Z, (long) npad, Akk + (long) NB * (ld + 1), ld, rows, s)) return 1;
+        } else {
+            HdmGemmArgs u = {};
+            u.A = P; u.lda = ld; u.B = Z; u.ldb = npad; u.C = Akk + (long) NB * (ld + 1); u.ldc = ld;
+            u.M = rows; u.N = rows; u.K = NB; u.batch = 1; u.alpha = -1.0; u.beta = 1.0;
+            u.lower_only = 1; u.epilogue = HDM_EPI_STORE;
+            if (hdm_launch_gemm(u, s)) return 1;
+        }
+    }
+    int info[2] = {0, 0};
+    HDM_HIP_CHECK(hipMemcpyAsync(info, sinfo_dev, sizeof(int) * 2, hipMemcpyDeviceToHost, s));
+    HDM_HIP_CHECK(hipStreamSynchronize(s));
+    if (info[0] > n) info[0] = 0;
+    if (info_host) *info_host = info[0];
+    if (nneg_host) *nneg_host = info[1];
+    factored = (info[0] == 0);
+    have_inv = false;
+    logdet_ok = false;
+    return 0;
+}
+
+int HdmChol::reverse_signs(double *sig_dev, hipStream_t s) {
+    if (!sgn || !factored) return 1;
+    hipLaunchKernelGGL(hdm_reverse_signs_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, (const double *) sgn, sig_dev, n, npad);
+    HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }
 

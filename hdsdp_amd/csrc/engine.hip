@@ -49,6 +49,7 @@ __global__ void mi_csc_scatter_kernel(HdmMatView Mv, const int *__restrict__ row
                                       const double *__restrict__ vals);
 __global__ void mi_get_row_kernel(HdmMatView Mv, int i, int m, double *__restrict__ out);
 #include "lp_kernels.h"   // the LP cone's kernels (engine_lp.h)
+#include "primal_kernels.h"   // the signed KKT_TYPE_PRIMAL route's kernels (engine_build.h)
 
 namespace {
 

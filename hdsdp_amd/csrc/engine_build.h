@@ -207,6 +207,117 @@ hdsdp_retcode exchange_and_gram(MiCone *c, bool staged = false) {
     return gram_reduce(c) ? HDSDP_RETCODE_FAILED : HDSDP_RETCODE_OK;
 }
 
+// KKT_TYPE_PRIMAL, route 1 (build_primal): X = W^T diag(sigma) W with sigma = +-1, the transformed rows are At_i = W A_i W^T, and
+//   M_ij = tr(A_i X A_j X) = sum_{k,l} sigma_k sigma_l At_i(k, l) At_j(k, l),
+// the Gram product of the packed rows with the weight sigma_k sigma_l on packed column (k, l).  The plain Gram product G has run
+// with weight +1 everywhere; the columns of weight -1 (one index in the negative set, the other not) or those of weight +1,
+// whichever are fewer, are gathered into a compact operand and their own Gram product G- / G+ is added with alpha -2 / +2:
+//   signed G = G - 2 G-  =  2 G+ - G.
+// Chunks of at most 2 GiB of gathered operand; the Gram role's kernel on the chunk (split-K into the slabs, which are free after
+// the plain product's reduction), then Gm = (+-1) Gm + sum of the slabs.  Sharded: this rank's partial Gm over its own K range
+// (all rows of it are here after the exchange), before the all-reduce.  Fixed order throughout: bitwise reproducible.
+static constexpr long PSIG_GATHER_BYTES = 2L << 30;
+int signed_correction(MiCone *c) {
+    c->primal_cols = 0;
+    std::vector<double> sg((size_t) c->n16);
+    HIP_RC(hipMemcpyAsync(sg.data(), c->gram_sig, sizeof(double) * (size_t) c->n16, hipMemcpyDeviceToHost, g.stream));
+    HIP_RC(hipStreamSynchronize(g.stream));
+    // p-block q: sub-block q >> 4 of the blocked lower triangle (numbered column by column, column bj starting at
+    // bj nblk - bj (bj - 1) / 2), matrix column bj 16 + (q & 15); its packed columns q 16 + r are the rows bi 16 + r
+    const long pb0 = (long) c->rank * c->npb_loc, pb1 = std::min(c->npb, pb0 + c->npb_loc);
+    auto start = [&](long bj) { return bj * c->nblk - bj * (bj - 1) / 2; };
+    std::vector<int> neg, pos;
+    long bj = 0;
+    for (long q = pb0; q < pb1; ++q) {
+        const long sub = q >> 4;
+        while (bj + 1 < c->nblk && start(bj + 1) <= sub) ++bj;
+        const long bi = bj + (sub - start(bj)), col = bj * 16 + (q & 15);
+        if (col >= c->n) continue;
+        for (int r = 0; r < 16; ++r) {
+            const long row = bi * 16 + r;
+            if (row >= c->n) break;
+            ((sg[row] * sg[col] < 0.0) ? neg : pos).push_back((int) (q * 16 + r));
+        }
+    }
+    const bool use_neg = neg.size() <= pos.size();
+    const std::vector<int> &cols = use_neg ? neg : pos;
+    const double alpha = use_neg ? -2.0 : 2.0, beta0 = use_neg ? 1.0 : -1.0;
+    const long ncols = (long) cols.size(), R = c->R;
+    c->primal_cols = ncols;
+    if (ncols == 0) {
+        if (use_neg) return 0;                                        // no column of weight -1 here: G is already signed
+        hipLaunchKernelGGL(mi_psig_combine_kernel, dim3((unsigned) ((R * R + 255) / 256)), dim3(256), 0, g.stream, c->Gm,
+                           (const double *) c->slabs, R * R, 0, R, -1.0);
+        HIP_RC(hipGetLastError());
+        return 0;
+    }
+    if (c->pcols_cap < ncols) {
+        if (c->pcols) HIP_RC(hipFree(c->pcols));
+        c->pcols = nullptr; c->pcols_cap = 0;
+        HIP_RC(hipMalloc((void **) &c->pcols, sizeof(int) * (size_t) ncols));
+        c->pcols_cap = ncols;
+    }
+    HIP_RC(hipMemcpyAsync(c->pcols, cols.data(), sizeof(int) * (size_t) ncols, hipMemcpyHostToDevice, g.stream));
+    HIP_RC(hipStreamSynchronize(g.stream));      // (pageable source going out of scope)
+    const long RT = (R + HDM_TILE - 1) / HDM_TILE, tiles = RT * (RT + 1) / 2;
+    const long ncols16 = hdm_roundup(ncols, 16);
+    const long kc = std::min(ncols16, std::max(16L, (PSIG_GATHER_BYTES / (8 * R)) & ~15L));   // columns per chunk
+    // the Gram role's tile loads carry no row mask: up to RT * 128 rows of the last k block are read
+    const long need = R * kc + RT * HDM_TILE * 16 + HDM_OPERAND_PAD_DOUBLES;
+    if (c->pgat_cap < need) {
+        if (c->pgat) HIP_RC(hipFree(c->pgat));
+        c->pgat = nullptr; c->pgat_cap = 0;
+        HIP_RC(hipMalloc((void **) &c->pgat, sizeof(double) * (size_t) need));
+        HIP_RC(hipMemsetAsync(c->pgat, 0, sizeof(double) * (size_t) need, g.stream));
+        c->pgat_cap = need;
+    }
+    // split-K over the slabs: enough (split, tile) jobs to fill the chip, at least 8 k blocks per split
+    int nz = (int) std::max(1L, std::min<long>({(long) c->nslab, (1024 + tiles - 1) / tiles, std::max(1L, kc / 16 / 8)}));
+    const long seg_stride = c->npb_loc * c->Lr * 16;
+    std::vector<hipEvent_t> ev;
+    auto mark = [&]() { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return 1; ev.push_back(e);
+                        return hipEventRecord(e, g.stream) != hipSuccess ? 1 : 0; };
+    int rc = 0;
+    for (long j0 = 0; j0 < ncols && !rc; j0 += kc) {
+        const long nc = std::min(kc, ncols - j0), nc16 = hdm_roundup(nc, 16);
+        const long tot = R * nc16;
+        rc |= mark();
+        hipLaunchKernelGGL(mi_psig_gather_kernel, dim3((unsigned) std::min<long>((tot + 255) / 256, 16384)), dim3(256), 0, g.stream,
+                           (const double *) c->AhatAll, seg_stride, c->Lr, R, (const int *) (c->pcols + j0), nc, nc16, pb0, c->pgat);
+        if (hipGetLastError() != hipSuccess) rc = 1;
+        rc |= mark();
+        HdmGemmArgs gq = {};
+        gq.A = c->pgat; gq.B = c->pgat; gq.a_kmajor = 1; gq.b_kmajor = 1;
+        gq.lda = 16; gq.ldb = 16; gq.a_kblk = R * 16; gq.b_kblk = R * 16;
+        gq.ldc = R; gq.M = (int) R; gq.N = (int) R; gq.K = (int) nc16;
+        gq.lower_only = 1; gq.epilogue = HDM_EPI_SLAB; gq.batch = nz;
+        gq.k_chunk = (nc16 / 16 + nz - 1) / nz * 16; gq.k_base = 0; gq.slab_stride = R * R;
+        gq.alpha = alpha; gq.beta = (j0 == 0) ? 0.0 : 1.0; gq.role = HDM_ROLE_GRAM;
+        gq.queue_global = c->gram_queue_global ? 1 : 0;
+        gq.spanA = gq.spanB = c->pgat_cap;
+        gq.C = c->slabs;
+        gq.flops = (double) R * (R + 1) * 0.5 * (double) nc * 2.0;
+        if (!rc && hdm_launch_gemm(gq, g.stream)) rc = 1;
+    }
+    rc |= mark();
+    if (!rc) {
+        hipLaunchKernelGGL(mi_psig_combine_kernel, dim3((unsigned) ((R * R + 255) / 256)), dim3(256), 0, g.stream, c->Gm,
+                           (const double *) c->slabs, R * R, nz, R, beta0);
+        if (hipGetLastError() != hipSuccess) rc = 1;
+    }
+    rc |= mark();
+    if (hipEventSynchronize(ev.back()) != hipSuccess) rc = 1;
+    double gat = 0.0, gem = 0.0, cmb = 0.0;
+    float t = 0.f;
+    for (size_t k = 0; !rc && k + 1 < ev.size(); ++k) {
+        if (hipEventElapsedTime(&t, ev[k], ev[k + 1]) != hipSuccess) { rc = 1; break; }
+        if (k + 2 == ev.size()) cmb += t; else if (k % 2 == 0) gat += t; else gem += t;
+    }
+    for (hipEvent_t e : ev) (void) hipEventDestroy(e);
+    c->primal_ms[1] = gat; c->primal_ms[2] = gem; c->primal_ms[3] = cmb;
+    return rc;
+}
+
 hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKKT, HdmChol *chOverride = nullptr);
 double *kkt_Mdev(hdsdp_kkt *kkt, long *ld);
 HdmMatView kkt_view(hdsdp_kkt *kkt);
@@ -279,6 +390,90 @@ hdsdp_retcode build_primal_general(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, con
     return HDSDP_RETCODE_OK;
 }
 
+// Route 1 of KKT_TYPE_PRIMAL: the signed factor of an X that is not positive definite, and its acceptance test.  J X J = F S F^T
+// without pivoting (HdmChol::factor_signed), W = J F^T J (lower triangular, in Linv's place as on route 0), sigma = J S J, so
+// X = W^T diag(sigma) W.  An LDL' without pivoting can grow without bound, and M's rounding error scales with |W|^4 where the
+// positive definite route's scales with |X|^2; so the factor is only used when, measured on the device,
+//   residual = |W^T diag(sigma) W - X|_F / |X|_F <= PSIG_MAX_RESIDUAL   and   growth = |W|_F^2 / |X|_F <= PSIG_MAX_GROWTH sqrt(n)
+// ("KKT_TYPE_PRIMAL with an indefinite X", says why these two).  For a positive definite X the growth is
+// tr X / |X|_F <= sqrt(n).  Returns 0 and *ok; `why` names the failed check.
+static constexpr double PSIG_MAX_RESIDUAL = 1e-11;
+static constexpr double PSIG_MAX_GROWTH = 8.0;
+int primal_signed_factor(MiCone *c, HdmChol &ch, const double *Xr, const double *X, bool *ok, const char **why) {
+    *ok = false; *why = "zero pivot";
+    const double t0 = host_now();
+    int info = 0, nneg = 0;
+    if (ch.load_host(Xr, c->n, g.stream)) return 1;
+    HIP_RC(hipStreamSynchronize(g.stream));
+    if (ch.factor_signed(g.stream, &info, &nneg)) return 1;
+    c->primal_q = nneg;
+    c->primal_growth = 0.0; c->primal_resid = 0.0;
+    if (info != 0) return 0;                           // an exactly zero (or non-finite) pivot: no factor of this form exists
+    if (ch.set_reverse_inverse(g.stream)) return 1;
+    const long np = ch.npad;
+    if (!c->psig) HIP_RC(hipMalloc((void **) &c->psig, sizeof(double) * (size_t) np));
+    if (ch.reverse_signs(c->psig, g.stream)) return 1;
+    long ldx = 0;
+    if (cone_upload_X(c, X, &ldx)) return 1;
+    if (ldx != np) { fprintf(stderr, "[hdsdp_mi355x] KKT_TYPE_PRIMAL: factor and primal matrix disagree on their padding\n"); return 1; }
+    const size_t np2 = sizeof(double) * (size_t) np * np;
+    if (!c->Pr1) HIP_RC(hipMalloc((void **) &c->Pr1, np2));
+    if (!c->Pr2) HIP_RC(hipMalloc((void **) &c->Pr2, np2));
+    if (!c->pchk) HIP_RC(hipMalloc((void **) &c->pchk, sizeof(double) * (3 * MI_PSIG_BLOCKS + 8)));
+    // Pr1 = diag(sigma) W,  Pr2 = W^T Pr1   (A operand element (i, k) = W(k, i), B operand element (j, k) = Pr1(k, j): both K-major)
+    hipLaunchKernelGGL(mi_psig_rowscale_kernel, dim3((unsigned) ((np * np + 255) / 256)), dim3(256), 0, g.stream,
+                       (const double *) ch.Linv, (const double *) c->psig, c->Pr1, np, (int) np);
+    HIP_RC(hipGetLastError());
+    HdmGemmArgs q = {};
+    q.A = ch.Linv; q.lda = np; q.a_kmajor = 1; q.B = c->Pr1; q.ldb = np; q.b_kmajor = 1; q.C = c->Pr2; q.ldc = np;
+    q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE;
+    RC(hdm_launch_gemm(q, g.stream));
+    hipLaunchKernelGGL(mi_psig_norms_kernel, dim3(MI_PSIG_BLOCKS), dim3(256), 0, g.stream, (const double *) c->Pr2, (const double *) c->Xup,
+                       (const double *) ch.Linv, np, c->n, c->pchk);
+    hipLaunchKernelGGL(mi_psig_norms_final_kernel, dim3(1), dim3(64), 0, g.stream, (const double *) c->pchk, MI_PSIG_BLOCKS,
+                       c->pchk + 3 * MI_PSIG_BLOCKS);
+    HIP_RC(hipGetLastError());
+    double nr[3] = {0, 0, 0};
+    HIP_RC(hipMemcpyAsync(nr, c->pchk + 3 * MI_PSIG_BLOCKS, sizeof(nr), hipMemcpyDeviceToHost, g.stream));
+    HIP_RC(hipStreamSynchronize(g.stream));
+    const double xf = std::sqrt(nr[1]);
+    c->primal_resid = xf > 0.0 ? std::sqrt(nr[0]) / xf : INFINITY;
+    c->primal_growth = xf > 0.0 ? nr[2] / xf : INFINITY;
+    c->primal_ms[0] = (host_now() - t0) * 1e3;
+    if (!(c->primal_resid <= PSIG_MAX_RESIDUAL)) { *why = "reconstruction residual"; return 0; }
+    if (!(c->primal_growth <= PSIG_MAX_GROWTH * std::sqrt((double) c->n))) { *why = "growth"; return 0; }
+    *ok = true; *why = "";
+    return 0;
+}
+
+static bool primal_signed_enabled() {
+    const char *e = getenv("HDSDP_MI355X_PRIMAL_SIGNED");
+    return !(e && atoi(e) == 0);
+}
+
+// Every shard of a sharded block factors the same replicated X with the same kernels, so all of them must come to the same
+// decision (a shard that went on alone would wait for the others in the exchange).  Checked, not assumed: the sums of
+// (accepted, q) over the ranks must be world times this rank's.
+int primal_shards_agree(MiCone *c, bool ok, bool *agree) {
+    *agree = true;
+    if (c->world <= 1) return 0;
+    if (!c->allreduce) return 1;
+    if (!c->pchk) HIP_RC(hipMalloc((void **) &c->pchk, sizeof(double) * (3 * MI_PSIG_BLOCKS + 8)));
+    double *w = c->pchk + 3 * MI_PSIG_BLOCKS + 4;
+    const double mine[2] = {ok ? 1.0 : 0.0, (double) c->primal_q};
+    HIP_RC(hipMemcpyAsync(w, mine, sizeof(mine), hipMemcpyHostToDevice, g.stream));
+    HIP_RC(hipStreamSynchronize(g.stream));
+    if (c->allreduce(c->xctx, w, 2)) return 1;
+    double sum[2] = {0, 0};
+    HIP_RC(hipMemcpyAsync(sum, w, sizeof(sum), hipMemcpyDeviceToHost, g.stream));
+    HIP_RC(hipStreamSynchronize(g.stream));
+    *agree = sum[0] == c->world * mine[0] && sum[1] == c->world * mine[1];
+    return 0;
+}
+
+// KKT_TYPE_PRIMAL routing: 0 = X positive definite, the Cholesky factor (unchanged); 1 = the signed factor passed its acceptance
+// test: the congruence + Gram path with the signed Gram correction; 2 = neither: the row-by-row fallback on one device, a refusal
+// on a sharded block.  HDSDP_MI355X_PRIMAL_SIGNED=0: route 1 is never tried (0 or 2, as before it existed).
 hdsdp_retcode build_primal(MiCone *c, int iCone, hdsdp_kkt *kkt, MiKKTPriv *pv) {
     if (!kkt->dPrimalX || !kkt->dPrimalX[iCone]) return HDSDP_RETCODE_FAILED;   // :1747-1750
     const double *X = kkt->dPrimalX[iCone];
@@ -295,9 +490,40 @@ hdsdp_retcode build_primal(MiCone *c, int iCone, hdsdp_kkt *kkt, MiKKTPriv *pv) 
     if (ch.load_host(Xr.data(), n, g.stream)) return HDSDP_RETCODE_FAILED;
     HIP_RC(hipStreamSynchronize(g.stream));   // Xr is pageable host memory going out of scope
     if (ch.factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
-    if (info != 0) return build_primal_general(c, kkt, pv, X);   // X is not positive definite: no factor to lean on
-    if (ch.set_reverse_inverse(g.stream)) return HDSDP_RETCODE_FAILED;
-    return build_gemm_path(c, kkt, pv, KKT_TYPE_PRIMAL, &ch);
+    if (info == 0) {
+        c->primal_route = 0; c->primal_q = 0; c->primal_growth = 0.0;
+        if (ch.set_reverse_inverse(g.stream)) return HDSDP_RETCODE_FAILED;
+        return build_gemm_path(c, kkt, pv, KKT_TYPE_PRIMAL, &ch);
+    }
+    if (!primal_signed_enabled()) {               // X is not positive definite: no factor to lean on
+        c->primal_route = 2; c->primal_q = 0; c->primal_growth = 0.0;
+        return build_primal_general(c, kkt, pv, X);
+    }
+    bool ok = false, agree = true;
+    const char *why = "";
+    if (primal_signed_factor(c, ch, Xr.data(), X, &ok, &why)) return HDSDP_RETCODE_FAILED;
+    if (primal_shards_agree(c, ok, &agree)) return HDSDP_RETCODE_FAILED;
+    if (!agree) {
+        fprintf(stderr, "[hdsdp_mi355x] KKT_TYPE_PRIMAL: the shards of a block disagree about the signed factor of the same X\n");
+        return HDSDP_RETCODE_FAILED;
+    }
+    if (!ok) {
+        c->primal_route = 2;
+        if (c->world > 1) {
+            fprintf(stderr, "[hdsdp_mi355x] KKT_TYPE_PRIMAL: an indefinite primal matrix is not supported on a sharded block unless its "
+                            "signed factor passes; it failed the %s check (negative pivots %d, growth %.3g, residual %.3g)\n",
+                    why, c->primal_q, c->primal_growth, c->primal_resid);
+            return HDSDP_RETCODE_FAILED;
+        }
+        return build_primal_general(c, kkt, pv, X);
+    }
+    c->primal_route = 1;
+    c->gram_sig = c->psig;
+    hdsdp_retcode rc = build_gemm_path(c, kkt, pv, KKT_TYPE_PRIMAL, &ch);
+    c->gram_sig = nullptr;
+    // the "S row" back to I for every other build (it is written once, at allocation: cone_alloc_gemm_work)
+    if (c->rank == 0 && c->work_ready && hdm_blocked_eye(c->AhatLoc, c->Lr, c->mloc + 1, c->nblk, c->n, g.stream)) rc = HDSDP_RETCODE_FAILED;
+    return rc;
 }
 
 hdsdp_retcode cone_build_schur(void *cd, int iCone, void *kktv, int typeKKT) {
@@ -375,6 +601,11 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
         if (cone_alloc_gemm_work(c)) return HDSDP_RETCODE_MEMORY;
         c->work_ready = true;
     }
+    if (c->gram_sig && c->rank == 0) {   // route 1 of KKT_TYPE_PRIMAL: the "S row" carries diag(sigma) (build_primal restores I)
+        hipLaunchKernelGGL(mi_psig_srow_kernel, dim3(c->nblk), dim3(256), 0, g.stream, c->AhatLoc, (long) c->Lr, (long) c->mloc + 1,
+                           c->nblk, c->n, c->gram_sig);
+        HIP_RC(hipGetLastError());
+    }
     HIP_RC(hipEventRecord(g.ev[0], g.stream));
     RC(ch.invert_factor(g.stream));
     HIP_RC(hipEventRecord(g.ev[1], g.stream));
@@ -435,6 +666,7 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
     c->prof.valid = false;
     if (c->world > 1) { RC(exchange_and_gram(c, staged)); }
     else { RC(gram_all(c)); }
+    if (c->gram_sig) RC(signed_correction(c));   // this rank's partial, before the all-reduce
     HIP_RC(hipEventRecord(g.ev[3], g.stream));
     if (c->world > 1) {
         HIP_RC(hipStreamSynchronize(g.stream));

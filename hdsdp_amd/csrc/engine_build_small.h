@@ -164,6 +164,8 @@ void cone_destroy_data(void **pcd) {
     if (c->small.sgn) (void) hipFree(c->small.sgn);
     if (c->small.io_host) (void) hipHostFree(c->small.io_host);
     if (c->corr) (void) hipFree(c->corr);
+    { double *pb[] = {c->psig, c->pgat, c->pchk}; for (double *b : pb) if (b) (void) hipFree(b); }
+    if (c->pcols) (void) hipFree(c->pcols);
     HFpLinsysDestroy(&c->dualFactor);
     if (c->primal) { c->primal->destroy(); delete c->primal; }
     if (c->lanczos) { c->lanczos->destroy(); delete c->lanczos; }

@@ -51,6 +51,16 @@ struct MiCone {
     double *corr = nullptr;    // sharded corrector build: this cone's 2m dot products before they join the operator's
     hdsdp_linsys_fp *dualFactor = nullptr;
     HdmChol *primal = nullptr; // KKT_TYPE_PRIMAL: factor object of the registered primal matrix (lazy)
+    // KKT_TYPE_PRIMAL with an indefinite X, route 1 (engine_build.h: build_primal): X = W^T diag(sigma) W from the signed factor
+    double *psig = nullptr;           // sigma on the device (npad, +1 in the padding)
+    const double *gram_sig = nullptr; // set for the duration of a route-1 build: the Gram product takes the signed weights
+    int *pcols = nullptr; long pcols_cap = 0;     // packed columns of the correction's sign (this rank's K range)
+    double *pgat = nullptr; long pgat_cap = 0;    // the gathered operand (one chunk)
+    double *pchk = nullptr;           // acceptance check: 3 * MI_PSIG_BLOCKS partial sums + 3 totals; then the shards' agreement words
+    int primal_route = -1, primal_q = 0;          // HMiConeGetPrimalRoute: the last KKT_TYPE_PRIMAL build
+    double primal_growth = 0.0, primal_resid = 0.0;
+    double primal_ms[4] = {0, 0, 0, 0};           // route 1: signed factor + check, gather, correction GEMMs, combine (ms)
+    long primal_cols = 0;                         // route 1: columns of the correction on this rank (0: none needed)
     HdmLanczos *lanczos = nullptr;  // ratio test state (lazy); dS lives in `dS`
     double nrm[4] = {0, 0, 0, 0}; bool norms_ready = false;   // data norms (rows abs / Frobenius, objective abs / Frobenius)
     double objScal = 1.0;           // product of the coneScal factors applied to C

@@ -662,6 +662,20 @@ void HMiConeGetExchangeStats(hdsdp_cone *cone, int *pieces, int *stagedLaunches)
     if (pieces) *pieces = c->last_pieces;
     if (stagedLaunches) *stagedLaunches = c->last_staged;
 }
+int HMiConeGetPrimalRoute(hdsdp_cone *cone, int *negativePivots, double *growth) {
+    const MiCone *c = cone_data(cone);
+    if (!c || c->primal_route < 0) return -1;
+    if (negativePivots) *negativePivots = c->primal_q;
+    if (growth) *growth = c->primal_growth;
+    return c->primal_route;
+}
+int HMiConeGetPrimalProfile(hdsdp_cone *cone, double *ms, int64_t *columns) {
+    const MiCone *c = cone_data(cone);
+    if (!c || c->primal_route != 1) return 1;
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->primal_ms[k];
+    if (columns) *columns = (int64_t) c->primal_cols;
+    return 0;
+}
 void HMiConeSetExchange(hdsdp_cone *cone, hmi_alltoall_fn a2a, hmi_allreduce_fn ar, void *ctx) {
     MiCone *c = cone_data(cone);
     if (!c) return;

@@ -364,6 +364,18 @@ void HMiConeBuildPrimalXSXDirection(hdsdp_cone *cone, double *dPrimalScalMatrix,
 /* what the last HKKTBuildUp did: pieces of the exchange (1 = one blocking all-to-all) and, when the congruence's second
  * step was staged by packed-index range, the number of launches it was cut into (0 = not staged) */
 void HMiConeGetExchangeStats(hdsdp_cone *cone, int *pieces, int *stagedLaunches);
+/* the last KKT_TYPE_PRIMAL build of the cone (for a group cone: shard 0's): returns its route -- 0 = X positive definite, Cholesky
+ * factor and congruence + Gram path; 1 = X indefinite, the signed factor X = W^T diag(sigma) W passed its acceptance test and the
+ * congruence + Gram path ran with the signed Gram correction; 2 = neither, the row-by-row fallback (one device) or a refusal
+ * (sharded block) -- with *negativePivots = q, the number of negative pivots of the signed factor, and *growth = |W|_F^2 / |X|_F
+ * (both 0 when no signed factor was formed: route 0, route 2 after a zero pivot or with HDSDP_MI355X_PRIMAL_SIGNED=0).
+ * -1: not an SDP cone of the engine, or no KKT_TYPE_PRIMAL build yet. */
+int HMiConeGetPrimalRoute(hdsdp_cone *cone, int *negativePivots, double *growth);
+/* where the last route-1 KKT_TYPE_PRIMAL build (shard 0 of a group cone) spent the time of its signed part, in ms: ms[0] signed
+ * factor + acceptance test (host clock, includes the upload of X), ms[1] gathers of the correction's packed columns, ms[2] the
+ * correction's Gram launches, ms[3] the final combination into the Gram matrix; *columns = packed columns gathered.  1 if the
+ * last KKT_TYPE_PRIMAL build was not on route 1. */
+int HMiConeGetPrimalProfile(hdsdp_cone *cone, double *ms, int64_t *columns);
 /* Where the last SHARDED Schur build (world > 1) of one shard spent its time, so that a multi-GPU bench line says where a step went
  * and not only how long it took (the cone loop being sharded: interface/hdsdp_schur.c:256-268).  `shard`: index inside an in-process
  * device group (0 for a process-per-GPU cone).  Milliseconds; device times are differences of HIP events on the shard's engine stream,
@@ -486,6 +498,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *  HDSDP_MI355X_AFFINE_S          by cost   0 / 1 / 2: dual matrix short-cuts (engine_cone.h)             test_gpu_switches.py
  *  HDSDP_MI355X_SMALL_CHECK       1         one-launch interior check of small blocks                     test_gpu_switches.py
  *  HDSDP_MI355X_ZS                by cost   0 / 1 / 2: zero-suppressed copy for the S / dS sweeps (schur.h) test_gpu_switches.py
+ *  HDSDP_MI355X_PRIMAL_SIGNED     1         KKT_TYPE_PRIMAL with an indefinite X: signed factor + signed  test_gpu_primal_signed.py
+ *                                           Gram correction (route 1); 0: row-by-row fallback / refusal
  *  HDSDP_MI355X_STREAM_A          by memory 0 / 1: synthetic constraint data resident / regenerated per     test_gpu_streamed.py
  *                                           batch (MiCone::streamed)
  *  HDM_TCAP_GIB                   32        GiB of congruence intermediates per launch group              test_gpu_switches.py, test_gpu_group.py
