@@ -36,7 +36,7 @@ EXPORTS = [
     "HMiConeScalByConstant", "HMiConeComputeATimesXpy", "HMiConeComputeXDotS", "HMiConeComputeTraceCX", "HMiConeGetDual", "HMiConeGetPresolve", "HMiConeDetectFeature", "HMiConeGetDualMatrix",
     "HMiConeGetTraces", "HMiConeGetPath", "HMiConeSweepInfo", "HMiConeGetStreaming", "HMiConeUseSweepCopy", "HMiKKTSetHostMirror", "HMiConeSetExchange", "HMiConeSetExchangePieces", "HMiConeGetExchangeStats", "HMiConeGetPrimalRoute", "HMiConeGetPrimalProfile", "HMiConeGetBuildProfile", "HMiConeBuildPrimalXSXDirection",
     "HMiConeGetExchangeBuffers", "HMiConeSetExchangeBuffers", "HMiKKTDeviceMatrix", "HMiKKTGetRows", "HMiDeviceInit",
-    "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
+    "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiGetAssembleCounts", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
@@ -175,6 +175,7 @@ def load_library():
         "HMiGetCallStats": (C.c_int, [dp, C.POINTER(C.c_int64), C.c_int]),
         "HMiCallStatName": (C.c_char_p, [C.c_int]),
         "HMiResetCallStats": (None, []),
+        "HMiGetAssembleCounts": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
         "HMiKKTPhaseAEligible": (C.c_int, [kp]),
         "HMiKKTPhaseA": (C.c_int, [kp, C.c_double, dp, dp, dp, dp, dp, ip, dp]),
         "HMiDeviceInit": (C.c_int, [C.c_int]),
@@ -277,6 +278,15 @@ def presolve_csc(n, m, beg, idx, val):
                               _iptr(out["kkt_strategy"]), C.byref(ot)), "HMiPresolveCSC")
     out["obj_type"] = ot.value
     return out
+
+
+def assemble_counts():
+    """process-wide answers to dual / step matrix requests (HMiGetAssembleCounts): [0] already in the buffer, [1] copy of S,
+    [2] S + alpha dS on the last ratio test's line, [3] sweep off that line, [4] refresh sweep, [5] step-matrix sweep,
+    [6] sweep of an untracked block"""
+    out = (C.c_int64 * 7)()
+    k = int(load_library().HMiGetAssembleCounts(out, 7))
+    return [int(out[i]) for i in range(min(k, 7))]
 
 
 def lanczos_start_vector(n):

@@ -461,6 +461,10 @@ int HMiGetCallStats(double *seconds, int64_t *calls, int n) {
     return ST_N;
 }
 const char *HMiCallStatName(int k) { return (k >= 0 && k < ST_N) ? g_stat_name[k] : ""; }
+int HMiGetAssembleCounts(int64_t *counts, int n) {
+    for (int k = 0; k < n && k < 7; ++k) if (counts) counts[k] = g_asm_counts[k];
+    return 7;
+}
 void HMiResetCallStats(void) { for (int k = 0; k < ST_N; ++k) { g_stat_sec[k] = 0.0; g_stat_calls[k] = 0; } g_stat_nfn = 0; }
 int HMiRcclSelfTest(int device) {
     if (ensure_ctx()) return 1;

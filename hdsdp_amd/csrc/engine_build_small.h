@@ -169,6 +169,9 @@ void cone_destroy_data(void **pcd) {
     HFpLinsysDestroy(&c->dualFactor);
     if (c->primal) { c->primal->destroy(); delete c->primal; }
     if (c->lanczos) { c->lanczos->destroy(); delete c->lanczos; }
+    if (c->lanczos_fresh) { c->lanczos_fresh->destroy(); delete c->lanczos_fresh; }
+    if (c->safe) { c->safe->destroy(); delete c->safe; }
+    if (c->Ssafe) (void) hipFree(c->Ssafe);
     if (c->chk_host) (void) hipHostFree(c->chk_host);
     if (c->checker) { c->checker->destroy(); delete c->checker; }
     for (hipEvent_t e : c->piece_ev) if (e) (void) hipEventDestroy(e);

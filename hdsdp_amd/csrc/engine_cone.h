@@ -62,6 +62,11 @@ struct MiCone {
     double primal_ms[4] = {0, 0, 0, 0};           // route 1: signed factor + check, gather, correction GEMMs, combine (ms)
     long primal_cols = 0;                         // route 1: columns of the correction on this rank (0: none needed)
     HdmLanczos *lanczos = nullptr;  // ratio test state (lazy); dS lives in `dS`
+    // the ratio test's safeguard (cone_ratio_test): a factor object and a buffer for S + step dS, and a Lanczos object that
+    // always starts fresh (lazy, only made when a step has failed the check)
+    HdmChol *safe = nullptr;
+    double *Ssafe = nullptr;
+    HdmLanczos *lanczos_fresh = nullptr;
     double nrm[4] = {0, 0, 0, 0}; bool norms_ready = false;   // data norms (rows abs / Frobenius, objective abs / Frobenius)
     double objScal = 1.0;           // product of the coneScal factors applied to C
     HdmChol *checker = nullptr;     // second factor object (primal recovery works on S without the residual term)
@@ -750,6 +755,56 @@ hdsdp_retcode cone_barrier(void *cd, double tau, double *y, int whichBuffer, dou
     return HDSDP_RETCODE_OK;
 }
 
+// The reference's Lanczos estimate accepts the first Ritz value whose residual bound is small; it certifies that an eigenvalue
+// lies near it, not that it is the largest.  A warm start (the previous test's Ritz image + 1e-3 x a fixed vector) can hold
+// almost nothing of the new operator's top eigenvector, and the test then stops at a lower eigenvalue: a step past alpha*
+// (n = 15, DESIGN.md: 0.678 for alpha* = 0.614, the reference's own recurrence gives the same number).  So a finite step is
+// checked: S + (1 - 1e-3) step dS is factored in a scratch object.  If that succeeds the reference's number stands unchanged; if not, a
+// Lanczos test from the fresh start vector is run (its own object: the warm-start state stays the reference's), the smaller
+// step taken, and it is cut by 10 % until the factorisation succeeds.
+hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *maxStep) {
+    // (a step of 1e6 or more stands for "unbounded": S + step dS is then rounding noise times the step, and no caller takes it)
+    if (!(*maxStep > 0.0) || !(*maxStep < 1e6)) return HDSDP_RETCODE_OK;
+    const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
+    if (!c->safe) {
+        c->safe = new HdmChol();
+        if (c->safe->init(c->n)) return HDSDP_RETCODE_MEMORY;
+    }
+    if (!c->Ssafe) HIP_RC(hipMalloc((void **) &c->Ssafe, nn));
+    const double *Sb = (whichBuffer == 0) ? c->S : c->Scheck;
+    auto inside = [&](double step, bool *ok) -> int {
+        int info = 0;
+        // (checked at (1 - 1e-3) step: the reference's own acceptance tolerance (gamma < 1e-3).  A step that is alpha* to
+        // rounding -- a rank-one dS, dS = -S -- or within that tolerance of it stands as the reference computed it, and
+        // the driver's trajectory with it; what is caught is a test that stopped at the wrong eigenvalue)
+        if (hdm_axpy_mat(c->Ssafe, Sb, c->dS, (1.0 - 1e-3) * step, (long) c->n16 * c->n16, g.stream) ||
+            c->safe->load_device(c->Ssafe, c->n16, g.stream) || c->safe->factor(g.stream, &info)) return 1;
+        *ok = (info == 0);
+        return 0;
+    };
+    bool ok = false;
+    if (inside(*maxStep, &ok)) return HDSDP_RETCODE_FAILED;
+    if (ok) return HDSDP_RETCODE_OK;
+    if (!c->lanczos_fresh) {
+        c->lanczos_fresh = new HdmLanczos();
+        if (c->lanczos_fresh->init(c->n)) return HDSDP_RETCODE_MEMORY;
+    }
+    c->lanczos_fresh->nComputed = 0;
+    double step = *maxStep, fresh = INFINITY;
+    int steps = 0;
+    if (c->lanczos_fresh->solve(fac->Linv, fac->npad, c->dS, c->n16, g.stream, &fresh, &steps) == 0 && fresh < step) step = fresh;
+    for (int it = 0; it < 64; ++it) {
+        if (inside(step, &ok)) return HDSDP_RETCODE_FAILED;
+        if (ok) break;
+        step *= 0.9;
+    }
+    static const bool dbg = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e); }();
+    if (dbg) fprintf(stderr, "[hdsdp_mi355x ratio] n %d: step %.6e left the cone, safeguarded to %.6e (fresh start %.6e)\n", c->n,
+                     *maxStep, step, fresh);
+    *maxStep = ok ? step : 0.0;
+    return HDSDP_RETCODE_OK;
+}
+
 // sdpDenseConeRatioTestImpl (hdsdp_conic_sdp.c:1640-1686): dS = dTauStep*C - sum dy_i A_i + dAdaRatio*Rd*I, then the
 // largest alpha with S + alpha dS >= 0 by Lanczos on L^-1 (-dS) L^-T (lanczos.hip).  L is the factor of the chosen
 // buffer: the current S (BUFFER_DUALVAR) or the trial point factored last in the checker (BUFFER_DUALCHECK).
@@ -771,7 +826,9 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
         HIP_RC(hipMemcpyAsync(&d0, c->dS, sizeof(double), hipMemcpyDeviceToHost, g.stream));
         HIP_RC(hipMemcpyAsync(&s0, (whichBuffer == 0) ? c->S : c->Scheck, sizeof(double), hipMemcpyDeviceToHost, g.stream));
         HIP_RC(hipStreamSynchronize(g.stream));
-        *maxStep = (d0 > 0.0) ? INFINITY : (-s0 / d0);
+        // (the reference tests d0 > 0, which turns d0 == 0 -- a zero step matrix -- into -s0 / 0 = -inf: a step of minus
+        // infinity for a direction that can be followed without limit)
+        *maxStep = (d0 >= 0.0) ? INFINITY : (-s0 / d0);
         return HDSDP_RETCODE_OK;
     }
     RC(hdm_mirror_lower(c->dS, c->n16, c->n, g.stream));
@@ -786,7 +843,7 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
     if (c->lanczos->solve(fac->Linv, fac->npad, c->dS, c->n16, g.stream, maxStep, &steps)) return HDSDP_RETCODE_FAILED;
     if (dbg) fprintf(stderr, "[hdsdp_mi355x ratio] n %d: %d Lanczos steps, step %.6e, solve %.1f us\n", c->n, steps, *maxStep,
                      1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    return HDSDP_RETCODE_OK;
+    return ratio_safeguard(c, fac, whichBuffer, maxStep);
 }
 
 // The cone's `getstat` slot: the reference's feature detection (sdpDenseConeFeatureDetectImpl / sdpSparseConeFeatureDetectImpl,

@@ -446,6 +446,12 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
 int HMiGetCallStats(double *seconds, int64_t *calls, int n);
 const char *HMiCallStatName(int k);
 void HMiResetCallStats(void);
+/* how the requests for a dual or step matrix of single-device blocks were answered so far (csrc/engine_cone.h: cone_assemble):
+ * [0] the buffer already held the point, [1] a copy of S, [2] S + alpha dS (+ delta I) on the last ratio test's line, [3] a
+ * sweep for a dual matrix off that line, [4] a refresh sweep after 16 in-place updates, [5] a step-matrix sweep, [6] a sweep of a
+ * block that does not track points.  Process-wide, never reset (the table HDSDP_MI355X_CALL_STATS=1 prints at exit).  Fills up
+ * to n entries; returns the number of counters. */
+int HMiGetAssembleCounts(int64_t *counts, int n);
 int HMiRcclSelfTest(int device);   /* one-rank communicator on `device` (-1: the engine's): all-reduce + grouped send/recv, checked */
 /* the same over a whole group of distinct devices, one host thread per device as the group's workers drive it: communicators,
  * an all-reduce, and the grouped ncclSend/ncclRecv of one piece of the sharded build's exchange, values compared bit for bit;
