@@ -35,7 +35,7 @@ EXPORTS = [
     "HMiConeAddStepToBufferAndCheck", "HMiConeReduceResi", "HMiConeSetPerturb", "HMiConeGetCoeffNorm", "HMiConeGetObjNorm",
     "HMiConeScalByConstant", "HMiConeComputeATimesXpy", "HMiConeComputeXDotS", "HMiConeComputeTraceCX", "HMiConeGetDual", "HMiConeGetPresolve", "HMiConeDetectFeature", "HMiConeGetDualMatrix",
     "HMiConeGetTraces", "HMiConeGetPath", "HMiConeSweepInfo", "HMiConeGetStreaming", "HMiConeUseSweepCopy", "HMiKKTSetHostMirror", "HMiConeSetExchange", "HMiConeSetExchangePieces", "HMiConeGetExchangeStats", "HMiConeGetPrimalRoute", "HMiConeGetPrimalProfile", "HMiConeGetBuildProfile", "HMiConeBuildPrimalXSXDirection",
-    "HMiConeGetExchangeBuffers", "HMiConeSetExchangeBuffers", "HMiKKTDeviceMatrix", "HMiKKTGetRows", "HMiDeviceInit",
+    "HMiConeGetExchangeBuffers", "HMiConeSetExchangeBuffers", "HMiKKTDeviceMatrix", "HMiKKTGetRows", "HMiKKTGetDiagTarget", "HMiKKTGetMatrixTraffic", "HMiDeviceInit",
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiGetAssembleCounts", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
@@ -164,6 +164,8 @@ def load_library():
         "HMiConeSetExchangeBuffers": (C.c_int, [vp, vp, vp]),
         "HMiKKTDeviceMatrix": (vp, [kp, C.POINTER(C.c_int64)]),
         "HMiKKTGetRows": (C.c_int, [kp, C.c_int, ip, dp]),
+        "HMiKKTGetDiagTarget": (C.c_int, [kp]),
+        "HMiKKTGetMatrixTraffic": (None, [kp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "HMiSetDevices": (C.c_int, [C.c_int, ip]),
         "HMiSetDevicesEx": (C.c_int, [C.c_int, ip, C.c_int]),
         "HMiRcclGroupSelfTest": (C.c_int, [C.c_int, ip, C.c_int]),
@@ -778,6 +780,21 @@ class KKT:
         out = np.zeros((rows.size, self.m))
         _check(load_library().HMiKKTGetRows(self._k, int(rows.size), _iptr(rows), _dptr(out)), "HMiKKTGetRows")
         return out
+
+    def set_host_mirror(self, on):
+        """HMiKKTSetHostMirror: 1 = the host copy of M is refreshed after every build; 0 = M stays on the device and kktDiag[]
+        points into the diagonal channel (refused, with a stderr line, while a host cone sits in the operator)"""
+        load_library().HMiKKTSetHostMirror(self._k, 1 if on else 0)
+
+    def diag_target(self):
+        """HMiKKTGetDiagTarget: 0 = kktDiag[] points into kktMatElem, 1 = into the diagonal channel"""
+        return int(load_library().HMiKKTGetDiagTarget(self._k))
+
+    def matrix_traffic(self):
+        """HMiKKTGetMatrixTraffic: (bytes of M and channel to the host, to the device) since HKKTInit"""
+        h, d = C.c_int64(0), C.c_int64(0)
+        load_library().HMiKKTGetMatrixTraffic(self._k, C.byref(h), C.byref(d))
+        return h.value, d.value
 
     def add_to_diag(self, v):
         """what the y-box cone does through kktDiag[] (interface/hdsdp_conic_bound.c:201-229)"""

@@ -329,10 +329,15 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
     if (ls->ch.npad != SMALL_P || lm->ch.npad != SMALL_P) return HDSDP_RETCODE_FAILED;
     // (the operator's accumulators as HKKTBuildUp(KKT_TYPE_INFEASIBLE) leaves them, hdsdp_schur.c:141-165, :256-268: the
     // kernel itself zeroes what it does not fill of the 128 x 128 device matrix)
+    // (as kkt_clean: the build starts an empty diagonal channel -- the stream is idle, the pinned channel is free to write)
+    memset(pv->chan, 0, sizeof(double) * (size_t) m);
+    pv->chan_folded = false;
     RC(hdm_small_phase_a(a, g.stream));
-    if (pv->mirror)
+    if (pv->mirror) {
         HIP_RC(hipMemcpy2DAsync(HKKT->kktMatElem, sizeof(double) * m, lm->Mdev, sizeof(double) * SMALL_P, sizeof(double) * m, m,
                                 hipMemcpyDeviceToHost, g.stream));
+        pv->bytes_d2h += (int64_t) sizeof(double) * m * m;
+    }
     HIP_RC(hipStreamSynchronize(g.stream));
     const int infoS = (int) out[0], infoM = (int) out[1];
     ls->ch.factored = (infoS == 0); ls->ch.have_inv = false;

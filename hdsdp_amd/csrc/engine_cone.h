@@ -152,6 +152,12 @@ struct MiKKTPriv {
     int *sp_rows = nullptr, *sp_cols = nullptr;
     int *sp_prow = nullptr, *sp_pcol = nullptr;   // the same entries in the factor object's (permuted, lower) coordinates, if it is permuted
     double *sp_vals = nullptr;
+    // diagonal channel (host mirror off, engine_kkt.h): kktDiag[i] -> chan[i], pinned; host cones add their diagonal terms
+    // there, and the first HKKTRegularize / HKKTFactorize after a build adds it (8 m bytes up) to the device matrix's diagonal
+    double *chan = nullptr;
+    double *chan_dev = nullptr;   // device: m doubles + 1 (the minimum the regulariser reads)
+    bool chan_folded = false;     // the channel of the current build is in the device matrix already
+    int64_t bytes_d2h = 0, bytes_h2d = 0;   // M and the channel moved since HKKTInit (HMiKKTGetMatrixTraffic)
 };
 
 // the kkt private state hangs off kktM->chol's MiLin (Mdev) plus a side struct keyed by the kkt pointer
@@ -174,6 +180,8 @@ void priv_drop(hdsdp_kkt *k) {
             if (g_priv[i].second->sp_pcol) (void) hipFree(g_priv[i].second->sp_pcol);
             if (g_priv[i].second->sp_cols) (void) hipFree(g_priv[i].second->sp_cols);
             if (g_priv[i].second->sp_vals) (void) hipFree(g_priv[i].second->sp_vals);
+            if (g_priv[i].second->chan) (void) hipHostFree(g_priv[i].second->chan);
+            if (g_priv[i].second->chan_dev) (void) hipFree(g_priv[i].second->chan_dev);
             delete g_priv[i].second;
             g_priv.erase(g_priv.begin() + i);
             return;

@@ -108,6 +108,32 @@ __global__ void mi_lower_dot_kernel(const double *__restrict__ S, long lds_, con
 
 
 
+// the diagonal channel (engine_kkt.h): one pass over diag(M) of the device matrix (dense or tile store), in one workgroup.
+// d = M_ii (+ chan[i]) (+ add); written back when it changed; *mn = min_i d in the host loop's sense (a NaN never wins).
+// The two additions are separate roundings, in that order: the host mirror's (M_ii + bound_i) + reg.
+__global__ void __launch_bounds__(1024) mi_diag_pass_kernel(HdmMatView Mv, int m, const double *__restrict__ chan, int do_add,
+                                                            double add, double *__restrict__ mn) {
+    __shared__ double red[16];
+    double lo = INFINITY;
+    for (int i = threadIdx.x; i < m; i += 1024) {
+        double *p = hdm_mat_at(Mv, i, i);
+        double d = *p;
+        if (chan) d = d + chan[i];
+        if (do_add) d = d + add;
+        if (chan || do_add) *p = d;
+        lo = (d < lo) ? d : lo;
+    }
+    if (!mn) return;
+    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(lo, off, 64); lo = (o < lo) ? o : lo; }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = lo;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = red[0];
+        for (int w = 1; w < 16; ++w) r = (red[w] < r) ? red[w] : r;
+        *mn = r;
+    }
+}
+
 // sparse Schur operator: entry p of the aggregated CSC pattern <-> element (rows[p], cols[p]) of the dense device matrix
 __global__ void mi_csc_gather_kernel(HdmMatView Mv, const int *__restrict__ rows, const int *__restrict__ cols, long nnz,
                                      double *__restrict__ vals) {

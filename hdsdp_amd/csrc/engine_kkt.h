@@ -354,7 +354,53 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
             cones[i]->coneBuildSchur == lp_build_schur) pv->n_engine += 1;
         else pv->n_foreign += 1;
     }
+    if (hipHostMalloc((void **) &pv->chan, sizeof(double) * std::max(1, nRow), hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void **) &pv->chan_dev, sizeof(double) * ((size_t) nRow + 1)) != hipSuccess)
+        return HDSDP_RETCODE_MEMORY;
+    memset(pv->chan, 0, sizeof(double) * std::max(1, nRow));
+    pv->chan_folded = false;
+    pv->bytes_d2h = pv->bytes_h2d = 0;
+    // HDSDP_MI355X_DEVICE_M=1: an unchanged driver keeps M on the device when it can.  Its host
+    // cones outside cones[] (the bound cone on y) write the diagonal only, and that goes through the channel.
+    if (const char *e = getenv("HDSDP_MI355X_DEVICE_M")) if (atoi(e) == 1) {
+        if (pv->n_engine > 0 && pv->n_foreign == 0) {
+            HMiKKTSetHostMirror(HKKT, 0);
+            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: M stays on the device (m = %d, diagonal channel)\n", nRow);
+        }
+        else if (pv->n_foreign > 0)
+            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: the host copy of M is kept: %d cone(s) of this operator accumulate on the host\n",
+                    pv->n_foreign);
+        else fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: the host copy of M is kept: the operator has no engine cone\n");
+    }
     HKKT->dPrimalX = nullptr;
+    return HDSDP_RETCODE_OK;
+}
+
+// kktDiag[] -> the host matrix's diagonal (mirror on) or the diagonal channel (mirror off)
+static void kkt_point_diag(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
+    if (!HKKT->kktDiag || !HKKT->kktMatElem || !pv->chan) return;
+    const int m = HKKT->nRow;
+    for (int i = 0; i < m; ++i)
+        HKKT->kktDiag[i] = !pv->mirror ? &pv->chan[i] :
+                           HKKT->isKKTSparse ? &HKKT->kktMatElem[HKKT->kktMatBeg[i]] : &HKKT->kktMatElem[i + (size_t) i * m];
+}
+
+// one pass over diag(M) on the device (mi_diag_pass_kernel): fold = upload the channel and add it (once per build), add = add
+// v; mn (optional) receives the minimum of the diagonal after the pass's additions
+static hdsdp_retcode kkt_diag_pass(hdsdp_kkt *HKKT, MiKKTPriv *pv, bool fold, bool add, double v, double *mn) {
+    const int m = HKKT->nRow;
+    if (fold) {
+        if (hipMemcpyAsync(pv->chan_dev, pv->chan, sizeof(double) * (size_t) m, hipMemcpyHostToDevice, g.stream) != hipSuccess)
+            return HDSDP_RETCODE_FAILED;
+        pv->bytes_h2d += (int64_t) sizeof(double) * m;
+        pv->chan_folded = true;
+    }
+    hipLaunchKernelGGL(mi_diag_pass_kernel, dim3(1), dim3(1024), 0, g.stream, kkt_view(HKKT), m, fold ? pv->chan_dev : nullptr,
+                       add ? 1 : 0, v, mn ? pv->chan_dev + m : nullptr);
+    if (hipGetLastError() != hipSuccess) return HDSDP_RETCODE_FAILED;
+    if (mn && (hipMemcpyAsync(mn, pv->chan_dev + m, sizeof(double), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+               hipStreamSynchronize(g.stream) != hipSuccess))
+        return HDSDP_RETCODE_FAILED;
     return HDSDP_RETCODE_OK;
 }
 
@@ -379,6 +425,8 @@ static hdsdp_retcode kkt_clean(hdsdp_kkt *HKKT, int typeKKT) {  // hdsdp_schur.c
         // of the whole m x m device matrix replaces every entry, and 8 m^2 bytes of host memset per call are saved: 4 ms at
         // m = 2000, twice per iteration of the reference's driver)
         else if (pv->mirror && !(pv->n_foreign == 0 && pv->n_engine > 0)) memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) m * m);
+        memset(pv->chan, 0, sizeof(double) * (size_t) m);       // (the diagonal channel: host cones add into it with the mirror off)
+        pv->chan_folded = false;
     }
     return HDSDP_RETCODE_OK;
 }
@@ -400,6 +448,7 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
         double *Mdev = kkt_Mdev(HKKT, &ld);
         double *dst = HKKT->kktMatElem;
         mcount = HKKT->isKKTSparse ? (size_t) pv->nnz : (size_t) m * m;
+        pv->bytes_d2h += (int64_t) (sizeof(double) * mcount);
         if (pv->n_foreign > 0) {
             if (!pv->Mtmp && hipHostMalloc((void **) &pv->Mtmp, sizeof(double) * std::max<size_t>(1, mcount)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
             dst = pv->Mtmp;
@@ -501,6 +550,7 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
         // it) or from the accumulation store, then factored level by level (bsparse.hip)
         if (pv->mirror) {
             if (l->bsp->zero_L(g.stream)) return HDSDP_RETCODE_FAILED;
+            pv->bytes_h2d += (int64_t) sizeof(double) * pv->nnz;
             if (pv->nnz > 0) {
                 if (hipMemcpyAsync(pv->sp_vals, HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
                     return HDSDP_RETCODE_FAILED;
@@ -508,7 +558,9 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
                                    pv->sp_rows, pv->sp_cols, pv->nnz, pv->sp_vals);
             }
         } else {
-            if (!pv->Mdev_valid || l->bsp->load_M(g.stream)) return HDSDP_RETCODE_FAILED;
+            // (the diagonal channel goes into the accumulation store first: the factor store is a copy of it)
+            if (!pv->Mdev_valid || (!pv->chan_folded && kkt_diag_pass(HKKT, pv, true, false, 0.0, nullptr) != HDSDP_RETCODE_OK) ||
+                l->bsp->load_M(g.stream)) return HDSDP_RETCODE_FAILED;
         }
         // LDL' like the reference's sparse direct solver (linalg/hdsdp_linsolver.c:596-626 over external/qdldl.c): an indefinite
         // matrix factors and the solves go on with the signed factor; only a pivot that is exactly zero is a failure
@@ -524,6 +576,7 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
         // the host CSC is authoritative: its values go up (nnz doubles) and are scattered over the zeroed dense device
         // matrix, which is then factored like the dense operator's
         if (hipMemsetAsync(l->Mdev, 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+        pv->bytes_h2d += (int64_t) sizeof(double) * pv->nnz;
         if (pv->nnz > 0) {
             if (hipMemcpyAsync(pv->sp_vals, HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
                 return HDSDP_RETCODE_FAILED;
@@ -534,8 +587,12 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
         l->srcHost = nullptr; l->srcDev = l->Mdev; l->srcLd = l->ch.npad;
     } else if (pv->mirror) {
         l->srcHost = HKKT->kktMatElem; l->srcDev = nullptr; l->srcLd = HKKT->nRow;
+        pv->bytes_h2d += (int64_t) sizeof(double) * HKKT->nRow * HKKT->nRow;    // (load_host, or the pivoted solver's load)
     } else {
+        // device M plus the diagonal channel: added in place, so the Cholesky, the permuted load and the pivoted solver
+        // (lin_factor_indef reads srcDev) all see the same matrix
         if (!pv->Mdev_valid) return HDSDP_RETCODE_FAILED;
+        if (!pv->chan_folded && kkt_diag_pass(HKKT, pv, true, false, 0.0, nullptr) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
         l->srcHost = nullptr; l->srcDev = l->Mdev; l->srcLd = l->ch.npad;
     }
     if (l->indef) return lin_factor_indef(l);     // switched earlier: stays switched (hdsdp_linsolver.c:1838)
@@ -573,42 +630,15 @@ hdsdp_retcode HKKTSolve(hdsdp_kkt *HKKT, double *dRhsVec, double *dLhsVec) {
 void HKKTRegularize(hdsdp_kkt *HKKT, double dKKTReg) {  // hdsdp_schur.c:348-373
     MiKKTPriv *pv = priv_of(HKKT);
     if (!pv->mirror) {
-        // device-resident M (HMiKKTSetHostMirror(.., 0)): same rule on the device copy; the diagonal (m doubles)
-        // makes the round trip, the matrix does not
-        MiLin *l = (MiLin *) HKKT->kktM->chol;
-        if (l->bsp) {
-            // tile form: the pattern's values make the round trip (nnz doubles), the rule runs on the diagonal entries (the first of
-            // every column), and they go back into the accumulation store
-            if (!pv->Mdev_valid || pv->nnz <= 0) return;
-            const int m = HKKT->nRow;
-            std::vector<double> v((size_t) pv->nnz);
-            hipLaunchKernelGGL(mi_csc_gather_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, l->bsp->view_M(),
-                               pv->sp_rows, pv->sp_cols, pv->nnz, pv->sp_vals);
-            if (hipMemcpyAsync(v.data(), pv->sp_vals, sizeof(double) * v.size(), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
-                hipStreamSynchronize(g.stream) != hipSuccess) return;
-            double mn = INFINITY;
-            for (int i = 0; i < m; ++i) mn = std::min(mn, v[HKKT->kktMatBeg[i]]);
-            const double reg = std::min(dKKTReg * mn, 1e-05);
-            if (reg < 1e-14) return;
-            for (int i = 0; i < m; ++i) v[HKKT->kktMatBeg[i]] += reg;
-            if (hipMemcpyAsync(pv->sp_vals, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, g.stream) != hipSuccess) return;
-            hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, l->bsp->view_M(),
-                               pv->sp_rows, pv->sp_cols, pv->nnz, pv->sp_vals);
-            (void) hipStreamSynchronize(g.stream);      // v is read by an asynchronous copy
-            return;
-        }
-        if (!pv->Mdev_valid || !l->Mdev) return;
-        const int m = HKKT->nRow;
-        const size_t pitch = sizeof(double) * ((size_t) l->ch.npad + 1);
-        std::vector<double> d(m);
-        if (hipStreamSynchronize(g.stream) != hipSuccess) return;
-        if (hipMemcpy2D(d.data(), sizeof(double), l->Mdev, pitch, sizeof(double), m, hipMemcpyDeviceToHost) != hipSuccess) return;
+        // device-resident M (HMiKKTSetHostMirror(.., 0)): the same rule on the device matrix's diagonal plus the channel.  The
+        // first call after a build adds the channel in place; every call then adds its regularisation on top, so the entries
+        // are ((M_ii + channel_i) + reg1) + reg2 ..., the host mirror's order.  No part of M crosses the bus.
+        if (!pv->Mdev_valid) return;
         double mn = INFINITY;
-        for (int i = 0; i < m; ++i) mn = std::min(mn, d[i]);
-        double reg = std::min(dKKTReg * mn, 1e-05);
+        if (kkt_diag_pass(HKKT, pv, !pv->chan_folded, false, 0.0, &mn) != HDSDP_RETCODE_OK) return;
+        const double reg = std::min(dKKTReg * mn, 1e-05);
         if (reg < 1e-14) return;
-        for (int i = 0; i < m; ++i) d[i] += reg;
-        (void) hipMemcpy2D(l->Mdev, pitch, d.data(), sizeof(double), sizeof(double), m, hipMemcpyHostToDevice);
+        (void) kkt_diag_pass(HKKT, pv, false, true, reg, nullptr);
         return;
     }
     double mn = INFINITY;
@@ -647,6 +677,17 @@ void HMiKKTSetHostMirror(hdsdp_kkt *HKKT, int mirrorM) {
         return;
     }
     pv->mirror = mirrorM;
+    kkt_point_diag(HKKT, pv);
+}
+int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
+    MiKKTPriv *pv = priv_of(HKKT);
+    if (!HKKT->kktDiag || !pv->chan) return -1;
+    return pv->mirror ? 0 : 1;
+}
+void HMiKKTGetMatrixTraffic(hdsdp_kkt *HKKT, int64_t *bytesToHost, int64_t *bytesToDevice) {
+    const MiKKTPriv *pv = priv_of(HKKT);
+    if (bytesToHost) *bytesToHost = pv->bytes_d2h;
+    if (bytesToDevice) *bytesToDevice = pv->bytes_h2d;
 }
 void HMiConeSetExchangePieces(hdsdp_cone *cone, hmi_alltoall_piece_fn start, hmi_alltoall_wait_fn wait, int npieces) {
     MiCone *c = cone_data(cone);
@@ -716,6 +757,7 @@ hdsdp_retcode HMiKKTGetRows(hdsdp_kkt *HKKT, int nRows, const int *rows, double 
     hdsdp_retcode rc = HDSDP_RETCODE_OK;
     for (int r = 0; r < nRows && rc == HDSDP_RETCODE_OK; ++r) {
         if (rows[r] < 0 || rows[r] >= m) { rc = HDSDP_RETCODE_FAILED; break; }
+        pv->bytes_d2h += (int64_t) sizeof(double) * m;
         hipLaunchKernelGGL(mi_get_row_kernel, dim3((m + 255) / 256), dim3(256), 0, g.stream, kkt_view(HKKT), rows[r], m, tmp);
         if (hipMemcpyAsync(out + (size_t) r * m, tmp, sizeof(double) * (size_t) m, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
             hipStreamSynchronize(g.stream) != hipSuccess) rc = HDSDP_RETCODE_FAILED;

@@ -335,6 +335,16 @@ int HMiConeUseSweepCopy(hdsdp_cone *cone, int on);
  * HBM, these keep M on the device between BuildUp / Factorize / Solve (no PCIe round trip of M).  */
 void HMiKKTSetHostMirror(hdsdp_kkt *HKKT, int mirrorM);   /* default 1: kktMatElem is refreshed after BuildUp; with 0
                                                               HKKTRegularize / Factorize / Solve act on the device copy */
+/* The diagonal channel.  With the mirror off, kktDiag[i] points into a pinned m-vector instead of
+ * kktMatElem: host cones handed to HKKTBuildUpExtraCone (the driver's bound cone on y) add their diagonal terms there.  A
+ * build (not KKT_TYPE_CORRECTOR) zeroes it; the first HKKTRegularize or HKKTFactorize after the build uploads it (8 m bytes)
+ * and adds it to the device matrix's diagonal, and HKKTRegularize takes its minimum over M_ii + channel_i, so the factor
+ * input is (M_ii + channel_i) + reg, bit for bit the host mirror's.  Host cones that write M off the diagonal need the mirror.
+ * HMiKKTGetDiagTarget: 0 = kktDiag points into kktMatElem (mirror on), 1 = into the channel, -1 = operator not initialised. */
+int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT);
+/* bytes of M (and of the channel) moved between host and device since HKKTInit: the mirror's copy after a build, its upload
+ * for a factorisation, the channel's uploads, rows read by HMiKKTGetRows.  The operator's vectors and scalars are not counted. */
+void HMiKKTGetMatrixTraffic(hdsdp_kkt *HKKT, int64_t *bytesToHost, int64_t *bytesToDevice);
 /* multi-GPU (world > 1): constraint rows are sharded (row i on rank i % world).  Each rank congruence-
  * transforms its own rows, a transpose (all-to-all) re-shards the transformed data from "by constraint"
  * to "by packed-index range", each rank forms the Gram partial sum over its range, and an all-reduce
@@ -508,6 +518,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           Gram correction (route 1); 0: row-by-row fallback / refusal
  *  HDSDP_MI355X_STREAM_A          by memory 0 / 1: synthetic constraint data resident / regenerated per     test_gpu_streamed.py
  *                                           batch (MiCone::streamed)
+ *  HDSDP_MI355X_DEVICE_M          0         1: HKKTInit turns the host mirror of M off when no cone of    test_gpu_device_m.py
+ *                                           cones[] is a host cone (diagonal channel); else one stderr line
  *  HDM_TCAP_GIB                   32        GiB of congruence intermediates per launch group              test_gpu_switches.py, test_gpu_group.py
  *  HDM_BC                         1024      constraints per congruence launch (upper bound)               test_gpu_switches.py
  *  HDM_NSPLIT                     by size   slabs of the Gram product's K splits                          test_gpu_switches.py
