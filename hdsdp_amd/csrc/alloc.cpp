@@ -1,5 +1,4 @@
 // alloc.cpp -- the engine's one way to device memory (hdm_common.h: hdm_malloc).
-#define HDM_MALLOC_IMPL       // this translation unit calls the runtime's own hipMalloc
 #include "hdm_common.h"
 
 hipError_t hdm_malloc(void **p, size_t bytes) {

@@ -37,20 +37,20 @@ struct HdmBsp {
     std::vector<int> bptr, brow;      // block pattern of L, lower incl. diagonal, by block column (host); tile number = position
     std::vector<int> lvl_ptr, lvl_tgt_ptr, lvl_pan_ptr;   // per level: block columns, update targets, panel tiles
     // device
-    int *perm_dev = nullptr, *tilemap = nullptr;
-    double *Mval = nullptr, *Lval = nullptr, *Winv = nullptr;   // (ntiles + 1) tiles each; nb inverted diagonal tiles
-    int *lvl_cols = nullptr;          // block columns ordered by level
-    int *tgt_tile = nullptr, *tgt_src_ptr = nullptr;   // update targets (ordered by level) and their source lists
-    int2 *src = nullptr;              // (tile (i, j), tile (k, j)) pairs: target (i, k) -= L(i, j) L(k, j)^T
-    int2 *pan = nullptr;              // (tile (i, k), k): L(i, k) <- A(i, k) W_k^T
-    int *row_ptr = nullptr, *row_col = nullptr, *row_tile = nullptr;   // strictly lower tiles by block row (forward substitution)
-    int *col_ptr = nullptr, *col_row = nullptr, *col_tile = nullptr;   // ... by block column (backward substitution)
-    int *diag_tile = nullptr;
-    double *vec = nullptr;            // nb * 128 solve vector
-    double *hvec = nullptr;           // pinned host staging of the same size
-    int *info_dev = nullptr;          // two words: first zero pivot + 1, negative pivots
-    double *sgn = nullptr;            // nb * 128 pivot signs of the last factorisation (+1 in the padding)
-    int *src_col = nullptr;           // block column of every source pair (whose signs the update applies)
+    HdmBuf<int> perm_dev, tilemap;
+    HdmBuf<double> Mval, Lval, Winv;   // (ntiles + 1) tiles each; nb inverted diagonal tiles
+    HdmBuf<int> lvl_cols;             // block columns ordered by level
+    HdmBuf<int> tgt_tile, tgt_src_ptr;   // update targets (ordered by level) and their source lists
+    HdmBuf<int2> src;                 // (tile (i, j), tile (k, j)) pairs: target (i, k) -= L(i, j) L(k, j)^T
+    HdmBuf<int2> pan;                 // (tile (i, k), k): L(i, k) <- A(i, k) W_k^T
+    HdmBuf<int> row_ptr, row_col, row_tile;   // strictly lower tiles by block row (forward substitution)
+    HdmBuf<int> col_ptr, col_row, col_tile;   // ... by block column (backward substitution)
+    HdmBuf<int> diag_tile;
+    HdmBuf<double> vec;               // nb * 128 solve vector
+    HdmPinned<double> hvec;           // pinned host staging of the same size
+    HdmBuf<int> info_dev;             // two words: first zero pivot + 1, negative pivots
+    HdmBuf<double> sgn;               // nb * 128 pivot signs of the last factorisation (+1 in the padding)
+    HdmBuf<int> src_col;              // block column of every source pair (whose signs the update applies)
     bool factored = false;
     int negative = 0;                 // negative pivots of the last factorisation (0: the matrix is positive definite)
     long dense_tiles() const { return (long) nb * (nb + 1) / 2; }
@@ -59,7 +59,6 @@ struct HdmBsp {
     // symbolic phase from the lower-triangular CSC pattern (host).  Returns 0, or 1 when the tile form would not pay
     // (`max_fraction` of the dense lower triangle's tiles) or cannot be built.
     int init(int m, const int *beg, const int *idx, double max_fraction);
-    void destroy();
     HdmMatView view_M() const;        // the accumulation store the builders write
     HdmMatView view_L() const;        // the factor store (values scattered from the host CSC land here)
     int zero_M(hipStream_t s);

@@ -191,9 +191,9 @@ __global__ void bs_pad_diag_kernel(double *L, const int *diag_tile, int nb, int 
 // ---------------------------------------------------------------------------------------------------------------------
 // host: symbolic phase
 // ---------------------------------------------------------------------------------------------------------------------
-template <class T> static int bs_upload(T **dev, const std::vector<T> &h) {
-    HDM_HIP_CHECK(hipMalloc((void **) dev, sizeof(T) * std::max<size_t>(1, h.size())));
-    if (!h.empty()) HDM_HIP_CHECK(hdm_memcpy_h2d_sync(*dev, h.data(), sizeof(T) * h.size()));
+template <class T> static int bs_upload(HdmBuf<T> &dev, const std::vector<T> &h) {
+    HDM_HIP_CHECK(dev.alloc(std::max<size_t>(1, h.size())));
+    if (!h.empty()) HDM_HIP_CHECK(hdm_memcpy_h2d_sync(dev.get(), h.data(), sizeof(T) * h.size()));
     return 0;
 }
 
@@ -312,47 +312,35 @@ int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
         cp[k + 1] = (int) cr.size();
     }
     // ---- device side
-    if (bs_upload(&perm_dev, perm) || bs_upload(&tilemap, tmap) || bs_upload(&lvl_cols, cols_by_level) || bs_upload(&tgt_tile, h_tgt) ||
-        bs_upload(&tgt_src_ptr, h_tsp) || bs_upload(&src, h_src) || bs_upload(&src_col, h_scol) || bs_upload(&pan, h_pan) || bs_upload(&row_ptr, rp) ||
-        bs_upload(&row_col, rc) || bs_upload(&row_tile, rt) || bs_upload(&col_ptr, cp) || bs_upload(&col_row, cr) ||
-        bs_upload(&col_tile, ct) || bs_upload(&diag_tile, diag))
+    if (bs_upload(perm_dev, perm) || bs_upload(tilemap, tmap) || bs_upload(lvl_cols, cols_by_level) || bs_upload(tgt_tile, h_tgt) ||
+        bs_upload(tgt_src_ptr, h_tsp) || bs_upload(src, h_src) || bs_upload(src_col, h_scol) || bs_upload(pan, h_pan) || bs_upload(row_ptr, rp) ||
+        bs_upload(row_col, rc) || bs_upload(row_tile, rt) || bs_upload(col_ptr, cp) || bs_upload(col_row, cr) ||
+        bs_upload(col_tile, ct) || bs_upload(diag_tile, diag))
         return 1;
     const size_t tb = sizeof(double) * BTT * ((size_t) ntiles + 1);
-    if (hipMalloc((void **) &Mval, tb) != hipSuccess || hipMalloc((void **) &Lval, tb) != hipSuccess ||
-        hipMalloc((void **) &Winv, sizeof(double) * BTT * (size_t) nb) != hipSuccess ||
-        hipMalloc((void **) &vec, sizeof(double) * BT * (size_t) nb) != hipSuccess ||
-        hipHostMalloc((void **) &hvec, sizeof(double) * BT * (size_t) nb, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **) &sgn, sizeof(double) * BT * (size_t) nb) != hipSuccess ||
-        hipMalloc((void **) &info_dev, 2 * sizeof(int)) != hipSuccess) {
+    if (Mval.alloc(BTT * ((size_t) ntiles + 1)) != hipSuccess || Lval.alloc(BTT * ((size_t) ntiles + 1)) != hipSuccess ||
+        Winv.alloc(BTT * (size_t) nb) != hipSuccess ||
+        vec.alloc(BT * (size_t) nb) != hipSuccess ||
+        hvec.alloc(BT * (size_t) nb) != hipSuccess ||
+        sgn.alloc(BT * (size_t) nb) != hipSuccess ||
+        info_dev.alloc(2) != hipSuccess) {
         (void) hipGetLastError();
         fprintf(stderr, "[hdsdp_mi355x] block-sparse Schur matrix: out of device memory (%.1f GiB of tiles)\n", (double) bytes() / (1 << 30));
         return 1;
     }
-    HDM_HIP_CHECK(hdm_memset_sync(Mval, 0, tb));
-    HDM_HIP_CHECK(hdm_memset_sync(Lval, 0, tb));
+    HDM_HIP_CHECK(hdm_memset_sync(Mval.get(), 0, tb));
+    HDM_HIP_CHECK(hdm_memset_sync(Lval.get(), 0, tb));
     if (hdm_potrf_sweep_configure()) return 1;
     factored = false;
     return 0;
 }
 
-void HdmBsp::destroy() {
-    for (void *p : {(void *) perm_dev, (void *) tilemap, (void *) Mval, (void *) Lval, (void *) Winv, (void *) lvl_cols, (void *) tgt_tile,
-                    (void *) tgt_src_ptr, (void *) src, (void *) pan, (void *) row_ptr, (void *) row_col, (void *) row_tile, (void *) col_ptr,
-                    (void *) col_row, (void *) col_tile, (void *) diag_tile, (void *) vec, (void *) info_dev, (void *) sgn, (void *) src_col})
-        if (p) (void) hipFree(p);
-    if (hvec) (void) hipHostFree(hvec);
-    perm_dev = tilemap = lvl_cols = tgt_tile = tgt_src_ptr = row_ptr = row_col = row_tile = col_ptr = col_row = col_tile = diag_tile = info_dev = nullptr;
-    Mval = Lval = Winv = vec = hvec = sgn = nullptr;
-    src_col = nullptr;
-    src = pan = nullptr;
-}
-
-HdmMatView HdmBsp::view_M() const { HdmMatView v; v.base = Mval; v.ld = 0; v.tilemap = tilemap; v.perm = perm_dev; v.nbt = nb; v.trash = ntiles; return v; }
-HdmMatView HdmBsp::view_L() const { HdmMatView v = view_M(); v.base = Lval; return v; }
-int HdmBsp::zero_M(hipStream_t s) { HDM_HIP_CHECK(hipMemsetAsync(Mval, 0, sizeof(double) * BTT * (size_t) ntiles, s)); return 0; }
-int HdmBsp::zero_L(hipStream_t s) { HDM_HIP_CHECK(hipMemsetAsync(Lval, 0, sizeof(double) * BTT * (size_t) ntiles, s)); factored = false; return 0; }
+HdmMatView HdmBsp::view_M() const { HdmMatView v; v.base = Mval.get(); v.ld = 0; v.tilemap = tilemap.get(); v.perm = perm_dev.get(); v.nbt = nb; v.trash = ntiles; return v; }
+HdmMatView HdmBsp::view_L() const { HdmMatView v = view_M(); v.base = Lval.get(); return v; }
+int HdmBsp::zero_M(hipStream_t s) { HDM_HIP_CHECK(hipMemsetAsync(Mval.get(), 0, sizeof(double) * BTT * (size_t) ntiles, s)); return 0; }
+int HdmBsp::zero_L(hipStream_t s) { HDM_HIP_CHECK(hipMemsetAsync(Lval.get(), 0, sizeof(double) * BTT * (size_t) ntiles, s)); factored = false; return 0; }
 int HdmBsp::load_M(hipStream_t s) {
-    HDM_HIP_CHECK(hipMemcpyAsync(Lval, Mval, sizeof(double) * BTT * (size_t) ntiles, hipMemcpyDeviceToDevice, s));
+    HDM_HIP_CHECK(hipMemcpyAsync(Lval.get(), Mval.get(), sizeof(double) * BTT * (size_t) ntiles, hipMemcpyDeviceToDevice, s));
     factored = false;
     return 0;
 }
@@ -361,19 +349,19 @@ int HdmBsp::load_M(hipStream_t s) {
 // numeric factorisation and substitutions
 // ---------------------------------------------------------------------------------------------------------------------
 int HdmBsp::factor(hipStream_t s, int *info_host, int *nneg_host) {
-    HDM_HIP_CHECK(hipMemsetAsync(info_dev, 0, 2 * sizeof(int), s));
-    if (m % BT) hipLaunchKernelGGL(bs_pad_diag_kernel, dim3(1), dim3(BT), 0, s, Lval, diag_tile, nb, m);
+    HDM_HIP_CHECK(hipMemsetAsync(info_dev.get(), 0, 2 * sizeof(int), s));
+    if (m % BT) hipLaunchKernelGGL(bs_pad_diag_kernel, dim3(1), dim3(BT), 0, s, Lval.get(), diag_tile.get(), nb, m);
     for (int l = 0; l < nlevels; ++l) {
         const int nt = lvl_tgt_ptr[l + 1] - lvl_tgt_ptr[l], nc = lvl_ptr[l + 1] - lvl_ptr[l], np = lvl_pan_ptr[l + 1] - lvl_pan_ptr[l];
         if (nt > 0)
-            hipLaunchKernelGGL(bs_tile_kernel<0>, dim3(nt), dim3(256), 0, s, Lval, Winv, tgt_tile, tgt_src_ptr, src, pan, lvl_tgt_ptr[l], sgn, src_col);
-        if (hdm_potrf_sweep_batched(Lval, diag_tile, lvl_cols + lvl_ptr[l], nc, Winv, info_dev, m, s, sgn)) return 1;
+            hipLaunchKernelGGL(bs_tile_kernel<0>, dim3(nt), dim3(256), 0, s, Lval.get(), Winv.get(), tgt_tile.get(), tgt_src_ptr.get(), src.get(), pan.get(), lvl_tgt_ptr[l], sgn.get(), src_col.get());
+        if (hdm_potrf_sweep_batched(Lval.get(), diag_tile.get(), lvl_cols.get() + lvl_ptr[l], nc, Winv.get(), info_dev.get(), m, s, sgn.get())) return 1;
         if (np > 0)
-            hipLaunchKernelGGL(bs_tile_kernel<1>, dim3(np), dim3(256), 0, s, Lval, Winv, tgt_tile, tgt_src_ptr, src, pan, lvl_pan_ptr[l], sgn, src_col);
+            hipLaunchKernelGGL(bs_tile_kernel<1>, dim3(np), dim3(256), 0, s, Lval.get(), Winv.get(), tgt_tile.get(), tgt_src_ptr.get(), src.get(), pan.get(), lvl_pan_ptr[l], sgn.get(), src_col.get());
     }
     HDM_HIP_CHECK(hipGetLastError());
     int info[2] = {0, 0};
-    HDM_HIP_CHECK(hipMemcpyAsync(info, info_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HDM_HIP_CHECK(hipMemcpyAsync(info, info_dev.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HDM_HIP_CHECK(hipStreamSynchronize(s));
     if (info[0] > m) info[0] = 0;
     if (info_host) *info_host = info[0];
@@ -386,19 +374,19 @@ int HdmBsp::factor(hipStream_t s, int *info_host, int *nneg_host) {
 int HdmBsp::solve_host(const double *rhs, double *sol, hipStream_t s) {
     if (!factored) return 1;
     HDM_HIP_CHECK(hipStreamSynchronize(s));                     // the staging buffer is free
-    memset(hvec, 0, sizeof(double) * BT * (size_t) nb);
-    for (int i = 0; i < m; ++i) hvec[perm[i]] = rhs[i];
-    HDM_HIP_CHECK(hipMemcpyAsync(vec, hvec, sizeof(double) * BT * (size_t) nb, hipMemcpyHostToDevice, s));
+    memset(hvec.get(), 0, sizeof(double) * BT * (size_t) nb);
+    for (int i = 0; i < m; ++i) hvec.get()[perm[i]] = rhs[i];
+    HDM_HIP_CHECK(hipMemcpyAsync(vec.get(), hvec.get(), sizeof(double) * BT * (size_t) nb, hipMemcpyHostToDevice, s));
     for (int l = 0; l < nlevels; ++l)
-        hipLaunchKernelGGL(bs_fwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval, Winv, lvl_cols, row_ptr, row_col, row_tile,
-                           vec, lvl_ptr[l]);
+        hipLaunchKernelGGL(bs_fwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval.get(), Winv.get(), lvl_cols.get(), row_ptr.get(), row_col.get(), row_tile.get(),
+                           vec.get(), lvl_ptr[l]);
     for (int l = nlevels - 1; l >= 0; --l)
-        hipLaunchKernelGGL(bs_bwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval, Winv, lvl_cols, col_ptr, col_row, col_tile,
-                           vec, lvl_ptr[l], sgn);
+        hipLaunchKernelGGL(bs_bwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval.get(), Winv.get(), lvl_cols.get(), col_ptr.get(), col_row.get(), col_tile.get(),
+                           vec.get(), lvl_ptr[l], sgn.get());
     HDM_HIP_CHECK(hipGetLastError());
-    HDM_HIP_CHECK(hipMemcpyAsync(hvec, vec, sizeof(double) * BT * (size_t) nb, hipMemcpyDeviceToHost, s));
+    HDM_HIP_CHECK(hipMemcpyAsync(hvec.get(), vec.get(), sizeof(double) * BT * (size_t) nb, hipMemcpyDeviceToHost, s));
     HDM_HIP_CHECK(hipStreamSynchronize(s));
-    for (int i = 0; i < m; ++i) sol[i] = hvec[perm[i]];
+    for (int i = 0; i < m; ++i) sol[i] = hvec.get()[perm[i]];
     return 0;
 }
 

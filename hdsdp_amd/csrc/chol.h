@@ -5,13 +5,13 @@
 
 struct HdmChol {
     int n = 0, npad = 0, nblk = 0;
-    double *L = nullptr;     // npad x npad, column-major; lower triangle = Cholesky factor after factor()
-    double *Linv = nullptr;  // npad x npad, lower triangular inverse (explicit zeros above the diagonal)
-    double *Dinv = nullptr;  // nblk x (128 x 128) inverted diagonal blocks
-    double *Z = nullptr;     // npad x 128 scratch for invert_factor
-    double *Zd = nullptr;    // npad x npad scratch for the recursive-doubling variant of invert_factor
-    double *vec = nullptr;   // 4 * npad scratch vectors
-    int *info_dev = nullptr;
+    HdmBuf<double> L;        // npad x npad, column-major; lower triangle = Cholesky factor after factor()
+    HdmBuf<double> Linv;     // npad x npad, lower triangular inverse (explicit zeros above the diagonal)
+    HdmBuf<double> Dinv;     // nblk x (128 x 128) inverted diagonal blocks
+    HdmBuf<double> Z;        // npad x 128 scratch for invert_factor
+    HdmBuf<double> Zd;       // npad x npad scratch for the recursive-doubling variant of invert_factor
+    HdmBuf<double> vec;      // 4 * npad scratch vectors
+    HdmBuf<int> info_dev;
     bool factored = false, have_inv = false;
     bool logdet_ok = false;  // log det of the factored matrix is known (single-launch small-block check): 2 sum log L_kk
     double logdet_val = 0.0;
@@ -24,8 +24,8 @@ struct HdmChol {
     int nsolves = 0, factor_runs = 0, solve_runs = 0;
     bool graphs_ok = true;
     // single-launch block substitution (hdm_trsv_flow_kernel): per (rhs, direction, block) publication flags + error word
-    int *flow_flags = nullptr;
-    int *flow_err = nullptr;     // mapped host word: a workgroup gave up waiting
+    HdmBuf<int> flow_flags;
+    HdmPinned<int> flow_err;     // mapped host word: a workgroup gave up waiting
     int flow_epoch = 0;
     bool flow_ok = true, flow_pending = false;
     int flow_cap = -1;           // co-residency bound on this object's device (workgroups), computed at the first solve
@@ -35,14 +35,15 @@ struct HdmChol {
     // A Cholesky factor fills inside the row envelope only, so the factorisation's panel and trailing update of block column k
     // stop at row env_colh[k] and the substitutions skip the blocks outside.  Empty = dense.
     std::vector<int> env_first, env_colh;
-    int *env_dev = nullptr;      // device copy: first[nblk], then colh[nblk]
+    HdmBuf<int> env_dev;         // device copy: first[nblk], then colh[nblk]
     // factor_signed (KKT_TYPE_PRIMAL with an indefinite X): the pivot signs and two info words of the last signed factorisation
-    double *sgn = nullptr;       // npad: sign of pivot k (+1 in the identity padding)
-    int *sinfo_dev = nullptr;    // [0] first zero / non-finite pivot + 1, [1] negative pivots
+    HdmBuf<double> sgn;          // npad: sign of pivot k (+1 in the identity padding)
+    HdmBuf<int> sinfo_dev;       // [0] first zero / non-finite pivot + 1, [1] negative pivots
 
     int init(int n);
     int set_envelope(const int *first_blockcol_of_blockrow);   // nblk entries; nullptr = dense.  Before the first factor().
     void destroy();
+    ~HdmChol() { destroy(); }
     int load_host(const double *A, long lda, hipStream_t s);
     int load_device(const double *A, long lda, hipStream_t s);
     int finish_load(hipStream_t s);

@@ -167,14 +167,14 @@ hdsdp_retcode HMiPresolveCSC(int nRow, int nCol, const int *coneMatBeg, const in
 hdsdp_retcode HMiConeGetDualMatrix(hdsdp_cone *cone, double *S) {
     MiCone *c = cone_data(cone);
     if (!c) return HDSDP_RETCODE_FAILED;
-    if (hipMemcpy2DAsync(S, sizeof(double) * c->n, c->S, sizeof(double) * c->n16, sizeof(double) * c->n, c->n,
+    if (hipMemcpy2DAsync(S, sizeof(double) * c->n, c->S.get(), sizeof(double) * c->n16, sizeof(double) * c->n, c->n,
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     return hipStreamSynchronize(g.stream) == hipSuccess ? HDSDP_RETCODE_OK : HDSDP_RETCODE_FAILED;
 }
 hdsdp_retcode HMiConeGetTraces(hdsdp_cone *cone, double *trA) {
     MiCone *c = cone_data(cone);
-    if (!c || !c->trA) return HDSDP_RETCODE_FAILED;
-    memcpy(trA, c->trA, sizeof(double) * c->m);
+    if (!c || c->trA.empty()) return HDSDP_RETCODE_FAILED;
+    memcpy(trA, c->trA.data(), sizeof(double) * c->m);
     return HDSDP_RETCODE_OK;
 }
 int HMiConeGetPath(hdsdp_cone *cone) { const MiCone *c = cone_data(cone); return c ? c->path : -1; }
@@ -277,19 +277,18 @@ static int small_plan(MiCone *c) {
     }
     dense_rows.resize(SMALL_NDENSE, 0);
     const size_t nf = std::max<size_t>(1, fi.size());
-    if (hipMalloc((void **) &sp.fp, sizeof(int) * (m + 1)) != hipSuccess || hipMalloc((void **) &sp.fi, sizeof(int) * nf) != hipSuccess ||
-        hipMalloc((void **) &sp.fv, sizeof(double) * nf) != hipSuccess || hipMalloc((void **) &sp.sgn, sizeof(double) * m) != hipSuccess ||
-        hipMalloc((void **) &sp.dense_of, sizeof(int) * m) != hipSuccess ||
-        hipMalloc((void **) &sp.dense_rows, sizeof(int) * SMALL_NDENSE) != hipSuccess ||
-        hipHostMalloc((void **) &sp.io_host, sizeof(double) * (7 * (size_t) m + 16), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **) &sp.io_dev, sp.io_host, 0) != hipSuccess)
+    if (sp.fp.alloc(m + 1) != hipSuccess || sp.fi.alloc(nf) != hipSuccess ||
+        sp.fv.alloc(nf) != hipSuccess || sp.sgn.alloc(m) != hipSuccess ||
+        sp.dense_of.alloc(m) != hipSuccess ||
+        sp.dense_rows.alloc(SMALL_NDENSE) != hipSuccess ||
+        sp.io.alloc(7 * (size_t) m + 16, hipHostMallocMapped) != hipSuccess)
         return -1;
-    if (hdm_memcpy_h2d_sync(sp.fp, fp.data(), sizeof(int) * (m + 1)) != hipSuccess ||
-        (fi.size() && (hdm_memcpy_h2d_sync(sp.fi, fi.data(), sizeof(int) * fi.size()) != hipSuccess ||
-                       hdm_memcpy_h2d_sync(sp.fv, fv.data(), sizeof(double) * fv.size()) != hipSuccess)) ||
-        hdm_memcpy_h2d_sync(sp.sgn, sg.data(), sizeof(double) * m) != hipSuccess ||
-        hdm_memcpy_h2d_sync(sp.dense_of, dense_of.data(), sizeof(int) * m) != hipSuccess ||
-        hdm_memcpy_h2d_sync(sp.dense_rows, dense_rows.data(), sizeof(int) * SMALL_NDENSE) != hipSuccess)
+    if (hdm_memcpy_h2d_sync(sp.fp.get(), fp.data(), sizeof(int) * (m + 1)) != hipSuccess ||
+        (fi.size() && (hdm_memcpy_h2d_sync(sp.fi.get(), fi.data(), sizeof(int) * fi.size()) != hipSuccess ||
+                       hdm_memcpy_h2d_sync(sp.fv.get(), fv.data(), sizeof(double) * fv.size()) != hipSuccess)) ||
+        hdm_memcpy_h2d_sync(sp.sgn.get(), sg.data(), sizeof(double) * m) != hipSuccess ||
+        hdm_memcpy_h2d_sync(sp.dense_of.get(), dense_of.data(), sizeof(int) * m) != hipSuccess ||
+        hdm_memcpy_h2d_sync(sp.dense_rows.get(), dense_rows.data(), sizeof(int) * SMALL_NDENSE) != hipSuccess)
         return -1;
     sp.ndense = 0;
     for (int q = 0; q < m; ++q) sp.ndense += (dense_of[q] >= 0);
@@ -315,26 +314,26 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
     MiLin *ls = (MiLin *) c->dualFactor->chol, *lm = (MiLin *) HKKT->kktM->chol;
     const int m = c->m, n = c->n;
     HIP_RC(hipStreamSynchronize(g.stream));            // the mapped block is about to be rewritten
-    double *yin = sp.io_host, *bin = sp.io_host + m, *out = sp.io_host + 2 * (size_t) m;
+    double *yin = sp.io.get(), *bin = sp.io.get() + m, *out = sp.io.get() + 2 * (size_t) m;
     for (int i = 0; i < m; ++i) { yin[i] = rowDual ? rowDual[i] : 0.0; bin[i] = rhs ? rhs[i] : 0.0; }
     out[0] = -1.0;
     HdmSmallArgs a = {};
-    a.n = n; a.m = m; a.C = c->Cfull; a.ldc = c->n16;
-    a.fp = sp.fp; a.fi = sp.fi; a.fv = sp.fv; a.sgn = sp.sgn; a.dense_of = sp.dense_of; a.ndense = sp.ndense; a.dense_rows = sp.dense_rows;
-    a.y = sp.io_dev; a.b = sp.io_dev + m; a.out = sp.io_dev + 2 * (size_t) m;
+    a.n = n; a.m = m; a.C = c->Cfull.get(); a.ldc = c->n16;
+    a.fp = sp.fp.get(); a.fi = sp.fi.get(); a.fv = sp.fv.get(); a.sgn = sp.sgn.get(); a.dense_of = sp.dense_of.get(); a.ndense = sp.ndense; a.dense_rows = sp.dense_rows.get();
+    a.y = sp.io.dev(); a.b = sp.io.dev() + m; a.out = sp.io.dev() + 2 * (size_t) m;
     a.tau = barHsdTau; a.eye = -c->Rd + c->perturb; a.Rd = c->Rd;
-    a.Sout = c->S; a.lds = c->n16;
+    a.Sout = c->S.get(); a.lds = c->n16;
     c->pS_ok = false;                                  // (the pass writes S itself)
-    a.LS = ls->ch.L; a.WS = ls->ch.Dinv; a.M = lm->Mdev; a.ldm = lm->ch.npad; a.LM = lm->ch.L; a.WM = lm->ch.Dinv;
+    a.LS = ls->ch.L.get(); a.WS = ls->ch.Dinv.get(); a.M = lm->Mdev.get(); a.ldm = lm->ch.npad; a.LM = lm->ch.L.get(); a.WM = lm->ch.Dinv.get();
     if (ls->ch.npad != SMALL_P || lm->ch.npad != SMALL_P) return HDSDP_RETCODE_FAILED;
     // (the operator's accumulators as HKKTBuildUp(KKT_TYPE_INFEASIBLE) leaves them, hdsdp_schur.c:141-165, :256-268: the
     // kernel itself zeroes what it does not fill of the 128 x 128 device matrix)
     // (as kkt_clean: the build starts an empty diagonal channel -- the stream is idle, the pinned channel is free to write)
-    memset(pv->chan, 0, sizeof(double) * (size_t) m);
+    memset(pv->chan.get(), 0, sizeof(double) * (size_t) m);
     pv->chan_folded = false;
     RC(hdm_small_phase_a(a, g.stream));
     if (pv->mirror) {
-        HIP_RC(hipMemcpy2DAsync(HKKT->kktMatElem, sizeof(double) * m, lm->Mdev, sizeof(double) * SMALL_P, sizeof(double) * m, m,
+        HIP_RC(hipMemcpy2DAsync(HKKT->kktMatElem, sizeof(double) * m, lm->Mdev.get(), sizeof(double) * SMALL_P, sizeof(double) * m, m,
                                 hipMemcpyDeviceToHost, g.stream));
         pv->bytes_d2h += (int64_t) sizeof(double) * m * m;
     }
@@ -350,7 +349,7 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
     HKKT->dTraceSinv = (c->Rd != 0.0) ? out[3] : 0.0;
     pv->Mdev_valid = true;
     lm->ch.factored = (infoM == 0); lm->ch.have_inv = false;
-    lm->srcHost = nullptr; lm->srcDev = lm->Mdev; lm->srcLd = SMALL_P;
+    lm->srcHost = nullptr; lm->srcDev = lm->Mdev.get(); lm->srcLd = SMALL_P;
     HKKT->kktM->nFactorizes += 1;
     if (infoM != 0) {
         // the Schur matrix is not numerically positive definite: the multi-launch path's way out (pivoted solver) takes over
@@ -407,19 +406,19 @@ int HMiBspSolve(int m, const int *colBeg, const int *rowIdx, const double *val, 
     if (ensure_ctx()) return 1;
     HdmBsp bs;
     int rc = 1;
-    int *rows_d = nullptr, *cols_d = nullptr;
-    double *vals_d = nullptr;
+    HdmBuf<int> rows_d, cols_d;   // (declared after bs: freed before it, as ever)
+    HdmBuf<double> vals_d;
     do {
         if (bs.init(m, colBeg, rowIdx, 1.0)) break;
         const long nnz = colBeg[m];
         std::vector<int> cols((size_t) nnz);
         for (int c = 0; c < m; ++c) for (int q = colBeg[c]; q < colBeg[c + 1]; ++q) cols[q] = c;
-        if (hipMalloc((void **) &rows_d, sizeof(int) * nnz) != hipSuccess || hipMalloc((void **) &cols_d, sizeof(int) * nnz) != hipSuccess ||
-            hipMalloc((void **) &vals_d, sizeof(double) * nnz) != hipSuccess) break;
-        if (hipMemcpy(rows_d, rowIdx, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(cols_d, cols.data(), sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(vals_d, val, sizeof(double) * nnz, hipMemcpyHostToDevice) != hipSuccess) break;
-        hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((nnz + 255) / 256)), dim3(256), 0, g.stream, bs.view_M(), rows_d, cols_d, nnz, vals_d);
+        if (rows_d.alloc(nnz) != hipSuccess || cols_d.alloc(nnz) != hipSuccess ||
+            vals_d.alloc(nnz) != hipSuccess) break;
+        if (hipMemcpy(rows_d.get(), rowIdx, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(cols_d.get(), cols.data(), sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(vals_d.get(), val, sizeof(double) * nnz, hipMemcpyHostToDevice) != hipSuccess) break;
+        hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((nnz + 255) / 256)), dim3(256), 0, g.stream, bs.view_M(), rows_d.get(), cols_d.get(), nnz, vals_d.get());
         int inf = 0;
         const int reps = ms ? 3 : 1;
         float best = 1e30f;
@@ -441,10 +440,6 @@ int HMiBspSolve(int m, const int *colBeg, const int *rowIdx, const double *val, 
         if (inf == 0 && b && x && bs.solve_host(b, x, g.stream)) break;
         rc = 0;
     } while (0);
-    if (rows_d) (void) hipFree(rows_d);
-    if (cols_d) (void) hipFree(cols_d);
-    if (vals_d) (void) hipFree(vals_d);
-    bs.destroy();
     return rc;
 }
 void HMiKKTEnvelopeInfo(hdsdp_kkt *HKKT, int *permuted, double *fraction) {

@@ -30,23 +30,23 @@ int congruence_rows(MiCone *c, HdmChol &ch, const double *Asrc, long astride, lo
     for (int b0 = 0; b0 < count; b0 += c->Bc) {
         const int nb = std::min(c->Bc, count - b0);
         HdmGemmArgs k1 = {};
-        k1.A = ch.Linv; k1.lda = ch.npad; k1.strideA = 0;
+        k1.A = ch.Linv.get(); k1.lda = ch.npad; k1.strideA = 0;
         k1.B = Asrc + (long) b0 * astride; k1.ldb = c->n16; k1.strideB = astride; k1.b_kmajor = 1; k1.b_sky = 1;
-        k1.C = c->T; k1.ldc = c->n16; k1.strideC = nn;
+        k1.C = c->T.get(); k1.ldc = c->n16; k1.strideC = nn;
         k1.M = c->n16; k1.N = c->n16; k1.K = c->n16; k1.batch = nb; k1.alpha = 1.0;
         k1.klimit = HDM_KLIM_BAND; k1.lower_only = 1; k1.epilogue = HDM_EPI_STORE; k1.role = HDM_ROLE_CONG1;
         k1.flops = (double) nb * n3 / 3.0;
         const long linv_span = (long) ch.npad * ch.npad;
         const long t_span = nn * c->Bc + (long) (hdm_operand_pad(c->n16) / sizeof(double));
         k1.spanA = linv_span; k1.spanB = asrc_span - (long) b0 * astride;
-        if (phase != 2 && c->shared_ts && hdm_zero_diag_upper(c->T, nn, c->n16, nb, g.stream)) return 1;
+        if (phase != 2 && c->shared_ts && hdm_zero_diag_upper(c->T.get(), nn, c->n16, nb, g.stream)) return 1;
         if (phase != 2 && hdm_launch_gemm(k1, g.stream)) return 1;
         if (phase == 1) continue;
         HdmGemmArgs k2 = {};
-        k2.A = c->T; k2.lda = c->n16; k2.strideA = nn;
-        k2.B = ch.Linv; k2.ldb = ch.npad; k2.strideB = 0;
-        k2.A2 = ch.Linv; k2.lda2 = ch.npad; k2.strideA2 = 0;
-        k2.B2 = c->T; k2.ldb2 = c->n16; k2.strideB2 = nn;
+        k2.A = c->T.get(); k2.lda = c->n16; k2.strideA = nn;
+        k2.B = ch.Linv.get(); k2.ldb = ch.npad; k2.strideB = 0;
+        k2.A2 = ch.Linv.get(); k2.lda2 = ch.npad; k2.strideA2 = 0;
+        k2.B2 = c->T.get(); k2.ldb2 = c->n16; k2.strideB2 = nn;
         k2.C = c->AhatLoc; k2.M = c->n16; k2.N = c->n16; k2.K = c->n16; k2.batch = nb; k2.alpha = 1.0;
         k2.klimit = HDM_KLIM_BY_N; k2.lower_only = 1; k2.epilogue = HDM_EPI_BLOCKED;
         k2.blk_row_stride = c->Lr; k2.blk_row0 = row0 + b0; k2.nblk = c->nblk; k2.role = HDM_ROLE_CONG2;
@@ -96,7 +96,7 @@ int gram_range(MiCone *c, int z0, int nz, bool fresh) {
     return 0;
 }
 int gram_reduce(MiCone *c) {
-    return hdm_slab_reduce(c->slabs, c->R * c->R, c->slabs_used, c->Gm, c->R * c->R, c->R, g.stream);
+    return hdm_slab_reduce(c->slabs, c->R * c->R, c->slabs_used, c->Gm.get(), c->R * c->R, c->R, g.stream);
 }
 int gram_all(MiCone *c) {
     // Gm(lower) = sum over this rank's p-range of Ahat * Ahat^T, rows in segment order (more splits than slabs:
@@ -246,30 +246,22 @@ int signed_correction(MiCone *c) {
     c->primal_cols = ncols;
     if (ncols == 0) {
         if (use_neg) return 0;                                        // no column of weight -1 here: G is already signed
-        hipLaunchKernelGGL(mi_psig_combine_kernel, dim3((unsigned) ((R * R + 255) / 256)), dim3(256), 0, g.stream, c->Gm,
+        hipLaunchKernelGGL(mi_psig_combine_kernel, dim3((unsigned) ((R * R + 255) / 256)), dim3(256), 0, g.stream, c->Gm.get(),
                            (const double *) c->slabs, R * R, 0, R, -1.0);
         HIP_RC(hipGetLastError());
         return 0;
     }
-    if (c->pcols_cap < ncols) {
-        if (c->pcols) HIP_RC(hipFree(c->pcols));
-        c->pcols = nullptr; c->pcols_cap = 0;
-        HIP_RC(hipMalloc((void **) &c->pcols, sizeof(int) * (size_t) ncols));
-        c->pcols_cap = ncols;
-    }
-    HIP_RC(hipMemcpyAsync(c->pcols, cols.data(), sizeof(int) * (size_t) ncols, hipMemcpyHostToDevice, g.stream));
+    HIP_RC(c->pcols.reserve((size_t) ncols));
+    HIP_RC(hipMemcpyAsync(c->pcols.get(), cols.data(), sizeof(int) * (size_t) ncols, hipMemcpyHostToDevice, g.stream));
     HIP_RC(hipStreamSynchronize(g.stream));      // (pageable source going out of scope)
     const long RT = (R + HDM_TILE - 1) / HDM_TILE, tiles = RT * (RT + 1) / 2;
     const long ncols16 = hdm_roundup(ncols, 16);
     const long kc = std::min(ncols16, std::max(16L, (PSIG_GATHER_BYTES / (8 * R)) & ~15L));   // columns per chunk
     // the Gram role's tile loads carry no row mask: up to RT * 128 rows of the last k block are read
     const long need = R * kc + RT * HDM_TILE * 16 + HDM_OPERAND_PAD_DOUBLES;
-    if (c->pgat_cap < need) {
-        if (c->pgat) HIP_RC(hipFree(c->pgat));
-        c->pgat = nullptr; c->pgat_cap = 0;
-        HIP_RC(hipMalloc((void **) &c->pgat, sizeof(double) * (size_t) need));
-        HIP_RC(hipMemsetAsync(c->pgat, 0, sizeof(double) * (size_t) need, g.stream));
-        c->pgat_cap = need;
+    if (c->pgat.count() < (size_t) need) {
+        HIP_RC(c->pgat.alloc((size_t) need));
+        HIP_RC(hipMemsetAsync(c->pgat.get(), 0, sizeof(double) * (size_t) need, g.stream));
     }
     // split-K over the slabs: enough (split, tile) jobs to fill the chip, at least 8 k blocks per split
     int nz = (int) std::max(1L, std::min<long>({(long) c->nslab, (1024 + tiles - 1) / tiles, std::max(1L, kc / 16 / 8)}));
@@ -283,25 +275,25 @@ int signed_correction(MiCone *c) {
         const long tot = R * nc16;
         rc |= mark();
         hipLaunchKernelGGL(mi_psig_gather_kernel, dim3((unsigned) std::min<long>((tot + 255) / 256, 16384)), dim3(256), 0, g.stream,
-                           (const double *) c->AhatAll, seg_stride, c->Lr, R, (const int *) (c->pcols + j0), nc, nc16, pb0, c->pgat);
+                           (const double *) c->AhatAll, seg_stride, c->Lr, R, (const int *) (c->pcols.get() + j0), nc, nc16, pb0, c->pgat.get());
         if (hipGetLastError() != hipSuccess) rc = 1;
         rc |= mark();
         HdmGemmArgs gq = {};
-        gq.A = c->pgat; gq.B = c->pgat; gq.a_kmajor = 1; gq.b_kmajor = 1;
+        gq.A = c->pgat.get(); gq.B = c->pgat.get(); gq.a_kmajor = 1; gq.b_kmajor = 1;
         gq.lda = 16; gq.ldb = 16; gq.a_kblk = R * 16; gq.b_kblk = R * 16;
         gq.ldc = R; gq.M = (int) R; gq.N = (int) R; gq.K = (int) nc16;
         gq.lower_only = 1; gq.epilogue = HDM_EPI_SLAB; gq.batch = nz;
         gq.k_chunk = (nc16 / 16 + nz - 1) / nz * 16; gq.k_base = 0; gq.slab_stride = R * R;
         gq.alpha = alpha; gq.beta = (j0 == 0) ? 0.0 : 1.0; gq.role = HDM_ROLE_GRAM;
         gq.queue_global = c->gram_queue_global ? 1 : 0;
-        gq.spanA = gq.spanB = c->pgat_cap;
+        gq.spanA = gq.spanB = (long) c->pgat.count();
         gq.C = c->slabs;
         gq.flops = (double) R * (R + 1) * 0.5 * (double) nc * 2.0;
         if (!rc && hdm_launch_gemm(gq, g.stream)) rc = 1;
     }
     rc |= mark();
     if (!rc) {
-        hipLaunchKernelGGL(mi_psig_combine_kernel, dim3((unsigned) ((R * R + 255) / 256)), dim3(256), 0, g.stream, c->Gm,
+        hipLaunchKernelGGL(mi_psig_combine_kernel, dim3((unsigned) ((R * R + 255) / 256)), dim3(256), 0, g.stream, c->Gm.get(),
                            (const double *) c->slabs, R * R, nz, R, beta0);
         if (hipGetLastError() != hipSuccess) rc = 1;
     }
@@ -344,43 +336,41 @@ hdsdp_retcode build_primal_general(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, con
     long ldx = 0, ldm = 0;
     RC(cone_upload_X(c, X, &ldx));
     const size_t np2 = sizeof(double) * (size_t) ldx * ldx;
-    if (!c->Pr1) HIP_RC(hipMalloc((void **) &c->Pr1, np2));
-    if (!c->Pr2) HIP_RC(hipMalloc((void **) &c->Pr2, np2));
+    HIP_RC(c->Pr1.reserve(np2 / sizeof(double)));
+    HIP_RC(c->Pr2.reserve(np2 / sizeof(double)));
     (void) ldm;
     const HdmMatView Mview = kkt_view(kkt);
-    double *row = nullptr, *ALsq = nullptr;
-    HIP_RC(hipMalloc((void **) &row, sizeof(double) * (size_t) m));
-    HIP_RC(hipMalloc((void **) &ALsq, sizeof(double) * (size_t) c->n16 * c->n16 + hdm_operand_pad(c->n16)));
+    HdmBuf<double> row, ALsq;   // freed on every way out
+    HIP_RC(row.alloc((size_t) m));
+    HIP_RC(ALsq.alloc((size_t) c->n16 * c->n16, hdm_operand_pad(c->n16)));
     HdmGemmArgs q = {};
     q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE; q.ldc = ldx;
     // vectors: ASinv_i = <A_i, X>, ASinvRdSinv_i = Rd <A_i, X^2>   (Pr2 <- X X^T)
-    q.A = c->Xup; q.lda = ldx; q.B = c->Xup; q.ldb = ldx; q.C = c->Pr2;
+    q.A = c->Xup.get(); q.lda = ldx; q.B = c->Xup.get(); q.ldb = ldx; q.C = c->Pr2.get();
     hdsdp_retcode rc = HDSDP_RETCODE_OK;
     if (hdm_launch_gemm(q, g.stream) ||
-        cone_sym_dot2(c, c->Xup, c->Pr2, ldx, pv->vecs, pv->vecs + m, 2.0, 2.0 * c->Rd))
+        cone_sym_dot2(c, c->Xup.get(), c->Pr2.get(), ldx, pv->vecs.get(), pv->vecs.get() + m, 2.0, 2.0 * c->Rd))
         rc = HDSDP_RETCODE_FAILED;
     for (int qi = 0; qi < c->mloc && rc == HDSDP_RETCODE_OK; ++qi) {
         // this fallback multiplies with A_L as a generic operand in both orientations: unpack the row's skyline storage
         // into a square scratch matrix first
         const double *Arow = cone_rows(c, qi, 1);
-        if (!Arow || hdm_sky_to_square(Arow, ALsq, c->n16, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
-        const double *AL = ALsq;
+        if (!Arow || hdm_sky_to_square(Arow, ALsq.get(), c->n16, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
+        const double *AL = ALsq.get();
         // Pr1 = X A_L            (B operand element (j, k) = A_L(k, j): K-major)
-        q.A = c->Xup; q.lda = ldx; q.a_kmajor = 0; q.B = AL; q.ldb = c->n16; q.b_kmajor = 1; q.C = c->Pr1; q.beta = 0.0;
+        q.A = c->Xup.get(); q.lda = ldx; q.a_kmajor = 0; q.B = AL; q.ldb = c->n16; q.b_kmajor = 1; q.C = c->Pr1.get(); q.beta = 0.0;
         if (hdm_launch_gemm(q, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
         // Pr1 += X A_L^T         (B operand element (j, k) = A_L(j, k): M-major)
         q.b_kmajor = 0; q.beta = 1.0;
         if (hdm_launch_gemm(q, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
         // Pr2 = Pr1 X            (B operand element (j, k) = X(k, j): K-major)
-        q.A = c->Pr1; q.lda = ldx; q.B = c->Xup; q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr2; q.beta = 0.0;
+        q.A = c->Pr1.get(); q.lda = ldx; q.B = c->Xup.get(); q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr2.get(); q.beta = 0.0;
         if (hdm_launch_gemm(q, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
-        if (hipMemsetAsync(row, 0, sizeof(double) * (size_t) m, g.stream) != hipSuccess ||
-            cone_sym_dot2(c, c->Pr2, nullptr, ldx, row, row, 2.0, 0.0)) { rc = HDSDP_RETCODE_FAILED; break; }
-        hipLaunchKernelGGL(mi_put_row_kernel, dim3((m + 255) / 256), dim3(256), 0, g.stream, Mview, c->own[qi], row, m);
+        if (hipMemsetAsync(row.get(), 0, sizeof(double) * (size_t) m, g.stream) != hipSuccess ||
+            cone_sym_dot2(c, c->Pr2.get(), nullptr, ldx, row.get(), row.get(), 2.0, 0.0)) { rc = HDSDP_RETCODE_FAILED; break; }
+        hipLaunchKernelGGL(mi_put_row_kernel, dim3((m + 255) / 256), dim3(256), 0, g.stream, Mview, c->own[qi], row.get(), m);
     }
     if (hipStreamSynchronize(g.stream) != hipSuccess) rc = HDSDP_RETCODE_FAILED;
-    (void) hipFree(row);
-    (void) hipFree(ALsq);
     if (rc != HDSDP_RETCODE_OK) return rc;
     if (c->Rd != 0.0) {                      // dTraceSinv += tr X (hdsdp_conic_sdp.c:1767-1769)
         double tr = 0.0;
@@ -411,30 +401,30 @@ int primal_signed_factor(MiCone *c, HdmChol &ch, const double *Xr, const double 
     if (info != 0) return 0;                           // an exactly zero (or non-finite) pivot: no factor of this form exists
     if (ch.set_reverse_inverse(g.stream)) return 1;
     const long np = ch.npad;
-    if (!c->psig) HIP_RC(hipMalloc((void **) &c->psig, sizeof(double) * (size_t) np));
-    if (ch.reverse_signs(c->psig, g.stream)) return 1;
+    HIP_RC(c->psig.reserve((size_t) np));
+    if (ch.reverse_signs(c->psig.get(), g.stream)) return 1;
     long ldx = 0;
     if (cone_upload_X(c, X, &ldx)) return 1;
     if (ldx != np) { fprintf(stderr, "[hdsdp_mi355x] KKT_TYPE_PRIMAL: factor and primal matrix disagree on their padding\n"); return 1; }
     const size_t np2 = sizeof(double) * (size_t) np * np;
-    if (!c->Pr1) HIP_RC(hipMalloc((void **) &c->Pr1, np2));
-    if (!c->Pr2) HIP_RC(hipMalloc((void **) &c->Pr2, np2));
-    if (!c->pchk) HIP_RC(hipMalloc((void **) &c->pchk, sizeof(double) * (3 * MI_PSIG_BLOCKS + 8)));
+    HIP_RC(c->Pr1.reserve(np2 / sizeof(double)));
+    HIP_RC(c->Pr2.reserve(np2 / sizeof(double)));
+    HIP_RC(c->pchk.reserve(3 * MI_PSIG_BLOCKS + 8));
     // Pr1 = diag(sigma) W,  Pr2 = W^T Pr1   (A operand element (i, k) = W(k, i), B operand element (j, k) = Pr1(k, j): both K-major)
     hipLaunchKernelGGL(mi_psig_rowscale_kernel, dim3((unsigned) ((np * np + 255) / 256)), dim3(256), 0, g.stream,
-                       (const double *) ch.Linv, (const double *) c->psig, c->Pr1, np, (int) np);
+                       (const double *) ch.Linv.get(), (const double *) c->psig.get(), c->Pr1.get(), np, (int) np);
     HIP_RC(hipGetLastError());
     HdmGemmArgs q = {};
-    q.A = ch.Linv; q.lda = np; q.a_kmajor = 1; q.B = c->Pr1; q.ldb = np; q.b_kmajor = 1; q.C = c->Pr2; q.ldc = np;
+    q.A = ch.Linv.get(); q.lda = np; q.a_kmajor = 1; q.B = c->Pr1.get(); q.ldb = np; q.b_kmajor = 1; q.C = c->Pr2.get(); q.ldc = np;
     q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE;
     RC(hdm_launch_gemm(q, g.stream));
-    hipLaunchKernelGGL(mi_psig_norms_kernel, dim3(MI_PSIG_BLOCKS), dim3(256), 0, g.stream, (const double *) c->Pr2, (const double *) c->Xup,
-                       (const double *) ch.Linv, np, c->n, c->pchk);
-    hipLaunchKernelGGL(mi_psig_norms_final_kernel, dim3(1), dim3(64), 0, g.stream, (const double *) c->pchk, MI_PSIG_BLOCKS,
-                       c->pchk + 3 * MI_PSIG_BLOCKS);
+    hipLaunchKernelGGL(mi_psig_norms_kernel, dim3(MI_PSIG_BLOCKS), dim3(256), 0, g.stream, (const double *) c->Pr2.get(), (const double *) c->Xup.get(),
+                       (const double *) ch.Linv.get(), np, c->n, c->pchk.get());
+    hipLaunchKernelGGL(mi_psig_norms_final_kernel, dim3(1), dim3(64), 0, g.stream, (const double *) c->pchk.get(), MI_PSIG_BLOCKS,
+                       c->pchk.get() + 3 * MI_PSIG_BLOCKS);
     HIP_RC(hipGetLastError());
     double nr[3] = {0, 0, 0};
-    HIP_RC(hipMemcpyAsync(nr, c->pchk + 3 * MI_PSIG_BLOCKS, sizeof(nr), hipMemcpyDeviceToHost, g.stream));
+    HIP_RC(hipMemcpyAsync(nr, c->pchk.get() + 3 * MI_PSIG_BLOCKS, sizeof(nr), hipMemcpyDeviceToHost, g.stream));
     HIP_RC(hipStreamSynchronize(g.stream));
     const double xf = std::sqrt(nr[1]);
     c->primal_resid = xf > 0.0 ? std::sqrt(nr[0]) / xf : INFINITY;
@@ -458,8 +448,8 @@ int primal_shards_agree(MiCone *c, bool ok, bool *agree) {
     *agree = true;
     if (c->world <= 1) return 0;
     if (!c->allreduce) return 1;
-    if (!c->pchk) HIP_RC(hipMalloc((void **) &c->pchk, sizeof(double) * (3 * MI_PSIG_BLOCKS + 8)));
-    double *w = c->pchk + 3 * MI_PSIG_BLOCKS + 4;
+    HIP_RC(c->pchk.reserve(3 * MI_PSIG_BLOCKS + 8));
+    double *w = c->pchk.get() + 3 * MI_PSIG_BLOCKS + 4;
     const double mine[2] = {ok ? 1.0 : 0.0, (double) c->primal_q};
     HIP_RC(hipMemcpyAsync(w, mine, sizeof(mine), hipMemcpyHostToDevice, g.stream));
     HIP_RC(hipStreamSynchronize(g.stream));
@@ -479,7 +469,7 @@ hdsdp_retcode build_primal(MiCone *c, int iCone, hdsdp_kkt *kkt, MiKKTPriv *pv) 
     const double *X = kkt->dPrimalX[iCone];
     const int n = c->n;
     if (!c->primal) {
-        c->primal = new HdmChol();
+        c->primal.reset(new HdmChol());
         if (c->primal->init(n)) return HDSDP_RETCODE_MEMORY;
     }
     std::vector<double> Xr((size_t) n * n);
@@ -518,7 +508,7 @@ hdsdp_retcode build_primal(MiCone *c, int iCone, hdsdp_kkt *kkt, MiKKTPriv *pv) 
         return build_primal_general(c, kkt, pv, X);
     }
     c->primal_route = 1;
-    c->gram_sig = c->psig;
+    c->gram_sig = c->psig.get();
     hdsdp_retcode rc = build_gemm_path(c, kkt, pv, KKT_TYPE_PRIMAL, &ch);
     c->gram_sig = nullptr;
     // the "S row" back to I for every other build (it is written once, at allocation: cone_alloc_gemm_work)
@@ -551,43 +541,43 @@ HdmMatView kkt_view(hdsdp_kkt *kkt) {
     MiLin *l = (MiLin *) kkt->kktM->chol;
     if (l->bsp) return l->bsp->view_M();
     HdmMatView v;
-    v.base = l->Mdev; v.ld = l->ch.npad;
+    v.base = l->Mdev.get(); v.ld = l->ch.npad;
     return v;
 }
 double *kkt_Mdev(hdsdp_kkt *kkt, long *ld) {
     MiLin *l = (MiLin *) kkt->kktM->chol;
     if (ld) *ld = l->ch.npad;
-    return l->Mdev;
+    return l->Mdev.get();
 }
 
 hdsdp_retcode corrector_components(MiCone *c, HdmChol &ch, MiKKTPriv *pv, int m) {
     // ASinv_i = <A_i, S^-1>, ASinvRdSinv_i = Rd <A_i, S^-2>   (hdsdp_conic_sdp.c:1035-1056)
     const size_t nn = sizeof(double) * (size_t) ch.npad * ch.npad;
-    if (!c->Xinv) { if (hipMalloc((void **) &c->Xinv, nn) != hipSuccess) return HDSDP_RETCODE_MEMORY; }
-    if (!c->Yinv) { if (hipMalloc((void **) &c->Yinv, nn) != hipSuccess) return HDSDP_RETCODE_MEMORY; }
-    RC(ch.inverse_full(c->Xinv, ch.npad, g.stream));
+    if (c->Xinv.reserve(nn / sizeof(double)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
+    if (c->Yinv.reserve(nn / sizeof(double)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
+    RC(ch.inverse_full(c->Xinv.get(), ch.npad, g.stream));
     const double *Y = nullptr;
     if (c->Rd != 0.0) {
         HdmGemmArgs q = {};  // Y = X * X^T = S^-2
-        q.A = c->Xinv; q.lda = ch.npad; q.B = c->Xinv; q.ldb = ch.npad; q.C = c->Yinv; q.ldc = ch.npad;
+        q.A = c->Xinv.get(); q.lda = ch.npad; q.B = c->Xinv.get(); q.ldb = ch.npad; q.C = c->Yinv.get(); q.ldc = ch.npad;
         q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE;
         RC(hdm_launch_gemm(q, g.stream));
-        Y = c->Yinv;
+        Y = c->Yinv.get();
     }
     // A is stored in A_L form: <A, X> = 2 <A_L, X>
     if (c->world == 1) {
-        RC(cone_sym_dot2(c, c->Xinv, Y, ch.npad, pv->vecs, pv->vecs + m, 2.0, 2.0 * c->Rd));
+        RC(cone_sym_dot2(c, c->Xinv.get(), Y, ch.npad, pv->vecs.get(), pv->vecs.get() + m, 2.0, 2.0 * c->Rd));
         return HDSDP_RETCODE_OK;
     }
     // Sharded block: pv->vecs is the accumulator of the whole operator (every engine cone adds into it), so the sum
     // over the ranks runs on this cone's own contribution only and is added afterwards; reducing pv->vecs itself would
     // multiply what the cones before this one have put there by the number of ranks.
-    if (!c->corr) HIP_RC(hipMalloc((void **) &c->corr, sizeof(double) * 2 * (size_t) m));
-    HIP_RC(hipMemsetAsync(c->corr, 0, sizeof(double) * 2 * (size_t) m, g.stream));
-    RC(cone_sym_dot2(c, c->Xinv, Y, ch.npad, c->corr, c->corr + m, 2.0, 2.0 * c->Rd));
+    HIP_RC(c->corr.reserve(2 * (size_t) m));
+    HIP_RC(hipMemsetAsync(c->corr.get(), 0, sizeof(double) * 2 * (size_t) m, g.stream));
+    RC(cone_sym_dot2(c, c->Xinv.get(), Y, ch.npad, c->corr.get(), c->corr.get() + m, 2.0, 2.0 * c->Rd));
     HIP_RC(hipStreamSynchronize(g.stream));
-    if (!c->allreduce || c->allreduce(c->xctx, c->corr, (int64_t) 2 * m)) return HDSDP_RETCODE_FAILED;
-    if (c->kkt_owner) RC(hdm_axpy_mat(pv->vecs, pv->vecs, c->corr, 1.0, 2L * m, g.stream));
+    if (!c->allreduce || c->allreduce(c->xctx, c->corr.get(), (int64_t) 2 * m)) return HDSDP_RETCODE_FAILED;
+    if (c->kkt_owner) RC(hdm_axpy_mat(pv->vecs.get(), pv->vecs.get(), c->corr.get(), 1.0, 2L * m, g.stream));
     HIP_RC(hipStreamSynchronize(g.stream));
     return HDSDP_RETCODE_OK;
 }
@@ -630,32 +620,32 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
             if (!A) return HDSDP_RETCODE_FAILED;
             RC(congruence_rows(c, ch, A, c->astride, c->astride * (long) c->Bs + opad, nb, q0));
         }
-    } else if (!staged) RC(congruence_rows(c, ch, c->Afull, c->astride, afull_span, c->mloc, 0));
+    } else if (!staged) RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc, 0));
     if (c->rank == 0) {
         // "I row": A = I => T = Linv, At = Linv Linv^T.  Reuse step 2 with T := Linv.
         HdmGemmArgs k2 = {};
-        k2.A = ch.Linv; k2.lda = ch.npad; k2.B = ch.Linv; k2.ldb = ch.npad; k2.C = c->AhatLoc;
+        k2.A = ch.Linv.get(); k2.lda = ch.npad; k2.B = ch.Linv.get(); k2.ldb = ch.npad; k2.C = c->AhatLoc;
         k2.M = c->n16; k2.N = c->n16; k2.K = c->n16; k2.batch = 1; k2.alpha = 1.0;
         k2.klimit = HDM_KLIM_BY_N; k2.lower_only = 1; k2.epilogue = HDM_EPI_BLOCKED;
         k2.blk_row_stride = c->Lr; k2.blk_row0 = c->mloc; k2.nblk = c->nblk;
         RC(hdm_launch_gemm(k2, g.stream));
         if (typeKKT == KKT_TYPE_HOMOGENEOUS) {
-            if (!c->CL) {
-                HIP_RC(hipMalloc((void **) &c->CL, sizeof(double) * (size_t) c->astride + hdm_operand_pad(c->n16)));
-                HIP_RC(hipMemsetAsync(c->CL, 0, sizeof(double) * (size_t) c->astride, g.stream));
-                RC(hdm_lower_half(c->Cfull, c->CL, c->n, c->n16, g.stream));
+            if (!c->CL.get()) {
+                HIP_RC(c->CL.alloc((size_t) c->astride, hdm_operand_pad(c->n16)));
+                HIP_RC(hipMemsetAsync(c->CL.get(), 0, sizeof(double) * (size_t) c->astride, g.stream));
+                RC(hdm_lower_half(c->Cfull.get(), c->CL.get(), c->n, c->n16, g.stream));
             }
-            RC(congruence_rows(c, ch, c->CL, c->astride, c->astride + opad, 1, c->mloc + 2));
+            RC(congruence_rows(c, ch, c->CL.get(), c->astride, c->astride + opad, 1, c->mloc + 2));
         }
     }
     if (staged) {
-        RC(congruence_rows(c, ch, c->Afull, c->astride, afull_span, c->mloc, 0, 1));
+        RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc, 0, 1));
         if (prof_record(c->pe_s1, g.stream)) return HDSDP_RETCODE_FAILED;
         const unsigned long long all = (NT >= 64) ? ~0ULL : ((1ULL << NT) - 1);
         unsigned long long done = 0;
         for (int k = 0; k < P; ++k) {
             unsigned long long mk = (k == P - 1 ? all : piece_tile_cols(c, k, P)) & all & ~done;
-            if (mk) { RC(congruence_rows(c, ch, c->Afull, c->astride, afull_span, c->mloc, 0, 2, mk)); c->last_staged += 1; }
+            if (mk) { RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc, 0, 2, mk)); c->last_staged += 1; }
             done |= mk;
             if (!c->piece_ev[k]) HIP_RC(hipEventCreateWithFlags(&c->piece_ev[k], hipEventDisableTiming));
             HIP_RC(hipEventRecord(c->piece_ev[k], g.stream));
@@ -671,14 +661,14 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
     if (c->world > 1) {
         HIP_RC(hipStreamSynchronize(g.stream));
         const double t0 = host_now();
-        if (!c->allreduce || c->allreduce(c->xctx, c->Gm, (int64_t) c->R * c->R)) return HDSDP_RETCODE_FAILED;
+        if (!c->allreduce || c->allreduce(c->xctx, c->Gm.get(), (int64_t) c->R * c->R)) return HDSDP_RETCODE_FAILED;
         c->prof.allreduce_host = (host_now() - t0) * 1e3;
     }
     const int hsd = (typeKKT == KKT_TYPE_HOMOGENEOUS);
     const long pI = (c->world == 1) ? c->mloc : (c->m + c->world - 1) / c->world;  // rows owned by rank 0 = position of the "I row"
     if (c->kkt_owner)
-        RC(hdm_extract(c->Gm, c->R, c->R, pI, c->rows_seg, kkt_view(kkt), pv->vecs, pv->vecs + m, pv->vecs + 2 * m,
-                       pv->vecs + 3 * m, c->Rd, hsd, g.stream));
+        RC(hdm_extract(c->Gm.get(), c->R, c->R, pI, c->rows_seg.get(), kkt_view(kkt), pv->vecs.get(), pv->vecs.get() + m, pv->vecs.get() + 2 * m,
+                       pv->vecs.get() + 3 * m, c->Rd, hsd, g.stream));
     HIP_RC(hipEventRecord(g.ev[4], g.stream));
     HIP_RC(hipEventSynchronize(g.ev[4]));
     float ms = 0;

@@ -22,7 +22,7 @@ struct MiCone {
     MiBlockData blk;           // presolve results (empty rows for synthetic)
     std::vector<int> own;      // global indices of the owned constraints
     // device data
-    double *Afull = nullptr;   // mloc x (n16 x n16) constraint matrices in A_L form: strict lower + half diagonal
+    HdmBuf<double> Afull;      // mloc x (n16 x n16) constraint matrices in A_L form: strict lower + half diagonal
     HdmZs zs; int zs_state = 0; // zero-suppressed copy of Afull for the S / dS sweeps (schur.h); 0 = not looked at, 1 = in use, -1 = not built
     // STREAMED constraint data (synthetic family only): the A_L forms are not resident -- BASELINE configs[4] on one
     // device is 136 GB of them beside 130 GB of transformed rows -- and every consumer walks them batch by batch through
@@ -31,65 +31,66 @@ struct MiCone {
     bool streamed = false;
     bool rows_from_zs = false; // streamed INGESTED rows (round 5): the zero-suppressed copy is the only image of the constraint data, a
                                // batch of A_L forms is expanded from it (hdm_zs_expand) where the synthetic family runs its generator
-    double *Abatch = nullptr;  // regeneration buffer, Bs matrices
+    HdmBuf<double> Abatch;     // regeneration buffer, Bs matrices
     int Bs = 0;
-    double *Cfull = nullptr;   // n16 x n16 objective, full symmetric
-    double *CL = nullptr;      // objective in A_L form (GEMM path, HSD builds)
-    double *Avec = nullptr;    // n16 x mloc16 rank-one factors (R1 path)
-    double *sgn = nullptr;     // mloc signs (R1 path)
+    HdmBuf<double> Cfull;      // n16 x n16 objective, full symmetric
+    HdmBuf<double> CL;         // objective in A_L form (GEMM path, HSD builds)
+    HdmBuf<double> Avec;       // n16 x mloc16 rank-one factors (R1 path)
+    HdmBuf<double> sgn;        // mloc signs (R1 path)
     int mloc16 = 0;
     long astride = 0;          // elements per constraint matrix in Afull (skyline storage of the A_L form, hdm_common.h)
-    int *sp_rp = nullptr, *sp_ti = nullptr, *sp_tj = nullptr;  // sparse path: triplets of the owned rows
-    double *sp_tv = nullptr;
-    int *rows_seg = nullptr;   // world*Lr: segment-ordered Gram row -> global constraint (-1 pad, -2.. aug)
-    int *rows_own = nullptr;   // mloc: owned row -> global constraint
-    double *S = nullptr, *Scheck = nullptr;  // n x n (ld n16) dual matrix buffers
-    double *ydev = nullptr;
-    double *yhost = nullptr;   // pinned staging of the owned multipliers (the upload is asynchronous)
-    double *chk_host = nullptr, *chk_dev = nullptr;   // mapped pinned block of the single-launch small-block check: y[mloc], then info, log det
+    HdmBuf<int> sp_rp, sp_ti, sp_tj;   // sparse path: triplets of the owned rows
+    HdmBuf<double> sp_tv;
+    HdmBuf<int> rows_seg;      // world*Lr: segment-ordered Gram row -> global constraint (-1 pad, -2.. aug)
+    HdmBuf<int> rows_own;      // mloc: owned row -> global constraint
+    HdmBuf<double> S, Scheck;  // n x n (ld n16) dual matrix buffers
+    HdmBuf<double> ydev;
+    HdmPinned<double> yhost;   // pinned staging of the owned multipliers (the upload is asynchronous)
+    HdmPinned<double> chk;     // mapped pinned block of the single-launch small-block check: y[mloc], then info, log det
     bool fac_ok = false; int fac_psd = 0;             // the dual factor object holds the factorisation of S = T(pS) (result: fac_psd)
-    double *corr = nullptr;    // sharded corrector build: this cone's 2m dot products before they join the operator's
+    HdmBuf<double> corr;       // sharded corrector build: this cone's 2m dot products before they join the operator's
     hdsdp_linsys_fp *dualFactor = nullptr;
-    HdmChol *primal = nullptr; // KKT_TYPE_PRIMAL: factor object of the registered primal matrix (lazy)
+    std::unique_ptr<HdmChol> primal;   // KKT_TYPE_PRIMAL: factor object of the registered primal matrix (lazy)
     // KKT_TYPE_PRIMAL with an indefinite X, route 1 (engine_build.h: build_primal): X = W^T diag(sigma) W from the signed factor
-    double *psig = nullptr;           // sigma on the device (npad, +1 in the padding)
-    const double *gram_sig = nullptr; // set for the duration of a route-1 build: the Gram product takes the signed weights
-    int *pcols = nullptr; long pcols_cap = 0;     // packed columns of the correction's sign (this rank's K range)
-    double *pgat = nullptr; long pgat_cap = 0;    // the gathered operand (one chunk)
-    double *pchk = nullptr;           // acceptance check: 3 * MI_PSIG_BLOCKS partial sums + 3 totals; then the shards' agreement words
+    HdmBuf<double> psig;              // sigma on the device (npad, +1 in the padding)
+    const double *gram_sig = nullptr; // not owned (psig): set for the duration of a route-1 build: the Gram product takes the signed weights
+    HdmBuf<int> pcols;                // packed columns of the correction's sign (this rank's K range)
+    HdmBuf<double> pgat;              // the gathered operand (one chunk)
+    HdmBuf<double> pchk;              // acceptance check: 3 * MI_PSIG_BLOCKS partial sums + 3 totals; then the shards' agreement words
     int primal_route = -1, primal_q = 0;          // HMiConeGetPrimalRoute: the last KKT_TYPE_PRIMAL build
     double primal_growth = 0.0, primal_resid = 0.0;
     double primal_ms[4] = {0, 0, 0, 0};           // route 1: signed factor + check, gather, correction GEMMs, combine (ms)
     long primal_cols = 0;                         // route 1: columns of the correction on this rank (0: none needed)
-    HdmLanczos *lanczos = nullptr;  // ratio test state (lazy); dS lives in `dS`
+    std::unique_ptr<HdmLanczos> lanczos;   // ratio test state (lazy); dS lives in `dS`
     // the ratio test's safeguard (cone_ratio_test): a factor object and a buffer for S + step dS, and a Lanczos object that
     // always starts fresh (lazy, only made when a step has failed the check)
-    HdmChol *safe = nullptr;
-    double *Ssafe = nullptr;
-    HdmLanczos *lanczos_fresh = nullptr;
+    std::unique_ptr<HdmChol> safe;
+    HdmBuf<double> Ssafe;
+    std::unique_ptr<HdmLanczos> lanczos_fresh;
     double nrm[4] = {0, 0, 0, 0}; bool norms_ready = false;   // data norms (rows abs / Frobenius, objective abs / Frobenius)
     double objScal = 1.0;           // product of the coneScal factors applied to C
-    HdmChol *checker = nullptr;     // second factor object (primal recovery works on S without the residual term)
-    double *dS = nullptr;
-    double *Xup = nullptr;          // uploaded primal matrix of the cone utilities
-    double *Pr1 = nullptr, *Pr2 = nullptr;   // primal recovery scratch (npad x npad each; Xinv / Yinv are sized per builder path)
+    std::unique_ptr<HdmChol> checker;   // second factor object (primal recovery works on S without the residual term)
+    HdmBuf<double> dS;
+    HdmBuf<double> Xup;             // uploaded primal matrix of the cone utilities
+    HdmBuf<double> Pr1, Pr2;        // primal recovery scratch (npad x npad each; Xinv / Yinv are sized per builder path)
     double Rd = 0.0, perturb = 0.0;
-    double *trA = nullptr;     // host: tr(A_i) of all m constraints (b of the synthetic family)
+    std::vector<double> trA;   // host: tr(A_i) of all m constraints (b of the synthetic family)
     // work space
     int Bc = 8;                // constraints per congruence batch
-    double *T = nullptr;       // Bc x n16 x n16
+    HdmBuf<double> T;          // Bc x n16 x n16
+    HdmBuf<double> ahat_loc_own, ahat_all_own;   // what AhatLoc / AhatAll point at, unless the caller supplied them (HMiConeSetExchangeBuffers: torch-owned, for RCCL; these two then stay empty)
     double *AhatLoc = nullptr; // [world*npb_loc][Lr][16] congruence output of the owned rows
-    double *AhatAll = nullptr; // [world][npb_loc][Lr][16] after the transpose (== AhatLoc when world == 1)
-    bool ext_ahat = false;     // buffers supplied by the caller (torch-owned, for RCCL)
-    double *slabs = nullptr;   // nslab x R x R
-    double *Gm = nullptr;      // R x R augmented Gram (lower valid)
+    double *AhatAll = nullptr; // [world][npb_loc][Lr][16] after the transpose (== AhatLoc when world == 1: not owned)
+    HdmBuf<double> slabs_own;  // the Gram slabs where they have a buffer of their own (!shared_ts)
+    double *slabs = nullptr;   // nslab x R x R; not owned: slabs_own or, with shared_ts, T
+    HdmBuf<double> Gm;         // R x R augmented Gram (lower valid)
     int nsplit = 1;            // K splits of the Gram product
     int nslab = 1;             // slabs they are summed into; more splits than slabs run in groups that accumulate (engine_build.h: gram_range)
     int slabs_used = 0;        // slabs the current build's groups have written
     bool gram_queue_global = false;   // the Gram launch's workgroups draw (split, tile) jobs from ONE queue in split order
     long R = 0;                // world * Lr
     // R1 work
-    double *U = nullptr, *V = nullptr, *Gr1 = nullptr, *Ct = nullptr, *W = nullptr, *Xinv = nullptr, *Yinv = nullptr;
+    HdmBuf<double> U, V, Gr1, Ct, W, Xinv, Yinv;
     // exchange hooks (world > 1)
     hmi_alltoall_fn alltoall = nullptr;
     hmi_alltoall_piece_fn a2a_start = nullptr;   // piecewise exchange overlapped with the Gram product (optional)
@@ -130,32 +131,32 @@ struct MiCone {
     // fused single-launch Phase-A pass of a small rank-one block (small.hip): factors as a CSR, built on first use
     struct SmallPlan {
         int state = 0;         // 0 = not looked at, 1 = ready, -1 = not eligible
-        int *fp = nullptr, *fi = nullptr, *dense_of = nullptr, *dense_rows = nullptr;
-        double *fv = nullptr, *sgn = nullptr;
+        HdmBuf<int> fp, fi, dense_of, dense_rows;
+        HdmBuf<double> fv, sgn;
         int ndense = 0;
-        double *io_host = nullptr, *io_dev = nullptr;   // mapped pinned block: y[m], b[m] in; 4 + 5 m doubles out
+        HdmPinned<double> io;  // mapped pinned block: y[m], b[m] in; 4 + 5 m doubles out
     } small;
 };
 
 struct MiKKTPriv {
     int mirror = 1;
-    double *vecs = nullptr;   // device: ASinv[m], ASinvRdSinv[m], ASinvCSinv[m], scal[4]
-    double *rhs = nullptr;
+    HdmBuf<double> vecs;      // device: ASinv[m], ASinvRdSinv[m], ASinvCSinv[m], scal[4]
+    HdmBuf<double> rhs;
     bool Mdev_valid = false;  // device M holds the result of the last BuildUp
     // cones of HKKT->cones[] whose coneBuildSchur is this engine's (they accumulate on the device) and the others (the
     // reference's CPU cones: they accumulate into the host fields, hdsdp_conic_*.c)
     int n_engine = 0, n_foreign = 0;
-    double *Mtmp = nullptr;   // pinned m x m staging buffer for the mixed case (device part added to the host part)
+    HdmPinned<double> Mtmp;   // pinned m x m staging buffer for the mixed case (device part added to the host part)
     // sparse Schur operator (isKKTSparse, hdsdp_schur.c:46-139): the host matrix is the aggregated CSC pattern; its
     // entries as (row, column) pairs on the device, plus a staging vector of nnz values
     long nnz = 0;
-    int *sp_rows = nullptr, *sp_cols = nullptr;
-    int *sp_prow = nullptr, *sp_pcol = nullptr;   // the same entries in the factor object's (permuted, lower) coordinates, if it is permuted
-    double *sp_vals = nullptr;
+    HdmBuf<int> sp_rows, sp_cols;
+    HdmBuf<int> sp_prow, sp_pcol;   // the same entries in the factor object's (permuted, lower) coordinates, if it is permuted
+    HdmBuf<double> sp_vals;
     // diagonal channel (host mirror off, engine_kkt.h): kktDiag[i] -> chan[i], pinned; host cones add their diagonal terms
     // there, and the first HKKTRegularize / HKKTFactorize after a build adds it (8 m bytes up) to the device matrix's diagonal
-    double *chan = nullptr;
-    double *chan_dev = nullptr;   // device: m doubles + 1 (the minimum the regulariser reads)
+    HdmPinned<double> chan;
+    HdmBuf<double> chan_dev;      // device: m doubles + 1 (the minimum the regulariser reads)
     bool chan_folded = false;     // the channel of the current build is in the device matrix already
     int64_t bytes_d2h = 0, bytes_h2d = 0;   // M and the channel moved since HKKTInit (HMiKKTGetMatrixTraffic)
 };
@@ -172,16 +173,6 @@ MiKKTPriv *priv_of(hdsdp_kkt *k) {
 void priv_drop(hdsdp_kkt *k) {
     for (size_t i = 0; i < g_priv.size(); ++i)
         if (g_priv[i].first == k) {
-            if (g_priv[i].second->vecs) (void) hipFree(g_priv[i].second->vecs);
-            if (g_priv[i].second->rhs) (void) hipFree(g_priv[i].second->rhs);
-            if (g_priv[i].second->Mtmp) (void) hipHostFree(g_priv[i].second->Mtmp);
-            if (g_priv[i].second->sp_rows) (void) hipFree(g_priv[i].second->sp_rows);
-            if (g_priv[i].second->sp_prow) (void) hipFree(g_priv[i].second->sp_prow);
-            if (g_priv[i].second->sp_pcol) (void) hipFree(g_priv[i].second->sp_pcol);
-            if (g_priv[i].second->sp_cols) (void) hipFree(g_priv[i].second->sp_cols);
-            if (g_priv[i].second->sp_vals) (void) hipFree(g_priv[i].second->sp_vals);
-            if (g_priv[i].second->chan) (void) hipHostFree(g_priv[i].second->chan);
-            if (g_priv[i].second->chan_dev) (void) hipFree(g_priv[i].second->chan_dev);
             delete g_priv[i].second;
             g_priv.erase(g_priv.begin() + i);
             return;
@@ -214,12 +205,12 @@ int cone_alloc_common(MiCone *c) {
     int maxloc = compact ? c->mloc : (c->m + c->world - 1) / c->world;
     c->Lr = (c->world == 1) ? (int) hdm_roundup(maxloc + 3, 8) : (int) hdm_roundup(maxloc + 3, HDM_TILE);
     c->R = (long) c->world * c->Lr;
-    const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
-    HDM_HIP_CHECK(hipMalloc((void **) &c->S, nn));
-    HDM_HIP_CHECK(hipMalloc((void **) &c->Scheck, nn));
-    HDM_HIP_CHECK(hipMalloc((void **) &c->Cfull, nn));
-    HDM_HIP_CHECK(hdm_memset_sync(c->Cfull, 0, nn));
-    HDM_HIP_CHECK(hipMalloc((void **) &c->ydev, sizeof(double) * (size_t) std::max(1, c->m)));
+    const size_t n2 = (size_t) c->n16 * c->n16, nn = sizeof(double) * n2;
+    HDM_HIP_CHECK(c->S.alloc(n2));
+    HDM_HIP_CHECK(c->Scheck.alloc(n2));
+    HDM_HIP_CHECK(c->Cfull.alloc(n2));
+    HDM_HIP_CHECK(hdm_memset_sync(c->Cfull.get(), 0, nn));
+    HDM_HIP_CHECK(c->ydev.alloc((size_t) std::max(1, c->m)));
     std::vector<int> rs((size_t) c->R, -1);
     for (int gq = 0; gq < c->world; ++gq) {
         int cnt = 0;
@@ -227,16 +218,16 @@ int cone_alloc_common(MiCone *c) {
         else for (int i = gq; i < c->m; i += c->world) rs[(size_t) gq * c->Lr + cnt++] = i;
         if (gq == 0) { rs[cnt] = -2; rs[cnt + 1] = -3; rs[cnt + 2] = -4; }  // I, S, C rows
     }
-    HDM_HIP_CHECK(hipMalloc((void **) &c->rows_seg, sizeof(int) * (size_t) c->R));
-    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->rows_seg, rs.data(), sizeof(int) * (size_t) c->R));
-    HDM_HIP_CHECK(hipMalloc((void **) &c->rows_own, sizeof(int) * (size_t) std::max(1, c->mloc)));
-    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->rows_own, c->own.data(), sizeof(int) * (size_t) c->mloc));
+    HDM_HIP_CHECK(c->rows_seg.alloc((size_t) c->R));
+    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->rows_seg.get(), rs.data(), sizeof(int) * (size_t) c->R));
+    HDM_HIP_CHECK(c->rows_own.alloc((size_t) std::max(1, c->mloc)));
+    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->rows_own.get(), c->own.data(), sizeof(int) * (size_t) c->mloc));
     if (HFpLinsysCreate(&c->dualFactor, c->n, HDSDP_LINSYS_DENSE_DIRECT) != HDSDP_RETCODE_OK) return 1;
     return 0;
 }
 
 int cone_alloc_gemm_work(MiCone *c) {
-    const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
+    const size_t n2 = (size_t) c->n16 * c->n16, nn = sizeof(double) * n2;
     {   // The zero-suppressed sweep copy (cone_build_zs) was made at creation, before these work buffers: it must never be the
         // reason they come out smaller -- every allocation below degrades quietly (smaller batches, fewer splits) when memory is
         // short.  If what is free does not cover a generous bound of what the builders take, the copy goes (the sweeps then read
@@ -267,20 +258,21 @@ int cone_alloc_gemm_work(MiCone *c) {
         const long launches = (rows + bc - 1) / bc;
         bc = (rows + launches - 1) / launches;
         c->Bc = (int) bc;
-        if (hipMalloc((void **) &c->T, nn * (size_t) c->Bc + hdm_operand_pad(c->n16)) == hipSuccess) break;
+        if (c->T.alloc(n2 * (size_t) c->Bc, hdm_operand_pad(c->n16)) == hipSuccess) break;
         (void) hipGetLastError();
-        c->T = nullptr;
         if (bc <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the congruence intermediates\n"); return 1; }
         bc /= 2;
     }
-    HDM_HIP_CHECK(hdm_memset_sync(c->T, 0, nn * (size_t) c->Bc));  // step 1 writes lower tiles only; the rest must read as 0
+    HDM_HIP_CHECK(hdm_memset_sync(c->T.get(), 0, nn * (size_t) c->Bc));  // step 1 writes lower tiles only; the rest must read as 0
     const size_t ahat = sizeof(double) * (size_t) c->world * c->npb_loc * c->Lr * 16;
     if (!c->AhatLoc) {
-        HDM_HIP_CHECK(hipMalloc((void **) &c->AhatLoc, ahat + sizeof(double) * HDM_OPERAND_PAD_DOUBLES));
+        HDM_HIP_CHECK(c->ahat_loc_own.alloc(ahat / sizeof(double) + HDM_OPERAND_PAD_DOUBLES));
+        c->AhatLoc = c->ahat_loc_own.get();
         HDM_HIP_CHECK(hdm_memset_sync(c->AhatLoc, 0, ahat));
         if (c->world == 1) c->AhatAll = c->AhatLoc;
         else {
-            HDM_HIP_CHECK(hipMalloc((void **) &c->AhatAll, ahat + sizeof(double) * HDM_OPERAND_PAD_DOUBLES));
+            HDM_HIP_CHECK(c->ahat_all_own.alloc(ahat / sizeof(double) + HDM_OPERAND_PAD_DOUBLES));
+            c->AhatAll = c->ahat_all_own.get();
             HDM_HIP_CHECK(hdm_memset_sync(c->AhatAll, 0, ahat));
         }
     }
@@ -362,13 +354,11 @@ int cone_alloc_gemm_work(MiCone *c) {
         for (;;) {
             c->nsplit = (int) ns;
             const size_t sbytes = sizeof(double) * (size_t) c->R * c->R * c->nsplit;
-            if (sbytes <= tbytes) { c->slabs = c->T; c->shared_ts = true; break; }
+            if (sbytes <= tbytes) { c->slabs = c->T.get(); c->shared_ts = true; break; }
             // the slabs are the bigger of the two: one buffer of their size serves both
-            (void) hipFree(c->T);
-            c->T = nullptr;
-            if (hipMalloc((void **) &c->T, sbytes + hdm_operand_pad(c->n16)) == hipSuccess) { c->slabs = c->T; c->shared_ts = true; break; }
+            if (c->T.alloc(sbytes / sizeof(double), hdm_operand_pad(c->n16)) == hipSuccess) { c->slabs = c->T.get(); c->shared_ts = true; break; }
             (void) hipGetLastError();
-            if (hipMalloc((void **) &c->T, tbytes) != hipSuccess) { (void) hipGetLastError(); c->T = nullptr; return 1; }
+            if (c->T.alloc(n2 * (size_t) c->Bc, hdm_operand_pad(c->n16)) != hipSuccess) { (void) hipGetLastError(); return 1; }
             if (ns <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the Gram slabs\n"); return 1; }
             ns = std::max(8L, (ns / 2) & ~7L);
         }
@@ -376,9 +366,8 @@ int cone_alloc_gemm_work(MiCone *c) {
     // the slabs are the one allocation here that is a tuning choice: halve the split count until it fits
     for (; !c->shared_ts;) {
         c->nsplit = (int) ns;
-        if (hipMalloc((void **) &c->slabs, sizeof(double) * (size_t) c->R * c->R * c->nsplit) == hipSuccess) break;
+        if (c->slabs_own.alloc((size_t) c->R * c->R * c->nsplit) == hipSuccess) { c->slabs = c->slabs_own.get(); break; }
         (void) hipGetLastError();
-        c->slabs = nullptr;
         if (ns <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the Gram slabs\n"); return 1; }
         ns = std::max(8L, (ns / 2) & ~7L);
     }
@@ -386,7 +375,7 @@ int cone_alloc_gemm_work(MiCone *c) {
     if (total_splits > c->nslab) c->nsplit = (int) total_splits;
     c->gram_queue_global = true;
     if (const char *e = getenv("HDM_GRAM_QUEUE")) c->gram_queue_global = atoi(e) != 0;   // 0: one queue per XCD over the splits x, x + 8, ...
-    HDM_HIP_CHECK(hipMalloc((void **) &c->Gm, sizeof(double) * (size_t) c->R * c->R));
+    HDM_HIP_CHECK(c->Gm.alloc((size_t) c->R * c->R));
     // the "S row" (At = I) never changes
     if (c->rank == 0) {
         if (hdm_blocked_eye(c->AhatLoc, c->Lr, c->mloc + 1, c->nblk, c->n, g.stream)) return 1;
@@ -427,19 +416,19 @@ void cone_get_kkt_map(void *cd, int iCol, int *schurMatCol) {
 // cone -- the batch buffer after regenerating them into it (count <= c->Bs; valid until the next call; ordered on the engine
 // stream behind whatever still reads the previous batch).
 const double *cone_rows(MiCone *c, int q0, int count) {
-    if (!c->streamed) return c->Afull ? c->Afull + (long) q0 * c->astride : nullptr;
-    if (!c->Abatch || count > c->Bs || q0 < 0 || q0 + count > c->mloc) return nullptr;
-    if (c->rows_from_zs) return hdm_zs_expand(c->zs, q0, count, c->Abatch, c->astride, g.stream) ? nullptr : c->Abatch;
+    if (!c->streamed) return c->Afull.get() ? c->Afull.get() + (long) q0 * c->astride : nullptr;
+    if (!c->Abatch.get() || count > c->Bs || q0 < 0 || q0 + count > c->mloc) return nullptr;
+    if (c->rows_from_zs) return hdm_zs_expand(c->zs, q0, count, c->Abatch.get(), c->astride, g.stream) ? nullptr : c->Abatch.get();
     if (c->world == 1) {                       // owned rows are consecutive in the global numbering
-        if (hdm_synth_fill_low(c->Abatch, c->astride, c->n, c->n16, c->own[q0], count, g.stream)) return nullptr;
+        if (hdm_synth_fill_low(c->Abatch.get(), c->astride, c->n, c->n16, c->own[q0], count, g.stream)) return nullptr;
     } else {
         for (int q = 0; q < count; ++q)
-            if (hdm_synth_fill_low(c->Abatch + (long) q * c->astride, c->astride, c->n, c->n16, c->own[q0 + q], 1, g.stream)) return nullptr;
+            if (hdm_synth_fill_low(c->Abatch.get() + (long) q * c->astride, c->astride, c->n, c->n16, c->own[q0 + q], 1, g.stream)) return nullptr;
     }
-    return c->Abatch;
+    return c->Abatch.get();
 }
 int cone_batch(const MiCone *c) { return c->streamed ? std::max(1, c->Bs) : std::max(1, c->mloc); }
-bool cone_has_rows(const MiCone *c) { return c->streamed ? c->Abatch != nullptr : c->Afull != nullptr; }
+bool cone_has_rows(const MiCone *c) { return c->streamed ? c->Abatch.get() != nullptr : c->Afull.get() != nullptr; }
 
 // The zero-suppressed copy of the constraint data (schur.h: HdmZs) that the S / dS sweeps and the corrector's dot products
 // read: made once, when the block's data has arrived (cone creation -- format preparation like the unpacking into A_L form; the
@@ -463,9 +452,9 @@ int cone_build_zs(MiCone *c) {
 int cone_assemble(MiCone *c, double tau, const double *y_host, double *target, const double *eye_override = nullptr) {
     // the upload below is asynchronous: the source is a pinned buffer of the cone, and the previous upload from it has
     // been consumed by the time it is rewritten (every caller synchronises on the factorisation that follows)
-    if (!c->yhost) HDM_HIP_CHECK(hipHostMalloc((void **) &c->yhost, sizeof(double) * (size_t) std::max(1, c->mloc), hipHostMallocDefault));
+    if (!c->yhost) HDM_HIP_CHECK(c->yhost.alloc((size_t) std::max(1, c->mloc)));
     HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
-    double *yo = c->yhost;
+    double *yo = c->yhost.get();
     bool any = false;
     for (int q = 0; q < c->mloc; ++q) { yo[q] = y_host ? y_host[c->own[q]] : 0.0; any |= (yo[q] != 0.0); }
     const double eye_now = eye_override ? *eye_override : (-c->Rd + c->perturb);
@@ -485,12 +474,12 @@ int cone_assemble(MiCone *c, double tau, const double *y_host, double *target, c
     const long sweep_bytes = (long) c->mloc * c->n * (c->n + 1) * 4;
     const int aff_mode = aff_env >= 0 ? aff_env : (sweep_bytes >= (16L << 20) ? 2 : 1);
     const bool track = aff_mode > 0 && c->world == 1;
-    if (track && target != c->dS && c->pS_ok) {
+    if (track && target != c->dS.get() && c->pS_ok) {
         const int np = c->mloc + 2;
         auto comp = [&](int i) { return i == 0 ? tau : i == 1 ? eye_now : yo[i - 2]; };
         bool same = true;
         for (int i = 0; i < np && same; ++i) same = (comp(i) == c->pS[i]);
-        if (same && target == c->S) { g_asm_counts[0] += 1; return 0; }        // S already is T(p)
+        if (same && target == c->S.get()) { g_asm_counts[0] += 1; return 0; }        // S already is T(p)
         double alpha = 0.0, eye_delta = 0.0;
         bool hit = same;
         if (!same && c->pD_ok && aff_mode >= 2) {
@@ -521,47 +510,47 @@ int cone_assemble(MiCone *c, double tau, const double *y_host, double *target, c
                 double dd = 0.0, pp = 0.0, dp = 0.0;
                 for (int i = 2; i < np; ++i) { const double d = comp(i) - c->pS[i]; dd += d * d; pp += c->pD[i] * c->pD[i]; dp += d * c->pD[i]; }
                 fprintf(stderr, "[hdsdp_mi355x affine] miss (%s): alpha %.6e, %d of %d components off the tested line, worst relative %.3e at %d; "
-                                "d tau %.3e, d eye %.3e, |d y| %.3e, |pD y| %.3e, cos %.9f\n", target == c->S ? "S" : "checker", alpha, bad, np, worst, wi,
+                                "d tau %.3e, d eye %.3e, |d y| %.3e, |pD y| %.3e, cos %.9f\n", target == c->S.get() ? "S" : "checker", alpha, bad, np, worst, wi,
                         comp(0) - c->pS[0], comp(1) - c->pS[1], sqrt(dd), sqrt(pp), (dd > 0 && pp > 0) ? dp / sqrt(dd * pp) : 0.0);
             }
         }
         if (hit && same) {                                                     // the same point into the other buffer: a copy
-            HDM_HIP_CHECK(hipMemcpyAsync(target, c->S, sizeof(double) * (size_t) c->n16 * c->n16, hipMemcpyDeviceToDevice, g.stream));
+            HDM_HIP_CHECK(hipMemcpyAsync(target, c->S.get(), sizeof(double) * (size_t) c->n16 * c->n16, hipMemcpyDeviceToDevice, g.stream));
             g_asm_counts[1] += 1;
             return 0;
         }
-        if (hit && c->dS && !(target != c->S || c->aff_chain < 16)) g_asm_counts[4] += 1;
+        if (hit && c->dS.get() && !(target != c->S.get() || c->aff_chain < 16)) g_asm_counts[4] += 1;
         else if (!hit) g_asm_counts[3] += 1;
-        if (hit && c->dS && (target != c->S || c->aff_chain < 16)) {
+        if (hit && c->dS.get() && (target != c->S.get() || c->aff_chain < 16)) {
             g_asm_counts[2] += 1;
-            if (eye_delta == 0.0 ? hdm_axpy_mat(target, c->S, c->dS, alpha, (long) c->n16 * c->n16, g.stream)
-                                 : hdm_axpy_mat_eye(target, c->S, c->dS, alpha, eye_delta, c->n16, c->n, g.stream)) return 1;
-            if (target == c->S) {
+            if (eye_delta == 0.0 ? hdm_axpy_mat(target, c->S.get(), c->dS.get(), alpha, (long) c->n16 * c->n16, g.stream)
+                                 : hdm_axpy_mat_eye(target, c->S.get(), c->dS.get(), alpha, eye_delta, c->n16, c->n, g.stream)) return 1;
+            if (target == c->S.get()) {
                 for (int i = 0; i < np; ++i) c->pS[i] = comp(i);
                 c->aff_chain += 1;
             }
             return 0;
         }
     }
-    if (target == c->dS) g_asm_counts[5] += 1;
+    if (target == c->dS.get()) g_asm_counts[5] += 1;
     else if (!(track && c->pS_ok)) g_asm_counts[track ? 3 : 6] += 1;          // (no point known yet: a first assembly)
-    HDM_HIP_CHECK(hipMemcpyAsync(c->ydev, yo, sizeof(double) * c->mloc, hipMemcpyHostToDevice, g.stream));
-    if (track && (target == c->S || target == c->dS)) {
-        std::vector<double> &pp = (target == c->S) ? c->pS : c->pD;
+    HDM_HIP_CHECK(hipMemcpyAsync(c->ydev.get(), yo, sizeof(double) * c->mloc, hipMemcpyHostToDevice, g.stream));
+    if (track && (target == c->S.get() || target == c->dS.get())) {
+        std::vector<double> &pp = (target == c->S.get()) ? c->pS : c->pD;
         pp.resize((size_t) c->mloc + 2);
         pp[0] = tau; pp[1] = eye_now;
         for (int q = 0; q < c->mloc; ++q) pp[2 + q] = yo[q];
-        (target == c->S ? c->pS_ok : c->pD_ok) = true;
-        if (target == c->S) c->aff_chain = 0;
+        (target == c->S.get() ? c->pS_ok : c->pD_ok) = true;
+        if (target == c->S.get()) c->aff_chain = 0;
     }
     const double lead = (c->rank == 0) ? 1.0 : 0.0;
     // The sweep reads the zero-suppressed copy of the constraint data where one exists (cone_build_zs: made at creation).
     if (any && c->zs_state == 0 && cone_build_zs(c)) return 1;
     if (any && c->zs_state == 1) {
-        if (hdm_sym_combine_zs(c->zs, c->ydev, c->Cfull, lead * tau, lead * (eye_override ? *eye_override : (-c->Rd + c->perturb)),
+        if (hdm_sym_combine_zs(c->zs, c->ydev.get(), c->Cfull.get(), lead * tau, lead * (eye_override ? *eye_override : (-c->Rd + c->perturb)),
                                target, c->n, c->n16, c->n16, g.stream)) return 1;
     } else if (!c->streamed || !any) {
-        if (hdm_sym_combine(c->Afull, c->astride, any ? c->mloc : 0, c->ydev, c->Cfull, lead * tau,
+        if (hdm_sym_combine(c->Afull.get(), c->astride, any ? c->mloc : 0, c->ydev.get(), c->Cfull.get(), lead * tau,
                             lead * (eye_override ? *eye_override : (-c->Rd + c->perturb)), target, c->n, c->n16, c->n16, g.stream)) return 1;
     } else {
         // streamed data without a sweep copy: batch after batch, the later ones on top of what the earlier ones left in the
@@ -570,7 +559,7 @@ int cone_assemble(MiCone *c, double tau, const double *y_host, double *target, c
             const int nb = std::min(c->Bs, c->mloc - q0);
             const double *A = cone_rows(c, q0, nb);
             if (!A) return 1;
-            if (hdm_sym_combine(A, c->astride, nb, c->ydev + q0, q0 == 0 ? c->Cfull : target, q0 == 0 ? lead * tau : 1.0,
+            if (hdm_sym_combine(A, c->astride, nb, c->ydev.get() + q0, q0 == 0 ? c->Cfull.get() : target, q0 == 0 ? lead * tau : 1.0,
                                 q0 == 0 ? lead * (eye_override ? *eye_override : (-c->Rd + c->perturb)) : 0.0, target, c->n, c->n16,
                                 c->n16, g.stream)) return 1;
         }
@@ -585,11 +574,11 @@ int cone_assemble(MiCone *c, double tau, const double *y_host, double *target, c
 // <A_i, X> (and <A_i, Y>) over the owned constraints: from the zero-suppressed copy when the cone has one, else from the dense storage
 int cone_sym_dot2(MiCone *c, const double *X, const double *Y, long ldx, double *outx, double *outy, double sx, double sy) {
     if (c->zs_state == 1)
-        return hdm_sym_dot2_zs(c->zs, c->n16, c->n16, X, Y, ldx, outx, outy, c->rows_own, sx, sy, g.stream);
+        return hdm_sym_dot2_zs(c->zs, c->n16, c->n16, X, Y, ldx, outx, outy, c->rows_own.get(), sx, sy, g.stream);
     for (int q0 = 0, B = cone_batch(c); q0 < c->mloc; q0 += B) {     // (one batch = everything when the data is resident)
         const int nb = std::min(B, c->mloc - q0);
         const double *A = cone_rows(c, q0, nb);
-        if (!A || hdm_sym_dot2(A, c->astride, c->n16, c->n16, nb, X, Y, ldx, outx, outy, c->rows_own + q0, sx, sy, g.stream)) return 1;
+        if (!A || hdm_sym_dot2(A, c->astride, c->n16, c->n16, nb, X, Y, ldx, outx, outy, c->rows_own.get() + q0, sx, sy, g.stream)) return 1;
     }
     return 0;
 }
@@ -609,17 +598,16 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
     // (a single workgroup walks the resident constraint data: up to 1 MB of it in general, 4 MB for blocks of dimension <= 64,
     // where the call-by-call assembly's few workgroups are latency-bound themselves -- theta1: 0.45 ms per check)
     const long resident = (long) c->mloc * c->n16 * c->n16;
-    if (!on || c->world != 1 || !c->Afull || c->n16 > SMALL_P || resident > ((c->n16 <= 64) ? (1L << 19) : (1L << 17))) return 1;
+    if (!on || c->world != 1 || !c->Afull.get() || c->n16 > SMALL_P || resident > ((c->n16 <= 64) ? (1L << 19) : (1L << 17))) return 1;
     HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
     if (whichBuffer != 0) { if (cone_checker(c, &ch) != HDSDP_RETCODE_OK) return 1; }
     if (ch->npad != SMALL_P || ch->nblk != 1) return 1;
     const double eye_now = eye_override ? *eye_override : (-c->Rd + c->perturb);
     const int np = c->mloc + 2;
-    if (!c->chk_host) {
-        if (hipHostMalloc((void **) &c->chk_host, sizeof(double) * (size_t) (c->mloc + 4), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **) &c->chk_dev, c->chk_host, 0) != hipSuccess) { (void) hipGetLastError(); c->chk_host = nullptr; return 1; }
+    if (!c->chk) {
+        if (c->chk.alloc((size_t) (c->mloc + 4), hipHostMallocMapped) != hipSuccess) { (void) hipGetLastError(); return 1; }
     }
-    double *yo = c->chk_host;
+    double *yo = c->chk.get();
     bool same = (whichBuffer == 0 && c->pS_ok && (int) c->pS.size() == np && c->pS[0] == tau && c->pS[1] == eye_now);
     for (int q = 0; q < c->mloc; ++q) {
         const double v = y_host ? y_host[c->own[q]] : 0.0;
@@ -628,10 +616,10 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
     }
     if (same && c->fac_ok) { if (isPsd) *isPsd = c->fac_psd; return 0; }      // S = T(p) and its factor are in place
     HdmSmallCheckArgs a = {};
-    a.n = c->n; a.n16 = c->n16; a.m = c->mloc; a.A = c->Afull; a.astride = c->astride; a.C = c->Cfull;
-    a.y = c->chk_dev; a.tau = tau; a.eye = eye_now;
-    a.Sout = (whichBuffer == 0) ? c->S : c->Scheck;
-    a.L = ch->L; a.W = ch->Dinv; a.out = c->chk_dev + c->mloc;
+    a.n = c->n; a.n16 = c->n16; a.m = c->mloc; a.A = c->Afull.get(); a.astride = c->astride; a.C = c->Cfull.get();
+    a.y = c->chk.dev(); a.tau = tau; a.eye = eye_now;
+    a.Sout = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
+    a.L = ch->L.get(); a.W = ch->Dinv.get(); a.out = c->chk.dev() + c->mloc;
     yo[c->mloc] = -1.0;
     if (hdm_small_check(a, g.stream) || hipStreamSynchronize(g.stream) != hipSuccess) { *rc = HDSDP_RETCODE_FAILED; return 0; }
     const int info = (int) yo[c->mloc];
@@ -653,13 +641,13 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
 void cone_update(void *cd, double tau, double *y) {
     StatScope stat_(ST_ASSEMBLE_FACTOR, __func__);
     ((MiCone *) cd)->fac_ok = false;          // S moves, its factor does not follow
-    cone_assemble((MiCone *) cd, tau, y, ((MiCone *) cd)->S);
+    cone_assemble((MiCone *) cd, tau, y, ((MiCone *) cd)->S.get());
 }
 
 hdsdp_retcode cone_factor_S(MiCone *c, int *isPsd) {
     MiLin *l = (MiLin *) c->dualFactor->chol;
     c->fac_ok = false;
-    RC(l->ch.load_device(c->S, c->n16, g.stream));
+    RC(l->ch.load_device(c->S.get(), c->n16, g.stream));
     int info = 0;
     RC(l->ch.factor(g.stream, &info));
     c->dualFactor->nFactorizes += 1;
@@ -671,10 +659,10 @@ hdsdp_retcode cone_factor_S(MiCone *c, int *isPsd) {
 // primal recovery are factored here so that the factor of the current S stays valid
 hdsdp_retcode cone_checker(MiCone *c, HdmChol **out) {
     if (!c->checker) {
-        c->checker = new HdmChol();
+        c->checker.reset(new HdmChol());
         if (c->checker->init(c->n)) return HDSDP_RETCODE_MEMORY;
     }
-    *out = c->checker;
+    *out = c->checker.get();
     return HDSDP_RETCODE_OK;
 }
 
@@ -682,7 +670,7 @@ hdsdp_retcode cone_factor_check(MiCone *c, int *isPsd) {
     HdmChol *ch = nullptr;
     RC(cone_checker(c, &ch));
     int info = 0;
-    if (ch->load_device(c->Scheck, c->n16, g.stream) || ch->factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
+    if (ch->load_device(c->Scheck.get(), c->n16, g.stream) || ch->factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
     if (isPsd) *isPsd = (info == 0);
     return HDSDP_RETCODE_OK;
 }
@@ -696,7 +684,7 @@ hdsdp_retcode cone_interior_expert(void *cd, double dCCoef, double dACoefScal, d
     std::vector<double> ys(std::max(1, c->m), 0.0);
     for (int i = 0; i < c->m; ++i) ys[i] = -dACoefScal * (dACoef ? dACoef[i] : 0.0);   // cone_assemble subtracts
     const double eye = dEyeCoef + c->perturb;
-    double *target = (whichBuffer == 0) ? c->S : c->Scheck;
+    double *target = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     {
         hdsdp_retcode rcs;
         if (cone_small_check(c, dCCoef, ys.data(), &eye, whichBuffer, isInterior, &rcs) == 0) return rcs;
@@ -711,11 +699,11 @@ hdsdp_retcode cone_interior_expert(void *cd, double dCCoef, double dACoefScal, d
 hdsdp_retcode cone_axpy_check(void *cd, double dStep, int whichBuffer, int *isInterior) {
     StatScope stat_(ST_ASSEMBLE_FACTOR, __func__);
     MiCone *c = (MiCone *) cd;
-    if (!c->dS) return HDSDP_RETCODE_FAILED;
+    if (!c->dS.get()) return HDSDP_RETCODE_FAILED;
     const long cnt = (long) c->n16 * c->n16;
-    double *target = (whichBuffer == 0) ? c->S : c->Scheck;
+    double *target = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     if (whichBuffer == 0) { c->pS_ok = false; c->fac_ok = false; }   // S moves without a point being named: the next request assembles it
-    RC(hdm_axpy_mat(target, c->S, c->dS, dStep, cnt, g.stream));
+    RC(hdm_axpy_mat(target, c->S.get(), c->dS.get(), dStep, cnt, g.stream));
     return (whichBuffer == 0) ? cone_factor_S(c, isInterior) : cone_factor_check(c, isInterior);
 }
 
@@ -730,7 +718,7 @@ hdsdp_retcode cone_interior(void *cd, double tau, double *y, int *isInterior) {
         hdsdp_retcode rcs;
         if (cone_small_check(c, tau, y, nullptr, 0, isInterior, &rcs) == 0) return rcs;
     }
-    RC(cone_assemble(c, tau, y, c->S));
+    RC(cone_assemble(c, tau, y, c->S.get()));
     return cone_factor_S(c, isInterior);
 }
 
@@ -743,12 +731,12 @@ hdsdp_retcode cone_barrier(void *cd, double tau, double *y, int whichBuffer, dou
         hdsdp_retcode rcs;
         if (cone_small_check(c, tau, y, nullptr, 0, &psd, &rcs) == 0) { if (rcs != HDSDP_RETCODE_OK || !psd) return HDSDP_RETCODE_FAILED; }
         else {
-            RC(cone_assemble(c, tau, y, c->S));
+            RC(cone_assemble(c, tau, y, c->S.get()));
             if (cone_factor_S(c, &psd) != HDSDP_RETCODE_OK || !psd) return HDSDP_RETCODE_FAILED;
         }
     }
     {   // a factor that came from the single-launch check brought its log det along
-        const HdmChol *fq = (whichBuffer == 0) ? &((MiLin *) c->dualFactor->chol)->ch : c->checker;
+        const HdmChol *fq = (whichBuffer == 0) ? &((MiLin *) c->dualFactor->chol)->ch : c->checker.get();
         if (fq && fq->factored && fq->logdet_ok) { *logdet = fq->logdet_val; return HDSDP_RETCODE_OK; }
     }
     std::vector<double> d(c->n);
@@ -775,18 +763,18 @@ hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *
     if (!(*maxStep > 0.0) || !(*maxStep < 1e6)) return HDSDP_RETCODE_OK;
     const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
     if (!c->safe) {
-        c->safe = new HdmChol();
+        c->safe.reset(new HdmChol());
         if (c->safe->init(c->n)) return HDSDP_RETCODE_MEMORY;
     }
-    if (!c->Ssafe) HIP_RC(hipMalloc((void **) &c->Ssafe, nn));
-    const double *Sb = (whichBuffer == 0) ? c->S : c->Scheck;
+    HIP_RC(c->Ssafe.reserve(nn / sizeof(double)));
+    const double *Sb = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     auto inside = [&](double step, bool *ok) -> int {
         int info = 0;
         // (checked at (1 - 1e-3) step: the reference's own acceptance tolerance (gamma < 1e-3).  A step that is alpha* to
         // rounding -- a rank-one dS, dS = -S -- or within that tolerance of it stands as the reference computed it, and
         // the driver's trajectory with it; what is caught is a test that stopped at the wrong eigenvalue)
-        if (hdm_axpy_mat(c->Ssafe, Sb, c->dS, (1.0 - 1e-3) * step, (long) c->n16 * c->n16, g.stream) ||
-            c->safe->load_device(c->Ssafe, c->n16, g.stream) || c->safe->factor(g.stream, &info)) return 1;
+        if (hdm_axpy_mat(c->Ssafe.get(), Sb, c->dS.get(), (1.0 - 1e-3) * step, (long) c->n16 * c->n16, g.stream) ||
+            c->safe->load_device(c->Ssafe.get(), c->n16, g.stream) || c->safe->factor(g.stream, &info)) return 1;
         *ok = (info == 0);
         return 0;
     };
@@ -794,13 +782,13 @@ hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *
     if (inside(*maxStep, &ok)) return HDSDP_RETCODE_FAILED;
     if (ok) return HDSDP_RETCODE_OK;
     if (!c->lanczos_fresh) {
-        c->lanczos_fresh = new HdmLanczos();
+        c->lanczos_fresh.reset(new HdmLanczos());
         if (c->lanczos_fresh->init(c->n)) return HDSDP_RETCODE_MEMORY;
     }
     c->lanczos_fresh->nComputed = 0;
     double step = *maxStep, fresh = INFINITY;
     int steps = 0;
-    if (c->lanczos_fresh->solve(fac->Linv, fac->npad, c->dS, c->n16, g.stream, &fresh, &steps) == 0 && fresh < step) step = fresh;
+    if (c->lanczos_fresh->solve(fac->Linv.get(), fac->npad, c->dS.get(), c->n16, g.stream, &fresh, &steps) == 0 && fresh < step) step = fresh;
     for (int it = 0; it < 64; ++it) {
         if (inside(step, &ok)) return HDSDP_RETCODE_FAILED;
         if (ok) break;
@@ -820,35 +808,35 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
     StatScope stat_(ST_RATIO, __func__);
     MiCone *c = (MiCone *) cd;
     MiLin *l = (MiLin *) c->dualFactor->chol;
-    HdmChol *fac = (whichBuffer == 0) ? &l->ch : c->checker;   // LTarget, :1661-1665
+    HdmChol *fac = (whichBuffer == 0) ? &l->ch : c->checker.get();   // LTarget, :1661-1665
     if (!fac || !fac->factored) return HDSDP_RETCODE_FAILED;
     const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
-    if (!c->dS) {
-        HIP_RC(hipMalloc((void **) &c->dS, nn));
-        HIP_RC(hdm_memset_sync(c->dS, 0, nn));
+    if (!c->dS.get()) {
+        HIP_RC(c->dS.alloc(nn / sizeof(double)));
+        HIP_RC(hdm_memset_sync(c->dS.get(), 0, nn));
     }
     const double eye = dAdaRatio * c->Rd;
-    if (cone_assemble(c, dTauStep, dy, c->dS, &eye)) return HDSDP_RETCODE_FAILED;
+    if (cone_assemble(c, dTauStep, dy, c->dS.get(), &eye)) return HDSDP_RETCODE_FAILED;
     if (c->n == 1) {   // :1668-1675
         double s0 = 0.0, d0 = 0.0;
-        HIP_RC(hipMemcpyAsync(&d0, c->dS, sizeof(double), hipMemcpyDeviceToHost, g.stream));
-        HIP_RC(hipMemcpyAsync(&s0, (whichBuffer == 0) ? c->S : c->Scheck, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+        HIP_RC(hipMemcpyAsync(&d0, c->dS.get(), sizeof(double), hipMemcpyDeviceToHost, g.stream));
+        HIP_RC(hipMemcpyAsync(&s0, (whichBuffer == 0) ? c->S.get() : c->Scheck.get(), sizeof(double), hipMemcpyDeviceToHost, g.stream));
         HIP_RC(hipStreamSynchronize(g.stream));
         // (the reference tests d0 > 0, which turns d0 == 0 -- a zero step matrix -- into -s0 / 0 = -inf: a step of minus
         // infinity for a direction that can be followed without limit)
         *maxStep = (d0 >= 0.0) ? INFINITY : (-s0 / d0);
         return HDSDP_RETCODE_OK;
     }
-    RC(hdm_mirror_lower(c->dS, c->n16, c->n, g.stream));
+    RC(hdm_mirror_lower(c->dS.get(), c->n16, c->n, g.stream));
     if (fac->invert_factor(g.stream)) return HDSDP_RETCODE_FAILED;
     if (!c->lanczos) {
-        c->lanczos = new HdmLanczos();
+        c->lanczos.reset(new HdmLanczos());
         if (c->lanczos->init(c->n)) return HDSDP_RETCODE_MEMORY;
     }
     int steps = 0;
     static const bool dbg = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e); }();
     const auto t0 = std::chrono::steady_clock::now();
-    if (c->lanczos->solve(fac->Linv, fac->npad, c->dS, c->n16, g.stream, maxStep, &steps)) return HDSDP_RETCODE_FAILED;
+    if (c->lanczos->solve(fac->Linv.get(), fac->npad, c->dS.get(), c->n16, g.stream, maxStep, &steps)) return HDSDP_RETCODE_FAILED;
     if (dbg) fprintf(stderr, "[hdsdp_mi355x ratio] n %d: %d Lanczos steps, step %.6e, solve %.1f us\n", c->n, steps, *maxStep,
                      1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return ratio_safeguard(c, fac, whichBuffer, maxStep);
@@ -945,29 +933,28 @@ int cone_data_norms(MiCone *c, double *rows_abs, double *rows_fro, double *obj_a
         coeff_norms(c->blk.obj, c->n, &oa, &of2);
         oa *= c->objScal; of2 *= c->objScal * c->objScal;
     } else {
-        double *tmp = nullptr;
-        HDM_HIP_CHECK(hipMalloc((void **) &tmp, sizeof(double) * 4));
-        HDM_HIP_CHECK(hipMemsetAsync(tmp, 0, sizeof(double) * 4, g.stream));
+        HdmBuf<double> tmp;
+        HDM_HIP_CHECK(tmp.alloc(4));
+        HDM_HIP_CHECK(hipMemsetAsync(tmp.get(), 0, sizeof(double) * 4, g.stream));
         for (int q0 = 0, B = cone_batch(c); q0 < c->mloc; q0 += B) {
             const int nb = std::min(B, c->mloc - q0);
             const double *A = cone_rows(c, q0, nb);
-            if (!A) { (void) hipFree(tmp); return 1; }
-            hipLaunchKernelGGL(mi_low_norms_kernel, dim3(nb), dim3(256), 0, g.stream, A, c->astride, c->n, (long) c->n16, nb, 1, tmp);
+            if (!A) return 1;
+            hipLaunchKernelGGL(mi_low_norms_kernel, dim3(nb), dim3(256), 0, g.stream, A, c->astride, c->n, (long) c->n16, nb, 1, tmp.get());
         }
-        hipLaunchKernelGGL(mi_low_norms_kernel, dim3(1), dim3(256), 0, g.stream, c->Cfull, 0L, c->n, (long) c->n16, 1, 0, tmp + 2);
+        hipLaunchKernelGGL(mi_low_norms_kernel, dim3(1), dim3(256), 0, g.stream, c->Cfull.get(), 0L, c->n, (long) c->n16, 1, 0, tmp.get() + 2);
         double h[4];
-        HDM_HIP_CHECK(hipMemcpyAsync(h, tmp, sizeof(h), hipMemcpyDeviceToHost, g.stream));
+        HDM_HIP_CHECK(hipMemcpyAsync(h, tmp.get(), sizeof(h), hipMemcpyDeviceToHost, g.stream));
         HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
-        (void) hipFree(tmp);
+        tmp.reset();   // (before the all-reduce, as ever)
         ra = h[0]; rf2 = h[1]; oa = h[2]; of2 = h[3];
         if (c->world > 1 && c->allreduce) {   // rows are sharded: sum the two row totals over the ranks
-            double *dv = nullptr;
-            HDM_HIP_CHECK(hipMalloc((void **) &dv, sizeof(double) * 2));
+            HdmBuf<double> dv;
+            HDM_HIP_CHECK(dv.alloc(2));
             double two[2] = {ra, rf2};
-            HDM_HIP_CHECK(hipMemcpy(dv, two, sizeof(two), hipMemcpyHostToDevice));
-            if (c->allreduce(c->xctx, dv, 2)) return 1;
-            HDM_HIP_CHECK(hipMemcpy(two, dv, sizeof(two), hipMemcpyDeviceToHost));
-            (void) hipFree(dv);
+            HDM_HIP_CHECK(hipMemcpy(dv.get(), two, sizeof(two), hipMemcpyHostToDevice));
+            if (c->allreduce(c->xctx, dv.get(), 2)) return 1;
+            HDM_HIP_CHECK(hipMemcpy(two, dv.get(), sizeof(two), hipMemcpyDeviceToHost));
             ra = two[0]; rf2 = two[1];
         }
     }
@@ -992,8 +979,8 @@ void cone_scal(void *cd, double dScal) {
     StatScope stat_(ST_PRIMAL_UTIL, __func__);             // sdpDenseConeScal, :1604-1614: the objective is scaled, nothing else
     MiCone *c = (MiCone *) cd;
     const long cnt = (long) c->n16 * c->n16;
-    hipLaunchKernelGGL(mi_scale_kernel, dim3((unsigned) ((cnt + 255) / 256)), dim3(256), 0, g.stream, c->Cfull, cnt, dScal);
-    if (c->CL) hipLaunchKernelGGL(mi_scale_kernel, dim3((unsigned) ((c->astride + 255) / 256)), dim3(256), 0, g.stream, c->CL, c->astride, dScal);
+    hipLaunchKernelGGL(mi_scale_kernel, dim3((unsigned) ((cnt + 255) / 256)), dim3(256), 0, g.stream, c->Cfull.get(), cnt, dScal);
+    if (c->CL.get()) hipLaunchKernelGGL(mi_scale_kernel, dim3((unsigned) ((c->astride + 255) / 256)), dim3(256), 0, g.stream, c->CL.get(), c->astride, dScal);
     c->objScal *= dScal;
     c->norms_ready = false;
     c->pS_ok = c->pD_ok = false;     // S and dS were assembled with the old objective: no short-cut from them (cone_assemble)
@@ -1005,9 +992,9 @@ static int cone_upload_X(MiCone *c, const double *X, long *ldx) {
     MiLin *l = (MiLin *) c->dualFactor->chol;
     const long ld = l->ch.npad;
     const size_t np2 = sizeof(double) * (size_t) ld * ld;
-    if (!c->Xup) HDM_HIP_CHECK(hipMalloc((void **) &c->Xup, np2));   // (Xinv / Yinv belong to the builders, sized per path)
-    HDM_HIP_CHECK(hipMemsetAsync(c->Xup, 0, np2, g.stream));
-    HDM_HIP_CHECK(hipMemcpy2DAsync(c->Xup, sizeof(double) * ld, X, sizeof(double) * c->n, sizeof(double) * c->n, c->n,
+    HDM_HIP_CHECK(c->Xup.reserve(np2 / sizeof(double)));   // (Xinv / Yinv belong to the builders, sized per path)
+    HDM_HIP_CHECK(hipMemsetAsync(c->Xup.get(), 0, np2, g.stream));
+    HDM_HIP_CHECK(hipMemcpy2DAsync(c->Xup.get(), sizeof(double) * ld, X, sizeof(double) * c->n, sizeof(double) * c->n, c->n,
                                    hipMemcpyHostToDevice, g.stream));
     *ldx = ld;
     return 0;
@@ -1023,27 +1010,27 @@ void cone_build_primal_dir(void *cd, void *kktv, double *X, double *XSX, int iDu
     MiCone *c = (MiCone *) cd;
     const int n = c->n;
     long ldx = 0;
-    const double *D = iDualMat ? c->S : c->dS;
+    const double *D = iDualMat ? c->S.get() : c->dS.get();
     if (!D) { fprintf(stderr, "[hdsdp_mi355x] primal direction: no dual step has been formed yet\n"); return; }
     if (cone_upload_X(c, X, &ldx)) return;
     const size_t np2 = sizeof(double) * (size_t) ldx * ldx;
-    if (!c->Pr1 && hipMalloc((void **) &c->Pr1, np2) != hipSuccess) return;
-    if (!c->Pr2 && hipMalloc((void **) &c->Pr2, np2) != hipSuccess) return;
+    if (c->Pr1.reserve(np2 / sizeof(double)) != hipSuccess) return;
+    if (c->Pr2.reserve(np2 / sizeof(double)) != hipSuccess) return;
     // Pr1 <- D as a full symmetric matrix (the resident copy has its lower triangle valid), zero padded
-    if (hipMemsetAsync(c->Pr1, 0, np2, g.stream) != hipSuccess) return;
-    if (hipMemcpy2DAsync(c->Pr1, sizeof(double) * ldx, D, sizeof(double) * c->n16, sizeof(double) * n, n,
+    if (hipMemsetAsync(c->Pr1.get(), 0, np2, g.stream) != hipSuccess) return;
+    if (hipMemcpy2DAsync(c->Pr1.get(), sizeof(double) * ldx, D, sizeof(double) * c->n16, sizeof(double) * n, n,
                          hipMemcpyDeviceToDevice, g.stream) != hipSuccess) return;
-    if (hdm_mirror_lower(c->Pr1, ldx, n, g.stream)) return;
+    if (hdm_mirror_lower(c->Pr1.get(), ldx, n, g.stream)) return;
     HdmGemmArgs q = {};
     q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE; q.ldc = ldx;
     // T = D X   (B operand element (j, k) = X(k, j): K-major)
-    q.A = c->Pr1; q.lda = ldx; q.a_kmajor = 0; q.B = c->Xup; q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr2;
+    q.A = c->Pr1.get(); q.lda = ldx; q.a_kmajor = 0; q.B = c->Xup.get(); q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr2.get();
     if (hdm_launch_gemm(q, g.stream)) return;
     // P = X^T T   (A operand element (i, k) = X(k, i): K-major; B operand element (j, k) = T(k, j): K-major)
-    q.A = c->Xup; q.lda = ldx; q.a_kmajor = 1; q.B = c->Pr2; q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr1;
+    q.A = c->Xup.get(); q.lda = ldx; q.a_kmajor = 1; q.B = c->Pr2.get(); q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr1.get();
     if (hdm_launch_gemm(q, g.stream)) return;
     std::vector<double> h((size_t) n * n);
-    if (hipMemcpy2DAsync(h.data(), sizeof(double) * n, c->Pr1, sizeof(double) * ldx, sizeof(double) * n, n,
+    if (hipMemcpy2DAsync(h.data(), sizeof(double) * n, c->Pr1.get(), sizeof(double) * ldx, sizeof(double) * n, n,
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess) return;
     if (hipStreamSynchronize(g.stream) != hipSuccess) return;
     for (size_t e = 0; e < h.size(); ++e) XSX[e] += h[e];
@@ -1053,50 +1040,51 @@ void cone_a_times_x(void *cd, double *X, double *ATimesX) {
     StatScope stat_(ST_PRIMAL_UTIL, __func__);   // sdpDenseConeATimesX, :2470-2477: y_i += <A_i, X>
     MiCone *c = (MiCone *) cd;
     long ldx = 0;
-    double *out = nullptr;
+    HdmBuf<double> out_own;   // per call, as ever: freed on return
     if (cone_upload_X(c, X, &ldx)) return;
-    if (hipMalloc((void **) &out, sizeof(double) * 2 * (size_t) c->m) != hipSuccess) return;
+    if (out_own.alloc(2 * (size_t) c->m) != hipSuccess) return;
+    double *out = out_own.get();
     (void) hipMemsetAsync(out, 0, sizeof(double) * 2 * (size_t) c->m, g.stream);
     // A is stored in A_L form: <A, X> = 2 <A_L, X> for symmetric X
-    if (cone_sym_dot2(c, c->Xup, nullptr, ldx, out, out + c->m, 2.0, 0.0) == 0) {
+    if (cone_sym_dot2(c, c->Xup.get(), nullptr, ldx, out, out + c->m, 2.0, 0.0) == 0) {
         if (c->world > 1 && c->allreduce) { (void) hipStreamSynchronize(g.stream); (void) c->allreduce(c->xctx, out, c->m); }
         std::vector<double> h(c->m);
         if (hipMemcpyAsync(h.data(), out, sizeof(double) * c->m, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
             hipStreamSynchronize(g.stream) == hipSuccess)
             for (int i = 0; i < c->m; ++i) ATimesX[i] += h[i];
     }
-    (void) hipFree(out);
 }
 
 static double cone_dot_with(MiCone *c, const double *dev, long ldd, int lower_valid, double *X) {
     long ldx = 0;
-    double *out = nullptr, h = NAN;
+    HdmBuf<double> out_own;   // per call, as ever: freed on return
+    double h = NAN;
     if (cone_upload_X(c, X, &ldx)) return NAN;
-    if (hipMalloc((void **) &out, sizeof(double)) != hipSuccess) return NAN;
+    if (out_own.alloc(1) != hipSuccess) return NAN;
+    double *out = out_own.get();
     (void) hipMemsetAsync(out, 0, sizeof(double), g.stream);
-    if (lower_valid) hipLaunchKernelGGL(mi_lower_dot_kernel, dim3(1), dim3(256), 0, g.stream, dev, ldd, c->Xup, ldx, c->n, out);
-    else hipLaunchKernelGGL(mi_mat_dot_kernel, dim3(1), dim3(256), 0, g.stream, dev, ldd, c->Xup, ldx, c->n, 0, 1.0, out);
+    if (lower_valid) hipLaunchKernelGGL(mi_lower_dot_kernel, dim3(1), dim3(256), 0, g.stream, dev, ldd, c->Xup.get(), ldx, c->n, out);
+    else hipLaunchKernelGGL(mi_mat_dot_kernel, dim3(1), dim3(256), 0, g.stream, dev, ldd, c->Xup.get(), ldx, c->n, 0, 1.0, out);
     if (hipMemcpyAsync(&h, out, sizeof(double), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
         hipStreamSynchronize(g.stream) != hipSuccess) h = NAN;
-    (void) hipFree(out);
     return h;
 }
 double cone_trace_cx(void *cd, double *X) {
     StatScope stat_(ST_PRIMAL_UTIL, __func__);   // sdpDenseConeTraceCX, :2520-2523
     MiCone *c = (MiCone *) cd;
-    return cone_dot_with(c, c->Cfull, c->n16, 0, X);
+    return cone_dot_with(c, c->Cfull.get(), c->n16, 0, X);
 }
 double cone_x_dot_s(void *cd, double *X) {
     StatScope stat_(ST_PRIMAL_UTIL, __func__);    // sdpDenseConeXDotS, :2549-2560 (S is lower-valid: fds_dot_fds, dense_opts.c:134-156)
     MiCone *c = (MiCone *) cd;
-    return cone_dot_with(c, c->S, c->n16, 1, X);
+    return cone_dot_with(c, c->S.get(), c->n16, 1, X);
 }
 void cone_get_dual(void *cd, double *dConeDual, double *dummy) {
     StatScope stat_(ST_PRIMAL_UTIL, __func__);   // sdpDenseConeGetDual, :2494-2506: S, symmetrised
     (void) dummy;
     MiCone *c = (MiCone *) cd;
     const int n = c->n;
-    if (hipMemcpy2DAsync(dConeDual, sizeof(double) * n, c->S, sizeof(double) * c->n16, sizeof(double) * n, n,
+    if (hipMemcpy2DAsync(dConeDual, sizeof(double) * n, c->S.get(), sizeof(double) * c->n16, sizeof(double) * n, n,
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess || hipStreamSynchronize(g.stream) != hipSuccess) return;
     for (int j = 0; j < n; ++j)
         for (int i = j + 1; i < n; ++i) dConeDual[(size_t) j + (size_t) i * n] = dConeDual[(size_t) i + (size_t) j * n];
@@ -1115,46 +1103,46 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
     const int n = c->n;
     const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
     auto fail = [](const char *what) { fprintf(stderr, "[hdsdp_mi355x] primal recovery: %s\n", what); };
-    if (cone_assemble(c, 1.0, y, c->Scheck, &zero)) return fail("S assembly failed");
+    if (cone_assemble(c, 1.0, y, c->Scheck.get(), &zero)) return fail("S assembly failed");
     HdmChol *chp = nullptr;
     if (cone_checker(c, &chp) != HDSDP_RETCODE_OK) return fail("out of memory");
     HdmChol &ch = *chp;
     int info = 0;
-    if (ch.load_device(c->Scheck, c->n16, g.stream) || ch.factor(g.stream, &info)) return fail("factorisation failed");
+    if (ch.load_device(c->Scheck.get(), c->n16, g.stream) || ch.factor(g.stream, &info)) return fail("factorisation failed");
     if (info != 0) {
         if (stat_trace()) fprintf(stderr, "[hdsdp_mi355x trace]     primal recovery: factorisation stopped at pivot %d (runs %d, graph %d)\n", info, ch.factor_runs, ch.factor_graph ? 1 : 0);
         printf("Recovery step is infeasible\n");
         return;
     }
-    if (!c->dS) {
-        if (hipMalloc((void **) &c->dS, nn) != hipSuccess || hdm_memset_sync(c->dS, 0, nn) != hipSuccess) return fail("out of memory");
+    if (!c->dS.get()) {
+        if (c->dS.alloc(nn / sizeof(double)) != hipSuccess || hdm_memset_sync(c->dS.get(), 0, nn) != hipSuccess) return fail("out of memory");
     }
     std::vector<double> ndy(c->m);
     for (int i = 0; i < c->m; ++i) ndy[i] = -dy[i];           // cone_assemble subtracts: dS = + sum dy_i A_i
-    if (cone_assemble(c, 0.0, ndy.data(), c->dS, &zero)) return fail("dS assembly failed");
+    if (cone_assemble(c, 0.0, ndy.data(), c->dS.get(), &zero)) return fail("dS assembly failed");
     if (hipStreamSynchronize(g.stream) != hipSuccess) return fail("stream");   // ndy is read by an async copy
-    if (hdm_mirror_lower(c->dS, c->n16, n, g.stream)) return fail("mirror");
+    if (hdm_mirror_lower(c->dS.get(), c->n16, n, g.stream)) return fail("mirror");
     if (ch.invert_factor(g.stream)) return fail("triangular inverse failed");
     const size_t np2 = sizeof(double) * (size_t) ch.npad * ch.npad;
-    if (!c->Pr1 && hipMalloc((void **) &c->Pr1, np2) != hipSuccess) return fail("out of memory");
-    if (!c->Pr2 && hipMalloc((void **) &c->Pr2, np2) != hipSuccess) return fail("out of memory");
+    if (c->Pr1.reserve(np2 / sizeof(double)) != hipSuccess) return fail("out of memory");
+    if (c->Pr2.reserve(np2 / sizeof(double)) != hipSuccess) return fail("out of memory");
     HdmGemmArgs q = {};
     q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE; q.ldc = ch.npad;
     // T1 = W dS          (W = Linv)
-    q.A = ch.Linv; q.lda = ch.npad; q.a_kmajor = 0; q.B = c->dS; q.ldb = c->n16; q.b_kmajor = 0; q.C = c->Pr1;
+    q.A = ch.Linv.get(); q.lda = ch.npad; q.a_kmajor = 0; q.B = c->dS.get(); q.ldb = c->n16; q.b_kmajor = 0; q.C = c->Pr1.get();
     if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
     // Z = T1 W^T
-    q.A = c->Pr1; q.lda = ch.npad; q.a_kmajor = 0; q.B = ch.Linv; q.ldb = ch.npad; q.b_kmajor = 0; q.C = c->Pr2;
+    q.A = c->Pr1.get(); q.lda = ch.npad; q.a_kmajor = 0; q.B = ch.Linv.get(); q.ldb = ch.npad; q.b_kmajor = 0; q.C = c->Pr2.get();
     if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
-    if (hdm_sym_scale(c->Pr2, ch.npad, c->n16, 1.0, 1.0, g.stream)) return fail("sym");
+    if (hdm_sym_scale(c->Pr2.get(), ch.npad, c->n16, 1.0, 1.0, g.stream)) return fail("sym");
     // T2 = W^T Z
-    q.A = ch.Linv; q.lda = ch.npad; q.a_kmajor = 1; q.B = c->Pr2; q.ldb = ch.npad; q.b_kmajor = 0; q.C = c->Pr1;
+    q.A = ch.Linv.get(); q.lda = ch.npad; q.a_kmajor = 1; q.B = c->Pr2.get(); q.ldb = ch.npad; q.b_kmajor = 0; q.C = c->Pr1.get();
     if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
     // X = T2 W
-    q.A = c->Pr1; q.lda = ch.npad; q.a_kmajor = 0; q.B = ch.Linv; q.ldb = ch.npad; q.b_kmajor = 1; q.C = c->Pr2;
+    q.A = c->Pr1.get(); q.lda = ch.npad; q.a_kmajor = 0; q.B = ch.Linv.get(); q.ldb = ch.npad; q.b_kmajor = 1; q.C = c->Pr2.get();
     if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
-    if (hdm_sym_scale(c->Pr2, ch.npad, n, 0.0, dBarrierMu, g.stream)) return fail("sym");
-    if (hipMemcpy2DAsync(X, sizeof(double) * n, c->Pr2, sizeof(double) * ch.npad, sizeof(double) * n, n,
+    if (hdm_sym_scale(c->Pr2.get(), ch.npad, n, 0.0, dBarrierMu, g.stream)) return fail("sym");
+    if (hipMemcpy2DAsync(X, sizeof(double) * n, c->Pr2.get(), sizeof(double) * ch.npad, sizeof(double) * n, n,
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess) return fail("copy");
     (void) hipStreamSynchronize(g.stream);
 }

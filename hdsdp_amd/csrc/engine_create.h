@@ -14,7 +14,7 @@ int grp_sum_launch(const double *const *ptrs, int W, long lo, long cnt, double *
 // into a packed image first -- a 16 MB memset and an 800 K-entry scatter per row on one core, one synchronisation per 16 rows:
 // most of the 14 s the reference's driver spent in its pre-solver at n = m = 2000.)
 struct RowUploader {
-    struct Stage { int *hi = nullptr, *di = nullptr; double *hv = nullptr, *dv = nullptr; long *hb = nullptr, *db = nullptr; hipEvent_t ev = nullptr; bool used = false; } st[2];
+    struct Stage { HdmPinned<int> hi; HdmBuf<int> di; HdmPinned<double> hv; HdmBuf<double> dv; HdmPinned<long> hb; HdmBuf<long> db; hipEvent_t ev = nullptr; bool used = false; } st[2];
     long cap = 0;
     static constexpr int rowcap = 1024;
     int which = 0;
@@ -29,11 +29,11 @@ struct RowUploader {
         // of many small blocks creates many cones: each would otherwise pin 384 MiB of host memory for a few KB of entries)
         cap = std::max(maxrow, std::min((long) ((192L << 20) / 12), std::max(1L, total)));
         for (auto &b : st) {
-            if (hipHostMalloc((void **) &b.hi, sizeof(int) * (size_t) cap, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **) &b.hv, sizeof(double) * (size_t) cap, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **) &b.hb, sizeof(long) * (rowcap + 1), hipHostMallocDefault) != hipSuccess ||
-                hipMalloc((void **) &b.di, sizeof(int) * (size_t) cap) != hipSuccess || hipMalloc((void **) &b.dv, sizeof(double) * (size_t) cap) != hipSuccess ||
-                hipMalloc((void **) &b.db, sizeof(long) * (rowcap + 1)) != hipSuccess || hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess)
+            if (b.hi.alloc((size_t) cap) != hipSuccess ||
+                b.hv.alloc((size_t) cap) != hipSuccess ||
+                b.hb.alloc(rowcap + 1) != hipSuccess ||
+                b.di.alloc((size_t) cap) != hipSuccess || b.dv.alloc((size_t) cap) != hipSuccess ||
+                b.db.alloc(rowcap + 1) != hipSuccess || hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess)
                 return 1;
         }
         return 0;
@@ -46,27 +46,28 @@ struct RowUploader {
             if (b.used && hipEventSynchronize(b.ev) != hipSuccess) return 1;   // its previous group has left the buffer
             int nc = 0;
             long tot = 0, mx = 0;
-            b.hb[0] = 0;
+            long *hb = b.hb.get();
+            hb[0] = 0;
             while (r0 + nc < q0 + count && nc < rowcap) {
                 const long k = (long) c->blk.rows[c->own[r0 + nc]].idx.size();
                 if (nc > 0 && tot + k > cap) break;
                 tot += k; mx = std::max(mx, k); nc += 1;
-                b.hb[nc] = tot;
+                hb[nc] = tot;
             }
             std::atomic<int> next{0};
             mi_parallel(tot >= (1L << 20) ? 0 : 1, [&](int) {
                 for (int q = next.fetch_add(1); q < nc; q = next.fetch_add(1)) {
                     const MiCoeff &co = c->blk.rows[c->own[r0 + q]];
                     if (co.idx.empty()) continue;
-                    memcpy(b.hi + b.hb[q], co.idx.data(), sizeof(int) * co.idx.size());
-                    memcpy(b.hv + b.hb[q], co.val.data(), sizeof(double) * co.val.size());
+                    memcpy(b.hi.get() + hb[q], co.idx.data(), sizeof(int) * co.idx.size());
+                    memcpy(b.hv.get() + hb[q], co.val.data(), sizeof(double) * co.val.size());
                 }
             });
             if (tot > 0) {
-                if (hipMemcpyAsync(b.di, b.hi, sizeof(int) * (size_t) tot, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
-                    hipMemcpyAsync(b.dv, b.hv, sizeof(double) * (size_t) tot, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
-                    hipMemcpyAsync(b.db, b.hb, sizeof(long) * (size_t) (nc + 1), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
-                    hdm_scatter_low(b.di, b.dv, b.db, mx, dst + (long) (r0 - q0) * c->astride, c->astride, c->n, c->n16, nc, g.stream))
+                if (hipMemcpyAsync(b.di.get(), b.hi.get(), sizeof(int) * (size_t) tot, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+                    hipMemcpyAsync(b.dv.get(), b.hv.get(), sizeof(double) * (size_t) tot, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+                    hipMemcpyAsync(b.db.get(), hb, sizeof(long) * (size_t) (nc + 1), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+                    hdm_scatter_low(b.di.get(), b.dv.get(), b.db.get(), mx, dst + (long) (r0 - q0) * c->astride, c->astride, c->n, c->n16, nc, g.stream))
                     return 1;
             }
             if (hipEventRecord(b.ev, g.stream) != hipSuccess) return 1;
@@ -75,15 +76,9 @@ struct RowUploader {
         }
         return 0;
     }
-    ~RowUploader() {
+    ~RowUploader() {   // (the stages' buffers go after this body: once their last copies have left them)
         for (auto &b : st) {
             if (b.ev) (void) hipEventSynchronize(b.ev);
-            if (b.hi) (void) hipHostFree(b.hi);
-            if (b.hv) (void) hipHostFree(b.hv);
-            if (b.hb) (void) hipHostFree(b.hb);
-            if (b.di) (void) hipFree(b.di);
-            if (b.dv) (void) hipFree(b.dv);
-            if (b.db) (void) hipFree(b.db);
             if (b.ev) (void) hipEventDestroy(b.ev);
         }
     }
@@ -92,26 +87,25 @@ struct RowUploader {
 static int upload_objective(MiCone *c) {   // full symmetric (it feeds the S assembly), through a packed image
     const long P = (long) c->n * (c->n + 1) / 2;
     const long nn = (long) c->n16 * c->n16;
-    double *stage_dev = nullptr, *stage_host = nullptr;
-    HDM_HIP_CHECK(hipMalloc((void **) &stage_dev, sizeof(double) * (size_t) P));
-    HDM_HIP_CHECK(hipHostMalloc((void **) &stage_host, sizeof(double) * (size_t) P, hipHostMallocDefault));
-    memset(stage_host, 0, sizeof(double) * (size_t) P);
-    for (size_t e = 0; e < c->blk.obj.idx.size(); ++e) stage_host[c->blk.obj.idx[e]] = c->blk.obj.val[e];
-    HDM_HIP_CHECK(hipMemcpyAsync(stage_dev, stage_host, sizeof(double) * (size_t) P, hipMemcpyHostToDevice, g.stream));
-    if (hdm_unpack_sym(stage_dev, P, c->Cfull, nn, c->n, c->n16, 1, g.stream)) return 1;
+    HdmBuf<double> stage_dev;
+    HdmPinned<double> stage_host;
+    HDM_HIP_CHECK(stage_dev.alloc((size_t) P));
+    HDM_HIP_CHECK(stage_host.alloc((size_t) P));
+    memset(stage_host.get(), 0, sizeof(double) * (size_t) P);
+    for (size_t e = 0; e < c->blk.obj.idx.size(); ++e) stage_host.get()[c->blk.obj.idx[e]] = c->blk.obj.val[e];
+    HDM_HIP_CHECK(hipMemcpyAsync(stage_dev.get(), stage_host.get(), sizeof(double) * (size_t) P, hipMemcpyHostToDevice, g.stream));
+    if (hdm_unpack_sym(stage_dev.get(), P, c->Cfull.get(), nn, c->n, c->n16, 1, g.stream)) return 1;
     HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
-    (void) hipFree(stage_dev);
-    (void) hipHostFree(stage_host);
     return 0;
 }
 
 // every owned constraint resident as an A_L form in skyline storage
 static int upload_dense_rows(MiCone *c) {
-    HDM_HIP_CHECK(hipMalloc((void **) &c->Afull, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc) + hdm_operand_pad(c->n16)));
-    HDM_HIP_CHECK(hdm_memset_sync(c->Afull, 0, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc)));
+    HDM_HIP_CHECK(c->Afull.alloc((size_t) c->astride * std::max(1, c->mloc), hdm_operand_pad(c->n16)));
+    HDM_HIP_CHECK(hdm_memset_sync(c->Afull.get(), 0, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc)));
     {
         RowUploader up;
-        if (up.init(c) || up.rows(c, 0, c->mloc, c->Afull) || hipStreamSynchronize(g.stream) != hipSuccess) return 1;
+        if (up.init(c) || up.rows(c, 0, c->mloc, c->Afull.get()) || hipStreamSynchronize(g.stream) != hipSuccess) return 1;
     }
     return upload_objective(c);
 }
@@ -147,11 +141,11 @@ static int cone_alloc_batch(MiCone *c) {
     if (const char *e = getenv("HDM_BC")) bmax = std::max(1L, atol(e));
     const long launches = (c->mloc + bmax - 1) / bmax;
     c->Bs = (int) ((c->mloc + launches - 1) / launches);
-    if (hipMalloc((void **) &c->Abatch, sizeof(double) * (size_t) c->astride * c->Bs + hdm_operand_pad(c->n16)) != hipSuccess) {
+    if (c->Abatch.alloc((size_t) c->astride * c->Bs, hdm_operand_pad(c->n16)) != hipSuccess) {
         fprintf(stderr, "[hdsdp_mi355x] cannot allocate %.1f GiB for a batch of constraint matrices\n", (double) c->astride * c->Bs * 8 / (1 << 30));
         return 1;
     }
-    return hdm_memset_sync(c->Abatch, 0, sizeof(double) * (size_t) c->astride * c->Bs) != hipSuccess;
+    return hdm_memset_sync(c->Abatch.get(), 0, sizeof(double) * (size_t) c->astride * c->Bs) != hipSuccess;
 }
 
 // INGESTED rows that are too many to stay resident (round 5): batch after batch they are scattered into the batch buffer and
@@ -166,8 +160,8 @@ static int upload_streamed_rows(MiCone *c) {
         if (up.init(c)) return 1;
         bool bad = false;
         auto source = [&](int q0, int nb) -> const double * {
-            if (hipMemsetAsync(c->Abatch, 0, sizeof(double) * (size_t) c->astride * nb, g.stream) != hipSuccess || up.rows(c, q0, nb, c->Abatch)) { bad = true; return nullptr; }
-            return c->Abatch;
+            if (hipMemsetAsync(c->Abatch.get(), 0, sizeof(double) * (size_t) c->astride * nb, g.stream) != hipSuccess || up.rows(c, q0, nb, c->Abatch.get())) { bad = true; return nullptr; }
+            return c->Abatch.get();
         };
         if (hdm_zs_build_from(source, c->Bs, c->astride, c->mloc, c->astride, 1.0, &c->zs, g.stream) || bad) return 1;
         if (hipStreamSynchronize(g.stream) != hipSuccess) return 1;
@@ -235,7 +229,7 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
         }
     }
     if (cone_alloc_common(c)) return HDSDP_RETCODE_MEMORY;
-    c->trA = (double *) calloc(nRow, sizeof(double));
+    c->trA.assign((size_t) nRow, 0.0);
     for (int i = 0; i < nRow; ++i) c->trA[i] = c->blk.rows[i].trace;
     c->path = natural_path(c->blk, nRow, nCol, world);
     const char *force = getenv("HDSDP_MI355X_FORCE_GEMM");
@@ -259,15 +253,15 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
             for (int r = 0; r < nCol; ++r) hA[(size_t) q * c->n16 + r] = co.factor[r];
             hs[q] = co.sign;
         }
-        if (hipMalloc((void **) &c->Avec, av) != hipSuccess || hipMalloc((void **) &c->U, av) != hipSuccess ||
-            hipMalloc((void **) &c->V, av) != hipSuccess || hipMalloc((void **) &c->W, std::max(av, sizeof(double) * (size_t) c->n16 * c->n16)) != hipSuccess ||
-            hipMalloc((void **) &c->sgn, sizeof(double) * c->mloc16) != hipSuccess ||
-            hipMalloc((void **) &c->Gr1, sizeof(double) * (size_t) c->mloc16 * c->mloc16) != hipSuccess ||
-            hipMalloc((void **) &c->Ct, sizeof(double) * (size_t) c->n16 * c->n16) != hipSuccess ||
-            hipMalloc((void **) &c->Xinv, sizeof(double) * (size_t) c->n16 * c->n16) != hipSuccess)
+        if (c->Avec.alloc(av / sizeof(double)) != hipSuccess || c->U.alloc(av / sizeof(double)) != hipSuccess ||
+            c->V.alloc(av / sizeof(double)) != hipSuccess || c->W.alloc(std::max(av, sizeof(double) * (size_t) c->n16 * c->n16) / sizeof(double)) != hipSuccess ||
+            c->sgn.alloc(c->mloc16) != hipSuccess ||
+            c->Gr1.alloc((size_t) c->mloc16 * c->mloc16) != hipSuccess ||
+            c->Ct.alloc((size_t) c->n16 * c->n16) != hipSuccess ||
+            c->Xinv.alloc((size_t) c->n16 * c->n16) != hipSuccess)
             return HDSDP_RETCODE_MEMORY;
-        if (hdm_memcpy_h2d_sync(c->Avec, hA.data(), av) != hipSuccess ||
-            hdm_memcpy_h2d_sync(c->sgn, hs.data(), sizeof(double) * c->mloc16) != hipSuccess)
+        if (hdm_memcpy_h2d_sync(c->Avec.get(), hA.data(), av) != hipSuccess ||
+            hdm_memcpy_h2d_sync(c->sgn.get(), hs.data(), sizeof(double) * c->mloc16) != hipSuccess)
             return HDSDP_RETCODE_FAILED;
     }
     if (c->path == PATH_SPARSE) {
@@ -285,17 +279,17 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
         }
         const size_t nt = std::max<size_t>(1, ti.size());
         const size_t nn2 = sizeof(double) * (size_t) hdm_roundup(nCol, 128) * hdm_roundup(nCol, 128);
-        if (hipMalloc((void **) &c->sp_rp, sizeof(int) * rp.size()) != hipSuccess ||
-            hipMalloc((void **) &c->sp_ti, sizeof(int) * nt) != hipSuccess ||
-            hipMalloc((void **) &c->sp_tj, sizeof(int) * nt) != hipSuccess ||
-            hipMalloc((void **) &c->sp_tv, sizeof(double) * nt) != hipSuccess ||
-            hipMalloc((void **) &c->Xinv, nn2) != hipSuccess || hipMalloc((void **) &c->Yinv, nn2) != hipSuccess ||
-            hipMalloc((void **) &c->W, nn2) != hipSuccess || hipMalloc((void **) &c->Ct, nn2) != hipSuccess)
+        if (c->sp_rp.alloc(rp.size()) != hipSuccess ||
+            c->sp_ti.alloc(nt) != hipSuccess ||
+            c->sp_tj.alloc(nt) != hipSuccess ||
+            c->sp_tv.alloc(nt) != hipSuccess ||
+            c->Xinv.alloc(nn2 / sizeof(double)) != hipSuccess || c->Yinv.alloc(nn2 / sizeof(double)) != hipSuccess ||
+            c->W.alloc(nn2 / sizeof(double)) != hipSuccess || c->Ct.alloc(nn2 / sizeof(double)) != hipSuccess)
             return HDSDP_RETCODE_MEMORY;
-        if (hdm_memcpy_h2d_sync(c->sp_rp, rp.data(), sizeof(int) * rp.size()) != hipSuccess ||
-            (ti.size() && (hdm_memcpy_h2d_sync(c->sp_ti, ti.data(), sizeof(int) * ti.size()) != hipSuccess ||
-                           hdm_memcpy_h2d_sync(c->sp_tj, tj.data(), sizeof(int) * tj.size()) != hipSuccess ||
-                           hdm_memcpy_h2d_sync(c->sp_tv, tv.data(), sizeof(double) * tv.size()) != hipSuccess)))
+        if (hdm_memcpy_h2d_sync(c->sp_rp.get(), rp.data(), sizeof(int) * rp.size()) != hipSuccess ||
+            (ti.size() && (hdm_memcpy_h2d_sync(c->sp_ti.get(), ti.data(), sizeof(int) * ti.size()) != hipSuccess ||
+                           hdm_memcpy_h2d_sync(c->sp_tj.get(), tj.data(), sizeof(int) * tj.size()) != hipSuccess ||
+                           hdm_memcpy_h2d_sync(c->sp_tv.get(), tv.data(), sizeof(double) * tv.size()) != hipSuccess)))
             return HDSDP_RETCODE_FAILED;
     }
     if (hipStreamSynchronize(g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
@@ -323,18 +317,18 @@ static hdsdp_retcode make_synth_cone(MiCone **out, int nCol, int nRow, int rank,
         fprintf(stderr, "[hdsdp_mi355x] block n = %d, m = %d: %.1f GiB of constraint data are streamed (regenerated %d matrices at a time), not resident\n",
                 c->n, c->mloc, (double) c->astride * c->mloc * 8 / (1 << 30), c->Bs);
     } else {
-        if (hipMalloc((void **) &c->Afull, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc) + hdm_operand_pad(c->n16)) != hipSuccess) {
+        if (c->Afull.alloc((size_t) c->astride * std::max(1, c->mloc), hdm_operand_pad(c->n16)) != hipSuccess) {
             fprintf(stderr, "[hdsdp_mi355x] cannot allocate %.1f GiB for the constraint matrices\n",
                     (double) c->astride * c->mloc * 8 / (1 << 30));
             return HDSDP_RETCODE_MEMORY;
         }
-        if (hdm_memset_sync(c->Afull, 0, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc)) != hipSuccess) return HDSDP_RETCODE_FAILED;
+        if (hdm_memset_sync(c->Afull.get(), 0, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc)) != hipSuccess) return HDSDP_RETCODE_FAILED;
         for (int q = 0; q < c->mloc; ++q)  // owned rows are strided in the global numbering
-            if (hdm_synth_fill_low(c->Afull + (long) q * c->astride, c->astride, c->n, c->n16, c->own[q], 1, g.stream)) return HDSDP_RETCODE_FAILED;
+            if (hdm_synth_fill_low(c->Afull.get() + (long) q * c->astride, c->astride, c->n, c->n16, c->own[q], 1, g.stream)) return HDSDP_RETCODE_FAILED;
     }
-    if (hdm_synth_obj(c->Cfull, c->n, c->n16, c->m, g.stream)) return HDSDP_RETCODE_FAILED;
+    if (hdm_synth_obj(c->Cfull.get(), c->n, c->n16, c->m, g.stream)) return HDSDP_RETCODE_FAILED;
     // b_i = tr(A_i): diagonal draws only (host, m*n splitmix evaluations)
-    c->trA = (double *) calloc(nRow, sizeof(double));
+    c->trA.assign((size_t) nRow, 0.0);
     const uint64_t P = (uint64_t) nCol * (nCol + 1) / 2, gam = 0x9E3779B97F4A7C15ULL;
     for (int i = 0; i < nRow; ++i) {
         double tr = 0.0;

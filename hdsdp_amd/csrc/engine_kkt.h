@@ -152,7 +152,7 @@ hdsdp_retcode HKKTCreate(hdsdp_kkt **pHKKT) {
 static std::vector<int> rcm_order(int m, const std::vector<int> &beg, const std::vector<int> &idx) { return hdm_rcm_order(m, beg, idx); }
 
 // a linear-system object for a sparse Schur operator in TILE form: the same vtable, no dense factor behind it
-static hdsdp_retcode linsys_create_tiles(hdsdp_linsys_fp **pHLin, int nCol, HdmBsp *bsp) {
+static hdsdp_retcode linsys_create_tiles(hdsdp_linsys_fp **pHLin, int nCol, std::unique_ptr<HdmBsp> bsp) {
     hdsdp_linsys_fp *h = (hdsdp_linsys_fp *) calloc(1, sizeof(hdsdp_linsys_fp));
     if (!h) return HDSDP_RETCODE_MEMORY;
     h->nCol = nCol; h->LinType = HDSDP_LINSYS_SPARSE_DIRECT;
@@ -160,7 +160,7 @@ static hdsdp_retcode linsys_create_tiles(hdsdp_linsys_fp **pHLin, int nCol, HdmB
     h->cholPsdCheck = lin_psdcheck; h->cholFSolve = lin_fsolve; h->cholBSolve = lin_bsolve; h->cholSolve = lin_solve;
     h->cholGetDiag = lin_getdiag; h->cholInvert = lin_invert; h->cholDestroy = lin_destroy;
     MiLin *l = new MiLin();
-    l->n = nCol; l->type = HDSDP_LINSYS_SPARSE_DIRECT; l->csc_in = true; l->bsp = bsp;
+    l->n = nCol; l->type = HDSDP_LINSYS_SPARSE_DIRECT; l->csc_in = true; l->bsp = std::move(bsp);
     h->chol = l;
     *pHLin = h;
     return HDSDP_RETCODE_OK;
@@ -232,6 +232,7 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
             if (!HKKT->kktMatBeg || !HKKT->kktMatIdx) return HDSDP_RETCODE_MEMORY;
             memcpy(HKKT->kktMatBeg, beg.data(), sizeof(int) * ((size_t) nRow + 1));
             memcpy(HKKT->kktMatIdx, idx.data(), sizeof(int) * nnz);
+            // (kktMatElem is a field of the reference's own struct: it stays a raw pointer, freed in HKKTClear)
             if (hipHostMalloc((void **) &HKKT->kktMatElem, sizeof(double) * std::max<size_t>(1, nnz), hipHostMallocDefault) != hipSuccess)
                 return HDSDP_RETCODE_MEMORY;
             memset(HKKT->kktMatElem, 0, sizeof(double) * nnz);
@@ -241,15 +242,16 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
             // pattern of the Cholesky factor -- O(tiles of L) memory, a level-scheduled left-looking factorisation.  Taken when
             // those tiles are at most half of the dense lower triangle's (HDSDP_MI355X_KKT_TILES=0: never); otherwise the dense
             // device matrix factored on its block envelope, as in round 2.
-            HdmBsp *bsp = nullptr;
+            std::unique_ptr<HdmBsp> bsp_own;
             {
                 static const bool use_tiles = [] { const char *e = getenv("HDSDP_MI355X_KKT_TILES"); return !(e && atoi(e) == 0); }();
                 if (use_tiles && nRow > 2 * 128) {
-                    bsp = new HdmBsp();
-                    if (bsp->init(nRow, beg.data(), idx.data(), 0.5)) { bsp->destroy(); delete bsp; bsp = nullptr; }
+                    bsp_own.reset(new HdmBsp());
+                    if (bsp_own->init(nRow, beg.data(), idx.data(), 0.5)) bsp_own.reset();
                 }
             }
-            hdsdp_retcode rcs = bsp ? linsys_create_tiles(&HKKT->kktM, nRow, bsp) : HFpLinsysCreate(&HKKT->kktM, nRow, HDSDP_LINSYS_SPARSE_DIRECT);
+            const HdmBsp *bsp = bsp_own.get();   // (for the report below; the operator's linear system owns it from here)
+            hdsdp_retcode rcs = bsp ? linsys_create_tiles(&HKKT->kktM, nRow, std::move(bsp_own)) : HFpLinsysCreate(&HKKT->kktM, nRow, HDSDP_LINSYS_SPARSE_DIRECT);
             if (rcs != HDSDP_RETCODE_OK) return rcs;
             rcs = HFpLinsysSymbolic(HKKT->kktM, HKKT->kktMatBeg, HKKT->kktMatIdx);
             if (rcs != HDSDP_RETCODE_OK) return rcs;
@@ -258,12 +260,12 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
             for (int iCol = 0; iCol < nRow; ++iCol)
                 for (int q = beg[iCol]; q < beg[iCol + 1]; ++q) cols[q] = iCol;
             pv0->nnz = (long) nnz;
-            if (hipMalloc((void **) &pv0->sp_rows, sizeof(int) * std::max<size_t>(1, nnz)) != hipSuccess ||
-                hipMalloc((void **) &pv0->sp_cols, sizeof(int) * std::max<size_t>(1, nnz)) != hipSuccess ||
-                hipMalloc((void **) &pv0->sp_vals, sizeof(double) * std::max<size_t>(1, nnz)) != hipSuccess)
+            if (pv0->sp_rows.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
+                pv0->sp_cols.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
+                pv0->sp_vals.alloc(std::max<size_t>(1, nnz)) != hipSuccess)
                 return HDSDP_RETCODE_MEMORY;
-            if (hdm_memcpy_h2d_sync(pv0->sp_rows, idx.data(), sizeof(int) * nnz) != hipSuccess ||
-                hdm_memcpy_h2d_sync(pv0->sp_cols, cols.data(), sizeof(int) * nnz) != hipSuccess)
+            if (hdm_memcpy_h2d_sync(pv0->sp_rows.get(), idx.data(), sizeof(int) * nnz) != hipSuccess ||
+                hdm_memcpy_h2d_sync(pv0->sp_cols.get(), cols.data(), sizeof(int) * nnz) != hipSuccess)
                 return HDSDP_RETCODE_FAILED;
             // the pattern's block envelope: the blocked Cholesky of the (dense, mostly zero) device matrix stops each block
             // column where the envelope ends and the substitutions skip the blocks outside (HdmChol::set_envelope).  The
@@ -306,11 +308,11 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
                             if (r < c) std::swap(r, c);
                             prow[q] = r; pcol[q] = c;
                         }
-                        if (hipMalloc((void **) &pv0->sp_prow, sizeof(int) * std::max<size_t>(1, nnz)) != hipSuccess ||
-                            hipMalloc((void **) &pv0->sp_pcol, sizeof(int) * std::max<size_t>(1, nnz)) != hipSuccess)
+                        if (pv0->sp_prow.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
+                            pv0->sp_pcol.alloc(std::max<size_t>(1, nnz)) != hipSuccess)
                             return HDSDP_RETCODE_MEMORY;
-                        if (hdm_memcpy_h2d_sync(pv0->sp_prow, prow.data(), sizeof(int) * nnz) != hipSuccess ||
-                            hdm_memcpy_h2d_sync(pv0->sp_pcol, pcol.data(), sizeof(int) * nnz) != hipSuccess)
+                        if (hdm_memcpy_h2d_sync(pv0->sp_prow.get(), prow.data(), sizeof(int) * nnz) != hipSuccess ||
+                            hdm_memcpy_h2d_sync(pv0->sp_pcol.get(), pcol.data(), sizeof(int) * nnz) != hipSuccess)
                             return HDSDP_RETCODE_FAILED;
                         lm->perm = perm;
                         if (lm->ch.set_envelope(first_rcm.data())) return HDSDP_RETCODE_FAILED;
@@ -343,21 +345,21 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     MiLin *l = (MiLin *) HKKT->kktM->chol;
     if (!l->bsp) {
         const size_t mm = sizeof(double) * (size_t) l->ch.npad * l->ch.npad;
-        if (hipMalloc((void **) &l->Mdev, mm) != hipSuccess) return HDSDP_RETCODE_MEMORY;
-        if (hdm_memset_sync(l->Mdev, 0, mm) != hipSuccess) return HDSDP_RETCODE_FAILED;
+        if (l->Mdev.alloc(mm / sizeof(double)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
+        if (hdm_memset_sync(l->Mdev.get(), 0, mm) != hipSuccess) return HDSDP_RETCODE_FAILED;
     }
     MiKKTPriv *pv = priv_of(HKKT);
-    if (hipMalloc((void **) &pv->vecs, sizeof(double) * (3 * (size_t) nRow + 4)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
+    if (pv->vecs.alloc(3 * (size_t) nRow + 4) != hipSuccess) return HDSDP_RETCODE_MEMORY;
     pv->n_engine = pv->n_foreign = 0;
     for (int i = 0; i < nCones; ++i) {
         if (cones[i]->coneBuildSchur == cone_build_schur || cones[i]->coneBuildSchur == gc_build_schur ||
             cones[i]->coneBuildSchur == lp_build_schur) pv->n_engine += 1;
         else pv->n_foreign += 1;
     }
-    if (hipHostMalloc((void **) &pv->chan, sizeof(double) * std::max(1, nRow), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **) &pv->chan_dev, sizeof(double) * ((size_t) nRow + 1)) != hipSuccess)
+    if (pv->chan.alloc((size_t) std::max(1, nRow)) != hipSuccess ||
+        pv->chan_dev.alloc((size_t) nRow + 1) != hipSuccess)
         return HDSDP_RETCODE_MEMORY;
-    memset(pv->chan, 0, sizeof(double) * std::max(1, nRow));
+    memset(pv->chan.get(), 0, sizeof(double) * std::max(1, nRow));
     pv->chan_folded = false;
     pv->bytes_d2h = pv->bytes_h2d = 0;
     // HDSDP_MI355X_DEVICE_M=1: an unchanged driver keeps M on the device when it can.  Its host
@@ -378,10 +380,10 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
 
 // kktDiag[] -> the host matrix's diagonal (mirror on) or the diagonal channel (mirror off)
 static void kkt_point_diag(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
-    if (!HKKT->kktDiag || !HKKT->kktMatElem || !pv->chan) return;
+    if (!HKKT->kktDiag || !HKKT->kktMatElem || !pv->chan.get()) return;
     const int m = HKKT->nRow;
     for (int i = 0; i < m; ++i)
-        HKKT->kktDiag[i] = !pv->mirror ? &pv->chan[i] :
+        HKKT->kktDiag[i] = !pv->mirror ? &pv->chan.get()[i] :
                            HKKT->isKKTSparse ? &HKKT->kktMatElem[HKKT->kktMatBeg[i]] : &HKKT->kktMatElem[i + (size_t) i * m];
 }
 
@@ -390,15 +392,15 @@ static void kkt_point_diag(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
 static hdsdp_retcode kkt_diag_pass(hdsdp_kkt *HKKT, MiKKTPriv *pv, bool fold, bool add, double v, double *mn) {
     const int m = HKKT->nRow;
     if (fold) {
-        if (hipMemcpyAsync(pv->chan_dev, pv->chan, sizeof(double) * (size_t) m, hipMemcpyHostToDevice, g.stream) != hipSuccess)
+        if (hipMemcpyAsync(pv->chan_dev.get(), pv->chan.get(), sizeof(double) * (size_t) m, hipMemcpyHostToDevice, g.stream) != hipSuccess)
             return HDSDP_RETCODE_FAILED;
         pv->bytes_h2d += (int64_t) sizeof(double) * m;
         pv->chan_folded = true;
     }
-    hipLaunchKernelGGL(mi_diag_pass_kernel, dim3(1), dim3(1024), 0, g.stream, kkt_view(HKKT), m, fold ? pv->chan_dev : nullptr,
-                       add ? 1 : 0, v, mn ? pv->chan_dev + m : nullptr);
+    hipLaunchKernelGGL(mi_diag_pass_kernel, dim3(1), dim3(1024), 0, g.stream, kkt_view(HKKT), m, fold ? pv->chan_dev.get() : nullptr,
+                       add ? 1 : 0, v, mn ? pv->chan_dev.get() + m : nullptr);
     if (hipGetLastError() != hipSuccess) return HDSDP_RETCODE_FAILED;
-    if (mn && (hipMemcpyAsync(mn, pv->chan_dev + m, sizeof(double), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+    if (mn && (hipMemcpyAsync(mn, pv->chan_dev.get() + m, sizeof(double), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
                hipStreamSynchronize(g.stream) != hipSuccess))
         return HDSDP_RETCODE_FAILED;
     return HDSDP_RETCODE_OK;
@@ -414,18 +416,18 @@ static hdsdp_retcode kkt_clean(hdsdp_kkt *HKKT, int typeKKT) {  // hdsdp_schur.c
         HKKT->dCSinv = HKKT->dCSinvCSinv = HKKT->dCSinvRdSinv = 0.0;
     }
     HKKT->dTraceSinv = 0.0;
-    if (hipMemsetAsync(pv->vecs, 0, sizeof(double) * (3 * (size_t) m + 4), g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+    if (hipMemsetAsync(pv->vecs.get(), 0, sizeof(double) * (3 * (size_t) m + 4), g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     if (typeKKT != KKT_TYPE_CORRECTOR) {
         MiLin *l = (MiLin *) HKKT->kktM->chol;
         if (l->bsp) { if (l->bsp->zero_M(g.stream)) return HDSDP_RETCODE_FAILED; }
-        else if (hipMemsetAsync(l->Mdev, 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess)
+        else if (hipMemsetAsync(l->Mdev.get(), 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess)
             return HDSDP_RETCODE_FAILED;
         if (HKKT->isKKTSparse) memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) HKKT->kktMatBeg[m]);   // (CPU cones add into it)
         // (dense host matrix: CPU cones add into it, so it starts from zero -- but with engine cones only, kkt_pull's copy
         // of the whole m x m device matrix replaces every entry, and 8 m^2 bytes of host memset per call are saved: 4 ms at
         // m = 2000, twice per iteration of the reference's driver)
         else if (pv->mirror && !(pv->n_foreign == 0 && pv->n_engine > 0)) memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) m * m);
-        memset(pv->chan, 0, sizeof(double) * (size_t) m);       // (the diagonal channel: host cones add into it with the mirror off)
+        memset(pv->chan.get(), 0, sizeof(double) * (size_t) m);       // (the diagonal channel: host cones add into it with the mirror off)
         pv->chan_folded = false;
     }
     return HDSDP_RETCODE_OK;
@@ -436,7 +438,7 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
     const int m = HKKT->nRow;
     MiKKTPriv *pv = priv_of(HKKT);
     std::vector<double> h(3 * (size_t) m + 4);
-    if (hipMemcpyAsync(h.data(), pv->vecs, sizeof(double) * h.size(), hipMemcpyDeviceToHost, g.stream) != hipSuccess)
+    if (hipMemcpyAsync(h.data(), pv->vecs.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, g.stream) != hipSuccess)
         return HDSDP_RETCODE_FAILED;
     // M: every cone ACCUMULATES (hdsdp_schur.c:256-268).  The engine's cones did so on the device, foreign (CPU) cones
     // straight into kktMatElem: with only engine cones the device matrix simply replaces the (zeroed) host one, with
@@ -450,16 +452,16 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
         mcount = HKKT->isKKTSparse ? (size_t) pv->nnz : (size_t) m * m;
         pv->bytes_d2h += (int64_t) (sizeof(double) * mcount);
         if (pv->n_foreign > 0) {
-            if (!pv->Mtmp && hipHostMalloc((void **) &pv->Mtmp, sizeof(double) * std::max<size_t>(1, mcount)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
-            dst = pv->Mtmp;
+            if (!pv->Mtmp && pv->Mtmp.alloc(std::max<size_t>(1, mcount)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
+            dst = pv->Mtmp.get();
             add_M = true;
         }
         if (HKKT->isKKTSparse) {
             // the pattern's entries of the dense device matrix (an engine cone only writes inside the pattern it declared)
             if (pv->nnz > 0) {
                 hipLaunchKernelGGL(mi_csc_gather_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, kkt_view(HKKT),
-                                   pv->sp_rows, pv->sp_cols, pv->nnz, pv->sp_vals);
-                if (hipMemcpyAsync(dst, pv->sp_vals, sizeof(double) * (size_t) pv->nnz, hipMemcpyDeviceToHost, g.stream) != hipSuccess)
+                                   pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
+                if (hipMemcpyAsync(dst, pv->sp_vals.get(), sizeof(double) * (size_t) pv->nnz, hipMemcpyDeviceToHost, g.stream) != hipSuccess)
                     return HDSDP_RETCODE_FAILED;
             }
         } else if (hipMemcpy2DAsync(dst, sizeof(double) * m, Mdev, sizeof(double) * ld, sizeof(double) * m, m,
@@ -468,10 +470,10 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
     }
     if (hipStreamSynchronize(g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     if (add_M) {
-        if (HKKT->isKKTSparse) for (size_t q = 0; q < mcount; ++q) HKKT->kktMatElem[q] += pv->Mtmp[q];
+        if (HKKT->isKKTSparse) for (size_t q = 0; q < mcount; ++q) HKKT->kktMatElem[q] += pv->Mtmp.get()[q];
         else
             for (int j = 0; j < m; ++j)                    // lower triangle, column-major
-                for (int i = j; i < m; ++i) HKKT->kktMatElem[i + (size_t) j * m] += pv->Mtmp[i + (size_t) j * m];
+                for (int i = j; i < m; ++i) HKKT->kktMatElem[i + (size_t) j * m] += pv->Mtmp.get()[i + (size_t) j * m];
     }
     for (int i = 0; i < m; ++i) {
         HKKT->dASinvVec[i] += h[i];
@@ -552,10 +554,10 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
             if (l->bsp->zero_L(g.stream)) return HDSDP_RETCODE_FAILED;
             pv->bytes_h2d += (int64_t) sizeof(double) * pv->nnz;
             if (pv->nnz > 0) {
-                if (hipMemcpyAsync(pv->sp_vals, HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
+                if (hipMemcpyAsync(pv->sp_vals.get(), HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
                     return HDSDP_RETCODE_FAILED;
                 hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, l->bsp->view_L(),
-                                   pv->sp_rows, pv->sp_cols, pv->nnz, pv->sp_vals);
+                                   pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
             }
         } else {
             // (the diagonal channel goes into the accumulation store first: the factor store is a copy of it)
@@ -575,16 +577,16 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
     if (pv->mirror && HKKT->isKKTSparse) {
         // the host CSC is authoritative: its values go up (nnz doubles) and are scattered over the zeroed dense device
         // matrix, which is then factored like the dense operator's
-        if (hipMemsetAsync(l->Mdev, 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+        if (hipMemsetAsync(l->Mdev.get(), 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
         pv->bytes_h2d += (int64_t) sizeof(double) * pv->nnz;
         if (pv->nnz > 0) {
-            if (hipMemcpyAsync(pv->sp_vals, HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
+            if (hipMemcpyAsync(pv->sp_vals.get(), HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
                 return HDSDP_RETCODE_FAILED;
             hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream,
-                               dense_view(l->Mdev, l->ch.npad), pv->sp_rows, pv->sp_cols, pv->nnz, pv->sp_vals);
+                               dense_view(l->Mdev.get(), l->ch.npad), pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
         }
         pv->Mdev_valid = true;
-        l->srcHost = nullptr; l->srcDev = l->Mdev; l->srcLd = l->ch.npad;
+        l->srcHost = nullptr; l->srcDev = l->Mdev.get(); l->srcLd = l->ch.npad;
     } else if (pv->mirror) {
         l->srcHost = HKKT->kktMatElem; l->srcDev = nullptr; l->srcLd = HKKT->nRow;
         pv->bytes_h2d += (int64_t) sizeof(double) * HKKT->nRow * HKKT->nRow;    // (load_host, or the pivoted solver's load)
@@ -593,7 +595,7 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
         // (lin_factor_indef reads srcDev) all see the same matrix
         if (!pv->Mdev_valid) return HDSDP_RETCODE_FAILED;
         if (!pv->chan_folded && kkt_diag_pass(HKKT, pv, true, false, 0.0, nullptr) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
-        l->srcHost = nullptr; l->srcDev = l->Mdev; l->srcLd = l->ch.npad;
+        l->srcHost = nullptr; l->srcDev = l->Mdev.get(); l->srcLd = l->ch.npad;
     }
     if (l->indef) return lin_factor_indef(l);     // switched earlier: stays switched (hdsdp_linsolver.c:1838)
     if (pv->mirror && !HKKT->isKKTSparse) {
@@ -603,14 +605,14 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
         // gathered from the device matrix otherwise) go to their permuted places in a zeroed image
         if (!pv->mirror && pv->nnz > 0)
             hipLaunchKernelGGL(mi_csc_gather_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream,
-                               dense_view(l->Mdev, l->ch.npad), pv->sp_rows, pv->sp_cols, pv->nnz, pv->sp_vals);
-        if (hipMemsetAsync(l->ch.L, 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+                               dense_view(l->Mdev.get(), l->ch.npad), pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
+        if (hipMemsetAsync(l->ch.L.get(), 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
         if (pv->nnz > 0)
             hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream,
-                               dense_view(l->ch.L, l->ch.npad), pv->sp_prow, pv->sp_pcol, pv->nnz, pv->sp_vals);
+                               dense_view(l->ch.L.get(), l->ch.npad), pv->sp_prow.get(), pv->sp_pcol.get(), pv->nnz, pv->sp_vals.get());
         if (l->ch.finish_load(g.stream)) return HDSDP_RETCODE_FAILED;
     } else {
-        if (l->ch.load_device(l->Mdev, l->ch.npad, g.stream)) return HDSDP_RETCODE_FAILED;
+        if (l->ch.load_device(l->Mdev.get(), l->ch.npad, g.stream)) return HDSDP_RETCODE_FAILED;
     }
     if (l->ch.factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
     if (info != 0) {
@@ -681,7 +683,7 @@ void HMiKKTSetHostMirror(hdsdp_kkt *HKKT, int mirrorM) {
 }
 int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
     MiKKTPriv *pv = priv_of(HKKT);
-    if (!HKKT->kktDiag || !pv->chan) return -1;
+    if (!HKKT->kktDiag || !pv->chan.get()) return -1;
     return pv->mirror ? 0 : 1;
 }
 void HMiKKTGetMatrixTraffic(hdsdp_kkt *HKKT, int64_t *bytesToHost, int64_t *bytesToDevice) {
@@ -735,7 +737,6 @@ hdsdp_retcode HMiConeSetExchangeBuffers(hdsdp_cone *cone, void *sendBuf, void *r
     if (!c || c->work_ready || !sendBuf || !recvBuf) return HDSDP_RETCODE_FAILED;
     c->AhatLoc = (double *) sendBuf;
     c->AhatAll = (c->world == 1) ? c->AhatLoc : (double *) recvBuf;
-    c->ext_ahat = true;
     const size_t ahat = sizeof(double) * (size_t) c->world * c->npb_loc * c->Lr * 16;
     if (hipMemsetAsync(c->AhatLoc, 0, ahat, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     if (c->AhatAll != c->AhatLoc && hipMemsetAsync(c->AhatAll, 0, ahat, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
@@ -752,16 +753,15 @@ hdsdp_retcode HMiKKTGetRows(hdsdp_kkt *HKKT, int nRows, const int *rows, double 
     MiKKTPriv *pv = priv_of(HKKT);
     const int m = HKKT->nRow;
     if (!pv->Mdev_valid) return HDSDP_RETCODE_FAILED;
-    double *tmp = nullptr;
-    HIP_RC(hipMalloc((void **) &tmp, sizeof(double) * (size_t) std::max(1, m)));
+    HdmBuf<double> tmp;
+    HIP_RC(tmp.alloc((size_t) std::max(1, m)));
     hdsdp_retcode rc = HDSDP_RETCODE_OK;
     for (int r = 0; r < nRows && rc == HDSDP_RETCODE_OK; ++r) {
         if (rows[r] < 0 || rows[r] >= m) { rc = HDSDP_RETCODE_FAILED; break; }
         pv->bytes_d2h += (int64_t) sizeof(double) * m;
-        hipLaunchKernelGGL(mi_get_row_kernel, dim3((m + 255) / 256), dim3(256), 0, g.stream, kkt_view(HKKT), rows[r], m, tmp);
-        if (hipMemcpyAsync(out + (size_t) r * m, tmp, sizeof(double) * (size_t) m, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+        hipLaunchKernelGGL(mi_get_row_kernel, dim3((m + 255) / 256), dim3(256), 0, g.stream, kkt_view(HKKT), rows[r], m, tmp.get());
+        if (hipMemcpyAsync(out + (size_t) r * m, tmp.get(), sizeof(double) * (size_t) m, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
             hipStreamSynchronize(g.stream) != hipSuccess) rc = HDSDP_RETCODE_FAILED;
     }
-    (void) hipFree(tmp);
     return rc;
 }

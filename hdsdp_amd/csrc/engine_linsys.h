@@ -8,23 +8,23 @@ struct MiLin {
     int n = 0;
     linsys_type type = HDSDP_LINSYS_DENSE_DIRECT;
     HdmChol ch;
-    double *work = nullptr;  // npad x npad device scratch (Invert)
+    HdmBuf<double> work;     // npad x npad device scratch (Invert)
     double relTol = 0, absTol = 0;
     int maxIter = -1;
     // Schur systems: M lives here (device, ld = ch.npad) before factorisation
-    double *Mdev = nullptr;
+    HdmBuf<double> Mdev;
     // sparse Schur operator in tile form (bsparse.h): the matrix and its factor are 128 x 128 tiles inside the block pattern of
     // the Cholesky factor; no dense m x m array exists anywhere (ch stays uninitialised, Mdev null)
-    HdmBsp *bsp = nullptr;
+    std::unique_ptr<HdmBsp> bsp;
     // symmetric-indefinite fallback (HFpLinsysSwitchToIndefinite, hdsdp_linsolver.c:1827-1857): once switched, every
     // later factorisation goes through the pivoted solver, like the reference's replaced vtable
-    HdmLu *lu = nullptr;
+    std::unique_ptr<HdmLu> lu;
     bool indef = false;
     // sparse Schur operator: the factor object holds P M P' (perm[old] = new, a bandwidth-reducing order of the pattern);
     // right-hand sides go in permuted and solutions come back in the caller's order.  Empty = identity.
     std::vector<int> perm;
     std::vector<double> pbuf;
-    const double *srcHost = nullptr, *srcDev = nullptr;   // where the last factorised matrix came from (lower valid)
+    const double *srcHost = nullptr, *srcDev = nullptr;   // not owned: where the last factorised matrix came from (lower valid)
     long srcLd = 0;
     // HDSDP_LINSYS_SPARSE_DIRECT (the reference's QDLDL backend for a sparse dual matrix, hdsdp_linsolver.c:509-809):
     // the matrix arrives as a lower-triangular CSC and is factored densely on the device.  Result-equivalent for every
@@ -77,8 +77,8 @@ hdsdp_retcode lin_factor_host(MiLin *l, const double *A, int *info) {
 // lapackIndefiniteLinSolverNumeric (hdsdp_linsolver.c:1706-1727): copy + pivoted factorisation; a singular matrix fails
 hdsdp_retcode lin_factor_indef(MiLin *l) {
     if (!l->lu) {
-        l->lu = new HdmLu();
-        if (l->lu->init(l->n)) { l->lu->destroy(); delete l->lu; l->lu = nullptr; return HDSDP_RETCODE_MEMORY; }
+        l->lu.reset(new HdmLu());
+        if (l->lu->init(l->n)) { l->lu.reset(); return HDSDP_RETCODE_MEMORY; }
     }
     if (l->srcDev) RC(l->lu->load_device_lower(l->srcDev, l->srcLd, g.stream));
     else if (l->srcHost) RC(l->lu->load_host_lower(l->srcHost, l->srcLd, g.stream));
@@ -183,22 +183,14 @@ void lin_invert(void *chol, double *dFull, double *) {
     MiLin *l = (MiLin *) chol;
     if (l->indef || l->bsp) return;              // :1790-1797
     HdmChol &c = l->ch;
-    if (!l->work) {
-        if (hipMalloc((void **) &l->work, sizeof(double) * (size_t) c.npad * c.npad) != hipSuccess) return;
-    }
-    if (c.inverse_full(l->work, c.npad, g.stream)) return;
-    (void) hipMemcpy2DAsync(dFull, sizeof(double) * c.n, l->work, sizeof(double) * c.npad, sizeof(double) * c.n, c.n,
+    if (l->work.reserve((size_t) c.npad * c.npad) != hipSuccess) return;
+    if (c.inverse_full(l->work.get(), c.npad, g.stream)) return;
+    (void) hipMemcpy2DAsync(dFull, sizeof(double) * c.n, l->work.get(), sizeof(double) * c.npad, sizeof(double) * c.n, c.n,
                             hipMemcpyDeviceToHost, g.stream);
     (void) hipStreamSynchronize(g.stream);
 }
 void lin_destroy(void **pchol) {
     if (!pchol || !*pchol) return;
-    MiLin *l = (MiLin *) *pchol;
-    l->ch.destroy();
-    if (l->lu) { l->lu->destroy(); delete l->lu; }
-    if (l->work) (void) hipFree(l->work);
-    if (l->Mdev) (void) hipFree(l->Mdev);
-    if (l->bsp) { l->bsp->destroy(); delete l->bsp; }
-    delete l;
+    delete (MiLin *) *pchol;
     *pchol = nullptr;
 }

@@ -20,19 +20,19 @@ struct MiLPCone {
     std::vector<int> cnt;                // entries per LP column
     std::vector<double> obj, dual, chk, step, dinv;
     double Rd = 0.0, perturb = 0.0;
-    int *d_rbeg = nullptr, *d_ridx = nullptr, *d_cbeg = nullptr, *d_cidx = nullptr;
-    double *d_rval = nullptr, *d_cval = nullptr, *d_obj = nullptr, *d_y = nullptr, *d_out = nullptr, *d_d = nullptr;
-    double *h_y = nullptr, *h_out = nullptr, *h_d = nullptr;     // pinned staging
+    HdmBuf<int> d_rbeg, d_ridx, d_cbeg, d_cidx;
+    HdmBuf<double> d_rval, d_cval, d_obj, d_y, d_out, d_d;
+    HdmPinned<double> h_y, h_out, h_d;   // pinned staging
     // dense path: W = A[:, chunk] diag(d) in the Gram role's K-major blocked layout, kc LP columns per chunk
     int mpad = 0, kc = 0;
-    double *W = nullptr;
+    HdmBuf<double> W;
     long wspan = 0;
     // sparse path: lower pairs (i, j) and their terms (k, A_ik A_jk)
     int64_t terms = 0;                   // sum over LP columns of nnz (nnz + 1) / 2
     long npair = 0;
-    int *p_row = nullptr, *p_col = nullptr, *t_col = nullptr;
-    long *p_beg = nullptr;
-    double *t_val = nullptr;
+    HdmBuf<int> p_row, p_col, t_col;
+    HdmBuf<long> p_beg;
+    HdmBuf<double> t_val;
     bool pairs_ready = false;
     int mode = 0, path = 0;              // mode: 0 auto, 1 dense, 2 sparse; path: what builds use (1 / 2)
     double cost_dense = 0.0, cost_sparse = 0.0;
@@ -91,15 +91,15 @@ int lp_build_pairs(MiLPCone *c) {
     pbeg.push_back((long) t.size());
     c->npair = (long) prow.size();
     const size_t np = std::max<size_t>(1, prow.size()), nt = std::max<size_t>(1, t.size());
-    if (hipMalloc((void **) &c->p_row, sizeof(int) * np) != hipSuccess || hipMalloc((void **) &c->p_col, sizeof(int) * np) != hipSuccess ||
-        hipMalloc((void **) &c->p_beg, sizeof(long) * (np + 1)) != hipSuccess || hipMalloc((void **) &c->t_col, sizeof(int) * nt) != hipSuccess ||
-        hipMalloc((void **) &c->t_val, sizeof(double) * nt) != hipSuccess)
+    if (c->p_row.alloc(np) != hipSuccess || c->p_col.alloc(np) != hipSuccess ||
+        c->p_beg.alloc(np + 1) != hipSuccess || c->t_col.alloc(nt) != hipSuccess ||
+        c->t_val.alloc(nt) != hipSuccess)
         return 1;
-    if ((c->npair && (hdm_memcpy_h2d_sync(c->p_row, prow.data(), sizeof(int) * prow.size()) != hipSuccess ||
-                      hdm_memcpy_h2d_sync(c->p_col, pcol.data(), sizeof(int) * pcol.size()) != hipSuccess ||
-                      hdm_memcpy_h2d_sync(c->t_col, tcol.data(), sizeof(int) * tcol.size()) != hipSuccess ||
-                      hdm_memcpy_h2d_sync(c->t_val, tval.data(), sizeof(double) * tval.size()) != hipSuccess)) ||
-        hdm_memcpy_h2d_sync(c->p_beg, pbeg.data(), sizeof(long) * pbeg.size()) != hipSuccess)
+    if ((c->npair && (hdm_memcpy_h2d_sync(c->p_row.get(), prow.data(), sizeof(int) * prow.size()) != hipSuccess ||
+                      hdm_memcpy_h2d_sync(c->p_col.get(), pcol.data(), sizeof(int) * pcol.size()) != hipSuccess ||
+                      hdm_memcpy_h2d_sync(c->t_col.get(), tcol.data(), sizeof(int) * tcol.size()) != hipSuccess ||
+                      hdm_memcpy_h2d_sync(c->t_val.get(), tval.data(), sizeof(double) * tval.size()) != hipSuccess)) ||
+        hdm_memcpy_h2d_sync(c->p_beg.get(), pbeg.data(), sizeof(long) * pbeg.size()) != hipSuccess)
         return 1;
     c->pairs_ready = true;
     return 0;
@@ -108,8 +108,8 @@ int lp_build_pairs(MiLPCone *c) {
 int lp_build_dense_buffer(MiLPCone *c) {
     if (c->W) return 0;
     c->wspan = (long) (c->kc / 16) * c->mpad * 16 + HDM_OPERAND_PAD_DOUBLES;
-    if (hipMalloc((void **) &c->W, sizeof(double) * (size_t) c->wspan) != hipSuccess) return 1;
-    return hdm_memset_sync(c->W, 0, sizeof(double) * (size_t) c->wspan) != hipSuccess;
+    if (c->W.alloc((size_t) c->wspan) != hipSuccess) return 1;
+    return hdm_memset_sync(c->W.get(), 0, sizeof(double) * (size_t) c->wspan) != hipSuccess;
 }
 
 int lp_set_path(MiLPCone *c, int mode) {
@@ -125,13 +125,13 @@ int lp_set_path(MiLPCone *c, int mode) {
 // out = A^T (a y), length nCol, on the device (csp_Axpy's arithmetic), copied back into `out`
 int lp_at_y(MiLPCone *c, double a, const double *y, double *out) {
     if (a == 0.0) { std::fill(out, out + c->n, 0.0); return 0; }     // (csp_Axpy returns at once, :23-25)
-    memcpy(c->h_y, y, sizeof(double) * c->m);
-    if (hipMemcpyAsync(c->d_y, c->h_y, sizeof(double) * c->m, hipMemcpyHostToDevice, g.stream) != hipSuccess) return 1;
-    hipLaunchKernelGGL(lp_col_axpy_kernel, dim3((c->n + 255) / 256), dim3(256), 0, g.stream, c->n, c->d_cbeg, c->d_cidx, c->d_cval, a,
-                       (const double *) c->d_y, c->d_out);
-    if (hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * c->n, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+    memcpy(c->h_y.get(), y, sizeof(double) * c->m);
+    if (hipMemcpyAsync(c->d_y.get(), c->h_y.get(), sizeof(double) * c->m, hipMemcpyHostToDevice, g.stream) != hipSuccess) return 1;
+    hipLaunchKernelGGL(lp_col_axpy_kernel, dim3((c->n + 255) / 256), dim3(256), 0, g.stream, c->n, c->d_cbeg.get(), c->d_cidx.get(), c->d_cval.get(), a,
+                       (const double *) c->d_y.get(), c->d_out.get());
+    if (hipMemcpyAsync(c->h_out.get(), c->d_out.get(), sizeof(double) * c->n, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
         hipStreamSynchronize(g.stream) != hipSuccess) return 1;
-    memcpy(out, c->h_out, sizeof(double) * c->n);
+    memcpy(out, c->h_out.get(), sizeof(double) * c->n);
     return 0;
 }
 
@@ -162,13 +162,6 @@ int lp_is_interior(const MiLPCone *c, const double *t) {
 void lp_destroy_data(void **pcd) {
     MiLPCone *c = (MiLPCone *) *pcd;
     if (!c) return;
-    int *ip[] = {c->d_rbeg, c->d_ridx, c->d_cbeg, c->d_cidx, c->p_row, c->p_col, c->t_col};
-    for (int *q : ip) if (q) (void) hipFree(q);
-    double *dp[] = {c->d_rval, c->d_cval, c->d_obj, c->d_y, c->d_out, c->d_d, c->W, c->t_val};
-    for (double *q : dp) if (q) (void) hipFree(q);
-    if (c->p_beg) (void) hipFree(c->p_beg);
-    double *hp[] = {c->h_y, c->h_out, c->h_d};
-    for (double *q : hp) if (q) (void) hipHostFree(q);
     delete c;
     *pcd = nullptr;
 }
@@ -211,16 +204,16 @@ hdsdp_retcode lp_build_schur(void *cd, int iCone, void *kktv, int typeKKT) {   /
             kkt->dCSinvCSinv += cs * cs;
         }
     HIP_RC(hipStreamSynchronize(g.stream));      // (h_d may still feed the previous build's copy)
-    memcpy(c->h_d, d, sizeof(double) * c->n);
-    HIP_RC(hipMemcpyAsync(c->d_d, c->h_d, sizeof(double) * c->n, hipMemcpyHostToDevice, g.stream));
+    memcpy(c->h_d.get(), d, sizeof(double) * c->n);
+    HIP_RC(hipMemcpyAsync(c->d_d.get(), c->h_d.get(), sizeof(double) * c->n, hipMemcpyHostToDevice, g.stream));
     if (c->m > 0)
-        hipLaunchKernelGGL(lp_vecs_kernel, dim3(c->m), dim3(256), 0, g.stream, c->m, (const int *) c->d_rbeg, (const int *) c->d_ridx,
-                           (const double *) c->d_rval, (const double *) c->d_d, (const double *) c->d_obj, c->Rd,
-                           typeKKT == KKT_TYPE_HOMOGENEOUS ? 1 : 0, pv->vecs);
+        hipLaunchKernelGGL(lp_vecs_kernel, dim3(c->m), dim3(256), 0, g.stream, c->m, (const int *) c->d_rbeg.get(), (const int *) c->d_ridx.get(),
+                           (const double *) c->d_rval.get(), (const double *) c->d_d.get(), (const double *) c->d_obj.get(), c->Rd,
+                           typeKKT == KKT_TYPE_HOMOGENEOUS ? 1 : 0, pv->vecs.get());
     HIP_RC(hipGetLastError());
     if (typeKKT == KKT_TYPE_CORRECTOR) return HDSDP_RETCODE_OK;
     MiLin *l = (MiLin *) kkt->kktM->chol;
-    if (kkt->isKKTSparse || l->bsp || !l->Mdev) {
+    if (kkt->isKKTSparse || l->bsp || !l->Mdev.get()) {
         fprintf(stderr, "[hdsdp_mi355x] LP cone: the Schur operator is not dense\n");   // (the reference asserts, :303-305)
         return HDSDP_RETCODE_FAILED;
     }
@@ -228,8 +221,8 @@ hdsdp_retcode lp_build_schur(void *cd, int iCone, void *kktv, int typeKKT) {   /
     if (c->path == 2) {
         if (c->npair > 0)
             hipLaunchKernelGGL(lp_pairs_kernel, dim3((unsigned) ((c->npair + 255) / 256)), dim3(256), 0, g.stream, c->npair,
-                               (const int *) c->p_row, (const int *) c->p_col, (const long *) c->p_beg, (const int *) c->t_col,
-                               (const double *) c->t_val, (const double *) c->d_d, l->Mdev, ldm);
+                               (const int *) c->p_row.get(), (const int *) c->p_col.get(), (const long *) c->p_beg.get(), (const int *) c->t_col.get(),
+                               (const double *) c->t_val.get(), (const double *) c->d_d.get(), l->Mdev.get(), ldm);
         HIP_RC(hipGetLastError());
         return HDSDP_RETCODE_OK;
     }
@@ -241,15 +234,15 @@ hdsdp_retcode lp_build_schur(void *cd, int iCone, void *kktv, int typeKKT) {   /
     const long ldb = (long) c->mpad * 16;
     for (int c0 = 0; c0 < c->n; c0 += c->kc) {
         const int kv = std::min(c->kc, c->n - c0), kp = (int) hdm_roundup(kv, 16);
-        HIP_RC(hipMemsetAsync(c->W, 0, sizeof(double) * (size_t) (kp / 16) * ldb, g.stream));
-        hipLaunchKernelGGL(lp_scatter_kernel, dim3((kv + 255) / 256), dim3(256), 0, g.stream, c0, kv, (const int *) c->d_cbeg,
-                           (const int *) c->d_cidx, (const double *) c->d_cval, (const double *) c->d_d, ldb, c->W);
+        HIP_RC(hipMemsetAsync(c->W.get(), 0, sizeof(double) * (size_t) (kp / 16) * ldb, g.stream));
+        hipLaunchKernelGGL(lp_scatter_kernel, dim3((kv + 255) / 256), dim3(256), 0, g.stream, c0, kv, (const int *) c->d_cbeg.get(),
+                           (const int *) c->d_cidx.get(), (const double *) c->d_cval.get(), (const double *) c->d_d.get(), ldb, c->W.get());
         HIP_RC(hipGetLastError());
         HdmGemmArgs q = {};
-        q.A = c->W; q.B = c->W; q.a_kmajor = 1; q.b_kmajor = 1;
+        q.A = c->W.get(); q.B = c->W.get(); q.a_kmajor = 1; q.b_kmajor = 1;
         q.lda = 16; q.ldb = 16; q.a_kblk = ldb; q.b_kblk = ldb;
         q.spanA = q.spanB = c->wspan;
-        q.C = l->Mdev; q.ldc = ldm;
+        q.C = l->Mdev.get(); q.ldc = ldm;
         q.M = m16; q.N = m16; q.K = kp; q.batch = 1;
         q.lower_only = 1; q.epilogue = HDM_EPI_STORE; q.alpha = 1.0; q.beta = 1.0; q.role = HDM_ROLE_GRAM;
         q.flops = (double) c->m * (c->m + 1) * (double) kv;     // lower triangle, 2 flops a term
@@ -357,7 +350,7 @@ void lp_scal(void *cd, double dScal) {   // :205-209: rscl, i.e. LAPACK drscl: x
     MiLPCone *c = (MiLPCone *) cd;
     const double r = 1.0 / dScal;
     for (int j = 0; j < c->n; ++j) c->obj[j] *= r;
-    if (hdm_memcpy_h2d_sync(c->d_obj, c->obj.data(), sizeof(double) * c->n) != hipSuccess)
+    if (hdm_memcpy_h2d_sync(c->d_obj.get(), c->obj.data(), sizeof(double) * c->n) != hipSuccess)
         fprintf(stderr, "[hdsdp_mi355x] LP cone: objective upload failed\n");
 }
 void lp_view(void *cd) {   // :560-565 (the reference prints its two counts the other way round)
@@ -451,21 +444,21 @@ hdsdp_retcode lp_cone_create(hdsdp_cone **pCone, int iCone, int nRow, int nCol, 
     c->kc = (int) std::min<long>(hdm_roundup(nCol, 16), std::max<long>(16, ((1L << 25) / c->mpad) / 16 * 16));
     c->kc = std::min(c->kc, LP_KC_MAX);
     const size_t nz1 = (size_t) std::max(1, nnz);
-    bool ok = hipMalloc((void **) &c->d_rbeg, sizeof(int) * (nRow + 1)) == hipSuccess && hipMalloc((void **) &c->d_ridx, sizeof(int) * nz1) == hipSuccess &&
-              hipMalloc((void **) &c->d_rval, sizeof(double) * nz1) == hipSuccess && hipMalloc((void **) &c->d_cbeg, sizeof(int) * (nCol + 1)) == hipSuccess &&
-              hipMalloc((void **) &c->d_cidx, sizeof(int) * nz1) == hipSuccess && hipMalloc((void **) &c->d_cval, sizeof(double) * nz1) == hipSuccess &&
-              hipMalloc((void **) &c->d_obj, sizeof(double) * nCol) == hipSuccess && hipMalloc((void **) &c->d_y, sizeof(double) * nRow) == hipSuccess &&
-              hipMalloc((void **) &c->d_out, sizeof(double) * nCol) == hipSuccess && hipMalloc((void **) &c->d_d, sizeof(double) * nCol) == hipSuccess &&
-              hipHostMalloc((void **) &c->h_y, sizeof(double) * nRow, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **) &c->h_out, sizeof(double) * nCol, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **) &c->h_d, sizeof(double) * nCol, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hdm_memcpy_h2d_sync(c->d_rbeg, c->rbeg.data(), sizeof(int) * (nRow + 1)) == hipSuccess &&
-         hdm_memcpy_h2d_sync(c->d_cbeg, cb.data(), sizeof(int) * (nCol + 1)) == hipSuccess &&
-         hdm_memcpy_h2d_sync(c->d_obj, c->obj.data(), sizeof(double) * nCol) == hipSuccess &&
-         (nnz == 0 || (hdm_memcpy_h2d_sync(c->d_ridx, c->ridx.data(), sizeof(int) * nnz) == hipSuccess &&
-                       hdm_memcpy_h2d_sync(c->d_rval, c->rval.data(), sizeof(double) * nnz) == hipSuccess &&
-                       hdm_memcpy_h2d_sync(c->d_cidx, ci.data(), sizeof(int) * nnz) == hipSuccess &&
-                       hdm_memcpy_h2d_sync(c->d_cval, cv.data(), sizeof(double) * nnz) == hipSuccess));
+    bool ok = c->d_rbeg.alloc(nRow + 1) == hipSuccess && c->d_ridx.alloc(nz1) == hipSuccess &&
+              c->d_rval.alloc(nz1) == hipSuccess && c->d_cbeg.alloc(nCol + 1) == hipSuccess &&
+              c->d_cidx.alloc(nz1) == hipSuccess && c->d_cval.alloc(nz1) == hipSuccess &&
+              c->d_obj.alloc(nCol) == hipSuccess && c->d_y.alloc(nRow) == hipSuccess &&
+              c->d_out.alloc(nCol) == hipSuccess && c->d_d.alloc(nCol) == hipSuccess &&
+              c->h_y.alloc(nRow) == hipSuccess &&
+              c->h_out.alloc(nCol) == hipSuccess &&
+              c->h_d.alloc(nCol) == hipSuccess;
+    ok = ok && hdm_memcpy_h2d_sync(c->d_rbeg.get(), c->rbeg.data(), sizeof(int) * (nRow + 1)) == hipSuccess &&
+         hdm_memcpy_h2d_sync(c->d_cbeg.get(), cb.data(), sizeof(int) * (nCol + 1)) == hipSuccess &&
+         hdm_memcpy_h2d_sync(c->d_obj.get(), c->obj.data(), sizeof(double) * nCol) == hipSuccess &&
+         (nnz == 0 || (hdm_memcpy_h2d_sync(c->d_ridx.get(), c->ridx.data(), sizeof(int) * nnz) == hipSuccess &&
+                       hdm_memcpy_h2d_sync(c->d_rval.get(), c->rval.data(), sizeof(double) * nnz) == hipSuccess &&
+                       hdm_memcpy_h2d_sync(c->d_cidx.get(), ci.data(), sizeof(int) * nnz) == hipSuccess &&
+                       hdm_memcpy_h2d_sync(c->d_cval.get(), cv.data(), sizeof(double) * nnz) == hipSuccess));
     lp_plan(c);
     ok = ok && lp_set_path(c, 0) == 0;
     if (!ok) {

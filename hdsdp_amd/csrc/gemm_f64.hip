@@ -56,7 +56,8 @@ int persist_counters(int **cnt, int *slots) {
     if (!pd.ring) {
         int cus = 0;
         HDM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        HDM_HIP_CHECK(hipMalloc((void **) &pd.ring, sizeof(int) * 8 * PERSIST_RING));
+        // raw on purpose (static storage: lives until the process ends, never freed -- no hipFree after the runtime has shut down)
+        HDM_HIP_CHECK(hdm_malloc((void **) &pd.ring, sizeof(int) * 8 * PERSIST_RING));
         pd.slots = 2 * std::max(1, cus);
     }
     static const int env_reserve = [] { const char *e = getenv("HDM_PERSIST_RESERVE_CUS"); return e ? atoi(e) : -1; }();
@@ -102,7 +103,8 @@ int get_tiles(int MT, int NT, int klimit, int lower_only, unsigned long long col
     for (size_t i = 0; i < v.size(); ++i) h[i] = v[i].second;
     TileList tl;
     tl.n = (int) h.size();
-    HDM_HIP_CHECK(hipMalloc((void **) &tl.dev, sizeof(int2) * std::max<size_t>(1, h.size())));
+    // raw on purpose (the tile-list cache has static storage: kept until the process ends, never freed)
+    HDM_HIP_CHECK(hdm_malloc((void **) &tl.dev, sizeof(int2) * std::max<size_t>(1, h.size())));
     HDM_HIP_CHECK(hdm_memcpy_h2d_sync(tl.dev, h.data(), sizeof(int2) * h.size()));
     g_tl_cache[key] = tl;
     out = tl;

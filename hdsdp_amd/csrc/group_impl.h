@@ -57,8 +57,13 @@ struct MiGroup {
     int bcount = 0;
     long bgen = 0;
     // all-reduce of the copy transport
-    std::vector<double *> ar_ptr, ar_tmp;
-    std::vector<size_t> ar_cap;
+    std::vector<double *> ar_ptr;        // not owned: the callers' buffers of the all-reduce in flight
+    // Slice r is allocated by worker r with its shard's device current and freed with the group: by `delete` in group_setup, on the
+    // CALLER's thread with the caller's device current (hipFree finds the pointer's device itself) -- the one place where memory goes
+    // at a point of the call sequence where it did not before: up to now a replaced group leaked them.  What else a replaced
+    // group held (its streams and contexts, its workers' per-thread sweep scratch) is still not released.  g_group itself is
+    // never destroyed at exit.
+    std::vector<HdmBuf<double>> ar_tmp;
 
     int barrier() {
         std::unique_lock<std::mutex> lk(bmu);
@@ -203,7 +208,7 @@ int group_setup(int n, const int *ids, int transport_request) {
     G->ctx.resize(n);
     G->cstream.assign(n, nullptr);
     G->rc.assign(n, 0);
-    G->ar_ptr.assign(n, nullptr); G->ar_tmp.assign(n, nullptr); G->ar_cap.assign(n, 0);
+    G->ar_ptr.assign(n, nullptr); G->ar_tmp.resize(n);
     for (int r = 0; r < n; ++r) {
         if (ctx_open(G->ctx[r], ids[r])) return bail("cannot open a context on one of the devices");
         if (hipStreamCreateWithFlags(&G->cstream[r], hipStreamNonBlocking) != hipSuccess) return bail("cannot create the exchange stream");
@@ -361,20 +366,16 @@ int grp_allreduce(void *vx, void *buf, int64_t count) {
     const int64_t per = (count + W - 1) / W;
     const int64_t lo = std::min<int64_t>(count, (int64_t) r * per), hi = std::min<int64_t>(count, lo + per);
     G->ar_ptr[r] = (double *) buf;
-    if ((size_t) per > G->ar_cap[r]) {
-        if (G->ar_tmp[r]) (void) hipFree(G->ar_tmp[r]);
-        if (hipMalloc((void **) &G->ar_tmp[r], sizeof(double) * (size_t) per) != hipSuccess) { G->ar_tmp[r] = nullptr; G->ar_cap[r] = 0; return 1; }
-        G->ar_cap[r] = (size_t) per;
-    }
+    if (G->ar_tmp[r].reserve((size_t) per) != hipSuccess) return 1;
     if (G->barrier()) return 1;
     if (hi > lo) {
-        if (grp_sum_launch(G->ar_ptr.data(), W, lo, hi - lo, G->ar_tmp[r], s)) return 1;
+        if (grp_sum_launch(G->ar_ptr.data(), W, lo, hi - lo, G->ar_tmp[r].get(), s)) return 1;
     }
     if (hipStreamSynchronize(s) != hipSuccess) return 1;
     if (G->barrier()) return 1;
     for (int q = 0; q < W; ++q) {
         const int64_t qlo = std::min<int64_t>(count, (int64_t) q * per), qhi = std::min<int64_t>(count, qlo + per);
-        if (qhi > qlo && hipMemcpyAsync((double *) buf + qlo, G->ar_tmp[q], sizeof(double) * (size_t) (qhi - qlo),
+        if (qhi > qlo && hipMemcpyAsync((double *) buf + qlo, G->ar_tmp[q].get(), sizeof(double) * (size_t) (qhi - qlo),
                                         hipMemcpyDefault, s) != hipSuccess) return 1;
     }
     if (hipStreamSynchronize(s) != hipSuccess) return 1;
@@ -660,7 +661,7 @@ int rccl_group_self_test(int n, const int *ids, int timeout_ms) {
         int rc = 0;
         hipStream_t s = nullptr;
         hipEvent_t ev = nullptr;
-        double *a = nullptr, *snd = nullptr, *rcv = nullptr;
+        HdmBuf<double> a_own, snd_own, rcv_own;
         std::vector<double> h((size_t) cnt * n), out((size_t) cnt * n);
         const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(timeout_ms);
         auto bounded_wait = [&]() {          // 0: the event has completed
@@ -676,9 +677,10 @@ int rccl_group_self_test(int n, const int *ids, int timeout_ms) {
             if (hipSetDevice(dev[r]) != hipSuccess) { rc = 1; break; }
             if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess ||
-                hipMalloc((void **) &a, sizeof(double) * cnt) != hipSuccess ||
-                hipMalloc((void **) &snd, sizeof(double) * (size_t) cnt * n) != hipSuccess ||
-                hipMalloc((void **) &rcv, sizeof(double) * (size_t) cnt * n) != hipSuccess) { rc = 3; break; }
+                a_own.alloc(cnt) != hipSuccess ||
+                snd_own.alloc((size_t) cnt * n) != hipSuccess ||
+                rcv_own.alloc((size_t) cnt * n) != hipSuccess) { rc = 3; break; }
+            double *a = a_own.get(), *snd = snd_own.get(), *rcv = rcv_own.get();
             for (int i = 0; i < cnt; ++i) h[i] = ar_val(r, i);
             if (hipMemcpy(a, h.data(), sizeof(double) * cnt, hipMemcpyHostToDevice) != hipSuccess) { rc = 3; break; }
             for (int d = 0; d < n; ++d) for (int i = 0; i < cnt; ++i) h[(size_t) d * cnt + i] = sr_val(r, d, i);
@@ -707,9 +709,9 @@ int rccl_group_self_test(int n, const int *ids, int timeout_ms) {
         } else if (failed.load() && comm[r]) {
             (void) ncclCommAbort(comm[r]); comm[r] = nullptr;
         }
-        if (a) (void) hipFree(a);
-        if (snd) (void) hipFree(snd);
-        if (rcv) (void) hipFree(rcv);
+        a_own.reset();   // (before the stream they were used on goes)
+        snd_own.reset();
+        rcv_own.reset();
         if (ev) (void) hipEventDestroy(ev);
         if (s) (void) hipStreamDestroy(s);
         (void) hipGetLastError();

@@ -17,10 +17,10 @@ static inline size_t hdm_operand_pad(long ld) { return (size_t) 128 * (size_t) (
 // a diagnostic -- the new memory filled with 0xFF bytes (NaN as a double, -1 as an int), so that a kernel that reads what
 // nobody has written shows up as NaNs in the results instead of as whatever the allocator recycled (round 4: one run of the
 // ingest test read an earlier cone's data out of a fresh buffer and nothing said so).
+// The engine's buffers are HdmBuf<T> / HdmPinned<T> (devbuf.h), whose alloc() calls it; the few buffers that live until the process
+// ends (gemm_f64.hip, schur.hip: never freed, raw pointers on purpose) call it by name.
 hipError_t hdm_malloc(void **p, size_t bytes);   // alloc.cpp
-#ifndef HDM_MALLOC_IMPL
-#define hipMalloc(p, bytes) hdm_malloc((void **) (p), (bytes))
-#endif
+#include "devbuf.h"
 
 #define HDM_TILE 128          // workgroup tile edge of the fp64 MFMA GEMM family
 #define HDM_BK 16             // k-depth of one LDS stage

@@ -1028,43 +1028,33 @@ int HdmLanczos::init(int n_) {
     n = n_;
     n16 = (n + 15) / 16 * 16;
     const size_t blk = sizeof(double) * (size_t) n16 * 8;
-    HDM_HIP_CHECK(hipMalloc((void **) &V, sizeof(double) * (size_t) n16 * (maxdim + 1)));
-    HDM_HIP_CHECK(hipMalloc((void **) &bv, blk));
-    HDM_HIP_CHECK(hipMalloc((void **) &b1, blk));
-    HDM_HIP_CHECK(hipMalloc((void **) &b2, blk));
-    HDM_HIP_CHECK(hipMalloc((void **) &bw, blk));
-    HDM_HIP_CHECK(hipMalloc((void **) &bz, blk));
-    HDM_HIP_CHECK(hipMalloc((void **) &warm, sizeof(double) * (size_t) n16));
-    HDM_HIP_CHECK(hipMalloc((void **) &tmp, sizeof(double) * (size_t) n16));
+    HDM_HIP_CHECK(V.alloc((size_t) n16 * (maxdim + 1)));
+    HDM_HIP_CHECK(bv.alloc(blk / sizeof(double)));
+    HDM_HIP_CHECK(b1.alloc(blk / sizeof(double)));
+    HDM_HIP_CHECK(b2.alloc(blk / sizeof(double)));
+    HDM_HIP_CHECK(bw.alloc(blk / sizeof(double)));
+    HDM_HIP_CHECK(bz.alloc(blk / sizeof(double)));
+    HDM_HIP_CHECK(warm.alloc((size_t) n16));
+    HDM_HIP_CHECK(tmp.alloc((size_t) n16));
     // the scalars that travel between host and device -- (alpha, beta) pairs, Ritz coefficients, residual norms -- live in one
     // block of mapped pinned host memory: the kernels write their results straight into it and the host reads them after its
     // synchronisation (a copy into pageable memory per group of steps cost more than the group's kernels at n = 2000)
-    HDM_HIP_CHECK(hipHostMalloc((void **) &scal_h, sizeof(double) * 128, hipHostMallocMapped));
-    memset(scal_h, 0, sizeof(double) * 128);
-    HDM_HIP_CHECK(hipHostGetDevicePointer((void **) &scal, scal_h, 0));
-    HDM_HIP_CHECK(hipMalloc((void **) &part, sizeof(double) * 32 * (size_t) n16));
-    for (double *b : {bv, b1, b2, bw, bz}) HDM_HIP_CHECK(hdm_memset_sync(b, 0, blk));
-    HDM_HIP_CHECK(hdm_memset_sync(warm, 0, sizeof(double) * (size_t) n16));
-    HDM_HIP_CHECK(hdm_memset_sync(tmp, 0, sizeof(double) * (size_t) n16));
+    HDM_HIP_CHECK(scal_h.alloc(128, hipHostMallocMapped));
+    memset(scal_h.get(), 0, sizeof(double) * 128);
+    HDM_HIP_CHECK(part.alloc(32 * (size_t) n16));
+    for (double *b : {bv.get(), b1.get(), b2.get(), bw.get(), bz.get()}) HDM_HIP_CHECK(hdm_memset_sync(b, 0, blk));
+    HDM_HIP_CHECK(hdm_memset_sync(warm.get(), 0, sizeof(double) * (size_t) n16));
+    HDM_HIP_CHECK(hdm_memset_sync(tmp.get(), 0, sizeof(double) * (size_t) n16));
     start.resize(n);
     hdm_lanczos_start_vector(n, start.data());
     {   // device copy of the start vector, zero padded (the single-launch form builds its own first vector)
         std::vector<double> sp(n16, 0.0);
         for (int i = 0; i < n; ++i) sp[i] = start[i];
-        HDM_HIP_CHECK(hipMalloc((void **) &startd, sizeof(double) * (size_t) n16));
-        HDM_HIP_CHECK(hipMemcpy(startd, sp.data(), sizeof(double) * (size_t) n16, hipMemcpyHostToDevice));
+        HDM_HIP_CHECK(startd.alloc((size_t) n16));
+        HDM_HIP_CHECK(hipMemcpy(startd.get(), sp.data(), sizeof(double) * (size_t) n16, hipMemcpyHostToDevice));
     }
     nComputed = 0;
     return 0;
-}
-
-void HdmLanczos::destroy() {
-    for (double *b : {V, bv, b1, b2, bw, bz, warm, tmp, part, startd, LT})
-        if (b) (void) hipFree(b);
-    if (gsync) (void) hipFree(gsync);
-    if (scal_h) (void) hipHostFree(scal_h);
-    gsync = nullptr; scal_h = nullptr;
-    V = bv = b1 = b2 = bw = bz = warm = tmp = scal = part = startd = LT = nullptr;
 }
 
 // out (column 0 of a vector block) = Linv * ( -dS * ( Linv^T * in ) ): three HBM-bound matrix-vector products with
@@ -1073,12 +1063,12 @@ void HdmLanczos::destroy() {
 int HdmLanczos::apply(const double *Linv, long ldl, const double *dS, long ldd, const double *in, double *out, hipStream_t s) {
     const int nchunk = LZ_NCHUNK;
     // t1 = Linv^T v            (column dots of the lower-triangular Linv)
-    hipLaunchKernelGGL(hdm_gemv_t_kernel, dim3((n16 + 3) / 4), dim3(256), 0, s, Linv, ldl, n16, 1, 1.0, in, b1);
+    hipLaunchKernelGGL(hdm_gemv_t_kernel, dim3((n16 + 3) / 4), dim3(256), 0, s, Linv, ldl, n16, 1, 1.0, in, b1.get());
     // t2 = -dS t1              (dS is symmetric: column dots again)
-    hipLaunchKernelGGL(hdm_gemv_t_kernel, dim3((n16 + 3) / 4), dim3(256), 0, s, dS, ldd, n16, 0, -1.0, b1, b2);
+    hipLaunchKernelGGL(hdm_gemv_t_kernel, dim3((n16 + 3) / 4), dim3(256), 0, s, dS, ldd, n16, 0, -1.0, b1.get(), b2.get());
     // w = Linv t2              (rows across lanes, 32 column chunks, deterministic two-level sum)
-    hipLaunchKernelGGL(hdm_gemv_n_kernel, dim3((n16 + 255) / 256, nchunk), dim3(256), 0, s, Linv, ldl, n16, 1, nchunk, b2, part);
-    if (out) hipLaunchKernelGGL(hdm_gemv_n_reduce_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, part, n16, nchunk, 1.0, out);   // (out == nullptr: the caller sums the partials itself)
+    hipLaunchKernelGGL(hdm_gemv_n_kernel, dim3((n16 + 255) / 256, nchunk), dim3(256), 0, s, Linv, ldl, n16, 1, nchunk, b2.get(), part.get());
+    if (out) hipLaunchKernelGGL(hdm_gemv_n_reduce_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, part.get(), n16, nchunk, 1.0, out);   // (out == nullptr: the caller sums the partials itself)
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1097,15 +1087,15 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
                                                   (int) (sizeof(double) * LZ_RESIDENT_MAX * (LZ_RESIDENT_MAX + 1))));
                 configured_dev = dev;
             }
-            hipLaunchKernelGGL(hdm_lanczos_whole_kernel<true>, dim3(1), dim3(1024), dyn, s, Linv, ldl, dS, ldd, n16, V, (long) n16, startd,
-                               warm, nComputed == 0 ? 1 : 0, scal + 60);
+            hipLaunchKernelGGL(hdm_lanczos_whole_kernel<true>, dim3(1), dim3(1024), dyn, s, Linv, ldl, dS, ldd, n16, V.get(), (long) n16, startd.get(),
+                               warm.get(), nComputed == 0 ? 1 : 0, scal_h.dev() + 60);
         } else {
-            hipLaunchKernelGGL(hdm_lanczos_whole_kernel<false>, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, V, (long) n16, startd,
-                               warm, nComputed == 0 ? 1 : 0, scal + 60);
+            hipLaunchKernelGGL(hdm_lanczos_whole_kernel<false>, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, V.get(), (long) n16, startd.get(),
+                               warm.get(), nComputed == 0 ? 1 : 0, scal_h.dev() + 60);
         }
         HDM_HIP_CHECK(hipGetLastError());
         HDM_HIP_CHECK(hipStreamSynchronize(s));
-        const double r[3] = {scal_h[60], scal_h[61], scal_h[62]};
+        const double r[3] = {scal_h.get()[60], scal_h.get()[61], scal_h.get()[62]};
         if (r[2] != 0.0) return 1;
         nComputed += 1;
         if (maxStep) *maxStep = r[0];
@@ -1116,9 +1106,9 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
     std::vector<double> H((size_t) nh * nh, 0.0);
     auto Hm = [&](int i, int j) -> double & { return H[(size_t) j * nh + i]; };
     // starting vector: fresh, or the previous Ritz image + 1e-3 * the same pseudo-random vector (:166-181), made on the device
-    hipLaunchKernelGGL(hdm_warm_start_kernel, dim3(1), dim3(1024), 0, s, tmp, warm, startd, n, n16, nComputed == 0 ? 1 : 0);
-    HDM_HIP_CHECK(hipMemsetAsync(V, 0, sizeof(double) * (size_t) n16 * (md + 1), s));
-    hipLaunchKernelGGL(hdm_normalize_kernel, dim3(1), dim3(1024), 0, s, tmp, V, bv, n16);
+    hipLaunchKernelGGL(hdm_warm_start_kernel, dim3(1), dim3(1024), 0, s, tmp.get(), warm.get(), startd.get(), n, n16, nComputed == 0 ? 1 : 0);
+    HDM_HIP_CHECK(hipMemsetAsync(V.get(), 0, sizeof(double) * (size_t) n16 * (md + 1), s));
+    hipLaunchKernelGGL(hdm_normalize_kernel, dim3(1), dim3(1024), 0, s, tmp.get(), V.get(), bv.get(), n16);
     HDM_HIP_CHECK(hipGetLastError());
 
     int checkFreq = md / 5;
@@ -1144,14 +1134,14 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
     }
     static const bool dbg2 = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e) >= 2; }();
     if (big) {
-        if (dbg2) HDM_HIP_CHECK(hipMemsetAsync(bz + 4 * (size_t) n16, 0, sizeof(double) * 16, s));
-        if (!LT) HDM_HIP_CHECK(hipMalloc((void **) &LT, sizeof(double) * (size_t) n16 * n16));
+        if (dbg2) HDM_HIP_CHECK(hipMemsetAsync(bz.get() + 4 * (size_t) n16, 0, sizeof(double) * 16, s));
+        HDM_HIP_CHECK(LT.reserve((size_t) n16 * n16));
         if (!gsync) {
-            HDM_HIP_CHECK(hipMalloc((void **) &gsync, sizeof(unsigned) * (64 + LZG_WG)));
-            HDM_HIP_CHECK(hipMemsetAsync(gsync, 0, sizeof(unsigned) * (64 + LZG_WG), s));
+            HDM_HIP_CHECK(gsync.alloc((64 + LZG_WG)));
+            HDM_HIP_CHECK(hipMemsetAsync(gsync.get(), 0, sizeof(unsigned) * (64 + LZG_WG), s));
             sync_epoch = 0;
         }
-        hipLaunchKernelGGL(hdm_transpose_kernel, dim3((n16 + 31) / 32, (n16 + 31) / 32), dim3(256), 0, s, Linv, ldl, LT, (long) n16, n16);
+        hipLaunchKernelGGL(hdm_transpose_kernel, dim3((n16 + 31) / 32, (n16 + 31) / 32), dim3(256), 0, s, Linv, ldl, LT.get(), (long) n16, n16);
         HDM_HIP_CHECK(hipGetLastError());
     }
     double grp[2 * 8 + 1] = {0.0};               // (alpha, beta) of the current group of steps, fused form
@@ -1162,11 +1152,11 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
             if (grp_k0 < 0 || k >= grp_k0 + grp_n) {       // next group: as many steps as lie before the next Ritz check
                 grp_k0 = k;
                 grp_n = std::min(std::min(checkFreq - (k % checkFreq), md - k), 8);
-                hipLaunchKernelGGL(hdm_lanczos_fused_kernel, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, V, (long) n16, k, grp_n,
-                                   hprev, bv, scal + 44);
+                hipLaunchKernelGGL(hdm_lanczos_fused_kernel, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, V.get(), (long) n16, k, grp_n,
+                                   hprev, bv.get(), scal_h.dev() + 44);
                 HDM_HIP_CHECK(hipGetLastError());
                 HDM_HIP_CHECK(hipStreamSynchronize(s));
-                for (int q = 0; q < 2 * grp_n + 1; ++q) grp[q] = scal_h[44 + q];   // (scal + 8 .. + 39, + 64 .. + 95: Ritz coefficients)
+                for (int q = 0; q < 2 * grp_n + 1; ++q) grp[q] = scal_h.get()[44 + q];   // (scal + 8 .. + 39, + 64 .. + 95: Ritz coefficients)
             }
             hs[0] = grp[2 * (k - grp_k0)]; hs[1] = grp[2 * (k - grp_k0) + 1];
         } else if (big) {
@@ -1175,17 +1165,17 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
                 grp_n = std::min(std::min(checkFreq - (k % checkFreq), md - k), 8);
                 LzgArgs a = {};
                 a.epoch0 = sync_epoch; sync_epoch += 3u * (unsigned) grp_n;     // (the barrier words are never reset: epochs only grow)
-                scal_h[44 + 2 * grp_n + 1] = 0.0;                               // give-up word of this launch
-                a.Linv = Linv; a.ldl = ldl; a.LinvT = LT; a.ldt = n16; a.dS = dS; a.ldd = ldd; a.n = n16; a.V = V; a.ldv = n16;
-                a.k0 = k; a.nsteps = grp_n; a.hprev = hprev; a.blk = bv; a.t1 = b1; a.t2 = b2; a.xw = b1 + n16;     // (the vector blocks are n16 x 8: column 1 of b1 is free)
-                a.out = scal + 44; a.sync = gsync; a.dbg = dbg2 ? bz + 4 * (size_t) n16 : nullptr;
+                scal_h.get()[44 + 2 * grp_n + 1] = 0.0;                               // give-up word of this launch
+                a.Linv = Linv; a.ldl = ldl; a.LinvT = LT.get(); a.ldt = n16; a.dS = dS; a.ldd = ldd; a.n = n16; a.V = V.get(); a.ldv = n16;
+                a.k0 = k; a.nsteps = grp_n; a.hprev = hprev; a.blk = bv.get(); a.t1 = b1.get(); a.t2 = b2.get(); a.xw = b1.get() + n16;     // (the vector blocks are n16 x 8: column 1 of b1 is free)
+                a.out = scal_h.dev() + 44; a.sync = gsync.get(); a.dbg = dbg2 ? bz.get() + 4 * (size_t) n16 : nullptr;
                 if (n16 <= 2048) hipLaunchKernelGGL(hdm_lanczos_group_kernel<8>, dim3(big_wg), dim3(256), 0, s, a);
                 else hipLaunchKernelGGL(hdm_lanczos_group_kernel<16>, dim3(big_wg), dim3(256), 0, s, a);
                 HDM_HIP_CHECK(hipGetLastError());
                 HDM_HIP_CHECK(hipStreamSynchronize(s));
-                for (int q = 0; q < 2 * grp_n + 1; ++q) grp[q] = scal_h[44 + q];
-                if (scal_h[44 + 2 * grp_n + 1] != 0.0) {
-                    HDM_HIP_CHECK(hipMemsetAsync(gsync, 0, sizeof(unsigned) * (64 + LZG_WG), s));
+                for (int q = 0; q < 2 * grp_n + 1; ++q) grp[q] = scal_h.get()[44 + q];
+                if (scal_h.get()[44 + 2 * grp_n + 1] != 0.0) {
+                    HDM_HIP_CHECK(hipMemsetAsync(gsync.get(), 0, sizeof(unsigned) * (64 + LZG_WG), s));
                     // a grid-wide wait ran out (the workgroups were not all resident): this object goes back to a launch per
                     // product for good, and this test starts over -- nothing of it has left the object yet
                     fprintf(stderr, "[hdsdp_mi355x] lanczos: grid-wide wait timed out, falling back to one launch per product\n");
@@ -1204,17 +1194,17 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
                 grp_n = group_env ? std::min(std::min(checkFreq - (k % checkFreq), md - k), 8) : 1;
                 for (int q = 0; q < grp_n; ++q) {
                     const int kk = k + q;
-                    if (apply(Linv, ldl, dS, ldd, bv, nullptr, s)) return 1;
-                    hipLaunchKernelGGL(hdm_lanczos_step_kernel, dim3(1), dim3(1024), 0, s, part, LZ_NCHUNK, bw,
-                                       kk > 0 ? V + (size_t) (kk - 1) * n16 : nullptr,
-                                       q > 0 ? scal + 44 + 2 * (q - 1) + 1 : scal + 43,
-                                       V + (size_t) kk * n16, V + (size_t) (kk + 1) * n16, bv, n16, scal + 44 + 2 * q);
+                    if (apply(Linv, ldl, dS, ldd, bv.get(), nullptr, s)) return 1;
+                    hipLaunchKernelGGL(hdm_lanczos_step_kernel, dim3(1), dim3(1024), 0, s, part.get(), LZ_NCHUNK, bw.get(),
+                                       kk > 0 ? V.get() + (size_t) (kk - 1) * n16 : nullptr,
+                                       q > 0 ? scal_h.dev() + 44 + 2 * (q - 1) + 1 : scal_h.dev() + 43,
+                                       V.get() + (size_t) kk * n16, V.get() + (size_t) (kk + 1) * n16, bv.get(), n16, scal_h.dev() + 44 + 2 * q);
                 }
                 HDM_HIP_CHECK(hipGetLastError());
                 HDM_HIP_CHECK(hipStreamSynchronize(s));
-                for (int q = 0; q < 2 * grp_n; ++q) grp[q] = scal_h[44 + q];
+                for (int q = 0; q < 2 * grp_n; ++q) grp[q] = scal_h.get()[44 + q];
                 // the last norm of this group is the next group's hprev: keep it where the next group's first step reads it
-                scal_h[43] = scal_h[44 + 2 * (grp_n - 1) + 1];
+                scal_h.get()[43] = scal_h.get()[44 + 2 * (grp_n - 1) + 1];
             }
             hs[0] = grp[2 * (k - grp_k0)]; hs[1] = grp[2 * (k - grp_k0) + 1];
         }
@@ -1241,17 +1231,17 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
                 // z1 = V y1 ; z2 = Op z1 ; warm start <- z2 ; resiVal1 = | z2 - eig1 z1 |
                 // z2' = V y2 ; resiVal2 = | Op z2' - eig1 z2' |   (the reference uses eig1 here too, :262-266)
                 // (both coefficient vectors go into the mapped block, everything is queued, one synchronisation)
-                for (int r = 0; r < kp; ++r) { scal_h[8 + r] = y1[r]; scal_h[64 + r] = y2[r]; }
-                hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, V, (long) n16, kp, scal + 8, bz, n16);
-                if (apply(Linv, ldl, dS, ldd, bz, bw, s)) return 1;
-                HDM_HIP_CHECK(hipMemcpyAsync(warm, bw, sizeof(double) * n16, hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, bw, bz, eig1, n16, scal + 2);
-                hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, V, (long) n16, kp, scal + 64, bz, n16);
-                if (apply(Linv, ldl, dS, ldd, bz, bw, s)) return 1;
-                hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, bw, bz, eig1, n16, scal + 3);
+                for (int r = 0; r < kp; ++r) { scal_h.get()[8 + r] = y1[r]; scal_h.get()[64 + r] = y2[r]; }
+                hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, V.get(), (long) n16, kp, scal_h.dev() + 8, bz.get(), n16);
+                if (apply(Linv, ldl, dS, ldd, bz.get(), bw.get(), s)) return 1;
+                HDM_HIP_CHECK(hipMemcpyAsync(warm.get(), bw.get(), sizeof(double) * n16, hipMemcpyDeviceToDevice, s));
+                hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, bw.get(), bz.get(), eig1, n16, scal_h.dev() + 2);
+                hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, V.get(), (long) n16, kp, scal_h.dev() + 64, bz.get(), n16);
+                if (apply(Linv, ldl, dS, ldd, bz.get(), bw.get(), s)) return 1;
+                hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, bw.get(), bz.get(), eig1, n16, scal_h.dev() + 3);
                 HDM_HIP_CHECK(hipGetLastError());
                 HDM_HIP_CHECK(hipStreamSynchronize(s));
-                const double r12[2] = {scal_h[2], scal_h[3]};
+                const double r12[2] = {scal_h.get()[2], scal_h.get()[3]};
                 // after the second apply() the vector block bv still holds v_{k+1}: the recurrence can continue
                 const double resiVal1 = r12[0], resiVal2 = r12[1];
                 const double resiDiff = eig1 - eig2 - resiVal2;
@@ -1270,7 +1260,7 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
     }
     if (big && dbg2) {
         double t[10];
-        HDM_HIP_CHECK(hipMemcpy(t, bz + 4 * (size_t) n16, sizeof(t), hipMemcpyDeviceToHost));
+        HDM_HIP_CHECK(hipMemcpy(t, bz.get() + 4 * (size_t) n16, sizeof(t), hipMemcpyDeviceToHost));
         fprintf(stderr, "[hdsdp_mi355x ratio] group kernel, workgroup 0, us: Linv^T v %.0f | wait %.0f | dS t1 %.0f | wait %.0f | Linv t2 + x %.0f | wait %.0f | "
                         "alpha, norm, v_{k+1} %.0f\n", t[0] / 100, t[1] / 100, t[2] / 100, t[3] / 100, t[4] / 100, t[5] / 100, t[6] / 100);
     }

@@ -4,15 +4,14 @@
 
 struct HdmLu {
     int n = 0, npad = 0;
-    double *A = nullptr;     // npad x npad, column-major, full; P*A = L*U in place after factor()
-    int *piv = nullptr;      // device, npad: row exchanged with row j at elimination step j
-    int *perm = nullptr;     // device, npad: the same exchanges as one gather (b_permuted[i] = b[perm[i]])
-    double *vec = nullptr;   // 4 * npad scratch vectors (host-side solves)
-    int *info_dev = nullptr;
+    HdmBuf<double> A;        // npad x npad, column-major, full; P*A = L*U in place after factor()
+    HdmBuf<int> piv;         // device, npad: row exchanged with row j at elimination step j
+    HdmBuf<int> perm;        // device, npad: the same exchanges as one gather (b_permuted[i] = b[perm[i]])
+    HdmBuf<double> vec;      // 4 * npad scratch vectors (host-side solves)
+    HdmBuf<int> info_dev;
     bool factored = false;
 
     int init(int n);
-    void destroy();
     int load_host_lower(const double *M, long ldm, hipStream_t s);     // lower triangle valid (the reference's M)
     int load_device_lower(const double *M, long ldm, hipStream_t s);
     int factor(hipStream_t s, int *info_host);                         // info = 0 ok, j+1 = exactly singular at step j

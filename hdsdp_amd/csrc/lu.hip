@@ -244,12 +244,12 @@ int HdmLu::init(int n_) {
     n = n_;
     npad = (int) hdm_roundup(n, HDM_TILE);
     size_t mat = sizeof(double) * (size_t) npad * npad;
-    HDM_HIP_CHECK(hipMalloc((void **) &A, mat + hdm_operand_pad(npad)));
-    HDM_HIP_CHECK(hipMalloc((void **) &piv, sizeof(int) * (size_t) npad));
-    HDM_HIP_CHECK(hipMalloc((void **) &perm, sizeof(int) * (size_t) npad));
-    HDM_HIP_CHECK(hipMalloc((void **) &vec, sizeof(double) * (size_t) npad * 4));
-    HDM_HIP_CHECK(hipMalloc((void **) &info_dev, sizeof(int)));
-    HDM_HIP_CHECK(hdm_memset_sync(A, 0, mat + hdm_operand_pad(npad)));
+    HDM_HIP_CHECK(A.alloc((size_t) npad * npad, hdm_operand_pad(npad)));
+    HDM_HIP_CHECK(piv.alloc((size_t) npad));
+    HDM_HIP_CHECK(perm.alloc((size_t) npad));
+    HDM_HIP_CHECK(vec.alloc((size_t) npad * 4));
+    HDM_HIP_CHECK(info_dev.alloc(1));
+    HDM_HIP_CHECK(hdm_memset_sync(A.get(), 0, mat + hdm_operand_pad(npad)));
     // the LDS limit of the solve kernel is a per-function attribute: only ever raise it
     static std::mutex lds_mu;
     static int lds_limit[64];
@@ -268,61 +268,52 @@ int HdmLu::init(int n_) {
     return 0;
 }
 
-void HdmLu::destroy() {
-    if (A) (void) hipFree(A);
-    if (piv) (void) hipFree(piv);
-    if (perm) (void) hipFree(perm);
-    if (vec) (void) hipFree(vec);
-    if (info_dev) (void) hipFree(info_dev);
-    A = vec = nullptr;
-    piv = perm = info_dev = nullptr;
-}
-
 static int lu_finish_load(HdmLu *lu, hipStream_t s) {
     long tot = (long) lu->npad * lu->npad;
-    hipLaunchKernelGGL(hdm_lu_mirror_pad_kernel, dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, s, lu->A,
-                       (long) lu->npad, lu->n, lu->npad, lu->piv);
+    hipLaunchKernelGGL(hdm_lu_mirror_pad_kernel, dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, s, lu->A.get(),
+                       (long) lu->npad, lu->n, lu->npad, lu->piv.get());
     HDM_HIP_CHECK(hipGetLastError());
     lu->factored = false;
     return 0;
 }
 
 int HdmLu::load_host_lower(const double *M, long ldm, hipStream_t s) {
-    HDM_HIP_CHECK(hipMemcpy2DAsync(A, sizeof(double) * npad, M, sizeof(double) * ldm, sizeof(double) * n, n,
+    HDM_HIP_CHECK(hipMemcpy2DAsync(A.get(), sizeof(double) * npad, M, sizeof(double) * ldm, sizeof(double) * n, n,
                                    hipMemcpyHostToDevice, s));
     return lu_finish_load(this, s);
 }
 
 int HdmLu::load_device_lower(const double *M, long ldm, hipStream_t s) {
-    HDM_HIP_CHECK(hipMemcpy2DAsync(A, sizeof(double) * npad, M, sizeof(double) * ldm, sizeof(double) * n, n,
+    HDM_HIP_CHECK(hipMemcpy2DAsync(A.get(), sizeof(double) * npad, M, sizeof(double) * ldm, sizeof(double) * n, n,
                                    hipMemcpyDeviceToDevice, s));
     return lu_finish_load(this, s);
 }
 
 int HdmLu::factor(hipStream_t s, int *info_host) {
-    HDM_HIP_CHECK(hipMemsetAsync(info_dev, 0, sizeof(int), s));
+    HDM_HIP_CHECK(hipMemsetAsync(info_dev.get(), 0, sizeof(int), s));
     const long ld = npad;
     const int nn = (int) hdm_roundup(n, LNB);     // everything behind nn is identity padding
+    double *const Ad = A.get();
     for (int j0 = 0; j0 < nn; j0 += LNB) {
-        hipLaunchKernelGGL(hdm_lu_panel_kernel, dim3(1), dim3(LPT), 0, s, A, ld, nn, j0, piv, info_dev);
+        hipLaunchKernelGGL(hdm_lu_panel_kernel, dim3(1), dim3(LPT), 0, s, Ad, ld, nn, j0, piv.get(), info_dev.get());
         HDM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(hdm_lu_swap_kernel, dim3((nn + 255) / 256), dim3(256), 0, s, A, ld, nn, j0, piv);
+        hipLaunchKernelGGL(hdm_lu_swap_kernel, dim3((nn + 255) / 256), dim3(256), 0, s, Ad, ld, nn, j0, piv.get());
         HDM_HIP_CHECK(hipGetLastError());
         const int rem = nn - j0 - LNB;
         if (rem <= 0) break;
-        hipLaunchKernelGGL(hdm_lu_trsm_kernel, dim3((rem + 255) / 256), dim3(256), 0, s, A, ld, nn, j0);
+        hipLaunchKernelGGL(hdm_lu_trsm_kernel, dim3((rem + 255) / 256), dim3(256), 0, s, Ad, ld, nn, j0);
         HDM_HIP_CHECK(hipGetLastError());
         HdmGemmArgs g = {};    // A22 -= L21 * U12   (B operand element (j,k) = U12(k,j): K-major)
-        g.A = A + (j0 + LNB) + (long) j0 * ld; g.lda = ld;
-        g.B = A + j0 + (long) (j0 + LNB) * ld; g.ldb = ld; g.b_kmajor = 1;
-        g.C = A + (long) (j0 + LNB) * (ld + 1); g.ldc = ld;
+        g.A = Ad + (j0 + LNB) + (long) j0 * ld; g.lda = ld;
+        g.B = Ad + j0 + (long) (j0 + LNB) * ld; g.ldb = ld; g.b_kmajor = 1;
+        g.C = Ad + (long) (j0 + LNB) * (ld + 1); g.ldc = ld;
         g.M = rem; g.N = rem; g.K = LNB; g.batch = 1; g.alpha = -1.0; g.beta = 1.0; g.epilogue = HDM_EPI_STORE;
         if (hdm_launch_gemm(g, s)) return 1;
     }
     int info = 0;
     std::vector<int> hp(npad), hperm(npad);
-    HDM_HIP_CHECK(hipMemcpyAsync(&info, info_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-    HDM_HIP_CHECK(hipMemcpyAsync(hp.data(), piv, sizeof(int) * (size_t) npad, hipMemcpyDeviceToHost, s));
+    HDM_HIP_CHECK(hipMemcpyAsync(&info, info_dev.get(), sizeof(int), hipMemcpyDeviceToHost, s));
+    HDM_HIP_CHECK(hipMemcpyAsync(hp.data(), piv.get(), sizeof(int) * (size_t) npad, hipMemcpyDeviceToHost, s));
     HDM_HIP_CHECK(hipStreamSynchronize(s));
     // index bookkeeping: the sequence of row exchanges as one gather
     for (int i = 0; i < npad; ++i) hperm[i] = i;
@@ -333,7 +324,7 @@ int HdmLu::factor(hipStream_t s, int *info_host) {
     }
     for (int i = 0; i < n; ++i)
         if (hperm[i] >= n) info = info ? info : n;   // a padding row was pulled in: the matrix is singular
-    HDM_HIP_CHECK(hipMemcpyAsync(perm, hperm.data(), sizeof(int) * (size_t) npad, hipMemcpyHostToDevice, s));
+    HDM_HIP_CHECK(hipMemcpyAsync(perm.get(), hperm.data(), sizeof(int) * (size_t) npad, hipMemcpyHostToDevice, s));
     HDM_HIP_CHECK(hipStreamSynchronize(s));
     if (info_host) *info_host = info;
     factored = (info == 0);
@@ -348,7 +339,7 @@ int HdmLu::solve_device(const double *b_dev, double *x_dev, int nrhs, long ldv, 
         fprintf(stderr, "[hdsdp_mi355x] indefinite solve: %d unknowns do not fit the LDS-resident solve\n", n);
         return 1;
     }
-    hipLaunchKernelGGL(hdm_lu_solve_kernel, dim3(nrhs), dim3(1024), shm, s, A, (long) npad, n, nn, perm, b_dev, x_dev, ldv);
+    hipLaunchKernelGGL(hdm_lu_solve_kernel, dim3(nrhs), dim3(1024), shm, s, A.get(), (long) npad, n, nn, perm.get(), b_dev, x_dev, ldv);
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -357,7 +348,7 @@ int HdmLu::solve_host(const double *rhs, double *sol, int nrhs, hipStream_t s) {
     const int chunk = 2;  // vec holds 4 * npad doubles: chunk rhs + chunk sol
     for (int c0 = 0; c0 < nrhs; c0 += chunk) {
         const int nc = (nrhs - c0 < chunk) ? nrhs - c0 : chunk;
-        double *b = vec, *x = vec + 2L * npad;
+        double *b = vec.get(), *x = vec.get() + 2L * npad;
         HDM_HIP_CHECK(hipMemcpy2DAsync(b, sizeof(double) * npad, rhs + (long) c0 * n, sizeof(double) * n,
                                        sizeof(double) * n, nc, hipMemcpyHostToDevice, s));
         if (solve_device(b, x, nc, npad, s)) return 1;

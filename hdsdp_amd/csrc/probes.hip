@@ -143,10 +143,9 @@ int HMiCholEnvelopeSolve(const double *A_host, int n, const int *first, const do
         if (ch.factor(g.stream, info)) break;
         if (info && *info != 0) { rc = 0; break; }
         if (b && x && ch.solve_host(b, x, 1, 0, g.stream)) break;
-        if (L_host && hipMemcpy2D(L_host, sizeof(double) * n, ch.L, sizeof(double) * ch.npad, sizeof(double) * n, n, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (L_host && hipMemcpy2D(L_host, sizeof(double) * n, ch.L.get(), sizeof(double) * ch.npad, sizeof(double) * n, n, hipMemcpyDeviceToHost) != hipSuccess) break;
         rc = 0;
     } while (0);
-    ch.destroy();
     return rc;
 }
 
@@ -164,7 +163,7 @@ __global__ void mi_band_spd_kernel(double *A, long ld, int n, int band) {
 int HMiCholEnvelopeProbe(int n, int band, int reps, double *ms_dense, double *ms_env) {
     if (ensure_ctx()) return 1;
     double *A = nullptr;
-    if (hipMalloc((void **) &A, sizeof(double) * (size_t) n * n) != hipSuccess) return 1;
+    if (hdm_malloc((void **) &A, sizeof(double) * (size_t) n * n) != hipSuccess) return 1;
     hipLaunchKernelGGL(mi_band_spd_kernel, dim3((unsigned) (((long) n * n + 255) / 256)), dim3(256), 0, g.stream, A, (long) n, n, band);
     int rc = 0;
     for (int pass = 0; pass < 2 && !rc; ++pass) {
@@ -186,7 +185,6 @@ int HMiCholEnvelopeProbe(int n, int band, int reps, double *ms_dense, double *ms
             if (r >= 0) total += ms;
         }
         *(pass == 0 ? ms_dense : ms_env) = total / std::max(1, reps);
-        ch.destroy();
     }
     (void) hipFree(A);
     return rc;
@@ -198,10 +196,9 @@ int HMiPotrf(double *A_dev, int n, int64_t lda, int *info) {
     if (ch.init(n)) return 1;
     if (ch.load_device(A_dev, lda, g.stream)) return 1;
     if (ch.factor(g.stream, info)) return 1;
-    HDM_HIP_CHECK(hipMemcpy2DAsync(A_dev, sizeof(double) * lda, ch.L, sizeof(double) * ch.npad, sizeof(double) * n, n,
+    HDM_HIP_CHECK(hipMemcpy2DAsync(A_dev, sizeof(double) * lda, ch.L.get(), sizeof(double) * ch.npad, sizeof(double) * n, n,
                                    hipMemcpyDeviceToDevice, g.stream));
     HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
-    ch.destroy();
     return 0;
 }
 
@@ -213,7 +210,7 @@ double HMiDiagBlockProbe(int variant, int reps) {
 double HMiMfmaPeakProbe(int iters) {
     if (ensure_ctx()) return -1.0;
     double *out = nullptr;
-    if (hipMalloc((void **) &out, 8) != hipSuccess) return -1.0;
+    if (hdm_malloc((void **) &out, 8) != hipSuccess) return -1.0;
     const int blocks = 256 * 8, threads = 256;
     hipLaunchKernelGGL(mi_mfma_probe_kernel, dim3(blocks), dim3(threads), 0, g.stream, out, 16);
     (void) hipEventRecord(g.ev[6], g.stream);
@@ -231,7 +228,7 @@ double HMiMfmaPeakProbe(int iters) {
 double HMiMfmaIssueProbe(int mode, int wgPerCu, int iters) {
     if (ensure_ctx()) return -1.0;
     double *out = nullptr;
-    if (hipMalloc((void **) &out, 8) != hipSuccess) return -1.0;
+    if (hdm_malloc((void **) &out, 8) != hipSuccess) return -1.0;
     const int blocks = 256 * wgPerCu, threads = 256;
     for (int rep = 0; rep < 2; ++rep) {
         if (rep == 1) (void) hipEventRecord(g.ev[6], g.stream);

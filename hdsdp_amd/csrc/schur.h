@@ -42,9 +42,9 @@ int hdm_sky_to_square(const double *sky, double *sq, int n, hipStream_t s);
 // that owns a chunk streams ONE contiguous range of memory for all matrices.  Same sums in the same order as the dense
 // sweep (the skipped terms are exact zeros): bit-identical results.
 struct HdmZs {
-    unsigned long long *meta = nullptr;   // [chunk][matrix][24]: 16 mask words, then 16 uint32 offsets relative to base[chunk]
-    double *val = nullptr;                // the non-zero values, chunk by chunk, matrix by matrix, in position order
-    unsigned long long *base = nullptr;   // [chunk]: first value of the chunk's range in val
+    HdmBuf<unsigned long long> meta;      // [chunk][matrix][24]: 16 mask words, then 16 uint32 offsets relative to base[chunk]
+    HdmBuf<double> val;                   // the non-zero values, chunk by chunk, matrix by matrix, in position order
+    HdmBuf<unsigned long long> base;      // [chunk]: first value of the chunk's range in val
     long nchunk = 0, sky = 0, nnz = 0;
     int m = 0;
 };

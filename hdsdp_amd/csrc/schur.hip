@@ -870,11 +870,12 @@ int hdm_zs_build_from(const std::function<const double *(int, int)> &source, int
     if (m <= 0 || sky <= 0 || batch <= 0) return 0;
     const long nchunk = (sky + 1023) / 1024;
     if ((double) m * 1024.0 >= 4.0e9) return 0;           // a chunk's offsets are 32-bit
-    unsigned long long *total = nullptr;
-    unsigned *run_dev = nullptr;
-    // every way out below leaves nothing behind but what `out` owns (hdm_zs_free)
-    auto fail = [&](int rc) { if (total && total != out->base) (void) hipFree(total); if (run_dev) (void) hipFree(run_dev); (void) hipGetLastError(); hdm_zs_free(out); return rc; };
-    if (hipMalloc((void **) &total, sizeof(unsigned long long) * nchunk) != hipSuccess) return fail(1);
+    HdmBuf<unsigned long long> total_own;
+    HdmBuf<unsigned> run_own;
+    // every way out below leaves nothing behind: the two locals go with the scope, `out` is emptied
+    auto fail = [&](int rc) { (void) hipGetLastError(); hdm_zs_free(out); return rc; };
+    if (total_own.alloc((size_t) nchunk) != hipSuccess) return fail(1);
+    unsigned long long *total = total_own.get();
     if (hipMemsetAsync(total, 0, sizeof(unsigned long long) * nchunk, s) != hipSuccess) return fail(1);
     for (int c0 = 0; c0 < m; c0 += batch) {
         const int nb = std::min(batch, m - c0);
@@ -889,25 +890,24 @@ int hdm_zs_build_from(const std::function<const double *(int, int)> &source, int
     unsigned long long run = 0;
     for (long b = 0; b < nchunk; ++b) { const unsigned long long k = h[b]; h[b] = run; run += k; }
     if ((double) run > max_fill * (double) m * (double) sky) return fail(0);   // not worth the memory
-    out->base = total;                                     // reused: counts -> exclusive offsets
-    if (hipMemcpyAsync(out->base, h.data(), sizeof(unsigned long long) * nchunk, hipMemcpyHostToDevice, s) != hipSuccess) return fail(1);
+    out->base = std::move(total_own);                      // reused: counts -> exclusive offsets
+    if (hipMemcpyAsync(out->base.get(), h.data(), sizeof(unsigned long long) * nchunk, hipMemcpyHostToDevice, s) != hipSuccess) return fail(1);
     // (+ 64 values of slack: the lanes behind a word's last non-zero read the slot that follows)
-    if (hipMalloc((void **) &out->val, sizeof(double) * (size_t) (run + 64)) != hipSuccess ||
-        hipMalloc((void **) &out->meta, sizeof(unsigned long long) * 24 * (size_t) nchunk * m) != hipSuccess ||
-        hipMalloc((void **) &run_dev, sizeof(unsigned) * nchunk) != hipSuccess)
+    if (out->val.alloc((size_t) (run + 64)) != hipSuccess || out->meta.alloc(24 * (size_t) nchunk * m) != hipSuccess ||
+        run_own.alloc((size_t) nchunk) != hipSuccess)
         return fail(0);                                    // no memory for the copy: the dense sweep stays
-    if (hipMemsetAsync(out->val + run, 0, sizeof(double) * 64, s) != hipSuccess ||
+    unsigned *run_dev = run_own.get();
+    if (hipMemsetAsync(out->val.get() + run, 0, sizeof(double) * 64, s) != hipSuccess ||
         hipMemsetAsync(run_dev, 0, sizeof(unsigned) * nchunk, s) != hipSuccess) return fail(1);
     for (int c0 = 0; c0 < m; c0 += batch) {
         const int nb = std::min(batch, m - c0);
         const double *A = source(c0, nb);
         if (!A) return fail(1);
-        hipLaunchKernelGGL(hdm_zs_fill_kernel, dim3((unsigned) nchunk), dim3(256), 0, s, A, astride, nb, sky, out->base, out->meta, out->val,
+        hipLaunchKernelGGL(hdm_zs_fill_kernel, dim3((unsigned) nchunk), dim3(256), 0, s, A, astride, nb, sky, out->base.get(), out->meta.get(), out->val.get(),
                            c0, m, run_dev);
         if (hipGetLastError() != hipSuccess) return fail(1);
     }
     if (hipStreamSynchronize(s) != hipSuccess) return fail(1);
-    (void) hipFree(run_dev);
     out->nchunk = nchunk; out->sky = sky; out->nnz = (long) run; out->m = m;
     return 0;
 }
@@ -916,7 +916,7 @@ int hdm_zs_expand(const HdmZs &z, int c0, int count, double *A, long astride, hi
     if (!z.val || c0 < 0 || count < 0 || c0 + count > z.m) return 1;
     if (count == 0) return 0;
     const unsigned gy = (unsigned) std::max(1, std::min(count, 16));
-    hipLaunchKernelGGL(hdm_zs_expand_kernel, dim3((unsigned) z.nchunk, gy), dim3(256), 0, s, z.meta, z.val, z.base, z.m, c0, count, A, astride, z.sky);
+    hipLaunchKernelGGL(hdm_zs_expand_kernel, dim3((unsigned) z.nchunk, gy), dim3(256), 0, s, z.meta.get(), z.val.get(), z.base.get(), z.m, c0, count, A, astride, z.sky);
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -925,16 +925,11 @@ int hdm_zs_build(const double *A, long astride, int m, long sky, double max_fill
     return hdm_zs_build_from([&](int c0, int) { return A + (long) c0 * astride; }, std::max(1, m), astride, m, sky, max_fill, out, s);
 }
 
-void hdm_zs_free(HdmZs *z) {
-    if (z->meta) (void) hipFree(z->meta);
-    if (z->val) (void) hipFree(z->val);
-    if (z->base) (void) hipFree(z->base);
-    *z = HdmZs();
-}
+void hdm_zs_free(HdmZs *z) { *z = HdmZs(); }
 
 int hdm_sym_combine_zs(const HdmZs &z, const double *y, const double *C, double tau, double eye, double *S, int n, long lda,
                        long lds_, hipStream_t s) {
-    hipLaunchKernelGGL(hdm_sym_combine_zs_kernel, dim3((unsigned) z.nchunk), dim3(128), 0, s, z.meta, z.val, z.base, z.m, y, C, tau,
+    hipLaunchKernelGGL(hdm_sym_combine_zs_kernel, dim3((unsigned) z.nchunk), dim3(128), 0, s, z.meta.get(), z.val.get(), z.base.get(), z.m, y, C, tau,
                        eye, S, n, (int) lda, lds_, z.sky);
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
@@ -943,7 +938,8 @@ int hdm_sym_combine_zs(const HdmZs &z, const double *y, const double *C, double 
 // partial-sum scratch of the two dot-product sweeps: one buffer per host thread AND device (a host thread normally drives one
 // device -- the caller's, or one shard of a device group -- but the caller's thread may move to another one over its life:
 // HMiDeviceInit on another id, HMiSetDevices followed by plain cones; a buffer bound to the device of the first call would then
-// be read by a kernel on the other).  Kept until the process ends.
+// be read by a kernel on the other).  Kept until the process ends: thread-local storage, so a raw pointer on purpose (an owning
+// type's destructor would call hipFree at thread or process exit, after the runtime may have shut down).
 static double *dot2_scratch(size_t need) {
     struct Buf { double *p = nullptr; size_t cap = 0; };
     static thread_local std::map<int, Buf> bufs;
@@ -953,7 +949,7 @@ static double *dot2_scratch(size_t need) {
     if (need > b.cap) {
         if (b.p) (void) hipFree(b.p);
         b.p = nullptr; b.cap = 0;
-        if (hipMalloc((void **) &b.p, need) != hipSuccess) { (void) hipGetLastError(); b.p = nullptr; return nullptr; }
+        if (hdm_malloc((void **) &b.p, need) != hipSuccess) { (void) hipGetLastError(); b.p = nullptr; return nullptr; }
         b.cap = need;
     }
     return b.p;
@@ -967,7 +963,7 @@ int hdm_sym_dot2_zs(const HdmZs &z, int n, long lda, const double *X, const doub
     double *part = dot2_scratch(sizeof(double) * 2 * (size_t) z.m * (size_t) (rows + nfold));
     if (!part) return 1;
     double *folded = part + 2 * (size_t) z.m * rows;
-    hipLaunchKernelGGL(hdm_sym_dot2_zs_kernel, dim3((unsigned) z.nchunk), dim3(128), 0, s, z.meta, z.val, z.base, z.m, X, Y, ldx, n,
+    hipLaunchKernelGGL(hdm_sym_dot2_zs_kernel, dim3((unsigned) z.nchunk), dim3(128), 0, s, z.meta.get(), z.val.get(), z.base.get(), z.m, X, Y, ldx, n,
                        (int) lda, z.sky, part);
     hipLaunchKernelGGL(hdm_dot2_fold_kernel, dim3((z.m + 255) / 256, nfold), dim3(256), 0, s, part, rows, z.m, nfold, folded);
     hipLaunchKernelGGL(hdm_sym_dot2_reduce_kernel, dim3((z.m + 255) / 256), dim3(256), 0, s, folded, z.m, nfold, Y ? 1 : 0, outx,
