@@ -39,6 +39,7 @@ EXPORTS = [
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiGetAssembleCounts", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
+    "HMiWorkPlanQuery", "HMiConeGetWorkPlan",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
 ]
 
@@ -197,6 +198,8 @@ def load_library():
         "HMiKKTNegativePivots": (C.c_int, [kp]),
         "HMiBspSolve": (C.c_int, [C.c_int, ip, ip, dp, dp, dp, ip, ip, dp]),
         "HMiRcmOrder": (C.c_int, [C.c_int, ip, ip, ip]),
+        "HMiWorkPlanQuery": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+        "HMiConeGetWorkPlan": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "HMiPresolveCSC": (C.c_int, [C.c_int, C.c_int, ip, ip, dp, ip, ip, ip, ip, ip, ip]),
         "HMiReadSDPA": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "HMiSDPAGetDims": (None, [vp, ip, ip, ip]),
@@ -280,6 +283,20 @@ def presolve_csc(n, m, beg, idx, val):
                               _iptr(out["kkt_strategy"]), C.byref(ot)), "HMiPresolveCSC")
     out["obj_type"] = ot.value
     return out
+
+
+WORK_PLAN_FIELDS = ("n16", "nblk", "npb", "npb_loc", "Lr", "R", "astride", "mloc", "Bc", "nsplit", "nslab", "shared_ts",
+                    "gram_queue_global", "t_bytes", "slab_bytes", "exchange_bytes", "gram_bytes")
+
+
+def work_plan(n, m, world=1, rank=0):
+    """what the engine would plan in this process for rank `rank` of `world` on a dense block (csrc/work_plan.h through
+    HMiWorkPlanQuery): layout, constraints per congruence launch, K splits and slabs of the Gram product, buffer sizes.
+    Host arithmetic under the process's HDM_* knobs; needs no GPU"""
+    out = (C.c_int64 * len(WORK_PLAN_FIELDS))()
+    if load_library().HMiWorkPlanQuery(n, m, world, rank, out, len(out)) != len(out):
+        raise HDSDPError(f"HMiWorkPlanQuery refused n={n} m={m} world={world} rank={rank}")
+    return dict(zip(WORK_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def assemble_counts():
@@ -580,6 +597,16 @@ class SDPCone:
         v, p = C.c_int64(0), C.c_int64(0)
         on = load_library().HMiConeSweepInfo(self._h, C.byref(v), C.byref(p))
         return bool(on), int(v.value), int(p.value)
+
+    def work_plan(self):
+        """what the cone holds once its first build has allocated the work space (a group cone: shard 0), to compare with
+        api.work_plan: dict of Bc, nsplit, nslab, shared_ts, gram_queue_global, t_bytes, slab_bytes; None before that"""
+        keys = ("Bc", "nsplit", "nslab", "shared_ts", "gram_queue_global", "t_bytes", "slab_bytes")
+        out = (C.c_int64 * len(keys))()
+        k = load_library().HMiConeGetWorkPlan(self._h, out, len(out))
+        if k < 0:
+            raise HDSDPError("HMiConeGetWorkPlan: not an SDP cone of the engine")
+        return dict(zip(keys, (int(v) for v in out))) if k else None
 
     def destroy(self):
         if self._h:

@@ -17,6 +17,7 @@
 #include "chol.h"
 #include "coeff.h"
 #include "hdm_common.h"
+#include "work_plan.h"
 #include "schur.h"
 #include "lanczos.h"
 #include "lu.h"

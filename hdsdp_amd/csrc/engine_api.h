@@ -201,6 +201,26 @@ int HMiConeSweepInfo(hdsdp_cone *cone, int64_t *values, int64_t *positions) {
     if (positions) *positions = on ? (int64_t) c->zs.sky * c->zs.m : 0;
     return on ? 1 : 0;
 }
+// the work plan (work_plan.h): what the engine would plan here and now -- host only, no context, no device -- and what a cone holds
+int HMiWorkPlanQuery(int n, int m, int world, int rank, int64_t *out, int cap) {
+    if (n < 1 || m < 0 || world < 1 || rank < 0 || rank >= world || !out || cap < 17) return -17;
+    const HdmLayout L = hdm_layout(n, world, (m + world - 1) / world);
+    const long mloc = hdm_rows_of_rank(m, world, rank);
+    const HdmWorkPlan p = hdm_work_plan(L, mloc, false, 0, hdm_knobs_from_env());
+    const int64_t v[17] = {L.n16, L.nblk, L.npb, L.npb_loc, L.Lr, L.R, L.astride, mloc, p.Bc, p.nsplit, p.nslab, p.shared_ts,
+                           p.gram_queue_global, (int64_t) p.t_bytes, (int64_t) p.slab_bytes, (int64_t) p.exch_bytes, (int64_t) p.gm_bytes};
+    memcpy(out, v, sizeof(v));
+    return 17;
+}
+int HMiConeGetWorkPlan(hdsdp_cone *cone, int64_t *out, int cap) {
+    const MiCone *c = cone_data(cone);
+    if (!c || !out || cap < 7) return -1;
+    if (!c->work_ready) return 0;
+    const int64_t v[7] = {c->Bc, c->nsplit, c->nslab, c->shared_ts, c->gram_queue_global, (int64_t) (sizeof(double) * c->T.count()),
+                          (int64_t) (sizeof(double) * (size_t) c->R * c->R * c->nslab)};
+    memcpy(out, v, sizeof(v));
+    return 7;
+}
 
 // ---------------------------------------------------------------- single-process multi-device mode (group_impl.h)
 int HMiSetDevicesEx(int nDevices, const int *deviceIds, int transport) {

@@ -70,7 +70,7 @@ int gram_splits(MiCone *c, int z0, int nz, int slab0 = -1, bool accumulate = fal
     const long chunk = (c->npb_loc + c->nsplit - 1) / c->nsplit;
     gq.k_chunk = chunk * 16; gq.slab_stride = c->R * c->R; gq.alpha = 1.0; gq.role = HDM_ROLE_GRAM;
     gq.k_base = (long) z0 * gq.k_chunk;
-    gq.spanA = gq.spanB = (long) c->world * c->npb_loc * c->Lr * 16 + HDM_OPERAND_PAD_DOUBLES;
+    gq.spanA = gq.spanB = (long) hdm_exchange_doubles(cone_layout(c)) + HDM_OPERAND_PAD_DOUBLES;
     gq.C = c->slabs + (long) (slab0 < 0 ? z0 : slab0) * gq.slab_stride;
     gq.beta = accumulate ? 1.0 : 0.0;
     gq.queue_global = c->gram_queue_global ? 1 : 0;
@@ -100,7 +100,7 @@ int gram_reduce(MiCone *c) {
 }
 int gram_all(MiCone *c) {
     // Gm(lower) = sum over this rank's p-range of Ahat * Ahat^T, rows in segment order (more splits than slabs:
-    // cone_alloc_gemm_work says why)
+    // work_plan.h says why)
     if (gram_range(c, 0, c->nsplit, true)) return 1;
     return gram_reduce(c);
 }

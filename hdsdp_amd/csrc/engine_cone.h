@@ -187,12 +187,9 @@ bool group_wants_block(const MiBlockData &blk);
 bool group_wants_synthetic(int nRow, int nCol);
 hdsdp_retcode group_create_cone(hdsdp_cone **pCone, int iCone, int nRow, int nCol, MiBlockData *blk, bool synthetic);
 
+HdmLayout cone_layout(const MiCone *c) { return {c->world, c->n16, c->nblk, c->npb, c->npb_loc, c->Lr, c->R, c->astride}; }
+
 int cone_alloc_common(MiCone *c) {
-    c->n16 = (int) hdm_roundup(c->n, 16);
-    c->astride = hdm_sky_size(c->n16);
-    c->nblk = c->n16 / 16;
-    c->npb = (long) c->nblk * (c->nblk + 1) / 2 * 16;
-    c->npb_loc = (c->npb + c->world - 1) / c->world;
     c->own.clear();
     // One GPU: constraints that are zero on this block (most of them in a many-block problem; the reference's
     // "sparse SDP cone", hdsdp_conic_sdp.c:1814-1886, loops over the non-zero ones only) are left out of the device
@@ -202,9 +199,8 @@ int cone_alloc_common(MiCone *c) {
     for (int i = c->rank; i < c->m; i += c->world)
         if (!compact || c->blk.rows[i].type != MI_COEFF_ZERO) c->own.push_back(i);
     c->mloc = (int) c->own.size();
-    int maxloc = compact ? c->mloc : (c->m + c->world - 1) / c->world;
-    c->Lr = (c->world == 1) ? (int) hdm_roundup(maxloc + 3, 8) : (int) hdm_roundup(maxloc + 3, HDM_TILE);
-    c->R = (long) c->world * c->Lr;
+    const HdmLayout L = hdm_layout(c->n, c->world, compact ? c->mloc : (c->m + c->world - 1) / c->world);   // work_plan.h
+    c->n16 = L.n16; c->nblk = L.nblk; c->npb = L.npb; c->npb_loc = L.npb_loc; c->Lr = L.Lr; c->R = L.R; c->astride = L.astride;
     const size_t n2 = (size_t) c->n16 * c->n16, nn = sizeof(double) * n2;
     HDM_HIP_CHECK(c->S.alloc(n2));
     HDM_HIP_CHECK(c->Scheck.alloc(n2));
@@ -226,155 +222,65 @@ int cone_alloc_common(MiCone *c) {
     return 0;
 }
 
+// The work space of the congruence + Gram path: the plan is work_plan.h's (hdm_work_plan: batch size, K splits, slabs, which
+// buffers are shared -- and why), what stays here is what depends on the device: every allocation degrades quietly when memory
+// is short, through the plan's own helpers, so that what the cone holds is always a plan the rule could have made.
 int cone_alloc_gemm_work(MiCone *c) {
-    const size_t n2 = (size_t) c->n16 * c->n16, nn = sizeof(double) * n2;
+    const HdmLayout L = cone_layout(c);
+    const size_t n2 = (size_t) c->n16 * c->n16, nn = sizeof(double) * n2, tpad = hdm_operand_pad(c->n16);
     {   // The zero-suppressed sweep copy (cone_build_zs) was made at creation, before these work buffers: it must never be the
-        // reason they come out smaller -- every allocation below degrades quietly (smaller batches, fewer splits) when memory is
-        // short.  If what is free does not cover a generous bound of what the builders take, the copy goes (the sweeps then read
-        // the dense storage).
+        // reason they come out smaller.  If what is free does not cover a generous bound of what the builders take, the copy
+        // goes (the sweeps then read the dense storage).
         size_t fr = 0, tot = 0;
         if (c->zs_state == 1 && !c->rows_from_zs && hipMemGetInfo(&fr, &tot) == hipSuccess) {
             const double rows = (double) std::max(1, c->mloc);
-            const double want = std::min(32.0 * (1L << 30), (double) nn * rows) +
-                                sizeof(double) * (double) c->world * c->npb_loc * c->Lr * 16 * (c->world == 1 ? 1.0 : 2.0) +
-                                41.0 * (1L << 30);
+            const double want = std::min(32.0 * (1L << 30), (double) nn * rows) + (double) hdm_exchange_bytes(L) + 41.0 * (1L << 30);
             if ((double) fr < want) { hdm_zs_free(&c->zs); c->zs_state = -1; }
         }
         (void) hipGetLastError();
     }
-    // batch size: as many constraints per launch as 32 GiB of intermediates allow, at most 1024 (each launch pays a
-    // dispatch ramp and a tail: measured step time 400.9 / 396.8 / 393.2 / 393.2 ms at 256 / 512 / 1000 / 2000 per launch on
-    // one box).  The launches are evened out (2000 rows -> 2 x 1000, a rank's 250 rows -> one launch); the kernel's
-    // XCD-local decode pads a batch to a multiple of 8 itself.  If the allocation fails the batch is halved.
-    long tcap = 32;   // GiB of intermediates
-    if (const char *e = getenv("HDM_TCAP_GIB")) tcap = atol(e);
-    long bc = (long) (((double) tcap * (1L << 30)) / (double) nn);
-    long bcmax = 1024;
-    if (const char *e = getenv("HDM_BC")) bcmax = atol(e);
-    if (c->streamed) bcmax = std::min<long>(bcmax, c->Bs);     // one congruence launch per regenerated batch
-    bc = std::max(1L, std::min(bc, bcmax));
-    const long rows = std::max(1, c->mloc);
-    for (;;) {
-        const long launches = (rows + bc - 1) / bc;
-        bc = (rows + launches - 1) / launches;
-        c->Bc = (int) bc;
-        if (c->T.alloc(n2 * (size_t) c->Bc, hdm_operand_pad(c->n16)) == hipSuccess) break;
+    const HdmKnobs knobs = hdm_knobs_from_env();
+    HdmWorkPlan p = hdm_work_plan(L, c->mloc, c->streamed, c->Bs, knobs);
+    // the intermediates: if the allocation fails the batch is halved (and the slab count planned again for that batch)
+    while (c->T.alloc(n2 * (size_t) p.Bc, tpad) != hipSuccess) {
         (void) hipGetLastError();
-        if (bc <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the congruence intermediates\n"); return 1; }
-        bc /= 2;
+        if (p.Bc <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the congruence intermediates\n"); return 1; }
+        p = hdm_work_plan(L, c->mloc, c->streamed, c->Bs, knobs, p.Bc / 2);
     }
-    HDM_HIP_CHECK(hdm_memset_sync(c->T.get(), 0, nn * (size_t) c->Bc));  // step 1 writes lower tiles only; the rest must read as 0
-    const size_t ahat = sizeof(double) * (size_t) c->world * c->npb_loc * c->Lr * 16;
+    c->Bc = (int) p.Bc;
+    HDM_HIP_CHECK(hdm_memset_sync(c->T.get(), 0, p.t_bytes));  // step 1 writes lower tiles only; the rest must read as 0
     if (!c->AhatLoc) {
-        HDM_HIP_CHECK(c->ahat_loc_own.alloc(ahat / sizeof(double) + HDM_OPERAND_PAD_DOUBLES));
+        const size_t ahat = hdm_exchange_doubles(L);
+        HDM_HIP_CHECK(c->ahat_loc_own.alloc(ahat + HDM_OPERAND_PAD_DOUBLES));
         c->AhatLoc = c->ahat_loc_own.get();
-        HDM_HIP_CHECK(hdm_memset_sync(c->AhatLoc, 0, ahat));
+        HDM_HIP_CHECK(hdm_memset_sync(c->AhatLoc, 0, sizeof(double) * ahat));
         if (c->world == 1) c->AhatAll = c->AhatLoc;
         else {
-            HDM_HIP_CHECK(c->ahat_all_own.alloc(ahat / sizeof(double) + HDM_OPERAND_PAD_DOUBLES));
+            HDM_HIP_CHECK(c->ahat_all_own.alloc(ahat + HDM_OPERAND_PAD_DOUBLES));
             c->AhatAll = c->ahat_all_own.get();
-            HDM_HIP_CHECK(hdm_memset_sync(c->AhatAll, 0, ahat));
+            HDM_HIP_CHECK(hdm_memset_sync(c->AhatAll, 0, sizeof(double) * ahat));
         }
     }
-    // Gram split-K.  The product over the packed index (K = 8 n(n+1) p-blocks of 16) is cut into K splits; a job is (split, tile),
-    // a persistent workgroup draws jobs from ONE queue in split order (HdmGemmArgs.queue_global), partial sums go to slabs that
-    // are reduced in fixed order.  What sets the split length (round 5, profiles/r05_a_8000_*, r05_b_*, r05_c_*): the Gram
-    // kernel is matrix-pipe bound at whatever clock the board's power limit leaves, and what costs power beside the MFMAs is
-    // HBM traffic.  A tile re-reads its two operand panels from the fabric for every job (L2 holds a few stages of them), so the
-    // fabric sees 13-60 x the algorithmic bytes -- which is harmless as long as they are served by the 256 MiB memory-side cache,
-    // i.e. as long as the operand bytes all workgroups of the chip are working on fit there.  With one queue in split order that
-    // is the panel of ONE split (+ the next one's beginning): R rows x k_chunk x 8 B.  At n = 2000, m = 8000 the former form (80
-    // splits of 25 000 k, one per XCD in flight) had 8 x 1.6 GB in use: 7.6 TB of HBM reads per Gram product, 99.7 % MFMA busy at
-    // 2.11 GHz, 68 TFLOP/s; with 256 stages (4096 k, 262 MB) per job 2.37 GHz and 75.5 TFLOP/s (1698 vs 1877 ms, same box;
-    // 192 / 384 / 512 stages: +0.7 / +2.4 / +5.7 %).  More splits than slabs: the splits run in groups of nslab, launch after
-    // launch, group g accumulating into the slabs of group g - 1 (gram_all); 16 slabs cost 0.4 % against 80.
-    // Short K ranges (small problems): among the multiples of 8 pick the split count whose last scheduling round is fullest.
-    const long RT = (c->R + HDM_TILE - 1) / HDM_TILE;
-    const long tiles = RT * (RT + 1) / 2;
-    const long kblocks = c->npb_loc;
-    const double slab_bytes = sizeof(double) * (double) c->R * c->R;
-    const long slab_cap = std::max(1L, (long) ((4LL << 30) / slab_bytes));  // <= 4 GiB of slabs
-    const long kcap = std::max(1L, kblocks / 64);
-    long ns = 1;
-    double best = -1.0;
-    for (long cand = 1; cand <= 64 && cand <= slab_cap && cand <= kcap; ++cand) {
-        if (cand > 8 && cand % 8) continue;
-        const double rounds = (double) (tiles * cand) / 512.0;
-        double eff = rounds / std::ceil(rounds);
-        if (rounds < 2.0) eff *= 0.5 + 0.25 * rounds;  // too few workgroups to hide the tail
-        if (cand < 8 && kcap >= 8 && slab_cap >= 8) eff *= 0.5;
-        if (eff > best + 1e-9) { best = eff; ns = cand; }
-    }
-    long total_splits = 0;   // > 0: one device, long K range: splits in all (ns = slabs)
-    {
-        const long byk = kblocks / 96;   // >= 96 k blocks (of 16) per job keeps prologue + epilogue under 4 %
-        const char *ek = getenv("HDM_GRAM_KSTAGES");   // A/B and test knob: stages per job, at any size
-        if ((byk >= 128 || ek) && c->world == 1) {
-            // stages per job, the smaller of two bounds (at least 96, at most 2048):
-            //  * the split's operand panel (R rows) fills the memory-side cache: 2^28 B / (128 B x R);
-            //  * what a job costs beside its K loop.  Per job about two stage times of prologue + epilogue (a share 2 / kst of
-            //    its time), and at the end of the launch the 512 workgroups run dry over about half a job (a share
-            //    256 kst / (tiles x kblocks) of the launch): least at kst = sqrt(tiles x kblocks / 128) -- 364 stages at
-            //    n = m = 2000 (343 splits), the floor of 96 at n = m = 1000 (336 splits, the count of rounds 2-4), beyond the
-            //    cache bound at m = 8000.
-            long kst = (long) ((double) (1L << 28) / (128.0 * (double) c->R));
-            kst = std::min(kst, (long) std::sqrt((double) tiles * (double) kblocks / 128.0));
-            kst = std::max(96L, std::min(kst, 2048L));
-            if (ek) kst = std::max(1L, atol(ek));
-            total_splits = std::max(8L, (kblocks + kst - 1) / kst);
-            // slabs: what fits the buffer the intermediates have anyway (one device: the two share it), at least 8 GiB worth, at least 8
-            const long cap8 = std::max(8L, (long) (std::max((double) (8LL << 30), (double) nn * (double) c->Bc) / slab_bytes));
-            ns = std::max(ns, std::min(total_splits, cap8));
-        } else if (byk >= 128) {
-            // sharded block: the exchange pieces are whole groups of splits whose launches overlap the transfers
-            // (engine_build.h), so the split count is a multiple of 8 (at most 1024), of the length the one-device rule gives.
-            // The slabs themselves are at most 8 GiB: a piece's splits run in groups of them, piece after piece
-            // accumulating (gram_range)
-            long kst = (long) ((double) (1L << 28) / (128.0 * (double) c->R));
-            kst = std::min(kst, (long) std::sqrt((double) tiles * (double) kblocks / 128.0));   // (the one-device rule above)
-            kst = std::max(96L, std::min(kst, 2048L));
-            const long big = std::min(1024L, ((kblocks + kst - 1) / kst + 7) & ~7L);
-            if (big > ns) {
-                total_splits = big;
-                ns = std::max(ns, std::min(big, std::max(8L, (long) ((8LL << 30) / slab_bytes))));
-            }
-        }
-    }
-    if (const char *e = getenv("HDM_NSPLIT")) ns = std::max(1L, std::min(atol(e), kblocks / 16));   // A/B knob: the slab count
-    // One GPU: the congruence intermediates T are dead by the time the Gram product writes its split-K slabs, so the two
-    // share ONE buffer (the larger of the two sizes: 33 GB instead of 32 + 33 GB at n = m = 2000).  The only thing step 2
-    // reads of T that step 1 does not write is the strict upper triangle of T's diagonal tiles: with the buffer shared
-    // it is re-zeroed before every batch (hdm_zero_diag_upper, 1 GB of stores per 1000 matrices) instead of once at
-    // allocation.  Sharded builds keep them apart: there the Gram splits of the early exchange pieces run while step 2
-    // still reads T for the later ones.  HDM_SHARE_T_SLABS=0 keeps two buffers (A/B runs).
-    bool share = (c->world == 1);
-    if (const char *e = getenv("HDM_SHARE_T_SLABS")) share = share && atoi(e) != 0;
-    if (share) {
-        const size_t tbytes = nn * (size_t) c->Bc + hdm_operand_pad(c->n16);
-        for (;;) {
-            c->nsplit = (int) ns;
-            const size_t sbytes = sizeof(double) * (size_t) c->R * c->R * c->nsplit;
-            if (sbytes <= tbytes) { c->slabs = c->T.get(); c->shared_ts = true; break; }
-            // the slabs are the bigger of the two: one buffer of their size serves both
-            if (c->T.alloc(sbytes / sizeof(double), hdm_operand_pad(c->n16)) == hipSuccess) { c->slabs = c->T.get(); c->shared_ts = true; break; }
+    // the slabs: in T where the two share a buffer (grown to the slabs' size if that is the larger), else in a buffer of their
+    // own; halved until they fit
+    if (p.shared_ts) {
+        while (p.slab_bytes > p.t_bytes + tpad && c->T.alloc(p.slab_bytes / sizeof(double), tpad) != hipSuccess) {
             (void) hipGetLastError();
-            if (c->T.alloc(n2 * (size_t) c->Bc, hdm_operand_pad(c->n16)) != hipSuccess) { (void) hipGetLastError(); return 1; }
-            if (ns <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the Gram slabs\n"); return 1; }
-            ns = std::max(8L, (ns / 2) & ~7L);
+            if (c->T.alloc(n2 * (size_t) p.Bc, tpad) != hipSuccess) { (void) hipGetLastError(); return 1; }
+            if (!hdm_plan_halve_slabs(p, L)) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the Gram slabs\n"); return 1; }
         }
+        c->slabs = c->T.get();
+    } else {
+        while (c->slabs_own.alloc(p.slab_bytes / sizeof(double)) != hipSuccess) {
+            (void) hipGetLastError();
+            if (!hdm_plan_halve_slabs(p, L)) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the Gram slabs\n"); return 1; }
+        }
+        c->slabs = c->slabs_own.get();
     }
-    // the slabs are the one allocation here that is a tuning choice: halve the split count until it fits
-    for (; !c->shared_ts;) {
-        c->nsplit = (int) ns;
-        if (c->slabs_own.alloc((size_t) c->R * c->R * c->nsplit) == hipSuccess) { c->slabs = c->slabs_own.get(); break; }
-        (void) hipGetLastError();
-        if (ns <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the Gram slabs\n"); return 1; }
-        ns = std::max(8L, (ns / 2) & ~7L);
-    }
-    c->nslab = c->nsplit;                                   // (the allocation loops above may have halved it)
-    if (total_splits > c->nslab) c->nsplit = (int) total_splits;
-    c->gram_queue_global = true;
-    if (const char *e = getenv("HDM_GRAM_QUEUE")) c->gram_queue_global = atoi(e) != 0;   // 0: one queue per XCD over the splits x, x + 8, ...
+    c->shared_ts = p.shared_ts;
+    c->nslab = (int) p.nslab;
+    c->nsplit = (int) p.nsplit;
+    c->gram_queue_global = p.gram_queue_global;
     HDM_HIP_CHECK(c->Gm.alloc((size_t) c->R * c->R));
     // the "S row" (At = I) never changes
     if (c->rank == 0) {

@@ -117,7 +117,7 @@ static int upload_dense_rows(MiCone *c) {
 static bool cone_wants_streaming(const MiCone *c) {
     const double rows = (double) std::max(1, c->mloc);
     const double afull = 8.0 * (double) c->astride * rows;
-    const double ahat = 8.0 * (double) c->world * c->npb_loc * c->Lr * 16 * (c->world == 1 ? 1.0 : 2.0);
+    const double ahat = (double) hdm_exchange_bytes(cone_layout(c));
     const double work = std::min(41.0 * (1L << 30), std::max(8.0 * (double) c->n16 * c->n16 * std::min(rows, 1024.0),
                                                              8.0 * (double) c->R * c->R * 8.0));
     // (the Schur matrix, its factor and its inverse blocks, plus 16 GiB of slack: at n = 2000, m = 8000 the resident form comes
@@ -136,11 +136,9 @@ static bool cone_wants_streaming(const MiCone *c) {
     return stream && c->mloc > 0;
 }
 static int cone_alloc_batch(MiCone *c) {
-    // batch = what one congruence launch takes (cone_alloc_gemm_work evens its launches out the same way)
-    long bmax = 1024;
-    if (const char *e = getenv("HDM_BC")) bmax = std::max(1L, atol(e));
-    const long launches = (c->mloc + bmax - 1) / bmax;
-    c->Bs = (int) ((c->mloc + launches - 1) / launches);
+    // batch = what one congruence launch takes: HDM_BC clamped to at least 1 here, launches evened out as the plan's are
+    // (work_plan.h: HdmKnobs::bc_max says which clamp the plan applies)
+    c->Bs = (int) hdm_even_out(c->mloc, std::max(1L, hdm_knobs_from_env().bc_max));
     if (c->Abatch.alloc((size_t) c->astride * c->Bs, hdm_operand_pad(c->n16)) != hipSuccess) {
         fprintf(stderr, "[hdsdp_mi355x] cannot allocate %.1f GiB for a batch of constraint matrices\n", (double) c->astride * c->Bs * 8 / (1 << 30));
         return 1;

@@ -737,7 +737,7 @@ hdsdp_retcode HMiConeSetExchangeBuffers(hdsdp_cone *cone, void *sendBuf, void *r
     if (!c || c->work_ready || !sendBuf || !recvBuf) return HDSDP_RETCODE_FAILED;
     c->AhatLoc = (double *) sendBuf;
     c->AhatAll = (c->world == 1) ? c->AhatLoc : (double *) recvBuf;
-    const size_t ahat = sizeof(double) * (size_t) c->world * c->npb_loc * c->Lr * 16;
+    const size_t ahat = sizeof(double) * hdm_exchange_doubles(cone_layout(c));
     if (hipMemsetAsync(c->AhatLoc, 0, ahat, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     if (c->AhatAll != c->AhatLoc && hipMemsetAsync(c->AhatAll, 0, ahat, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     return HDSDP_RETCODE_OK;

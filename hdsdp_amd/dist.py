@@ -11,8 +11,9 @@ Sharding (see DESIGN.md "Multi-GPU"):
   4. ONE all-reduce(sum) of the (m+3)^2 augmented Gram matrix assembles M, ASinv, ASinvRdSinv,
      ASinvCSinv and the scalars on every rank; Cholesky + solves are replicated (m^3/3 is noise).
 
-`ShardPlan` is the pure-Python statement of the layout the engine uses (hdsdp_amd/csrc/engine.hip
-cone_alloc_common); the CPU gloo tests drive it with numpy standing in for the kernels.
+`ShardPlan` is the pure-Python statement of the layout the engine uses (hdsdp_amd/csrc/work_plan.h:
+hdm_layout); the CPU gloo tests drive it with numpy standing in for the kernels.  Only `hbm_bytes` needs the
+built library: it reads the engine's own work plan.
 """
 import ctypes as C
 import os
@@ -39,70 +40,29 @@ class ShardPlan:
         self.pI = maxloc                                        # augmented rows sit in segment 0
         self.chunk = self.npb_loc * self.Lr * 16                # doubles per all-to-all chunk
 
-    def hbm_bytes(self, rank=0, tcap_gib=32, slab_cap_gib=40):
-        """device memory one rank of the sharded GEMM path allocates, mirroring engine.hip (cone_alloc_common,
-        cone_alloc_gemm_work, make_synth_cone / upload_dense_rows) and chol.hip: constraint data, congruence
-        intermediates, both exchange buffers, Gram slabs, and the small replicated matrices.  Returns a dict of parts
-        plus "total"."""
-        n16, nn = self.n16, self.n16 * self.n16 * 8
+    def hbm_bytes(self, rank=0):
+        """device memory one rank of the GEMM path allocates: constraint data, congruence intermediates, exchange buffers,
+        Gram slabs and Gram matrix as the engine plans them (csrc/work_plan.h, read through api.work_plan: the same function
+        cone_alloc_gemm_work allocates by, under this process's HDM_* knobs), plus estimates of what that plan does not own:
+        the small replicated matrices (engine_cone.h: cone_alloc_common; chol.hip), the Schur matrix with its factor, and the
+        optional sweep copy.  Returns a dict of parts plus "total"."""
+        from . import api
+        wp = api.work_plan(self.n, self.m, self.world, rank)
+        nn = self.n16 * self.n16 * 8
         npad = _roundup(self.n, 128)
-        mloc = len(self.owned(rank))
+        mloc, sky = wp["mloc"], wp["astride"]
         # constraint matrices: A_L form in skyline storage (csrc/hdm_common.h): 128-column panels from the diagonal down
-        t = (n16 + 127) // 128 - 1
-        sky = 128 * (t * n16 - 64 * t * (t - 1)) + (n16 - 128 * t) ** 2
         parts = {"A (A_L form, skyline)": mloc * sky * 8}
-        bc = max(1, min(int(tcap_gib * (1 << 30) / nn), 1024))
-        launches = -(-max(1, mloc) // bc)
-        bc = -(-max(1, mloc) // launches)
-        parts["congruence intermediates T"] = bc * nn
-        ahat = self.world * self.npb_loc * self.Lr * 16 * 8
-        parts["exchange buffers (send + recv)"] = ahat * (1 if self.world == 1 else 2)
-        kblocks = self.npb_loc
-        RT = -(-self.R // 128)
-        tiles = RT * (RT + 1) // 2
-        slab_cap = max(1, int((4 << 30) / (8.0 * self.R * self.R)))
-        kcap = max(1, kblocks // 64)
-        ns, best = 1, -1.0
-        for cand in range(1, 65):
-            if cand > slab_cap or cand > kcap:
-                break
-            if cand > 8 and cand % 8:
-                continue
-            rounds = tiles * cand / 512.0
-            eff = rounds / np.ceil(rounds)
-            if rounds < 2.0:
-                eff *= 0.5 + 0.25 * rounds
-            if cand < 8 and kcap >= 8 and slab_cap >= 8:
-                eff *= 0.5
-            if eff > best + 1e-9:
-                best, ns = eff, cand
-        big_cap = int((slab_cap_gib << 30) / (8.0 * self.R * self.R))
-        byk = kblocks // 96
-        splits = ns
-        if byk >= 128 and self.world == 1:
-            # one device, long packed index (round 5): K splits sized so that one split's operand panel fills the 256 MiB
-            # memory-side cache, run in groups over at most 8 GiB of slabs (engine_cone.h: cone_alloc_gemm_work)
-            kst = min(int((1 << 28) / (128.0 * self.R)), int(np.sqrt(tiles * kblocks / 128.0)))
-            kst = max(96, min(kst, 2048))
-            splits = max(8, -(-kblocks // kst))
-            ns = max(ns, min(splits, max(8, int(max(8 << 30, parts["congruence intermediates T"]) / (8.0 * self.R * self.R)))))
-            splits = max(splits, ns)
-        elif byk >= 128:
-            # sharded: as many splits as before (a multiple of 8: the exchange pieces are groups of them), at most 8 GiB of slabs
-            kst = min(int((1 << 28) / (128.0 * self.R)), int(np.sqrt(tiles * kblocks / 128.0)))
-            kst = max(96, min(kst, 2048))
-            big = min(1024, (-(-kblocks // kst) + 7) & ~7)
-            if big > ns:
-                splits = big
-                ns = max(ns, min(big, max(8, int((8 << 30) / (8.0 * self.R * self.R)))))
-        slab = ns * self.R * self.R * 8
-        if self.world == 1:
+        counts = "(%d slabs for %d splits)" % (wp["nslab"], wp["nsplit"])
+        if not wp["shared_ts"]:
+            parts["congruence intermediates T"] = wp["t_bytes"]
+        parts["exchange buffers (send + recv)"] = wp["exchange_bytes"]
+        if wp["shared_ts"]:
             # one GPU: T is dead when the Gram product starts, the two share one buffer of the larger size
-            tb = parts.pop("congruence intermediates T")
-            parts["congruence intermediates T / Gram slabs (%d slabs for %d splits), one shared buffer" % (ns, splits)] = max(tb, slab)
+            parts["congruence intermediates T / Gram slabs %s, one shared buffer" % counts] = max(wp["t_bytes"], wp["slab_bytes"])
         else:
-            parts["Gram slabs (%d slabs for %d splits)" % (ns, splits)] = slab
-        parts["Gram matrix"] = self.R * self.R * 8
+            parts["Gram slabs %s" % counts] = wp["slab_bytes"]
+        parts["Gram matrix"] = wp["gram_bytes"]
         parts["S, checker, C, dS + Cholesky / inverse of S"] = 4 * nn + 4 * npad * npad * 8
         mpad = _roundup(self.m, 128)
         parts["Schur matrix M + its factor (replicated)"] = 3 * mpad * mpad * 8

@@ -520,15 +520,16 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           batch (MiCone::streamed)
  *  HDSDP_MI355X_DEVICE_M          0         1: HKKTInit turns the host mirror of M off when no cone of    test_gpu_device_m.py
  *                                           cones[] is a host cone (diagonal channel); else one stderr line
+ *  -- the next six are the work plan's knobs: all read in csrc/work_plan.h (hdm_knobs_from_env), per allocation; HMiWorkPlanQuery sees them too --
  *  HDM_TCAP_GIB                   32        GiB of congruence intermediates per launch group              test_gpu_switches.py, test_gpu_group.py
  *  HDM_BC                         1024      constraints per congruence launch (upper bound)               test_gpu_switches.py
  *  HDM_NSPLIT                     by size   slabs of the Gram product's K splits                          test_gpu_switches.py
  *  HDM_GRAM_KSTAGES               by size   stages (16 k) per (split, tile) job of the Gram product on one    test_gpu_switches.py (with HDM_NSPLIT=8: more
  *                                           device; more splits than slabs run in groups (gram_all)           splits than slabs)
  *  HDM_GRAM_QUEUE                 1         Gram jobs from ONE queue in split order; 0: one queue per XCD      test_gpu_switches.py
+ *  HDM_SHARE_T_SLABS              1         intermediates and Gram slabs share one buffer (one GPU)       test_gpu_switches.py
  *  HDSDP_MI355X_HOST_THREADS      min(16,   host threads of the ingest (presolve per column, staging of the    test_gpu_switches.py; the threaded form: test_gpu_ingest.py (syn2000x32)
  *                                 cores)    upload)
- *  HDM_SHARE_T_SLABS              1         intermediates and Gram slabs share one buffer (one GPU)       test_gpu_switches.py
  *  -- fallbacks kept reachable (the default is the fast form) ----------------------------------------------------------
  *  HDM_PERSIST                    1         persistent GEMM workgroups; 0: one workgroup per tile         test_gpu_switches.py, test_gpu_kernels.py
  *  HDM_PERSIST_RESERVE_CUS        0 / 8     CUs a persistent launch leaves to the collectives             test_gpu_switches.py, test_gpu_kernels.py
@@ -571,6 +572,22 @@ const char *HMiVersion(void);
  * engine stream, milliseconds: [0] factor inverse, [1] congruence, [2] gram, [3] reduce+extract,
  * [4] gram kernel launches, [5] congruence kernel launches */
 void HMiGetStageTimes(double *ms, int n);
+
+/* The work plan of a dense block's Schur build on the congruence + Gram path (csrc/work_plan.h): constraints per congruence launch,
+ * K splits and slabs of the Gram product, buffer sizes.
+ * HMiWorkPlanQuery: what the engine would plan in THIS process (its HDM_* knobs as the environment states them now) for rank `rank`
+ * of `world` on a block of dimension n with m constraints, all rows resident and none dropped as zero.  Host arithmetic only: opens no
+ * context, touches no device, works without one.  out (cap >= 17): [0] n16 [1] nblk [2] npb [3] npb_loc [4] Lr [5] R [6] elements per
+ * constraint matrix (skyline) [7] rows owned [8] Bc [9] K splits [10] slabs [11] intermediates and slabs share one buffer [12] one Gram
+ * job queue [13] bytes of the intermediates T [14] of the slabs [15] of the exchange buffers [16] of the Gram matrix (payloads; the
+ * operand slack behind a buffer is not counted; with [11] set the one buffer has the larger of [13] and [14]).  Returns 17, or -17
+ * for a bad argument.
+ * HMiConeGetWorkPlan: what a cone HOLDS after its first build allocated the work space (for a group cone: shard 0's) -- the plan above
+ * unless device memory was short and an allocation was halved.  out (cap >= 7): [0] Bc [1] K splits [2] slabs [3] shared buffer
+ * [4] one Gram job queue [5] bytes of T (of the shared buffer, with [3]) [6] bytes of the slabs.  Returns 7, 0 before the first build
+ * (or for a cone on another path), -1 if `cone` is not an SDP cone of the engine. */
+int HMiWorkPlanQuery(int n, int m, int world, int rank, int64_t *out, int cap);
+int HMiConeGetWorkPlan(hdsdp_cone *cone, int64_t *out, int cap);
 
 /* live per-kernel timing with HIP events on the engine stream (for bench.py's roofline block): roles are
  * [0] helper GEMMs (Cholesky/TRTRI), [1] congruence step 1 (T = Linv A), [2] congruence step 2 without its full diagonal

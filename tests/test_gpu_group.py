@@ -377,7 +377,9 @@ def test_transport_request_is_honoured():
 
 def test_shard_plan_predicts_what_the_engine_allocates(group):
     """hdsdp_amd.dist.ShardPlan.hbm_bytes -- the statement that BASELINE configs[4] fits 8 x 288 GB
-    (tests/test_dist_cpu.py) -- against the device memory the engine really takes, one device and two shards"""
+    (tests/test_dist_cpu.py) -- against the device memory the engine really takes, one device and two shards; and the plan the
+    cone holds (HMiConeGetWorkPlan) against the pure query hbm_bytes reads (HMiWorkPlanQuery), exactly: at this size memory is
+    ample, so no allocation is halved and the two must be one plan"""
     import torch
     from hdsdp_amd import api
     from hdsdp_amd.dist import ShardPlan
@@ -395,6 +397,11 @@ def test_shard_plan_predicts_what_the_engine_allocates(group):
         kkt.factorize()
         free1, _ = torch.cuda.mem_get_info()
         used = free0 - free1
+        held, want = cone.work_plan(), api.work_plan(n, m, world, 0)
+        assert held is not None, world
+        differs = {k: (held[k], want[k]) for k in ("Bc", "nsplit", "nslab", "shared_ts") if held[k] != want[k]}
+        assert not differs, "world %d: the cone holds (first) another plan than the query states (second) -- an allocation " \
+                            "was halved for want of memory, or the two disagree: %r" % (world, differs)
         plan = sum(ShardPlan(n, m, world).hbm_bytes(r)["total"] for r in range(world))
         if world > 1:   # M and its factor exist once (the caller's operator), not per shard
             plan -= (world - 1) * ShardPlan(n, m, world).hbm_bytes(0)["Schur matrix M + its factor (replicated)"]
