@@ -18,6 +18,7 @@
 #include "coeff.h"
 #include "hdm_common.h"
 #include "work_plan.h"
+#include "dual_state.h"
 #include "schur.h"
 #include "lanczos.h"
 #include "lu.h"

@@ -181,7 +181,7 @@ int HMiConeGetPath(hdsdp_cone *cone) { const MiCone *c = cone_data(cone); return
 int HMiConeUseSweepCopy(hdsdp_cone *cone, int on) {
     MiCone *c = cone_data(cone);
     if (!c || ensure_ctx()) return 1;
-    c->pS_ok = c->pD_ok = false;     // the next request is assembled, not short-cut
+    c->dual.data_changed();          // the next request is assembled, not short-cut
     if (!on) { c->zs_state = -1; return 0; }
     if (!c->zs.val && cone_has_rows(c) && c->mloc > 0 &&
         hdm_zs_build_from([&](int q0, int nb) { return cone_rows(c, q0, nb); }, cone_batch(c), c->astride, c->mloc, c->astride, 1.0,
@@ -341,9 +341,9 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
     a.n = n; a.m = m; a.C = c->Cfull.get(); a.ldc = c->n16;
     a.fp = sp.fp.get(); a.fi = sp.fi.get(); a.fv = sp.fv.get(); a.sgn = sp.sgn.get(); a.dense_of = sp.dense_of.get(); a.ndense = sp.ndense; a.dense_rows = sp.dense_rows.get();
     a.y = sp.io.dev(); a.b = sp.io.dev() + m; a.out = sp.io.dev() + 2 * (size_t) m;
-    a.tau = barHsdTau; a.eye = -c->Rd + c->perturb; a.Rd = c->Rd;
+    a.tau = barHsdTau; a.eye = cone_eye(c); a.Rd = c->Rd;
     a.Sout = c->S.get(); a.lds = c->n16;
-    c->pS_ok = false;                                  // (the pass writes S itself)
+    c->dual.S_overwritten();                           // (the pass writes S itself)
     a.LS = ls->ch.L.get(); a.WS = ls->ch.Dinv.get(); a.M = lm->Mdev.get(); a.ldm = lm->ch.npad; a.LM = lm->ch.L.get(); a.WM = lm->ch.Dinv.get();
     if (ls->ch.npad != SMALL_P || lm->ch.npad != SMALL_P) return HDSDP_RETCODE_FAILED;
     // (the operator's accumulators as HKKTBuildUp(KKT_TYPE_INFEASIBLE) leaves them, hdsdp_schur.c:141-165, :256-268: the
@@ -482,8 +482,8 @@ int HMiGetCallStats(double *seconds, int64_t *calls, int n) {
 }
 const char *HMiCallStatName(int k) { return (k >= 0 && k < ST_N) ? g_stat_name[k] : ""; }
 int HMiGetAssembleCounts(int64_t *counts, int n) {
-    for (int k = 0; k < n && k < 7; ++k) if (counts) counts[k] = g_asm_counts[k];
-    return 7;
+    for (int k = 0; k < n && k < HDM_ASM_N; ++k) if (counts) counts[k] = g_asm_counts[k].load(std::memory_order_relaxed);
+    return HDM_ASM_N;
 }
 void HMiResetCallStats(void) { for (int k = 0; k < ST_N; ++k) { g_stat_sec[k] = 0.0; g_stat_calls[k] = 0; } g_stat_nfn = 0; }
 int HMiRcclSelfTest(int device) {

@@ -47,7 +47,6 @@ struct MiCone {
     HdmBuf<double> ydev;
     HdmPinned<double> yhost;   // pinned staging of the owned multipliers (the upload is asynchronous)
     HdmPinned<double> chk;     // mapped pinned block of the single-launch small-block check: y[mloc], then info, log det
-    bool fac_ok = false; int fac_psd = 0;             // the dual factor object holds the factorisation of S = T(pS) (result: fac_psd)
     HdmBuf<double> corr;       // sharded corrector build: this cone's 2m dot products before they join the operator's
     hdsdp_linsys_fp *dualFactor = nullptr;
     std::unique_ptr<HdmChol> primal;   // KKT_TYPE_PRIMAL: factor object of the registered primal matrix (lazy)
@@ -122,12 +121,10 @@ struct MiCone {
     // writes into it, the others stop after the all-reduce
     bool kkt_owner = true;
     int kkt_counted = 0;       // progress of the aggregated-pattern queries (cone_add_sym_nz)
-    // Where the dual matrix and the step matrix stand (single-device blocks): S = T(pS), dS = T(pD) for the linear map
-    // T(tau, y, eye) = tau C - sum y_i A_i + eye I.  A request for T(p) with p = pS + alpha pD is answered by S + alpha dS
-    // (one pass over n^2) instead of a sweep over all m constraint matrices (cone_assemble).
-    std::vector<double> pS, pD;          // tau, eye, then the mloc multipliers
-    bool pS_ok = false, pD_ok = false;
-    int aff_chain = 0;                   // updates of S in place since its last full assembly
+    // Where the dual matrix, the step matrix and the dual factor stand (dual_state.h): the points S and dS were assembled at,
+    // from which cone_assemble answers a request on the line through them without a sweep.  Every writer of S, dS or the
+    // dual factor object names what it did through one of this object's transitions.
+    HdmDualState dual;
     // fused single-launch Phase-A pass of a small rank-one block (small.hip): factors as a CSR, built on first use
     struct SmallPlan {
         int state = 0;         // 0 = not looked at, 1 = ready, -1 = not eligible
@@ -339,125 +336,38 @@ bool cone_has_rows(const MiCone *c) { return c->streamed ? c->Abatch.get() != nu
 // The zero-suppressed copy of the constraint data (schur.h: HdmZs) that the S / dS sweeps and the corrector's dot products
 // read: made once, when the block's data has arrived (cone creation -- format preparation like the unpacking into A_L form; the
 // two passes and the 14 GB allocation take 0.3-0.8 s at n = m = 2000, which does not belong into the first line search),
-// for blocks whose sweep costs something -- 16 MiB of constraint data or more -- unless over 60 % of the stored positions
-// are non-zero or the memory is not there (then the sweeps read the dense storage).  HDSDP_MI355X_ZS=0: never; 2: any size, any fill.
+// for blocks whose sweep costs something (dual_state.h: hdm_sweep_costs, 16 MiB of constraint data or more) unless over 60 %
+// of the stored positions are non-zero or the memory is not there (then the sweeps read the dense storage).
+// HDSDP_MI355X_ZS=0: never; 2: any size, any fill.
 int cone_build_zs(MiCone *c) {
     static const int zs_env = [] { const char *e = getenv("HDSDP_MI355X_ZS"); return e ? atoi(e) : 1; }();
     if (c->zs_state != 0) return 0;
     c->zs_state = -1;
-    const long sweep_bytes = (long) c->mloc * c->n * (c->n + 1) * 4;
-    if (!cone_has_rows(c) || c->mloc <= 0 || !zs_env || !(zs_env >= 2 || sweep_bytes >= (16L << 20))) return 0;
+    if (!cone_has_rows(c) || c->mloc <= 0 || !zs_env || !(zs_env >= 2 || hdm_sweep_costs(c->mloc, c->n))) return 0;
     if (hdm_zs_build_from([&](int q0, int nb) { return cone_rows(c, q0, nb); }, cone_batch(c), c->astride, c->mloc, c->astride,
                           zs_env >= 2 ? 1.0 : 0.6, &c->zs, g.stream)) return 1;
     if (c->zs.val) c->zs_state = 1;
     return 0;
 }
 
-// S <- tau*C - sum y_i A_i - Rd*I (+ perturb)   hdsdp_conic_sdp.c:343-402, :1616-1633
+// the identity coefficient of the dual matrix: the residual and the perturbation   hdsdp_conic_sdp.c:383-385
+double cone_eye(const MiCone *c) { return -c->Rd + c->perturb; }
+double *cone_dual_buffer(MiCone *c, HdmDualTarget which) {
+    return which == HDM_DUAL_S ? c->S.get() : which == HDM_DUAL_SCHECK ? c->Scheck.get() : c->dS.get();
+}
+
+// target <- T(p) by a sweep over the owned constraint matrices (p.y: the cone's pinned staging buffer, `any` of them non-zero)
 // Sharded: every rank sums its own rows (rank 0 also adds tau*C and the identity term), then all-reduce.
-int cone_assemble(MiCone *c, double tau, const double *y_host, double *target, const double *eye_override = nullptr) {
-    // the upload below is asynchronous: the source is a pinned buffer of the cone, and the previous upload from it has
-    // been consumed by the time it is rewritten (every caller synchronises on the factorisation that follows)
-    if (!c->yhost) HDM_HIP_CHECK(c->yhost.alloc((size_t) std::max(1, c->mloc)));
-    HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
-    double *yo = c->yhost.get();
-    bool any = false;
-    for (int q = 0; q < c->mloc; ++q) { yo[q] = y_host ? y_host[c->own[q]] : 0.0; any |= (yo[q] != 0.0); }
-    const double eye_now = eye_override ? *eye_override : (-c->Rd + c->perturb);
-    // ---- shortcut (see MiCone::pS).  The reference's line searches and correctors ask for the dual matrix twice at the same
-    // point (interior check, then barrier) and at points y + alpha dy along the direction whose dS the ratio test has just
-    // assembled: each a 32 GB sweep at n = m = 2000 (6 ms), 14 % of a whole solve's device time.  The request is compared
-    // with what the buffers hold, component by component; anything else takes the sweep.
-    // 1: only the exact case -- the same point again -- is short-cut, so every number is the one a sweep would have produced.
-    // 2: also points on the line through the last ratio test's direction (S + alpha dS); the results then differ from a
-    // sweep's in the last bits (as a sweep's differ from the reference's own summation order).  0: off.
-    // Default: 2 where a sweep costs something -- 16 MiB of constraint data or more, i.e. from about n = m = 160 on; at
-    // n = m = 2000 the reference's line searches and correctors ask for 344 such points per solve, 6 ms each -- and 1 on
-    // small blocks, where the sweep is free and the end game of a badly conditioned instance can turn on the last bits
-    // (gpp100 through the reference's driver in mode 2: same dual objective, a primal estimate 3e-4 further away).
-    // HDSDP_MI355X_AFFINE_S=0/1/2 overrides.
-    static const int aff_env = [] { const char *e = getenv("HDSDP_MI355X_AFFINE_S"); return e ? atoi(e) : -1; }();
-    const long sweep_bytes = (long) c->mloc * c->n * (c->n + 1) * 4;
-    const int aff_mode = aff_env >= 0 ? aff_env : (sweep_bytes >= (16L << 20) ? 2 : 1);
-    const bool track = aff_mode > 0 && c->world == 1;
-    if (track && target != c->dS.get() && c->pS_ok) {
-        const int np = c->mloc + 2;
-        auto comp = [&](int i) { return i == 0 ? tau : i == 1 ? eye_now : yo[i - 2]; };
-        bool same = true;
-        for (int i = 0; i < np && same; ++i) same = (comp(i) == c->pS[i]);
-        if (same && target == c->S.get()) { g_asm_counts[0] += 1; return 0; }        // S already is T(p)
-        double alpha = 0.0, eye_delta = 0.0;
-        bool hit = same;
-        if (!same && c->pD_ok && aff_mode >= 2) {
-            // Is p = pS + alpha pD + delta e_eye for some alpha, delta?  alpha from the largest multiplier component of pD (tau
-            // if it has none), checked on tau and every multiplier; the identity coefficient is free: the driver's trial points
-            // move y along the tested direction with the residual held, and its corrector ends at y + a (b d2 - d1) with the
-            // residual reduced (interface/hdsdp_algo.c:911-921) -- the tested direction plus a multiple of the identity, which
-            // costs n additions on top of S + alpha dS.  Tolerance 8e-15 relative per component: the driver forms those points
-            // in another association than pS + alpha pD, and the differences measured on a whole solve reach 4e-15 (a 1.8e-15
-            // bound, rounds 3-4, turned 157 of 345 such requests of the headline solve into 15.6 GB sweeps for one or two
-            // components at 2e-15: HDSDP_MI355X_AFFINE_DEBUG=1 prints every miss).
-            int kmax = -1;
-            for (int i = 2; i < np; ++i) if (c->pD[i] != 0.0 && (kmax < 0 || fabs(c->pD[i]) > fabs(c->pD[kmax]))) kmax = i;
-            if (kmax < 0 && c->pD[0] != 0.0) kmax = 0;
-            if (kmax >= 0) alpha = (comp(kmax) - c->pS[kmax]) / c->pD[kmax];
-            hit = std::isfinite(alpha);
-            double worst = 0.0; int bad = 0, wi = -1;
-            for (int i = 0; i < np; ++i) {
-                if (i == 1) continue;
-                const double d = comp(i) - c->pS[i], e = alpha * c->pD[i];
-                const double sc = fabs(comp(i)) + fabs(c->pS[i]) + fabs(e);
-                if (fabs(d - e) > 8e-15 * sc) { hit = false; bad += 1; }
-                if (sc > 0.0 && fabs(d - e) / sc > worst) { worst = fabs(d - e) / sc; wi = i; }
-            }
-            eye_delta = (comp(1) - c->pS[1]) - alpha * c->pD[1];
-            static const bool affdbg = [] { const char *e = getenv("HDSDP_MI355X_AFFINE_DEBUG"); return e && atoi(e); }();
-            if (affdbg && !hit) {
-                double dd = 0.0, pp = 0.0, dp = 0.0;
-                for (int i = 2; i < np; ++i) { const double d = comp(i) - c->pS[i]; dd += d * d; pp += c->pD[i] * c->pD[i]; dp += d * c->pD[i]; }
-                fprintf(stderr, "[hdsdp_mi355x affine] miss (%s): alpha %.6e, %d of %d components off the tested line, worst relative %.3e at %d; "
-                                "d tau %.3e, d eye %.3e, |d y| %.3e, |pD y| %.3e, cos %.9f\n", target == c->S.get() ? "S" : "checker", alpha, bad, np, worst, wi,
-                        comp(0) - c->pS[0], comp(1) - c->pS[1], sqrt(dd), sqrt(pp), (dd > 0 && pp > 0) ? dp / sqrt(dd * pp) : 0.0);
-            }
-        }
-        if (hit && same) {                                                     // the same point into the other buffer: a copy
-            HDM_HIP_CHECK(hipMemcpyAsync(target, c->S.get(), sizeof(double) * (size_t) c->n16 * c->n16, hipMemcpyDeviceToDevice, g.stream));
-            g_asm_counts[1] += 1;
-            return 0;
-        }
-        if (hit && c->dS.get() && !(target != c->S.get() || c->aff_chain < 16)) g_asm_counts[4] += 1;
-        else if (!hit) g_asm_counts[3] += 1;
-        if (hit && c->dS.get() && (target != c->S.get() || c->aff_chain < 16)) {
-            g_asm_counts[2] += 1;
-            if (eye_delta == 0.0 ? hdm_axpy_mat(target, c->S.get(), c->dS.get(), alpha, (long) c->n16 * c->n16, g.stream)
-                                 : hdm_axpy_mat_eye(target, c->S.get(), c->dS.get(), alpha, eye_delta, c->n16, c->n, g.stream)) return 1;
-            if (target == c->S.get()) {
-                for (int i = 0; i < np; ++i) c->pS[i] = comp(i);
-                c->aff_chain += 1;
-            }
-            return 0;
-        }
-    }
-    if (target == c->dS.get()) g_asm_counts[5] += 1;
-    else if (!(track && c->pS_ok)) g_asm_counts[track ? 3 : 6] += 1;          // (no point known yet: a first assembly)
-    HDM_HIP_CHECK(hipMemcpyAsync(c->ydev.get(), yo, sizeof(double) * c->mloc, hipMemcpyHostToDevice, g.stream));
-    if (track && (target == c->S.get() || target == c->dS.get())) {
-        std::vector<double> &pp = (target == c->S.get()) ? c->pS : c->pD;
-        pp.resize((size_t) c->mloc + 2);
-        pp[0] = tau; pp[1] = eye_now;
-        for (int q = 0; q < c->mloc; ++q) pp[2 + q] = yo[q];
-        (target == c->S.get() ? c->pS_ok : c->pD_ok) = true;
-        if (target == c->S.get()) c->aff_chain = 0;
-    }
-    const double lead = (c->rank == 0) ? 1.0 : 0.0;
+int cone_sweep(MiCone *c, const HdmDualPoint &p, bool any, double *target) {
+    HDM_HIP_CHECK(hipMemcpyAsync(c->ydev.get(), p.y, sizeof(double) * c->mloc, hipMemcpyHostToDevice, g.stream));
+    const double lead = (c->rank == 0) ? 1.0 : 0.0, ctau = lead * p.tau, ceye = lead * p.eye;
     // The sweep reads the zero-suppressed copy of the constraint data where one exists (cone_build_zs: made at creation).
     if (any && c->zs_state == 0 && cone_build_zs(c)) return 1;
     if (any && c->zs_state == 1) {
-        if (hdm_sym_combine_zs(c->zs, c->ydev.get(), c->Cfull.get(), lead * tau, lead * (eye_override ? *eye_override : (-c->Rd + c->perturb)),
-                               target, c->n, c->n16, c->n16, g.stream)) return 1;
+        if (hdm_sym_combine_zs(c->zs, c->ydev.get(), c->Cfull.get(), ctau, ceye, target, c->n, c->n16, c->n16, g.stream)) return 1;
     } else if (!c->streamed || !any) {
-        if (hdm_sym_combine(c->Afull.get(), c->astride, any ? c->mloc : 0, c->ydev.get(), c->Cfull.get(), lead * tau,
-                            lead * (eye_override ? *eye_override : (-c->Rd + c->perturb)), target, c->n, c->n16, c->n16, g.stream)) return 1;
+        if (hdm_sym_combine(c->Afull.get(), c->astride, any ? c->mloc : 0, c->ydev.get(), c->Cfull.get(), ctau, ceye, target, c->n,
+                            c->n16, c->n16, g.stream)) return 1;
     } else {
         // streamed data without a sweep copy: batch after batch, the later ones on top of what the earlier ones left in the
         // target (tau' = 1, no identity term; each element is read and rewritten by the one thread that owns it)
@@ -465,15 +375,45 @@ int cone_assemble(MiCone *c, double tau, const double *y_host, double *target, c
             const int nb = std::min(c->Bs, c->mloc - q0);
             const double *A = cone_rows(c, q0, nb);
             if (!A) return 1;
-            if (hdm_sym_combine(A, c->astride, nb, c->ydev.get() + q0, q0 == 0 ? c->Cfull.get() : target, q0 == 0 ? lead * tau : 1.0,
-                                q0 == 0 ? lead * (eye_override ? *eye_override : (-c->Rd + c->perturb)) : 0.0, target, c->n, c->n16,
-                                c->n16, g.stream)) return 1;
+            if (hdm_sym_combine(A, c->astride, nb, c->ydev.get() + q0, q0 == 0 ? c->Cfull.get() : target, q0 == 0 ? ctau : 1.0,
+                                q0 == 0 ? ceye : 0.0, target, c->n, c->n16, c->n16, g.stream)) return 1;
         }
     }
     if (c->world > 1) {
         HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
         if (!c->allreduce || c->allreduce(c->xctx, target, (int64_t) c->n16 * c->n16)) return 1;
     }
+    return 0;
+}
+
+// S (or the checker buffer, or dS) <- tau*C - sum y_i A_i - Rd*I (+ perturb)   hdsdp_conic_sdp.c:343-402, :1616-1633
+// The entry of every dual-matrix request.  What the buffers already hold decides how it is answered -- nothing, a copy,
+// S + alpha dS (+ delta I), or the sweep: the rule is hdm_dual_plan's (dual_state.h), this performs it and commits it.
+int cone_assemble(MiCone *c, double tau, const double *y_host, HdmDualTarget which, const double *eye_override = nullptr) {
+    // the upload of a sweep is asynchronous: the source is a pinned buffer of the cone, and the previous upload from it has
+    // been consumed by the time it is rewritten (every caller synchronises on the factorisation that follows)
+    if (!c->yhost) HDM_HIP_CHECK(c->yhost.alloc((size_t) std::max(1, c->mloc)));
+    HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
+    double *yo = c->yhost.get();
+    bool any = false;
+    for (int q = 0; q < c->mloc; ++q) { yo[q] = y_host ? y_host[c->own[q]] : 0.0; any |= (yo[q] != 0.0); }
+    HdmDualPoint p;
+    p.tau = tau; p.eye = eye_override ? *eye_override : cone_eye(c); p.y = yo; p.ny = c->mloc;
+    const HdmDualPlan plan = hdm_dual_plan(c->dual, p, which, hdm_dual_mode(c->mloc, c->n), c->world);
+    g_asm_counts[plan.counter].fetch_add(1, std::memory_order_relaxed);
+    if (plan.line_missed && hdm_dual_debug()) hdm_dual_print_miss(stderr, c->dual, p, which, plan);
+    double *target = cone_dual_buffer(c, which);
+    const long cnt = (long) c->n16 * c->n16;
+    switch (plan.action) {
+    case HDM_DUAL_NONE: break;
+    case HDM_DUAL_COPY_FROM_S:
+        HDM_HIP_CHECK(hipMemcpyAsync(target, c->S.get(), sizeof(double) * (size_t) cnt, hipMemcpyDeviceToDevice, g.stream));
+        break;
+    case HDM_DUAL_AXPY: if (hdm_axpy_mat(target, c->S.get(), c->dS.get(), plan.alpha, cnt, g.stream)) return 1; break;
+    case HDM_DUAL_AXPY_EYE: if (hdm_axpy_mat_eye(target, c->S.get(), c->dS.get(), plan.alpha, plan.delta, c->n16, c->n, g.stream)) return 1; break;
+    case HDM_DUAL_SWEEP: if (cone_sweep(c, p, any, target)) return 1; break;
+    }
+    c->dual.commit(plan, p, which);
     return 0;
 }
 
@@ -508,25 +448,21 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
     HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
     if (whichBuffer != 0) { if (cone_checker(c, &ch) != HDSDP_RETCODE_OK) return 1; }
     if (ch->npad != SMALL_P || ch->nblk != 1) return 1;
-    const double eye_now = eye_override ? *eye_override : (-c->Rd + c->perturb);
-    const int np = c->mloc + 2;
     if (!c->chk) {
         if (c->chk.alloc((size_t) (c->mloc + 4), hipHostMallocMapped) != hipSuccess) { (void) hipGetLastError(); return 1; }
     }
     double *yo = c->chk.get();
-    bool same = (whichBuffer == 0 && c->pS_ok && (int) c->pS.size() == np && c->pS[0] == tau && c->pS[1] == eye_now);
-    for (int q = 0; q < c->mloc; ++q) {
-        const double v = y_host ? y_host[c->own[q]] : 0.0;
-        if (same && c->pS[2 + q] != v) same = false;
-        yo[q] = v;
-    }
-    if (same && c->fac_ok) { if (isPsd) *isPsd = c->fac_psd; return 0; }      // S = T(p) and its factor are in place
+    for (int q = 0; q < c->mloc; ++q) yo[q] = y_host ? y_host[c->own[q]] : 0.0;
+    HdmDualPoint p;
+    p.tau = tau; p.eye = eye_override ? *eye_override : cone_eye(c); p.y = yo; p.ny = c->mloc;
+    if (whichBuffer == 0 && c->dual.S_factored_at(p, isPsd)) return 0;       // S = T(p) and its factor are in place
     HdmSmallCheckArgs a = {};
     a.n = c->n; a.n16 = c->n16; a.m = c->mloc; a.A = c->Afull.get(); a.astride = c->astride; a.C = c->Cfull.get();
-    a.y = c->chk.dev(); a.tau = tau; a.eye = eye_now;
+    a.y = c->chk.dev(); a.tau = tau; a.eye = p.eye;
     a.Sout = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     a.L = ch->L.get(); a.W = ch->Dinv.get(); a.out = c->chk.dev() + c->mloc;
     yo[c->mloc] = -1.0;
+    if (whichBuffer == 0) c->dual.S_overwritten();   // the launch writes S: what it holds is known again when the launch has reported
     if (hdm_small_check(a, g.stream) || hipStreamSynchronize(g.stream) != hipSuccess) { *rc = HDSDP_RETCODE_FAILED; return 0; }
     const int info = (int) yo[c->mloc];
     if (info < 0) { *rc = HDSDP_RETCODE_FAILED; return 0; }
@@ -534,11 +470,8 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
     ch->logdet_ok = (info == 0); ch->logdet_val = yo[c->mloc + 1];
     if (whichBuffer == 0) {
         c->dualFactor->nFactorizes += 1;
-        c->pS.resize((size_t) np);
-        c->pS[0] = tau; c->pS[1] = eye_now;
-        for (int q = 0; q < c->mloc; ++q) c->pS[2 + q] = yo[q];
-        c->pS_ok = true; c->aff_chain = 0;
-        c->fac_ok = true; c->fac_psd = (info == 0);
+        c->dual.S_assembled_at(p);
+        c->dual.S_factored(info == 0);
     }
     if (isPsd) *isPsd = (info == 0);
     return 0;
@@ -546,13 +479,13 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
 
 void cone_update(void *cd, double tau, double *y) {
     StatScope stat_(ST_ASSEMBLE_FACTOR, __func__);
-    ((MiCone *) cd)->fac_ok = false;          // S moves, its factor does not follow
-    cone_assemble((MiCone *) cd, tau, y, ((MiCone *) cd)->S.get());
+    ((MiCone *) cd)->dual.factor_stale();     // S moves, its factor does not follow
+    cone_assemble((MiCone *) cd, tau, y, HDM_DUAL_S);
 }
 
 hdsdp_retcode cone_factor_S(MiCone *c, int *isPsd) {
     MiLin *l = (MiLin *) c->dualFactor->chol;
-    c->fac_ok = false;
+    c->dual.factor_stale();
     RC(l->ch.load_device(c->S.get(), c->n16, g.stream));
     int info = 0;
     RC(l->ch.factor(g.stream, &info));
@@ -590,12 +523,11 @@ hdsdp_retcode cone_interior_expert(void *cd, double dCCoef, double dACoefScal, d
     std::vector<double> ys(std::max(1, c->m), 0.0);
     for (int i = 0; i < c->m; ++i) ys[i] = -dACoefScal * (dACoef ? dACoef[i] : 0.0);   // cone_assemble subtracts
     const double eye = dEyeCoef + c->perturb;
-    double *target = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     {
         hdsdp_retcode rcs;
         if (cone_small_check(c, dCCoef, ys.data(), &eye, whichBuffer, isInterior, &rcs) == 0) return rcs;
     }
-    if (cone_assemble(c, dCCoef, ys.data(), target, &eye)) return HDSDP_RETCODE_FAILED;
+    if (cone_assemble(c, dCCoef, ys.data(), whichBuffer == 0 ? HDM_DUAL_S : HDM_DUAL_SCHECK, &eye)) return HDSDP_RETCODE_FAILED;
     HIP_RC(hipStreamSynchronize(g.stream));   // ys is read by an asynchronous copy
     return (whichBuffer == 0) ? cone_factor_S(c, isInterior) : cone_factor_check(c, isInterior);
 }
@@ -608,7 +540,7 @@ hdsdp_retcode cone_axpy_check(void *cd, double dStep, int whichBuffer, int *isIn
     if (!c->dS.get()) return HDSDP_RETCODE_FAILED;
     const long cnt = (long) c->n16 * c->n16;
     double *target = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
-    if (whichBuffer == 0) { c->pS_ok = false; c->fac_ok = false; }   // S moves without a point being named: the next request assembles it
+    if (whichBuffer == 0) c->dual.S_overwritten();   // S moves without a point being named: the next request assembles it
     RC(hdm_axpy_mat(target, c->S.get(), c->dS.get(), dStep, cnt, g.stream));
     return (whichBuffer == 0) ? cone_factor_S(c, isInterior) : cone_factor_check(c, isInterior);
 }
@@ -624,7 +556,7 @@ hdsdp_retcode cone_interior(void *cd, double tau, double *y, int *isInterior) {
         hdsdp_retcode rcs;
         if (cone_small_check(c, tau, y, nullptr, 0, isInterior, &rcs) == 0) return rcs;
     }
-    RC(cone_assemble(c, tau, y, c->S.get()));
+    RC(cone_assemble(c, tau, y, HDM_DUAL_S));
     return cone_factor_S(c, isInterior);
 }
 
@@ -637,7 +569,7 @@ hdsdp_retcode cone_barrier(void *cd, double tau, double *y, int whichBuffer, dou
         hdsdp_retcode rcs;
         if (cone_small_check(c, tau, y, nullptr, 0, &psd, &rcs) == 0) { if (rcs != HDSDP_RETCODE_OK || !psd) return HDSDP_RETCODE_FAILED; }
         else {
-            RC(cone_assemble(c, tau, y, c->S.get()));
+            RC(cone_assemble(c, tau, y, HDM_DUAL_S));
             if (cone_factor_S(c, &psd) != HDSDP_RETCODE_OK || !psd) return HDSDP_RETCODE_FAILED;
         }
     }
@@ -722,7 +654,7 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
         HIP_RC(hdm_memset_sync(c->dS.get(), 0, nn));
     }
     const double eye = dAdaRatio * c->Rd;
-    if (cone_assemble(c, dTauStep, dy, c->dS.get(), &eye)) return HDSDP_RETCODE_FAILED;
+    if (cone_assemble(c, dTauStep, dy, HDM_DUAL_DS, &eye)) return HDSDP_RETCODE_FAILED;
     if (c->n == 1) {   // :1668-1675
         double s0 = 0.0, d0 = 0.0;
         HIP_RC(hipMemcpyAsync(&d0, c->dS.get(), sizeof(double), hipMemcpyDeviceToHost, g.stream));
@@ -889,7 +821,7 @@ void cone_scal(void *cd, double dScal) {
     if (c->CL.get()) hipLaunchKernelGGL(mi_scale_kernel, dim3((unsigned) ((c->astride + 255) / 256)), dim3(256), 0, g.stream, c->CL.get(), c->astride, dScal);
     c->objScal *= dScal;
     c->norms_ready = false;
-    c->pS_ok = c->pD_ok = false;     // S and dS were assembled with the old objective: no short-cut from them (cone_assemble)
+    c->dual.data_changed();          // S and dS were assembled with the old objective: no short-cut from them (cone_assemble)
     (void) hipStreamSynchronize(g.stream);
 }
 
@@ -1009,7 +941,7 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
     const int n = c->n;
     const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
     auto fail = [](const char *what) { fprintf(stderr, "[hdsdp_mi355x] primal recovery: %s\n", what); };
-    if (cone_assemble(c, 1.0, y, c->Scheck.get(), &zero)) return fail("S assembly failed");
+    if (cone_assemble(c, 1.0, y, HDM_DUAL_SCHECK, &zero)) return fail("S assembly failed");
     HdmChol *chp = nullptr;
     if (cone_checker(c, &chp) != HDSDP_RETCODE_OK) return fail("out of memory");
     HdmChol &ch = *chp;
@@ -1025,7 +957,7 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
     }
     std::vector<double> ndy(c->m);
     for (int i = 0; i < c->m; ++i) ndy[i] = -dy[i];           // cone_assemble subtracts: dS = + sum dy_i A_i
-    if (cone_assemble(c, 0.0, ndy.data(), c->dS.get(), &zero)) return fail("dS assembly failed");
+    if (cone_assemble(c, 0.0, ndy.data(), HDM_DUAL_DS, &zero)) return fail("dS assembly failed");
     if (hipStreamSynchronize(g.stream) != hipSuccess) return fail("stream");   // ndy is read by an async copy
     if (hdm_mirror_lower(c->dS.get(), c->n16, n, g.stream)) return fail("mirror");
     if (ch.invert_factor(g.stream)) return fail("triangular inverse failed");

@@ -456,7 +456,7 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
 int HMiGetCallStats(double *seconds, int64_t *calls, int n);
 const char *HMiCallStatName(int k);
 void HMiResetCallStats(void);
-/* how the requests for a dual or step matrix of single-device blocks were answered so far (csrc/engine_cone.h: cone_assemble):
+/* how the requests for a dual or step matrix of single-device blocks were answered so far (csrc/dual_state.h: hdm_dual_plan):
  * [0] the buffer already held the point, [1] a copy of S, [2] S + alpha dS (+ delta I) on the last ratio test's line, [3] a
  * sweep for a dual matrix off that line, [4] a refresh sweep after 16 in-place updates, [5] a step-matrix sweep, [6] a sweep of a
  * block that does not track points.  Process-wide, never reset (the table HDSDP_MI355X_CALL_STATS=1 prints at exit).  Fills up
@@ -511,7 +511,7 @@ void HMiSDPAFree(HMiSDPA **pp);
  *  HDSDP_MI355X_KKT_ENVELOPE      1         block-envelope factorisation of a sparse operator             test_gpu_switches.py
  *  HDSDP_MI355X_KKT_RCM           1         reverse Cuthill-McKee order of a sparse operator              test_gpu_switches.py
  *  HDSDP_MI355X_KKT_TILES         1         tile form of a sparse operator when it pays (bsparse.h)       test_gpu_switches.py
- *  HDSDP_MI355X_AFFINE_S          by cost   0 / 1 / 2: dual matrix short-cuts (engine_cone.h)             test_gpu_switches.py
+ *  HDSDP_MI355X_AFFINE_S          by cost   0 / 1 / 2: dual matrix short-cuts (dual_state.h)              test_gpu_switches.py
  *  HDSDP_MI355X_SMALL_CHECK       1         one-launch interior check of small blocks                     test_gpu_switches.py
  *  HDSDP_MI355X_ZS                by cost   0 / 1 / 2: zero-suppressed copy for the S / dS sweeps (schur.h) test_gpu_switches.py
  *  HDSDP_MI355X_PRIMAL_SIGNED     1         KKT_TYPE_PRIMAL with an indefinite X: signed factor + signed  test_gpu_primal_signed.py
@@ -558,7 +558,7 @@ void HMiSDPAFree(HMiSDPA **pp);
  *  HDSDP_MI355X_TRACE             0         synchronise and report after every entry                      (diagnostic)
  *  HDSDP_MI355X_RATIO_DEBUG       0         one line per ratio test: Lanczos steps, time                  (diagnostic)
  *  HDSDP_MI355X_AFFINE_DEBUG      0         one line per dual-matrix request that missed the last ratio    (diagnostic)
- *                                           test's line (engine_cone.h: cone_assemble)
+ *                                           test's line (dual_state.h: hdm_dual_print_miss)
  *  HDM_POISON                     0         new device memory is filled with 0xFF (NaN): a read of         (diagnostic; tools/poison_run.sh)
  *                                           never-written memory turns the results into NaNs
  */
