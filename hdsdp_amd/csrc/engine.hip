@@ -19,6 +19,7 @@
 #include "hdm_common.h"
 #include "work_plan.h"
 #include "dual_state.h"
+#include "kkt_store.h"
 #include "schur.h"
 #include "lanczos.h"
 #include "lu.h"

@@ -317,7 +317,7 @@ static int small_plan(MiCone *c) {
 }
 
 int HMiKKTPhaseAEligible(hdsdp_kkt *HKKT) {
-    if (!HKKT || HKKT->nCones != 1 || HKKT->isKKTSparse) return 0;
+    if (!HKKT || HKKT->nCones != 1 || priv_of(HKKT)->st.form() != HDM_KKT_DENSE) return 0;
     hdsdp_cone *hc = HKKT->cones[0];
     if (hc->coneBuildSchur != cone_build_schur) return 0;
     MiCone *c = (MiCone *) hc->coneData;
@@ -348,11 +348,10 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
     if (ls->ch.npad != SMALL_P || lm->ch.npad != SMALL_P) return HDSDP_RETCODE_FAILED;
     // (the operator's accumulators as HKKTBuildUp(KKT_TYPE_INFEASIBLE) leaves them, hdsdp_schur.c:141-165, :256-268: the
     // kernel itself zeroes what it does not fill of the 128 x 128 device matrix)
-    // (as kkt_clean: the build starts an empty diagonal channel -- the stream is idle, the pinned channel is free to write)
-    memset(pv->chan.get(), 0, sizeof(double) * (size_t) m);
-    pv->chan_folded = false;
+    // (the build starts an empty diagonal channel -- the stream is idle, the pinned channel is free to write)
+    kkt_channel_start(HKKT, pv, KKT_TYPE_INFEASIBLE);
     RC(hdm_small_phase_a(a, g.stream));
-    if (pv->mirror) {
+    if (pv->st.mirror()) {
         HIP_RC(hipMemcpy2DAsync(HKKT->kktMatElem, sizeof(double) * m, lm->Mdev.get(), sizeof(double) * SMALL_P, sizeof(double) * m, m,
                                 hipMemcpyDeviceToHost, g.stream));
         pv->bytes_d2h += (int64_t) sizeof(double) * m * m;
@@ -367,9 +366,8 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
     memset(HKKT->dASinvVec, 0, sizeof(double) * m); memset(HKKT->dASinvRdSinvVec, 0, sizeof(double) * m);
     for (int i = 0; i < m; ++i) { HKKT->dASinvVec[i] = out[4 + i]; HKKT->dASinvRdSinvVec[i] = out[4 + m + i]; }
     HKKT->dTraceSinv = (c->Rd != 0.0) ? out[3] : 0.0;
-    pv->Mdev_valid = true;
+    pv->st.small_pass_done(lm->Mdev.get(), SMALL_P);
     lm->ch.factored = (infoM == 0); lm->ch.have_inv = false;
-    lm->srcHost = nullptr; lm->srcDev = lm->Mdev.get(); lm->srcLd = SMALL_P;
     HKKT->kktM->nFactorizes += 1;
     if (infoM != 0) {
         // the Schur matrix is not numerically positive definite: the multi-launch path's way out (pivoted solver) takes over
@@ -395,7 +393,7 @@ hdsdp_retcode HMiKKTPhaseA(hdsdp_kkt *HKKT, double barHsdTau, double *rowDual, d
 int HMiRcmOrder(int m, const int *colBeg, const int *rowIdx, int *perm) {
     if (m <= 0 || !colBeg || !rowIdx || !perm) return 1;
     std::vector<int> beg(colBeg, colBeg + m + 1), idx(rowIdx, rowIdx + colBeg[m]);
-    const std::vector<int> p = rcm_order(m, beg, idx);
+    const std::vector<int> p = hdm_rcm_order(m, beg, idx);
     for (int i = 0; i < m; ++i) perm[i] = p[i];
     return 0;
 }

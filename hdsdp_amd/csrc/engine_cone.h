@@ -136,10 +136,11 @@ struct MiCone {
 };
 
 struct MiKKTPriv {
-    int mirror = 1;
+    // how M is stored, what state it is in and where the last factorised matrix came from (kkt_store.h); the operator's linear
+    // system (MiLin::st) points here
+    HdmKktState st;
     HdmBuf<double> vecs;      // device: ASinv[m], ASinvRdSinv[m], ASinvCSinv[m], scal[4]
     HdmBuf<double> rhs;
-    bool Mdev_valid = false;  // device M holds the result of the last BuildUp
     // cones of HKKT->cones[] whose coneBuildSchur is this engine's (they accumulate on the device) and the others (the
     // reference's CPU cones: they accumulate into the host fields, hdsdp_conic_*.c)
     int n_engine = 0, n_foreign = 0;
@@ -154,7 +155,6 @@ struct MiKKTPriv {
     // there, and the first HKKTRegularize / HKKTFactorize after a build adds it (8 m bytes up) to the device matrix's diagonal
     HdmPinned<double> chan;
     HdmBuf<double> chan_dev;      // device: m doubles + 1 (the minimum the regulariser reads)
-    bool chan_folded = false;     // the channel of the current build is in the device matrix already
     int64_t bytes_d2h = 0, bytes_h2d = 0;   // M and the channel moved since HKKTInit (HMiKKTGetMatrixTraffic)
 };
 

@@ -1,5 +1,8 @@
 // engine_kkt.h -- exported C ABI, first part: utilities, HFpLinsys* and HKKT* (dense and sparse Schur operator, RCM order, host mirror, row access)
 // Implementation header of engine.hip: included exactly once, there, in this order (inside extern "C"); split out of a 3 300-line file in round 3, nothing else changed.
+// The rules about the operator's matrix live in kkt_store.h: how it is stored (HdmKktForm), what state it is in (HdmKktState, one
+// transition per writer), and how it reaches the factor (hdm_kkt_load_plan, whose comment is the table of all cases).  This file
+// performs them: HKKTInit is a sequence of steps, HKKTFactorize gets the plan, stages, commits and loads.
 
 const char *HMiVersion(void) { return "hdsdp-mi355x 0.1 (gfx950, fp64 MFMA)"; }
 
@@ -37,6 +40,13 @@ void HMiGetStageTimes(double *ms, int n) {
 }
 
 // ---------------------------------------------------------------- HFpLinsys*
+// the eleven slots of the reference's linear-system vtable (hdsdp_linsolver.h): every object of the engine has the same ones
+static void lin_fill_vtable(hdsdp_linsys_fp *h, int nCol, linsys_type Ltype) {
+    h->nCol = nCol; h->LinType = Ltype;
+    h->cholCreate = lin_create; h->cholSetParam = lin_setparam; h->cholSymbolic = lin_symbolic; h->cholNumeric = lin_numeric;
+    h->cholPsdCheck = lin_psdcheck; h->cholFSolve = lin_fsolve; h->cholBSolve = lin_bsolve; h->cholSolve = lin_solve;
+    h->cholGetDiag = lin_getdiag; h->cholInvert = lin_invert; h->cholDestroy = lin_destroy;
+}
 hdsdp_retcode HFpLinsysCreate(hdsdp_linsys_fp **pHLin, int nCol, linsys_type Ltype) {
     if (!pHLin) return HDSDP_RETCODE_FAILED;
     switch (Ltype) {
@@ -52,19 +62,7 @@ hdsdp_retcode HFpLinsysCreate(hdsdp_linsys_fp **pHLin, int nCol, linsys_type Lty
     }
     hdsdp_linsys_fp *h = (hdsdp_linsys_fp *) calloc(1, sizeof(hdsdp_linsys_fp));
     if (!h) return HDSDP_RETCODE_MEMORY;
-    h->nCol = nCol;
-    h->LinType = Ltype;
-    h->cholCreate = lin_create;
-    h->cholSetParam = lin_setparam;
-    h->cholSymbolic = lin_symbolic;
-    h->cholNumeric = lin_numeric;
-    h->cholPsdCheck = lin_psdcheck;
-    h->cholFSolve = lin_fsolve;
-    h->cholBSolve = lin_bsolve;
-    h->cholSolve = lin_solve;
-    h->cholGetDiag = lin_getdiag;
-    h->cholInvert = lin_invert;
-    h->cholDestroy = lin_destroy;
+    lin_fill_vtable(h, nCol, Ltype);
     hdsdp_retcode rc = h->cholCreate(&h->chol, nCol);
     if (rc != HDSDP_RETCODE_OK) { free(h); return rc; }
     ((MiLin *) h->chol)->type = Ltype;
@@ -148,17 +146,11 @@ hdsdp_retcode HKKTCreate(hdsdp_kkt **pHKKT) {
     return HDSDP_RETCODE_OK;
 }
 
-// (reverse Cuthill-McKee: hdm_rcm_order, bsparse.hip)
-static std::vector<int> rcm_order(int m, const std::vector<int> &beg, const std::vector<int> &idx) { return hdm_rcm_order(m, beg, idx); }
-
 // a linear-system object for a sparse Schur operator in TILE form: the same vtable, no dense factor behind it
 static hdsdp_retcode linsys_create_tiles(hdsdp_linsys_fp **pHLin, int nCol, std::unique_ptr<HdmBsp> bsp) {
     hdsdp_linsys_fp *h = (hdsdp_linsys_fp *) calloc(1, sizeof(hdsdp_linsys_fp));
     if (!h) return HDSDP_RETCODE_MEMORY;
-    h->nCol = nCol; h->LinType = HDSDP_LINSYS_SPARSE_DIRECT;
-    h->cholCreate = lin_create; h->cholSetParam = lin_setparam; h->cholSymbolic = lin_symbolic; h->cholNumeric = lin_numeric;
-    h->cholPsdCheck = lin_psdcheck; h->cholFSolve = lin_fsolve; h->cholBSolve = lin_bsolve; h->cholSolve = lin_solve;
-    h->cholGetDiag = lin_getdiag; h->cholInvert = lin_invert; h->cholDestroy = lin_destroy;
+    lin_fill_vtable(h, nCol, HDSDP_LINSYS_SPARSE_DIRECT);
     MiLin *l = new MiLin();
     l->n = nCol; l->type = HDSDP_LINSYS_SPARSE_DIRECT; l->csc_in = true; l->bsp = std::move(bsp);
     h->chol = l;
@@ -166,18 +158,19 @@ static hdsdp_retcode linsys_create_tiles(hdsdp_linsys_fp **pHLin, int nCol, std:
     return HDSDP_RETCODE_OK;
 }
 
-hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones) {
-    if (ensure_ctx()) return HDSDP_RETCODE_FAILED;
-    {   // An LP cone builds on the caller's device and stream into the operator's matrix; a device-group cone's shards build on
-        // worker threads and devices of their own (group_impl.h: grun), with no ordering against the caller's stream that the LP
-        // cone's accumulation could rely on.  The two are not combined in one operator.
-        bool lp = false, grp = false;
-        for (int i = 0; i < nCones; ++i) { lp = lp || cones[i]->coneBuildSchur == lp_build_schur; grp = grp || cones[i]->coneBuildSchur == gc_build_schur; }
-        if (lp && grp) {
-            fprintf(stderr, "[hdsdp_mi355x] HKKTInit: an LP cone cannot share an operator with a device-group (sharded) cone\n");
-            return HDSDP_RETCODE_FAILED;
-        }
-    }
+// ---- HKKTInit's steps.  The rules they perform (sparse or dense, envelope and order, the five switches) are kkt_store.h's.
+// An LP cone builds on the caller's device and stream into the operator's matrix; a device-group cone's shards build on worker
+// threads and devices of their own (group_impl.h: grun), with no ordering against the caller's stream that the LP cone's
+// accumulation could rely on.  The two are not combined in one operator.
+static bool kkt_cones_combine(int nCones, hdsdp_cone **cones) {
+    bool lp = false, grp = false;
+    for (int i = 0; i < nCones; ++i) { lp = lp || cones[i]->coneBuildSchur == lp_build_schur; grp = grp || cones[i]->coneBuildSchur == gc_build_schur; }
+    if (lp && grp) fprintf(stderr, "[hdsdp_mi355x] HKKTInit: an LP cone cannot share an operator with a device-group (sharded) cone\n");
+    return !(lp && grp);
+}
+
+// the reference struct's host fields (hdsdp_schur.c:181-254)
+static hdsdp_retcode kkt_init_host_fields(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones) {
     HKKT->nRow = nRow;
     HKKT->nCones = nCones;
     HKKT->cones = cones;
@@ -195,160 +188,143 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     if (!HKKT->invBuffer || !HKKT->kktBuffer || !HKKT->kktBuffer2 || !HKKT->dASinvVec || !HKKT->dASinvCSinvVec ||
         !HKKT->dASinvRdSinvVec || !HKKT->kktDiag)
         return HDSDP_RETCODE_MEMORY;
-    // Dense Schur matrix (hdsdp_schur.c:11-44) or the aggregated-pattern CSC (:46-139): the reference's own rule.  A cone
-    // whose share of M reaches 0.3 m^2 entries makes it dense at once (:229-238); otherwise the columns' patterns are
-    // collected from the cones (coneAddSymNz / coneGetKKTMap) and the CSC is kept unless it grows to 0.3 m^2 (:104-108).
-    // HDSDP_MI355X_SPARSE_KKT=0 forces the dense matrix.
-    MiKKTPriv *pv0 = priv_of(HKKT);
-    HKKT->isKKTSparse = 1;
-    const int64_t nDense = (int64_t) (0.3 * (double) nRow * (double) nRow);     // HDSDP_SPARSE_SCHUR_THRESHOLD, hdsdp.h:29
-    if (const char *e = getenv("HDSDP_MI355X_SPARSE_KKT")) if (atoi(e) == 0) HKKT->isKKTSparse = 0;
-    for (int i = 0; i < nCones && HKKT->isKKTSparse; ++i) {
+    return HDSDP_RETCODE_OK;
+}
+
+struct KktPattern { std::vector<int> beg, idx, cols; };   // the aggregated pattern: lower-triangular CSC, plus each entry's column
+
+// Dense Schur matrix (hdsdp_schur.c:11-44) or the aggregated-pattern CSC (:46-139), by the reference's own rule
+// (kkt_store.h): the columns' patterns are collected from the cones (coneAddSymNz / coneGetKKTMap) unless a cone's share or
+// the growing pattern says dense.  False: the operator is dense.
+static bool kkt_collect_pattern(hdsdp_kkt *HKKT, const HdmKktSwitches &sw, KktPattern &pat) {
+    const int nRow = HKKT->nRow, nCones = HKKT->nCones;
+    hdsdp_cone **cones = HKKT->cones;
+    if (!sw.sparse) return false;
+    for (int i = 0; i < nCones; ++i)
         if (!cones[i]->coneGetSymNnz || !cones[i]->coneAddSymNz || !cones[i]->coneGetKKTMap ||
-            cones[i]->coneGetSymNnz(cones[i]->coneData) >= nDense) HKKT->isKKTSparse = 0;
+            !hdm_kkt_count_is_sparse(cones[i]->coneGetSymNnz(cones[i]->coneData), nRow)) return false;
+    for (int i = 0; i < nCones; ++i)      // an engine cone may serve a second operator: its pattern walk starts over
+        if (cones[i]->coneBuildSchur == cone_build_schur) ((MiCone *) cones[i]->coneData)->kkt_counted = 0;
+    std::vector<int> col((size_t) nRow);
+    pat.beg.assign((size_t) nRow + 1, 0);
+    for (int iCol = 0; iCol < nRow; ++iCol) {
+        std::fill(col.begin(), col.end(), 0);
+        for (int i = 0; i < nCones; ++i) cones[i]->coneAddSymNz(cones[i]->coneData, iCol, col.data());
+        for (int iRow = iCol; iRow < nRow; ++iRow)
+            if (col[iRow]) { col[iRow] = (int) pat.idx.size(); pat.idx.push_back(iRow); pat.cols.push_back(iCol); }
+        for (int i = 0; i < nCones; ++i) cones[i]->coneGetKKTMap(cones[i]->coneData, iCol, col.data());
+        pat.beg[iCol + 1] = (int) pat.idx.size();
+        if (!hdm_kkt_count_is_sparse((int64_t) pat.idx.size(), nRow)) return false;      // aggregation made it dense after all
     }
-    if (HKKT->isKKTSparse) {
-        for (int i = 0; i < nCones; ++i)      // an engine cone may serve a second operator: its pattern walk starts over
-            if (cones[i]->coneBuildSchur == cone_build_schur) ((MiCone *) cones[i]->coneData)->kkt_counted = 0;
-        std::vector<int> beg((size_t) nRow + 1, 0), idx, col((size_t) nRow);
-        for (int iCol = 0; iCol < nRow && HKKT->isKKTSparse; ++iCol) {
-            std::fill(col.begin(), col.end(), 0);
-            for (int i = 0; i < nCones; ++i) cones[i]->coneAddSymNz(cones[i]->coneData, iCol, col.data());
-            for (int iRow = iCol; iRow < nRow; ++iRow)
-                if (col[iRow]) { col[iRow] = (int) idx.size(); idx.push_back(iRow); }
-            for (int i = 0; i < nCones; ++i) cones[i]->coneGetKKTMap(cones[i]->coneData, iCol, col.data());
-            beg[iCol + 1] = (int) idx.size();
-            if ((int64_t) idx.size() >= nDense) HKKT->isKKTSparse = 0;      // aggregation made it dense after all
-        }
-        // a constraint no cone has data for leaves an empty column: the reference stops there ("KKT solver detects an
-        // empty column", :116-121); the engine keeps such an operator usable on the dense matrix, where the row simply
-        // stays zero until a CPU cone (the bound cone's diagonal) or the regularisation fills it
-        for (int iCol = 0; iCol < nRow && HKKT->isKKTSparse; ++iCol)
-            if (beg[iCol] == beg[iCol + 1] || idx[beg[iCol]] != iCol) HKKT->isKKTSparse = 0;
-        if (HKKT->isKKTSparse) {
-            const size_t nnz = idx.size();
-            HKKT->kktMatBeg = (int *) malloc(sizeof(int) * ((size_t) nRow + 1));
-            HKKT->kktMatIdx = (int *) malloc(sizeof(int) * std::max<size_t>(1, nnz));
-            if (!HKKT->kktMatBeg || !HKKT->kktMatIdx) return HDSDP_RETCODE_MEMORY;
-            memcpy(HKKT->kktMatBeg, beg.data(), sizeof(int) * ((size_t) nRow + 1));
-            memcpy(HKKT->kktMatIdx, idx.data(), sizeof(int) * nnz);
-            // (kktMatElem is a field of the reference's own struct: it stays a raw pointer, freed in HKKTClear)
-            if (hipHostMalloc((void **) &HKKT->kktMatElem, sizeof(double) * std::max<size_t>(1, nnz), hipHostMallocDefault) != hipSuccess)
-                return HDSDP_RETCODE_MEMORY;
-            memset(HKKT->kktMatElem, 0, sizeof(double) * nnz);
-            for (int iCol = 0; iCol < nRow; ++iCol) HKKT->kktDiag[iCol] = &HKKT->kktMatElem[beg[iCol]];
-            // Device storage of a sparse operator.  TILE form (bsparse.h) when it pays: the rows are reordered (dense rows last,
-            // reverse Cuthill-McKee for the rest), and matrix and factor exist only as the 128 x 128 tiles inside the block
-            // pattern of the Cholesky factor -- O(tiles of L) memory, a level-scheduled left-looking factorisation.  Taken when
-            // those tiles are at most half of the dense lower triangle's (HDSDP_MI355X_KKT_TILES=0: never); otherwise the dense
-            // device matrix factored on its block envelope, as in round 2.
-            std::unique_ptr<HdmBsp> bsp_own;
-            {
-                static const bool use_tiles = [] { const char *e = getenv("HDSDP_MI355X_KKT_TILES"); return !(e && atoi(e) == 0); }();
-                if (use_tiles && nRow > 2 * 128) {
-                    bsp_own.reset(new HdmBsp());
-                    if (bsp_own->init(nRow, beg.data(), idx.data(), 0.5)) bsp_own.reset();
-                }
+    return hdm_kkt_columns_are_sparse(nRow, pat.beg.data(), pat.idx.data());
+}
+
+// The block envelope of a sparse operator's dense device matrix, in the driver's order or -- where kkt_store.h's rule says it
+// is cheaper -- in a reverse Cuthill-McKee order of the pattern.  The factor object then holds P M P' (MiLin::perm): the
+// builders keep writing M at the driver's indices, the pattern's entries are scattered to their permuted places when the matrix
+// is loaded for factorisation, and right-hand sides / solutions are permuted on the host.
+static hdsdp_retcode kkt_init_envelope(MiKKTPriv *pv, MiLin *lm, const HdmKktSwitches &sw, const KktPattern &pat, int nRow) {
+    if (!sw.envelope || lm->ch.nblk <= 1) return HDSDP_RETCODE_OK;
+    const size_t nnz = pat.idx.size();
+    const HdmKktEnvelope nat = hdm_kkt_envelope(pat.idx.data(), pat.cols.data(), nnz, lm->ch.nblk, nullptr);
+    if (sw.rcm && hdm_kkt_rcm_eligible((int64_t) nnz, nRow)) {
+        std::vector<int> perm = hdm_rcm_order(nRow, pat.beg, pat.idx);
+        const HdmKktEnvelope rcm = hdm_kkt_envelope(pat.idx.data(), pat.cols.data(), nnz, lm->ch.nblk, perm.data());
+        if (hdm_kkt_rcm_taken(rcm.cost, nat.cost)) {
+            std::vector<int> prow(nnz), pcol(nnz);
+            for (size_t q = 0; q < nnz; ++q) {
+                int r = perm[pat.idx[q]], c = perm[pat.cols[q]];
+                if (r < c) std::swap(r, c);
+                prow[q] = r; pcol[q] = c;
             }
-            const HdmBsp *bsp = bsp_own.get();   // (for the report below; the operator's linear system owns it from here)
-            hdsdp_retcode rcs = bsp ? linsys_create_tiles(&HKKT->kktM, nRow, std::move(bsp_own)) : HFpLinsysCreate(&HKKT->kktM, nRow, HDSDP_LINSYS_SPARSE_DIRECT);
-            if (rcs != HDSDP_RETCODE_OK) return rcs;
-            rcs = HFpLinsysSymbolic(HKKT->kktM, HKKT->kktMatBeg, HKKT->kktMatIdx);
-            if (rcs != HDSDP_RETCODE_OK) return rcs;
-            // the pattern as (row, column) pairs on the device
-            std::vector<int> cols(nnz);
-            for (int iCol = 0; iCol < nRow; ++iCol)
-                for (int q = beg[iCol]; q < beg[iCol + 1]; ++q) cols[q] = iCol;
-            pv0->nnz = (long) nnz;
-            if (pv0->sp_rows.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
-                pv0->sp_cols.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
-                pv0->sp_vals.alloc(std::max<size_t>(1, nnz)) != hipSuccess)
+            if (pv->sp_prow.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
+                pv->sp_pcol.alloc(std::max<size_t>(1, nnz)) != hipSuccess)
                 return HDSDP_RETCODE_MEMORY;
-            if (hdm_memcpy_h2d_sync(pv0->sp_rows.get(), idx.data(), sizeof(int) * nnz) != hipSuccess ||
-                hdm_memcpy_h2d_sync(pv0->sp_cols.get(), cols.data(), sizeof(int) * nnz) != hipSuccess)
+            if (hdm_memcpy_h2d_sync(pv->sp_prow.get(), prow.data(), sizeof(int) * nnz) != hipSuccess ||
+                hdm_memcpy_h2d_sync(pv->sp_pcol.get(), pcol.data(), sizeof(int) * nnz) != hipSuccess)
                 return HDSDP_RETCODE_FAILED;
-            // the pattern's block envelope: the blocked Cholesky of the (dense, mostly zero) device matrix stops each block
-            // column where the envelope ends and the substitutions skip the blocks outside (HdmChol::set_envelope).  The
-            // factor of a matrix fills inside its row envelope only, so nothing is approximated.  If a reverse Cuthill-McKee
-            // order of the pattern makes the envelope cheaper, the factor object holds P M P' instead (MiLin::perm): the
-            // builders keep writing M at the driver's indices, the pattern's entries are scattered to their permuted places
-            // when the matrix is loaded for factorisation, and right-hand sides / solutions are permuted on the host.
-            {
-                static const bool use_env = [] { const char *e = getenv("HDSDP_MI355X_KKT_ENVELOPE"); return !(e && atoi(e) == 0); }();
-                static const bool use_rcm = [] { const char *e = getenv("HDSDP_MI355X_KKT_RCM"); return !(e && atoi(e) == 0); }();
-                MiLin *lm = (MiLin *) HKKT->kktM->chol;
-                if (use_env && lm && !lm->bsp && lm->ch.nblk > 1) {
-                    const int nb = lm->ch.nblk;
-                    auto envelope = [&](const std::vector<int> *perm, std::vector<int> &first) {   // returns the factorisation's cost in block products
-                        first.resize(nb);
-                        for (int b = 0; b < nb; ++b) first[b] = b;
-                        for (size_t q = 0; q < nnz; ++q) {
-                            int r = idx[q], c = cols[q];
-                            if (perm) { r = (*perm)[r]; c = (*perm)[c]; if (r < c) std::swap(r, c); }
-                            const int br = r / 128, bc = c / 128;
-                            if (bc < first[br]) first[br] = bc;
-                        }
-                        std::vector<int> colh(nb);
-                        for (int k = 0; k < nb; ++k) colh[k] = k;
-                        for (int b = 0; b < nb; ++b) for (int k = first[b]; k <= b; ++k) colh[k] = std::max(colh[k], b);
-                        double cost = 0.0;
-                        for (int k = 0; k < nb; ++k) { const double h = colh[k] - k; cost += 1.0 + h + 0.5 * h * (h + 1.0); }
-                        return cost;
-                    };
-                    std::vector<int> first_nat, first_rcm, perm;
-                    const double cost_nat = envelope(nullptr, first_nat);
-                    double cost_rcm = INFINITY;
-                    // (the reordering is looked for where it can pay: patterns up to 5e7 entries -- its adjacency lists take 8 bytes per
-                    // entry on the host -- that do not already fill most of the triangle)
-                    if (use_rcm && nnz <= 50000000 && (double) nnz < 0.15 * (double) nRow * nRow) { perm = rcm_order(nRow, beg, idx); cost_rcm = envelope(&perm, first_rcm); }
-                    if (cost_rcm < 0.8 * cost_nat) {
-                        std::vector<int> prow(nnz), pcol(nnz);
-                        for (size_t q = 0; q < nnz; ++q) {
-                            int r = perm[idx[q]], c = perm[cols[q]];
-                            if (r < c) std::swap(r, c);
-                            prow[q] = r; pcol[q] = c;
-                        }
-                        if (pv0->sp_prow.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
-                            pv0->sp_pcol.alloc(std::max<size_t>(1, nnz)) != hipSuccess)
-                            return HDSDP_RETCODE_MEMORY;
-                        if (hdm_memcpy_h2d_sync(pv0->sp_prow.get(), prow.data(), sizeof(int) * nnz) != hipSuccess ||
-                            hdm_memcpy_h2d_sync(pv0->sp_pcol.get(), pcol.data(), sizeof(int) * nnz) != hipSuccess)
-                            return HDSDP_RETCODE_FAILED;
-                        lm->perm = perm;
-                        if (lm->ch.set_envelope(first_rcm.data())) return HDSDP_RETCODE_FAILED;
-                    } else if (lm->ch.set_envelope(first_nat.data())) return HDSDP_RETCODE_FAILED;
-                }
-            }
-            printf("    Using sparse Schur complement (%d nnzs)\n", HKKT->kktMatBeg[nRow]);
-            if (bsp)
-                fprintf(stderr, "[hdsdp_mi355x] sparse Schur operator in tile form: %d of %ld tiles (%.2f GiB instead of %.2f), %d levels\n", bsp->ntiles,
-                        bsp->dense_tiles(), (double) bsp->bytes() / (1 << 30), 2.0 * 8.0 * (double) bsp->nb * 128 * bsp->nb * 128 / (1 << 30), bsp->nlevels);
+            lm->perm = std::move(perm);
+            return lm->ch.set_envelope(rcm.first.data()) ? HDSDP_RETCODE_FAILED : HDSDP_RETCODE_OK;
         }
     }
-    if (!HKKT->isKKTSparse) {
-        // pinned so the D2H/H2D of M after BuildUp / before Factorize runs at PCIe rate
-        if (hipHostMalloc((void **) &HKKT->kktMatElem, sizeof(double) * (size_t) nRow * nRow, hipHostMallocDefault) != hipSuccess)
-            return HDSDP_RETCODE_MEMORY;
-        memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) nRow * nRow);
-        hdsdp_retcode rc = HFpLinsysCreate(&HKKT->kktM, nRow, HDSDP_LINSYS_DENSE_ITERATIVE);
-        if (rc != HDSDP_RETCODE_OK) return rc;
-        double acc = 1e-12;  // KKT_ACCURACY (hdsdp.h:27); loosened for big systems exactly as hdsdp_schur.c:21-35
-        int iters = -1;
-        if (nRow > 20000) { acc *= 100.0; iters = 500; } else if (nRow > 15000) { acc *= 50.0; iters = 450; }
-        else if (nRow > 5000) { acc *= 5.0; iters = 120; }
-        HFpLinsysSetParam(HKKT->kktM, 5.0 * acc, acc, -1, iters, -1);
-        for (int i = 0; i < nRow; ++i) HKKT->kktDiag[i] = &HKKT->kktMatElem[i + (size_t) i * nRow];
+    return lm->ch.set_envelope(nat.first.data()) ? HDSDP_RETCODE_FAILED : HDSDP_RETCODE_OK;
+}
+
+// Storage of a sparse operator: the host CSC, and on the device the TILE form (bsparse.h) when it pays -- the rows are reordered
+// (dense rows last, reverse Cuthill-McKee for the rest), and matrix and factor exist only as the 128 x 128 tiles inside the block
+// pattern of the Cholesky factor: O(tiles of L) memory, a level-scheduled left-looking factorisation.  Taken when those tiles
+// are at most half of the dense lower triangle's; otherwise the dense device matrix factored on its block envelope.
+static hdsdp_retcode kkt_init_sparse_storage(hdsdp_kkt *HKKT, MiKKTPriv *pv, const HdmKktSwitches &sw, const KktPattern &pat) {
+    const int nRow = HKKT->nRow;
+    const size_t nnz = pat.idx.size();
+    HKKT->kktMatBeg = (int *) malloc(sizeof(int) * ((size_t) nRow + 1));
+    HKKT->kktMatIdx = (int *) malloc(sizeof(int) * std::max<size_t>(1, nnz));
+    if (!HKKT->kktMatBeg || !HKKT->kktMatIdx) return HDSDP_RETCODE_MEMORY;
+    memcpy(HKKT->kktMatBeg, pat.beg.data(), sizeof(int) * ((size_t) nRow + 1));
+    memcpy(HKKT->kktMatIdx, pat.idx.data(), sizeof(int) * nnz);
+    // (kktMatElem is a field of the reference's own struct: it stays a raw pointer, freed in HKKTClear)
+    if (hipHostMalloc((void **) &HKKT->kktMatElem, sizeof(double) * std::max<size_t>(1, nnz), hipHostMallocDefault) != hipSuccess)
+        return HDSDP_RETCODE_MEMORY;
+    memset(HKKT->kktMatElem, 0, sizeof(double) * nnz);
+    for (int iCol = 0; iCol < nRow; ++iCol) HKKT->kktDiag[iCol] = &HKKT->kktMatElem[pat.beg[iCol]];
+    std::unique_ptr<HdmBsp> bsp_own;
+    if (sw.tiles && nRow > 2 * HDM_KKT_BLOCK) {
+        bsp_own.reset(new HdmBsp());
+        if (bsp_own->init(nRow, pat.beg.data(), pat.idx.data(), 0.5)) bsp_own.reset();
     }
-    // On the device M stays a dense m x m matrix in either case: the cones' builders write it at global (row, column)
-    // indices, the blocked Cholesky factors it densely.  What the sparse form changes is the host side -- the matrix the
-    // driver, the CPU cones (through kktMapping / kktDiag) and HKKTRegularize see is the nnz-long CSC, not m^2 doubles.
+    const HdmBsp *bsp = bsp_own.get();   // (for the report below; the operator's linear system owns it from here)
+    hdsdp_retcode rc = bsp ? linsys_create_tiles(&HKKT->kktM, nRow, std::move(bsp_own)) : HFpLinsysCreate(&HKKT->kktM, nRow, HDSDP_LINSYS_SPARSE_DIRECT);
+    if (rc != HDSDP_RETCODE_OK) return rc;
+    rc = HFpLinsysSymbolic(HKKT->kktM, HKKT->kktMatBeg, HKKT->kktMatIdx);
+    if (rc != HDSDP_RETCODE_OK) return rc;
+    // the pattern as (row, column) pairs on the device
+    pv->nnz = (long) nnz;
+    if (pv->sp_rows.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
+        pv->sp_cols.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
+        pv->sp_vals.alloc(std::max<size_t>(1, nnz)) != hipSuccess)
+        return HDSDP_RETCODE_MEMORY;
+    if (hdm_memcpy_h2d_sync(pv->sp_rows.get(), pat.idx.data(), sizeof(int) * nnz) != hipSuccess ||
+        hdm_memcpy_h2d_sync(pv->sp_cols.get(), pat.cols.data(), sizeof(int) * nnz) != hipSuccess)
+        return HDSDP_RETCODE_FAILED;
+    if (!bsp && (rc = kkt_init_envelope(pv, (MiLin *) HKKT->kktM->chol, sw, pat, nRow)) != HDSDP_RETCODE_OK) return rc;
+    printf("    Using sparse Schur complement (%d nnzs)\n", HKKT->kktMatBeg[nRow]);
+    if (bsp)
+        fprintf(stderr, "[hdsdp_mi355x] sparse Schur operator in tile form: %d of %ld tiles (%.2f GiB instead of %.2f), %d levels\n", bsp->ntiles,
+                bsp->dense_tiles(), (double) bsp->bytes() / (1 << 30), 2.0 * 8.0 * (double) bsp->nb * 128 * bsp->nb * 128 / (1 << 30), bsp->nlevels);
+    return HDSDP_RETCODE_OK;
+}
+
+// Storage of a dense operator: the m x m host matrix and the Schur system's tolerances
+static hdsdp_retcode kkt_init_dense_storage(hdsdp_kkt *HKKT) {
+    const int nRow = HKKT->nRow;
+    // pinned so the D2H/H2D of M after BuildUp / before Factorize runs at PCIe rate
+    if (hipHostMalloc((void **) &HKKT->kktMatElem, sizeof(double) * (size_t) nRow * nRow, hipHostMallocDefault) != hipSuccess)
+        return HDSDP_RETCODE_MEMORY;
+    memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) nRow * nRow);
+    hdsdp_retcode rc = HFpLinsysCreate(&HKKT->kktM, nRow, HDSDP_LINSYS_DENSE_ITERATIVE);
+    if (rc != HDSDP_RETCODE_OK) return rc;
+    double acc = 1e-12;  // KKT_ACCURACY (hdsdp.h:27); loosened for big systems exactly as hdsdp_schur.c:21-35
+    int iters = -1;
+    if (nRow > 20000) { acc *= 100.0; iters = 500; } else if (nRow > 15000) { acc *= 50.0; iters = 450; }
+    else if (nRow > 5000) { acc *= 5.0; iters = 120; }
+    HFpLinsysSetParam(HKKT->kktM, 5.0 * acc, acc, -1, iters, -1);
+    for (int i = 0; i < nRow; ++i) HKKT->kktDiag[i] = &HKKT->kktMatElem[i + (size_t) i * nRow];
+    return HDSDP_RETCODE_OK;
+}
+
+// What every form has on the device: outside the tile form M stays a dense m x m matrix -- the cones' builders write it at
+// global (row, column) indices, the blocked Cholesky factors it densely; what the sparse form changes is the host side, where
+// the driver, the CPU cones (through kktMapping / kktDiag) and HKKTRegularize see the nnz-long CSC, not m^2 doubles -- plus the
+// accumulators, the diagonal channel, and the state the storage starts in.
+static hdsdp_retcode kkt_init_device_common(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
+    const int nRow = HKKT->nRow, nCones = HKKT->nCones;
+    hdsdp_cone **cones = HKKT->cones;
     MiLin *l = (MiLin *) HKKT->kktM->chol;
     if (!l->bsp) {
         const size_t mm = sizeof(double) * (size_t) l->ch.npad * l->ch.npad;
         if (l->Mdev.alloc(mm / sizeof(double)) != hipSuccess) return HDSDP_RETCODE_MEMORY;
         if (hdm_memset_sync(l->Mdev.get(), 0, mm) != hipSuccess) return HDSDP_RETCODE_FAILED;
     }
-    MiKKTPriv *pv = priv_of(HKKT);
     if (pv->vecs.alloc(3 * (size_t) nRow + 4) != hipSuccess) return HDSDP_RETCODE_MEMORY;
     pv->n_engine = pv->n_foreign = 0;
     for (int i = 0; i < nCones; ++i) {
@@ -360,20 +336,38 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
         pv->chan_dev.alloc((size_t) nRow + 1) != hipSuccess)
         return HDSDP_RETCODE_MEMORY;
     memset(pv->chan.get(), 0, sizeof(double) * std::max(1, nRow));
-    pv->chan_folded = false;
     pv->bytes_d2h = pv->bytes_h2d = 0;
-    // HDSDP_MI355X_DEVICE_M=1: an unchanged driver keeps M on the device when it can.  Its host
-    // cones outside cones[] (the bound cone on y) write the diagonal only, and that goes through the channel.
-    if (const char *e = getenv("HDSDP_MI355X_DEVICE_M")) if (atoi(e) == 1) {
-        if (pv->n_engine > 0 && pv->n_foreign == 0) {
-            HMiKKTSetHostMirror(HKKT, 0);
-            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: M stays on the device (m = %d, diagonal channel)\n", nRow);
-        }
-        else if (pv->n_foreign > 0)
-            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: the host copy of M is kept: %d cone(s) of this operator accumulate on the host\n",
-                    pv->n_foreign);
-        else fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: the host copy of M is kept: the operator has no engine cone\n");
+    l->st = &pv->st;
+    pv->st.storage_decided(l->bsp ? HDM_KKT_TILES : HKKT->isKKTSparse ? HDM_KKT_CSC : HDM_KKT_DENSE, !l->perm.empty());
+    return HDSDP_RETCODE_OK;
+}
+
+// HDSDP_MI355X_DEVICE_M=1: an unchanged driver keeps M on the device when it can.  Its host cones
+// outside cones[] (the bound cone on y) write the diagonal only, and that goes through the channel.
+static void kkt_apply_device_m(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
+    if (pv->n_engine > 0 && pv->n_foreign == 0) {
+        HMiKKTSetHostMirror(HKKT, 0);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: M stays on the device (m = %d, diagonal channel)\n", HKKT->nRow);
     }
+    else if (pv->n_foreign > 0)
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: the host copy of M is kept: %d cone(s) of this operator accumulate on the host\n",
+                pv->n_foreign);
+    else fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: the host copy of M is kept: the operator has no engine cone\n");
+}
+
+hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones) {
+    if (ensure_ctx() || !kkt_cones_combine(nCones, cones)) return HDSDP_RETCODE_FAILED;
+    const HdmKktSwitches sw = hdm_kkt_switches();
+    MiKKTPriv *pv = priv_of(HKKT);
+    hdsdp_retcode rc = kkt_init_host_fields(HKKT, nRow, nCones, cones);
+    if (rc != HDSDP_RETCODE_OK) return rc;
+    KktPattern pat;
+    HKKT->isKKTSparse = kkt_collect_pattern(HKKT, sw, pat) ? 1 : 0;
+    rc = HKKT->isKKTSparse ? kkt_init_sparse_storage(HKKT, pv, sw, pat) : kkt_init_dense_storage(HKKT);
+    if (rc != HDSDP_RETCODE_OK) return rc;
+    rc = kkt_init_device_common(HKKT, pv);
+    if (rc != HDSDP_RETCODE_OK) return rc;
+    if (sw.device_m) kkt_apply_device_m(HKKT, pv);
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
 }
@@ -383,19 +377,18 @@ static void kkt_point_diag(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
     if (!HKKT->kktDiag || !HKKT->kktMatElem || !pv->chan.get()) return;
     const int m = HKKT->nRow;
     for (int i = 0; i < m; ++i)
-        HKKT->kktDiag[i] = !pv->mirror ? &pv->chan.get()[i] :
+        HKKT->kktDiag[i] = !pv->st.mirror() ? &pv->chan.get()[i] :
                            HKKT->isKKTSparse ? &HKKT->kktMatElem[HKKT->kktMatBeg[i]] : &HKKT->kktMatElem[i + (size_t) i * m];
 }
 
-// one pass over diag(M) on the device (mi_diag_pass_kernel): fold = upload the channel and add it (once per build), add = add
-// v; mn (optional) receives the minimum of the diagonal after the pass's additions
+// one pass over diag(M) on the device (mi_diag_pass_kernel): fold = upload the channel and add it (once per build: the caller
+// tells the state), add = add v; mn (optional) receives the minimum of the diagonal after the pass's additions
 static hdsdp_retcode kkt_diag_pass(hdsdp_kkt *HKKT, MiKKTPriv *pv, bool fold, bool add, double v, double *mn) {
     const int m = HKKT->nRow;
     if (fold) {
         if (hipMemcpyAsync(pv->chan_dev.get(), pv->chan.get(), sizeof(double) * (size_t) m, hipMemcpyHostToDevice, g.stream) != hipSuccess)
             return HDSDP_RETCODE_FAILED;
         pv->bytes_h2d += (int64_t) sizeof(double) * m;
-        pv->chan_folded = true;
     }
     hipLaunchKernelGGL(mi_diag_pass_kernel, dim3(1), dim3(1024), 0, g.stream, kkt_view(HKKT), m, fold ? pv->chan_dev.get() : nullptr,
                        add ? 1 : 0, v, mn ? pv->chan_dev.get() + m : nullptr);
@@ -404,6 +397,31 @@ static hdsdp_retcode kkt_diag_pass(hdsdp_kkt *HKKT, MiKKTPriv *pv, bool fold, bo
                hipStreamSynchronize(g.stream) != hipSuccess))
         return HDSDP_RETCODE_FAILED;
     return HDSDP_RETCODE_OK;
+}
+
+static HdmMatView dense_view(double *base, long ld) { HdmMatView v; v.base = base; v.ld = ld; return v; }
+
+// The value buffer is scattered into `view` at (rows[q], cols[q]); with `hostVals`, the host CSC's values go up into it first
+// (nnz doubles).  Without, it holds them already.
+static hdsdp_retcode kkt_csc_scatter(MiKKTPriv *pv, const double *hostVals, HdmMatView view, const int *rows, const int *cols) {
+    if (pv->nnz <= 0) return HDSDP_RETCODE_OK;
+    if (hostVals && hipMemcpyAsync(pv->sp_vals.get(), hostVals, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
+        return HDSDP_RETCODE_FAILED;
+    hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, view, rows, cols, pv->nnz,
+                       pv->sp_vals.get());
+    return HDSDP_RETCODE_OK;
+}
+// the pattern's entries of `view` into the value buffer (an engine cone only writes inside the pattern it declared)
+static void kkt_csc_gather(MiKKTPriv *pv, HdmMatView view) {
+    if (pv->nnz > 0)
+        hipLaunchKernelGGL(mi_csc_gather_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, view, pv->sp_rows.get(),
+                           pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
+}
+
+// a build starts: host cones add their diagonal terms into an empty channel (a corrector build touches neither M nor the channel)
+static void kkt_channel_start(hdsdp_kkt *HKKT, MiKKTPriv *pv, int typeKKT) {
+    if (typeKKT != KKT_TYPE_CORRECTOR) memset(pv->chan.get(), 0, sizeof(double) * (size_t) HKKT->nRow);
+    pv->st.build_started(typeKKT == KKT_TYPE_CORRECTOR);
 }
 
 static hdsdp_retcode kkt_clean(hdsdp_kkt *HKKT, int typeKKT) {  // hdsdp_schur.c:141-165
@@ -426,10 +444,9 @@ static hdsdp_retcode kkt_clean(hdsdp_kkt *HKKT, int typeKKT) {  // hdsdp_schur.c
         // (dense host matrix: CPU cones add into it, so it starts from zero -- but with engine cones only, kkt_pull's copy
         // of the whole m x m device matrix replaces every entry, and 8 m^2 bytes of host memset per call are saved: 4 ms at
         // m = 2000, twice per iteration of the reference's driver)
-        else if (pv->mirror && !(pv->n_foreign == 0 && pv->n_engine > 0)) memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) m * m);
-        memset(pv->chan.get(), 0, sizeof(double) * (size_t) m);       // (the diagonal channel: host cones add into it with the mirror off)
-        pv->chan_folded = false;
+        else if (pv->st.mirror() && !(pv->n_foreign == 0 && pv->n_engine > 0)) memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) m * m);
     }
+    kkt_channel_start(HKKT, pv, typeKKT);
     return HDSDP_RETCODE_OK;
 }
 
@@ -445,7 +462,7 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
     // only foreign cones there is nothing to bring back, and in the mixed case the device part is added to the host part.
     bool add_M = false;
     size_t mcount = 0;     // entries of the host matrix that came back through Mtmp
-    if (typeKKT != KKT_TYPE_CORRECTOR && pv->mirror && pv->n_engine > 0) {
+    if (typeKKT != KKT_TYPE_CORRECTOR && pv->st.mirror() && pv->n_engine > 0) {
         long ld = 0;
         double *Mdev = kkt_Mdev(HKKT, &ld);
         double *dst = HKKT->kktMatElem;
@@ -457,13 +474,9 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
             add_M = true;
         }
         if (HKKT->isKKTSparse) {
-            // the pattern's entries of the dense device matrix (an engine cone only writes inside the pattern it declared)
-            if (pv->nnz > 0) {
-                hipLaunchKernelGGL(mi_csc_gather_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, kkt_view(HKKT),
-                                   pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
-                if (hipMemcpyAsync(dst, pv->sp_vals.get(), sizeof(double) * (size_t) pv->nnz, hipMemcpyDeviceToHost, g.stream) != hipSuccess)
-                    return HDSDP_RETCODE_FAILED;
-            }
+            kkt_csc_gather(pv, kkt_view(HKKT));
+            if (pv->nnz > 0 && hipMemcpyAsync(dst, pv->sp_vals.get(), sizeof(double) * (size_t) pv->nnz, hipMemcpyDeviceToHost, g.stream) != hipSuccess)
+                return HDSDP_RETCODE_FAILED;
         } else if (hipMemcpy2DAsync(dst, sizeof(double) * m, Mdev, sizeof(double) * ld, sizeof(double) * m, m,
                                     hipMemcpyDeviceToHost, g.stream) != hipSuccess)
             return HDSDP_RETCODE_FAILED;
@@ -486,7 +499,7 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
         HKKT->dCSinvCSinv += h[3 * (size_t) m + 2];
         HKKT->dCSinvRdSinv += h[3 * (size_t) m + 3];
     }
-    pv->Mdev_valid = (typeKKT != KKT_TYPE_CORRECTOR) ? true : pv->Mdev_valid;
+    pv->st.build_finished(typeKKT == KKT_TYPE_CORRECTOR);
     return HDSDP_RETCODE_OK;
 }
 
@@ -537,91 +550,64 @@ void HKKTExport(hdsdp_kkt *HKKT, double *dKKTASinvVec, double *dKKTASinvRdSinvVe
     if (dTraceSinv) *dTraceSinv = HKKT->dTraceSinv;
 }
 
-static HdmMatView dense_view(double *base, long ld) { HdmMatView v; v.base = base; v.ld = ld; return v; }
+// the plan's staging step (kkt_store.h: HdmKktStage)
+static hdsdp_retcode kkt_stage(hdsdp_kkt *HKKT, MiKKTPriv *pv, MiLin *l, HdmKktStage stage) {
+    switch (stage) {
+    case HDM_KKT_STAGE_NONE: break;
+    case HDM_KKT_STAGE_FOLD: return kkt_diag_pass(HKKT, pv, true, false, 0.0, nullptr);
+    case HDM_KKT_STAGE_CSC_TO_FACTOR:
+        RC(l->bsp->zero_L(g.stream));
+        return kkt_csc_scatter(pv, HKKT->kktMatElem, l->bsp->view_L(), pv->sp_rows.get(), pv->sp_cols.get());
+    case HDM_KKT_STAGE_CSC_TO_M:
+        if (hipMemsetAsync(l->Mdev.get(), 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+        return kkt_csc_scatter(pv, HKKT->kktMatElem, dense_view(l->Mdev.get(), l->ch.npad), pv->sp_rows.get(), pv->sp_cols.get());
+    }
+    return HDSDP_RETCODE_OK;
+}
+// the plan's load step (kkt_store.h: HdmKktLoad)
+static hdsdp_retcode kkt_load(hdsdp_kkt *HKKT, MiKKTPriv *pv, MiLin *l, const HdmKktLoadPlan &plan) {
+    switch (plan.load) {
+    case HDM_KKT_LOAD_STAGED: case HDM_KKT_LOAD_PIVOTED: break;
+    case HDM_KKT_LOAD_TILES: RC(l->bsp->load_M(g.stream)); break;
+    case HDM_KKT_LOAD_HOST: RC(l->ch.load_host(HKKT->kktMatElem, HKKT->nRow, g.stream)); break;
+    case HDM_KKT_LOAD_DEVICE: RC(l->ch.load_device(l->Mdev.get(), l->ch.npad, g.stream)); break;
+    case HDM_KKT_LOAD_PERMUTED:
+        if (plan.gather) kkt_csc_gather(pv, dense_view(l->Mdev.get(), l->ch.npad));
+        if (hipMemsetAsync(l->ch.L.get(), 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+        RC(kkt_csc_scatter(pv, nullptr, dense_view(l->ch.L.get(), l->ch.npad), pv->sp_prow.get(), pv->sp_pcol.get()));
+        RC(l->ch.finish_load(g.stream));
+        break;
+    }
+    return HDSDP_RETCODE_OK;
+}
 
 hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
     StatScope stat_(ST_FACTORIZE, __func__);
-    // hdsdp_schur.c:328-336.  With the host mirror on, the host matrix is authoritative (the driver and
-    // the CPU cones may have touched it through kktDiag / kktMatElem); otherwise factor the device copy.
+    // hdsdp_schur.c:328-336.  Where M comes from and how it reaches the factor is hdm_kkt_load_plan's rule (kkt_store.h, with
+    // the table); staged, the state records the source, which the pivoted solver reads (lin_factor_indef).
     MiKKTPriv *pv = priv_of(HKKT);
     MiLin *l = (MiLin *) HKKT->kktM->chol;
     HKKT->kktM->nFactorizes += 1;
-    int info = 0;
-    if (l->bsp) {
-        // tile form: the factor store is filled from the host CSC (host mirror on: the driver and the CPU cones may have touched
-        // it) or from the accumulation store, then factored level by level (bsparse.hip)
-        if (pv->mirror) {
-            if (l->bsp->zero_L(g.stream)) return HDSDP_RETCODE_FAILED;
-            pv->bytes_h2d += (int64_t) sizeof(double) * pv->nnz;
-            if (pv->nnz > 0) {
-                if (hipMemcpyAsync(pv->sp_vals.get(), HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
-                    return HDSDP_RETCODE_FAILED;
-                hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream, l->bsp->view_L(),
-                                   pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
-            }
-        } else {
-            // (the diagonal channel goes into the accumulation store first: the factor store is a copy of it)
-            if (!pv->Mdev_valid || (!pv->chan_folded && kkt_diag_pass(HKKT, pv, true, false, 0.0, nullptr) != HDSDP_RETCODE_OK) ||
-                l->bsp->load_M(g.stream)) return HDSDP_RETCODE_FAILED;
-        }
-        // LDL' like the reference's sparse direct solver (linalg/hdsdp_linsolver.c:596-626 over external/qdldl.c): an indefinite
-        // matrix factors and the solves go on with the signed factor; only a pivot that is exactly zero is a failure
-        int nneg = 0;
-        if (l->bsp->factor(g.stream, &info, &nneg)) return HDSDP_RETCODE_FAILED;
-        if (info != 0) {
-            fprintf(stderr, "[hdsdp_mi355x] HKKTFactorize: sparse Schur matrix (tile form): zero pivot at row %d of the reordered matrix\n", info);
-            return HDSDP_RETCODE_FAILED;
-        }
-        return HDSDP_RETCODE_OK;
+    const HdmKktLoadPlan plan = hdm_kkt_load_plan(pv->st);
+    if (!plan.ok) return HDSDP_RETCODE_FAILED;
+    if (kkt_stage(HKKT, pv, l, plan.stage) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
+    pv->bytes_h2d += plan.matrix_bytes(HKKT->nRow, pv->nnz);
+    pv->st.commit(plan, HKKT->kktMatElem, HKKT->nRow, l->Mdev.get(), l->ch.npad);
+    if (plan.load == HDM_KKT_LOAD_PIVOTED) return lin_factor_indef(l);     // switched earlier: stays switched (hdsdp_linsolver.c:1838)
+    if (kkt_load(HKKT, pv, l, plan) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
+    // the tile form factors LDL' like the reference's sparse direct solver (linalg/hdsdp_linsolver.c:596-626 over external/qdldl.c):
+    // an indefinite matrix factors and the solves go on with the signed factor; only a pivot that is exactly zero is a failure
+    int info = 0, nneg = 0;
+    if (l->bsp ? l->bsp->factor(g.stream, &info, &nneg) : l->ch.factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
+    if (info == 0) return HDSDP_RETCODE_OK;
+    if (plan.on_pivot == HDM_KKT_PIVOT_FAIL) {
+        fprintf(stderr, "[hdsdp_mi355x] HKKTFactorize: sparse Schur matrix (tile form): zero pivot at row %d of the reordered matrix\n", info);
+        return HDSDP_RETCODE_FAILED;
     }
-    if (pv->mirror && HKKT->isKKTSparse) {
-        // the host CSC is authoritative: its values go up (nnz doubles) and are scattered over the zeroed dense device
-        // matrix, which is then factored like the dense operator's
-        if (hipMemsetAsync(l->Mdev.get(), 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
-        pv->bytes_h2d += (int64_t) sizeof(double) * pv->nnz;
-        if (pv->nnz > 0) {
-            if (hipMemcpyAsync(pv->sp_vals.get(), HKKT->kktMatElem, sizeof(double) * (size_t) pv->nnz, hipMemcpyHostToDevice, g.stream) != hipSuccess)
-                return HDSDP_RETCODE_FAILED;
-            hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream,
-                               dense_view(l->Mdev.get(), l->ch.npad), pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
-        }
-        pv->Mdev_valid = true;
-        l->srcHost = nullptr; l->srcDev = l->Mdev.get(); l->srcLd = l->ch.npad;
-    } else if (pv->mirror) {
-        l->srcHost = HKKT->kktMatElem; l->srcDev = nullptr; l->srcLd = HKKT->nRow;
-        pv->bytes_h2d += (int64_t) sizeof(double) * HKKT->nRow * HKKT->nRow;    // (load_host, or the pivoted solver's load)
-    } else {
-        // device M plus the diagonal channel: added in place, so the Cholesky, the permuted load and the pivoted solver
-        // (lin_factor_indef reads srcDev) all see the same matrix
-        if (!pv->Mdev_valid) return HDSDP_RETCODE_FAILED;
-        if (!pv->chan_folded && kkt_diag_pass(HKKT, pv, true, false, 0.0, nullptr) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
-        l->srcHost = nullptr; l->srcDev = l->Mdev.get(); l->srcLd = l->ch.npad;
-    }
-    if (l->indef) return lin_factor_indef(l);     // switched earlier: stays switched (hdsdp_linsolver.c:1838)
-    if (pv->mirror && !HKKT->isKKTSparse) {
-        if (l->ch.load_host(HKKT->kktMatElem, HKKT->nRow, g.stream)) return HDSDP_RETCODE_FAILED;
-    } else if (HKKT->isKKTSparse && !l->perm.empty()) {
-        // the factor object holds P M P': the pattern's entries (already in sp_vals when they came up from the host CSC,
-        // gathered from the device matrix otherwise) go to their permuted places in a zeroed image
-        if (!pv->mirror && pv->nnz > 0)
-            hipLaunchKernelGGL(mi_csc_gather_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream,
-                               dense_view(l->Mdev.get(), l->ch.npad), pv->sp_rows.get(), pv->sp_cols.get(), pv->nnz, pv->sp_vals.get());
-        if (hipMemsetAsync(l->ch.L.get(), 0, sizeof(double) * (size_t) l->ch.npad * l->ch.npad, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
-        if (pv->nnz > 0)
-            hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((pv->nnz + 255) / 256)), dim3(256), 0, g.stream,
-                               dense_view(l->ch.L.get(), l->ch.npad), pv->sp_prow.get(), pv->sp_pcol.get(), pv->nnz, pv->sp_vals.get());
-        if (l->ch.finish_load(g.stream)) return HDSDP_RETCODE_FAILED;
-    } else {
-        if (l->ch.load_device(l->Mdev.get(), l->ch.npad, g.stream)) return HDSDP_RETCODE_FAILED;
-    }
-    if (l->ch.factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
-    if (info != 0) {
-        // hdsdp_linsolver.c:2034-2039: the Schur system falls back to the symmetric-indefinite solver
-        fprintf(stderr, "[hdsdp_mi355x] HKKTFactorize: Schur matrix is not positive definite (pivot %d). "
-                        "Switch to the pivoted (LDL-equivalent) solver.\n", info);
-        return lin_switch_indefinite(HKKT->kktM);
-    }
-    return HDSDP_RETCODE_OK;
+    // hdsdp_linsolver.c:2034-2039: the Schur system falls back to the symmetric-indefinite solver
+    fprintf(stderr, "[hdsdp_mi355x] HKKTFactorize: Schur matrix is not positive definite (pivot %d). "
+                    "Switch to the pivoted (LDL-equivalent) solver.\n", info);
+    return lin_switch_indefinite(HKKT->kktM);
 }
 
 hdsdp_retcode HKKTSolve(hdsdp_kkt *HKKT, double *dRhsVec, double *dLhsVec) {
@@ -631,13 +617,15 @@ hdsdp_retcode HKKTSolve(hdsdp_kkt *HKKT, double *dRhsVec, double *dLhsVec) {
 
 void HKKTRegularize(hdsdp_kkt *HKKT, double dKKTReg) {  // hdsdp_schur.c:348-373
     MiKKTPriv *pv = priv_of(HKKT);
-    if (!pv->mirror) {
+    if (!pv->st.mirror()) {
         // device-resident M (HMiKKTSetHostMirror(.., 0)): the same rule on the device matrix's diagonal plus the channel.  The
         // first call after a build adds the channel in place; every call then adds its regularisation on top, so the entries
         // are ((M_ii + channel_i) + reg1) + reg2 ..., the host mirror's order.  No part of M crosses the bus.
-        if (!pv->Mdev_valid) return;
+        if (!pv->st.m_valid()) return;
         double mn = INFINITY;
-        if (kkt_diag_pass(HKKT, pv, !pv->chan_folded, false, 0.0, &mn) != HDSDP_RETCODE_OK) return;
+        const bool fold = !pv->st.chan_folded();
+        if (kkt_diag_pass(HKKT, pv, fold, false, 0.0, &mn) != HDSDP_RETCODE_OK) return;
+        if (fold) pv->st.channel_folded();
         const double reg = std::min(dKKTReg * mn, 1e-05);
         if (reg < 1e-14) return;
         (void) kkt_diag_pass(HKKT, pv, false, true, reg, nullptr);
@@ -678,13 +666,13 @@ void HMiKKTSetHostMirror(hdsdp_kkt *HKKT, int mirrorM) {
                 pv->n_foreign);
         return;
     }
-    pv->mirror = mirrorM;
+    pv->st.mirror_switched(mirrorM != 0);
     kkt_point_diag(HKKT, pv);
 }
 int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
     MiKKTPriv *pv = priv_of(HKKT);
     if (!HKKT->kktDiag || !pv->chan.get()) return -1;
-    return pv->mirror ? 0 : 1;
+    return pv->st.mirror() ? 0 : 1;
 }
 void HMiKKTGetMatrixTraffic(hdsdp_kkt *HKKT, int64_t *bytesToHost, int64_t *bytesToDevice) {
     const MiKKTPriv *pv = priv_of(HKKT);
@@ -752,7 +740,7 @@ hdsdp_retcode HMiKKTGetRows(hdsdp_kkt *HKKT, int nRows, const int *rows, double 
     // full symmetric rows of the device copy of M (lower triangle stored: dense matrix or tile store)
     MiKKTPriv *pv = priv_of(HKKT);
     const int m = HKKT->nRow;
-    if (!pv->Mdev_valid) return HDSDP_RETCODE_FAILED;
+    if (!pv->st.m_valid()) return HDSDP_RETCODE_FAILED;
     HdmBuf<double> tmp;
     HIP_RC(tmp.alloc((size_t) std::max(1, m)));
     hdsdp_retcode rc = HDSDP_RETCODE_OK;

@@ -1,6 +1,8 @@
 // engine_linsys.h -- the linear-system objects behind HFpLinsys* (dense / CSC-in dual matrices, the Schur system with its pivoted way out)
 // Implementation header of engine.hip: included exactly once, there, in this order (the pieces share the anonymous namespace
 // and the engine's thread-local context `g`); split out of a 3 300-line file in round 3, nothing else changed.
+// Whether a system is switched to the pivoted solver and where its last factorised matrix came from is HdmKktState's
+// (kkt_store.h, with the table of how the Schur operator's matrix reaches the factor): lin_factor_indef reads the source from it.
 // =============================================================================================
 // linear-system objects
 // =============================================================================================
@@ -16,16 +18,16 @@ struct MiLin {
     // sparse Schur operator in tile form (bsparse.h): the matrix and its factor are 128 x 128 tiles inside the block pattern of
     // the Cholesky factor; no dense m x m array exists anywhere (ch stays uninitialised, Mdev null)
     std::unique_ptr<HdmBsp> bsp;
-    // symmetric-indefinite fallback (HFpLinsysSwitchToIndefinite, hdsdp_linsolver.c:1827-1857): once switched, every
-    // later factorisation goes through the pivoted solver, like the reference's replaced vtable
+    // symmetric-indefinite fallback (HFpLinsysSwitchToIndefinite, hdsdp_linsolver.c:1827-1857): once switched (st->indef()),
+    // every later factorisation goes through the pivoted solver, like the reference's replaced vtable
     std::unique_ptr<HdmLu> lu;
-    bool indef = false;
+    // whether the solver is switched and where the last factorised matrix came from (kkt_store.h).  A Schur operator's linear
+    // system shares the operator's state (HKKTInit points st at it); any other has its own: a dense host matrix.
+    HdmKktState own, *st = &own;
     // sparse Schur operator: the factor object holds P M P' (perm[old] = new, a bandwidth-reducing order of the pattern);
     // right-hand sides go in permuted and solutions come back in the caller's order.  Empty = identity.
     std::vector<int> perm;
     std::vector<double> pbuf;
-    const double *srcHost = nullptr, *srcDev = nullptr;   // not owned: where the last factorised matrix came from (lower valid)
-    long srcLd = 0;
     // HDSDP_LINSYS_SPARSE_DIRECT (the reference's QDLDL backend for a sparse dual matrix, hdsdp_linsolver.c:509-809):
     // the matrix arrives as a lower-triangular CSC and is factored densely on the device.  Result-equivalent for every
     // caller: QDLDL's forward / backward solves carry the D^-1/2 scaling (:669-721), i.e. they ARE the Cholesky factor's,
@@ -80,8 +82,8 @@ hdsdp_retcode lin_factor_indef(MiLin *l) {
         l->lu.reset(new HdmLu());
         if (l->lu->init(l->n)) { l->lu.reset(); return HDSDP_RETCODE_MEMORY; }
     }
-    if (l->srcDev) RC(l->lu->load_device_lower(l->srcDev, l->srcLd, g.stream));
-    else if (l->srcHost) RC(l->lu->load_host_lower(l->srcHost, l->srcLd, g.stream));
+    if (l->st->src_dev()) RC(l->lu->load_device_lower(l->st->src_dev(), l->st->src_ld(), g.stream));
+    else if (l->st->src_host()) RC(l->lu->load_host_lower(l->st->src_host(), l->st->src_ld(), g.stream));
     else return HDSDP_RETCODE_FAILED;
     int info = 0;
     RC(l->lu->factor(g.stream, &info));
@@ -95,8 +97,8 @@ hdsdp_retcode lin_numeric(void *chol, int *colMatBeg, int *colMatIdx, double *co
         colMatElem = const_cast<double *>(lin_densify(l, colMatBeg, colMatIdx, colMatElem));
         if (!colMatElem) return HDSDP_RETCODE_FAILED;
     }
-    l->srcHost = colMatElem; l->srcDev = nullptr; l->srcLd = l->n;
-    if (l->indef) return lin_factor_indef(l);
+    l->st->host_matrix_given(colMatElem, l->n);
+    if (l->st->indef()) return lin_factor_indef(l);
     int info = 0;
     if (lin_factor_host(l, colMatElem, &info) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
     return info == 0 ? HDSDP_RETCODE_OK : HDSDP_RETCODE_FAILED;
@@ -107,7 +109,7 @@ hdsdp_retcode lin_switch_indefinite(hdsdp_linsys_fp *HLin) {
     MiLin *l = (MiLin *) HLin->chol;
     if (l->bsp) return HDSDP_RETCODE_OK;      // the tile form's factorisation is an LDL' already (bsparse.h): nothing to switch to
     HLin->LinType = HDSDP_LINSYS_DENSE_INDEFINITE;
-    l->indef = true;
+    l->st->switched_to_pivoted();
     return lin_factor_indef(l);
 }
 // linalg/hdsdp_linsolver.c:1112-1144 (info > 0 => "not PSD" is a value, not an error)
@@ -118,7 +120,7 @@ hdsdp_retcode lin_psdcheck(void *chol, int *colMatBeg, int *colMatIdx, double *c
         colMatElem = const_cast<double *>(lin_densify(l, colMatBeg, colMatIdx, colMatElem));
         if (!colMatElem) return HDSDP_RETCODE_FAILED;
     }
-    if (l->indef) return HDSDP_RETCODE_FAILED;   // :1729-1739, no PSD check on the pivoted factor
+    if (l->st->indef()) return HDSDP_RETCODE_FAILED;   // :1729-1739, no PSD check on the pivoted factor
     int info = 0;
     if (lin_factor_host(l, colMatElem, &info) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
     *isPsd = (info == 0) ? 1 : 0;
@@ -127,7 +129,7 @@ hdsdp_retcode lin_psdcheck(void *chol, int *colMatBeg, int *colMatIdx, double *c
 // :1146-1196 dtrsm with L / L^T ; solVec == NULL => in place
 void lin_fsolve(void *chol, int nRhs, double *rhs, double *sol) {
     MiLin *l = (MiLin *) chol;
-    if (l->indef || l->bsp) return;                        // :1741-1759, no half solves with the pivoted factor
+    if (l->st->indef() || l->bsp) return;                        // :1741-1759, no half solves with the pivoted factor
     // the slot returns void (hdsdp_linsolver.h:22): a device failure can only be reported, and poisons the output so that
     // the caller's next NaN check (e.g. HFpLinsysSolve, :2085-2110) sees it
     if (l->ch.solve_host(rhs, sol ? sol : rhs, nRhs, 1, g.stream)) {
@@ -137,7 +139,7 @@ void lin_fsolve(void *chol, int nRhs, double *rhs, double *sol) {
 }
 void lin_bsolve(void *chol, int nRhs, double *rhs, double *sol) {
     MiLin *l = (MiLin *) chol;
-    if (l->indef || l->bsp) return;
+    if (l->st->indef() || l->bsp) return;
     if (l->ch.solve_host(rhs, sol ? sol : rhs, nRhs, 2, g.stream)) {
         fprintf(stderr, "[hdsdp_mi355x] backward substitution failed on the device\n");
         (sol ? sol : rhs)[0] = NAN;
@@ -146,7 +148,7 @@ void lin_bsolve(void *chol, int nRhs, double *rhs, double *sol) {
 // :1198-1225 dpotrs
 hdsdp_retcode lin_solve(void *chol, int nRhs, double *rhs, double *sol) {
     MiLin *l = (MiLin *) chol;
-    if (l->indef) {                              // :1761-1780 dsytrs
+    if (l->st->indef()) {                              // :1761-1780 dsytrs
         if (!l->lu || !l->lu->factored) return HDSDP_RETCODE_FAILED;
         RC(l->lu->solve_host(rhs, sol ? sol : rhs, nRhs, g.stream));
         return HDSDP_RETCODE_OK;
@@ -174,14 +176,14 @@ hdsdp_retcode lin_solve(void *chol, int nRhs, double *rhs, double *sol) {
 // :1227-1236
 hdsdp_retcode lin_getdiag(void *chol, double *diag) {
     MiLin *l = (MiLin *) chol;
-    if (l->indef || l->bsp) return HDSDP_RETCODE_FAILED;   // :1782-1788
+    if (l->st->indef() || l->bsp) return HDSDP_RETCODE_FAILED;   // :1782-1788
     RC(l->ch.get_diag(diag, g.stream));
     return HDSDP_RETCODE_OK;
 }
 // :1238-1260 dpotri + HUtilMatSymmetrize: full symmetric inverse into dFullMatrix (n x n)
 void lin_invert(void *chol, double *dFull, double *) {
     MiLin *l = (MiLin *) chol;
-    if (l->indef || l->bsp) return;              // :1790-1797
+    if (l->st->indef() || l->bsp) return;              // :1790-1797
     HdmChol &c = l->ch;
     if (l->work.reserve((size_t) c.npad * c.npad) != hipSuccess) return;
     if (c.inverse_full(l->work.get(), c.npad, g.stream)) return;
