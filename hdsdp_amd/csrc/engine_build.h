@@ -2,18 +2,6 @@
 // Implementation header of engine.hip: included exactly once, there, in this order (the pieces share the anonymous namespace
 // and the engine's thread-local context `g`); split out of a 3 300-line file in round 3, nothing else changed.
 // --- the GPU Schur builder ---------------------------------------------------------------------
-// share of step 2's work that falls into the tile columns of `mask` (tile (tm, tn), tm >= tn, runs tn + 1 K blocks)
-double cong2_mask_share(int NT, unsigned long long mask) {
-    if (!mask || NT > 64) return 1.0;
-    double all = 0.0, sel = 0.0;
-    for (int tn = 0; tn < NT; ++tn) {
-        const double w = (double) (NT - tn) * (tn + 1);
-        all += w;
-        if ((mask >> tn) & 1ULL) sel += w;
-    }
-    return all > 0.0 ? sel / all : 1.0;
-}
-
 // phase 0: both steps; 1: step 1 only; 2: step 2 only (count <= Bc, T still holds step 1's output), optionally only the
 // output tiles of the tile columns in `colmask` -- the multi-GPU build runs step 2 by packed-index range so that the
 // finished ranges can leave for the other ranks while the rest is still being computed
@@ -52,7 +40,7 @@ int congruence_rows(MiCone *c, HdmChol &ch, const double *Asrc, long astride, lo
         k2.blk_row_stride = c->Lr; k2.blk_row0 = row0 + b0; k2.nblk = c->nblk; k2.role = HDM_ROLE_CONG2;
         k2.tile_col_mask = colmask;
         k2.spanA = t_span; k2.spanB = linv_span; k2.spanA2 = linv_span; k2.spanB2 = t_span;
-        k2.flops = (double) nb * n3 * 2.0 / 3.0 * cong2_mask_share((c->n16 + HDM_TILE - 1) / HDM_TILE, colmask);
+        k2.flops = (double) nb * n3 * 2.0 / 3.0 * hdm_cong2_mask_share(hdm_ntiles(c->n16), colmask);
         if (hdm_launch_gemm(k2, g.stream)) return 1;
     }
     return 0;
@@ -124,16 +112,12 @@ void piece_range(const MiCone *c, int k, int P, long *lo, long *hi) {
     *hi = (k == P - 1) ? c->npb_loc : std::min<long>(c->npb_loc, (long) (k + 1) * zper * chunk);
 }
 // Tile columns of congruence step 2 whose output piece k needs.  P-block q belongs to the 16 x 16 sub-block q / 16 of the
-// blocked lower triangle, sub-blocks are numbered column by column (column bj starts at bj*nblk - bj(bj-1)/2), and tile
+// blocked lower triangle, sub-blocks are numbered column by column (gemm_geom.h: hdm_blk_col_of), and tile
 // column tn produces the sub-block columns 8 tn .. 8 tn + 7: a range of p-blocks is a range of tile columns.
 unsigned long long piece_tile_cols(const MiCone *c, int k, int P) {
     long lo, hi;
     piece_range(c, k, P, &lo, &hi);
-    auto col_of = [&](long sub) {
-        int bj = 0;
-        while (bj + 1 < c->nblk && (long) (bj + 1) * c->nblk - (long) (bj + 1) * bj / 2 <= sub) ++bj;
-        return bj;
-    };
+    auto col_of = [&](long sub) { return hdm_blk_col_of(sub, c->nblk); };
     unsigned long long mask = 0;
     for (int d = 0; d < c->world; ++d) {
         const long g0 = (long) d * c->npb_loc + lo, g1 = std::min<long>(c->npb, (long) d * c->npb_loc + hi);
@@ -222,19 +206,15 @@ int signed_correction(MiCone *c) {
     std::vector<double> sg((size_t) c->n16);
     HIP_RC(hipMemcpyAsync(sg.data(), c->gram_sig, sizeof(double) * (size_t) c->n16, hipMemcpyDeviceToHost, g.stream));
     HIP_RC(hipStreamSynchronize(g.stream));
-    // p-block q: sub-block q >> 4 of the blocked lower triangle (numbered column by column, column bj starting at
-    // bj nblk - bj (bj - 1) / 2), matrix column bj 16 + (q & 15); its packed columns q 16 + r are the rows bi 16 + r
+    // p-block q holds matrix column pb.col; its packed columns q 16 + r are the rows pb.bi 16 + r (gemm_geom.h: hdm_pblock_decode)
     const long pb0 = (long) c->rank * c->npb_loc, pb1 = std::min(c->npb, pb0 + c->npb_loc);
-    auto start = [&](long bj) { return bj * c->nblk - bj * (bj - 1) / 2; };
     std::vector<int> neg, pos;
-    long bj = 0;
     for (long q = pb0; q < pb1; ++q) {
-        const long sub = q >> 4;
-        while (bj + 1 < c->nblk && start(bj + 1) <= sub) ++bj;
-        const long bi = bj + (sub - start(bj)), col = bj * 16 + (q & 15);
+        const HdmPBlock pb = hdm_pblock_decode(q, c->nblk);
+        const long col = pb.col;
         if (col >= c->n) continue;
         for (int r = 0; r < 16; ++r) {
-            const long row = bi * 16 + r;
+            const long row = (long) pb.bi * 16 + r;
             if (row >= c->n) break;
             ((sg[row] * sg[col] < 0.0) ? neg : pos).push_back((int) (q * 16 + r));
         }
@@ -605,9 +585,9 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
     // crosses the links while the later ranges are still being computed (at two ranks the all-to-all moves 8 GB per
     // rank over a single link, more than the Gram product alone can hide).  Needs the piecewise exchange hooks, all
     // owned rows in one launch group and at most 64 tile columns.  HDSDP_MI355X_STAGED_A2A=0: drain, then exchange.
-    const int NT = (c->n16 + HDM_TILE - 1) / HDM_TILE;
+    const int NT = hdm_ntiles(c->n16);
     int P = (c->world > 1) ? exchange_pieces(c) : 1;
-    bool staged = c->world > 1 && P > 1 && P <= 64 && c->mloc <= c->Bc && NT <= 64;
+    bool staged = c->world > 1 && P > 1 && P <= 64 && c->mloc <= c->Bc && hdm_colmask_honoured(NT);
     if (const char *e = getenv("HDSDP_MI355X_STAGED_A2A")) staged = staged && atoi(e) != 0;
     c->last_pieces = P; c->last_staged = 0;
     if (c->streamed) {

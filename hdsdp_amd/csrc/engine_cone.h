@@ -38,7 +38,7 @@ struct MiCone {
     HdmBuf<double> Avec;       // n16 x mloc16 rank-one factors (R1 path)
     HdmBuf<double> sgn;        // mloc signs (R1 path)
     int mloc16 = 0;
-    long astride = 0;          // elements per constraint matrix in Afull (skyline storage of the A_L form, hdm_common.h)
+    long astride = 0;          // elements per constraint matrix in Afull (skyline storage of the A_L form, gemm_geom.h)
     HdmBuf<int> sp_rp, sp_ti, sp_tj;   // sparse path: triplets of the owned rows
     HdmBuf<double> sp_tv;
     HdmBuf<int> rows_seg;      // world*Lr: segment-ordered Gram row -> global constraint (-1 pad, -2.. aug)

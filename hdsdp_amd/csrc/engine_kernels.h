@@ -58,7 +58,7 @@ __global__ void mi_low_norms_kernel(const double *__restrict__ A, long astride, 
     const double *M = A + (long) blockIdx.x * astride;
     double sa = 0.0, sf = 0.0;
     if (a_l_form) {
-        // A_L form in skyline storage (hdm_common.h): everything that is stored and not zero is an entry on or below the
+        // A_L form in skyline storage (gemm_geom.h): everything that is stored and not zero is an entry on or below the
         // diagonal, so one linear pass over the matrix's storage does it (this loop once walked the n x n index space with
         // a division and the skyline offset per element: 1.0 s for 2000 matrices at n = 2000, now HBM-bound).  Off-diagonal
         // entries count twice; the diagonal is stored halved: |2v| = 2|v| as well, and (2v)^2 = 2v^2 + 2v^2 -- the second

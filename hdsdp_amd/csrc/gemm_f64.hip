@@ -67,40 +67,20 @@ int persist_counters(int **cnt, int *slots) {
     return 0;
 }
 
-// subset: 0 = all tiles; 1 = the full diagonal tiles only (tm == tn with 8 valid sub-tile rows; rows = the M dimension);
-// 2 = all the others
-int get_tiles(int MT, int NT, int klimit, int lower_only, unsigned long long colmask, TileList &out, int subset = 0, int rows = 0) {
+// the tile list of a launch (gemm_geom.h: hdm_tile_list; subset: 0 = all tiles, 1 = the full diagonal tiles only, 2 = all the others)
+int get_tiles(const HdmTileGeom &gm, TileList &out, int subset) {
     int dev = 0;
     HDM_HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_tl_mutex);
-    if (NT > 64) colmask = 0;
-    auto key = std::make_tuple(dev, MT, NT, klimit + 16 * subset + 64 * (subset ? rows : 0), lower_only, colmask);
+    auto key = std::make_tuple(dev, hdm_ntiles(gm.M), hdm_ntiles(gm.N), gm.klimit + 16 * subset + 64 * (subset ? gm.M : 0), gm.lower_only,
+                               hdm_colmask_effective(gm.colmask, hdm_ntiles(gm.N)));
     auto it = g_tl_cache.find(key);
     if (it != g_tl_cache.end()) {
         out = it->second;
         return 0;
     }
-    std::vector<std::pair<long, int2>> v;
-    for (int tm = 0; tm < MT; ++tm)
-        for (int tn = 0; tn < NT; ++tn) {
-            if (lower_only && tm < tn) continue;
-            if (colmask && !((colmask >> tn) & 1ULL)) continue;
-            if (subset) {
-                const bool full_diag = (tm == tn) && (((rows - tm * HDM_TILE + 15) >> 4) >= 8);
-                if ((subset == 1) != full_diag) continue;
-            }
-            long w = 1;
-            if (klimit == HDM_KLIM_BY_M) w = tm + 1;
-            if (klimit == HDM_KLIM_BY_N) w = tn + 1;
-            if (klimit == HDM_KLIM_BAND) { if (tm < tn) continue; w = tm - tn + 1; }
-            v.push_back({w, make_int2(tm, tn)});
-        }
-    // (tiles of equal weight stay in row-major order: a Z-order curve over (tm, tn), meant to let neighbours in the list
-    // share a column panel as well as a row panel in L2, RAISED the Gram kernel's fabric traffic from 391 to 425 GB per
-    // launch and changed no time -- same box, round 2)
-    std::stable_sort(v.begin(), v.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
-    std::vector<int2> h(v.size());
-    for (size_t i = 0; i < v.size(); ++i) h[i] = v[i].second;
+    std::vector<int2> h;
+    for (const HdmTile &t : hdm_tile_list(gm, subset)) h.push_back(make_int2(t.tm, t.tn));
     TileList tl;
     tl.n = (int) h.size();
     // raw on purpose (the tile-list cache has static storage: kept until the process ends, never freed)
@@ -114,56 +94,21 @@ int get_tiles(int MT, int NT, int klimit, int lower_only, unsigned long long col
 
 static int launch_tiles(const HdmGemmArgs &args, int subset, hipStream_t stream);
 
+// what gemm_geom.h needs to know of a launch
+static HdmTileGeom tile_geom(const HdmGemmArgs &a) {
+    return {a.M, a.N, a.K, a.klimit, a.lower_only, a.tile_col_mask, a.role, a.epilogue == HDM_EPI_SLAB, a.batch, a.k_base, a.k_chunk,
+            ((a.role == HDM_ROLE_CONG2 || a.role == HDM_ROLE_GENERIC) && a.A2) ? 2 : 1};
+}
+
 // Flops the MFMA instructions of one launch EXECUTE (2048 per v_mfma_f64_16x16x4_f64), counted on the host from the tile
-// list and the kernel's own stage sequences (gemm_tile.h: hdm_gemm_tile) -- next to HdmGemmArgs.flops, the algorithmic count
-// on valid data.  The difference is granularity: 16 x 16 sub-blocks that straddle a diagonal, the live ranges of the
-// triangular K blocks (stage-level skipping keeps 1280 of a diagonal block's 2048 MFMAs per tile where 1152 would do), the
-// cell-dealt tiles' diagonal blocks run in full, rows past the matrix edge, the zero stage that closes an odd stage count.
-// Held to the counters: SQ_VALU_MFMA_BUSY_CYCLES / 64 of profiles/r05_a_8000_* is this count to 2e-5 for the four kernels.
+// list and the tables the kernel's stage sequences are written from (gemm_geom.h: hdm_tile_mfmas) -- next to
+// HdmGemmArgs.flops, the algorithmic count on valid data.  The difference is granularity: 16 x 16 sub-blocks that straddle a
+// diagonal, the live ranges of the triangular K blocks (stage-level skipping keeps 1280 of a diagonal block's 2048 MFMAs per
+// tile where 1152 would do), the cell-dealt tiles' diagonal blocks run in full, rows past the matrix edge, the zero stage
+// that closes an odd stage count.  Held to the counters: SQ_VALU_MFMA_BUSY_CYCLES / 64 of profiles/r05_a_8000_* is this
+// count to 2e-5 for the four kernels.
 static double issued_mfma_flops(const HdmGemmArgs &a, int subset) {
-    const int MT = (a.M + HDM_TILE - 1) / HDM_TILE, NT = (a.N + HDM_TILE - 1) / HDM_TILE;
-    const unsigned long long colmask = (NT > 64) ? 0ULL : a.tile_col_mask;
-    const int npass = (a.role == HDM_ROLE_CONG2 && a.A2) ? 2 : ((a.role == HDM_ROLE_GENERIC && a.A2) ? 2 : 1);
-    auto pairs = [](long nst) { return nst <= 0 ? 0L : ((nst + 1) / 2) * 2; };
-    double mf = 0.0;   // MFMA instructions of ONE batch entry (SLAB: summed over the splits below)
-    const int nz = (a.epilogue == HDM_EPI_SLAB) ? a.batch : 1;
-    for (int z = 0; z < nz; ++z)
-        for (int tm = 0; tm < MT; ++tm)
-            for (int tn = 0; tn < NT; ++tn) {
-                if (a.lower_only && tm < tn) continue;
-                if (colmask && !((colmask >> tn) & 1ULL)) continue;
-                if (a.klimit == HDM_KLIM_BAND && tm < tn) continue;
-                const int m0 = tm * HDM_TILE, n0 = tn * HDM_TILE;
-                const int rvd = std::min(8, (a.M - m0 + 15) >> 4);
-                if (subset) {
-                    const bool full_diag = (tm == tn) && rvd >= 8;
-                    if ((subset == 1) != full_diag) continue;
-                }
-                long kbeg = 0, kend = a.K;
-                if (a.klimit == HDM_KLIM_BY_M) kend = std::min<long>(a.K, (long) (tm + 1) * HDM_TILE);
-                if (a.klimit == HDM_KLIM_BY_N) kend = std::min<long>(a.K, (long) (tn + 1) * HDM_TILE);
-                if (a.klimit == HDM_KLIM_BAND) { kbeg = (long) tn * HDM_TILE; kend = std::min<long>(a.K, (long) (tm + 1) * HDM_TILE); }
-                if (a.epilogue == HDM_EPI_SLAB) { kbeg = a.k_base + (long) z * a.k_chunk; kend = std::min(kend, kbeg + a.k_chunk); }
-                const long nst = std::max(0L, kend / HDM_BK - kbeg / HDM_BK) * npass;
-                if (a.role == HDM_ROLE_GENERIC) { mf += 256.0 * nst; continue; }
-                const int rvc = std::max(4, rvd);   // the cell lists exist for 4..7 valid sub-tile rows
-                const bool symdiag = (a.role == HDM_ROLE_CONG2D);
-                if (!symdiag && a.lower_only && tm == tn) {                              // diagonal tile, cell-dealt
-                    const int cells = (rvd < 8) ? rvc * (rvc + 1) / 2 : 36;
-                    mf += 4.0 * cells * pairs(nst);
-                } else if (!symdiag && tm != tn && m0 + HDM_TILE > a.M && n0 + HDM_TILE <= a.N) {   // bottom-edge tile
-                    mf += 4.0 * (8 * rvc) * pairs(nst);
-                } else if (a.role == HDM_ROLE_CONG2) {      // both products: full stages, then the diagonal block's live ranges 16+12+8+4
-                    mf += 2.0 * ((double) tn * 8 * 256 + 1280);
-                } else if (a.role == HDM_ROLE_CONG2D) {     // one product, both operands triangular in the last block: 16+9+4+1
-                    mf += (double) tn * 8 * 256 + 960;
-                } else if (a.role == HDM_ROLE_CONG1) {      // first and last K block triangular on one side each
-                    mf += 2.0 * 1280 + (double) (tm - tn - 1) * 2048;
-                } else {
-                    mf += 256.0 * pairs(nst);
-                }
-            }
-    return mf * 2048.0 * ((a.epilogue == HDM_EPI_SLAB) ? 1.0 : (double) a.batch);
+    return (double) hdm_launch_mfmas(tile_geom(a), subset) * 2048.0 * ((a.epilogue == HDM_EPI_SLAB) ? 1.0 : (double) a.batch);
 }
 
 int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream) {
@@ -177,7 +122,6 @@ int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream) {
         fprintf(stderr, "[hdsdp_mi355x] gemm: bad k_chunk\n");
         return 1;
     }
-    const int NT = (args.N + HDM_TILE - 1) / HDM_TILE;
     if (args.role == HDM_ROLE_CONG2) {
         // the role IS the SYR2K form lower(U W^T + W U^T) into the blocked layout: its full diagonal tiles compute one
         // product and add the transpose (gemm_tile.h: symdiag), which is only that tile if the second pair mirrors the first
@@ -202,24 +146,7 @@ int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream) {
         // Roles 1-3 stage whole 128-row tiles WITHOUT a row mask (SStager::load_nomask): rows past the matrix edge are
         // read and thrown away.  Every such launch therefore states how many elements are readable from each operand
         // pointer, and the launch is refused unless the farthest element an unmasked load can touch lies inside.
-        auto farthest = [&](bool kmajor, long ld, long kblk, long stride, int rows, bool seg) {
-            const long maxrow = (long) ((rows + HDM_TILE - 1) / HDM_TILE) * HDM_TILE - 1;
-            long kfirst = 0, klast = args.K - 1;
-            if (args.epilogue == HDM_EPI_SLAB) {
-                kfirst = args.k_base;
-                klast = std::min<long>(args.K, args.k_base + (long) args.batch * args.k_chunk) - 1;
-            }
-            (void) kfirst;
-            const long nb = (args.epilogue == HDM_EPI_SLAB) ? 1 : args.batch;
-            long off = (nb - 1) * stride;
-            if (kmajor) {
-                off += (klast / HDM_BK) * (kblk ? kblk : HDM_BK) + maxrow * ld + (HDM_BK - 1);
-                if (seg && args.seg_rows) off += (maxrow / args.seg_rows) * args.seg_extra;
-            } else {
-                off += klast * ld + maxrow;
-            }
-            return off + 1;
-        };
+        const HdmTileGeom gm = tile_geom(args);
         struct { const double *p; long span; bool km; long ld, kblk, stride; int rows; const char *nm; } ops[4] = {
             {args.A, args.spanA, args.a_kmajor != 0, args.lda, args.a_kblk, args.strideA, args.M, "A"},
             {args.B, args.spanB, args.b_kmajor != 0, args.ldb, args.b_kblk, args.strideB, args.N, "B"},
@@ -227,14 +154,7 @@ int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream) {
             {args.B2, args.spanB2, args.b_kmajor != 0, args.ldb2, (long) HDM_BK, args.strideB2, args.N, "B2"}};
         for (auto &o : ops) {
             if (!o.p) continue;
-            long need = farthest(o.km, o.ld, o.kblk, o.stride, o.rows, true);
-            if (o.p == args.B && args.b_sky) {
-                // skyline operand: the last panel (width w < 128 columns, height w) is read as 128 "rows" of its leading
-                // dimension, i.e. up to (128 - w) columns' worth past the matrix
-                const int t = (args.N + HDM_TILE - 1) / HDM_TILE - 1;
-                const long h = args.N - 128L * t;
-                need = (long) (args.batch - 1) * args.strideB + hdm_sky_panel(t, args.N) + 127 * h + h;
-            }
+            const long need = hdm_operand_need(gm, o.km, o.ld, o.kblk, o.stride, o.rows, args.seg_rows, args.seg_extra, o.p == args.B && args.b_sky);
             if (o.span < need) {
                 fprintf(stderr, "[hdsdp_mi355x] gemm role %d: operand %s needs %ld readable elements for its unmasked tile "
                                 "loads, the caller vouches for %ld: launch refused\n", args.role, o.nm, need, o.span);
@@ -244,18 +164,8 @@ int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream) {
     }
     if (args.role == HDM_ROLE_CONG2) {
         // two kernels: the full diagonal tiles as P + P^T (role HDM_ROLE_CONG2D), then everything else.  The launch's
-        // algorithmic flops are split by what the tiles hold: output element (i, j), i >= j, is 2 products x (j + 1) terms
-        double all = 0.0, diag = 0.0;
-        for (int tn = 0; tn < NT; ++tn) {
-            if (args.tile_col_mask && NT <= 64 && !((args.tile_col_mask >> tn) & 1ULL)) continue;
-            const int j0 = tn * HDM_TILE, j1 = std::min(args.N, j0 + HDM_TILE);
-            const bool full = (((args.M - j0 + 15) >> 4) >= 8);
-            for (int j = j0; j < j1; ++j) {
-                all += (double) (args.M - j) * (j + 1);
-                if (full) diag += (double) (j1 - j) * (j + 1);
-            }
-        }
-        const double share = all > 0.0 ? diag / all : 0.0;
+        // algorithmic flops are split by what the tiles hold (gemm_geom.h: hdm_cong2_diag_share)
+        const double share = hdm_cong2_diag_share(args.M, args.N, args.tile_col_mask);
         HdmGemmArgs dg = args;
         dg.role = HDM_ROLE_CONG2D; dg.A2 = nullptr; dg.B2 = nullptr; dg.flops = args.flops * share;
         if (launch_tiles(dg, 1, stream)) return 1;
@@ -268,9 +178,8 @@ int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream) {
 
 // one kernel launch over a subset of the tile list (get_tiles); args.role selects the kernel
 static int launch_tiles(const HdmGemmArgs &args, int subset, hipStream_t stream) {
-    const int MT = (args.M + HDM_TILE - 1) / HDM_TILE, NT = (args.N + HDM_TILE - 1) / HDM_TILE;
     TileList tl;
-    if (get_tiles(MT, NT, args.klimit, args.lower_only, args.tile_col_mask, tl, subset, args.M)) return 1;
+    if (get_tiles(tile_geom(args), tl, subset)) return 1;
     if (tl.n == 0) return 0;
     HdmGemmDev d;
     d.a = args;

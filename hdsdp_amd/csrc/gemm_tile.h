@@ -286,7 +286,7 @@ __device__ __forceinline__ void cell_epilogue(const HdmGemmArgs &a, int z, int m
             const int bi = (m0 >> 4) + T::si[c], bj = (n0 >> 4) + T::sj[c];
             if (T::si[c] >= rv || bi >= a.nblk || bj >= a.nblk) continue;
             const double sc = (bi == bj) ? 1.0 : 1.4142135623730951;
-            const long sub = (long) bj * a.nblk - (long) bj * (bj - 1) / 2 + (bi - bj);
+            const long sub = hdm_blk_sub(bi, bj, a.nblk);
             double *q = lane_base + sub * 16 * rs16;
 #pragma unroll
             for (int r = 0; r < 4; ++r) q[(long) (4 * r) * rs16] = sc * acc[c >> 2][c & 3][r];
@@ -533,7 +533,7 @@ __device__ __forceinline__ void cong2_direct_body(const HdmGemmArgs &a, int z, i
             const int bj = (n0 >> 4) + 2 * j + wn;
             if (bi < bj || bi >= a.nblk) continue;
             const double sc = (bi == bj) ? 1.0 : rt2;
-            const long sub = (long) bj * a.nblk - (long) bj * (bj - 1) / 2 + (bi - bj);
+            const long sub = hdm_blk_sub(bi, bj, a.nblk);
             double *q = lane_base + sub * 16 * rs16;
 #pragma unroll
             for (int r = 0; r < 4; ++r) q[(long) (4 * r) * rs16] = sc * acc[j][i][r];
@@ -563,6 +563,8 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
     const int l15 = lane & 15, lq = lane >> 4;
 
     const int m0 = tm * HDM_TILE, n0 = tn * HDM_TILE;
+    // (gemm_geom.h: hdm_tile_krange states this rule for the host; it is written out here, as are the two class predicates and
+    // the cell paths' row count below, because through the header's functions the compiler gives these kernels other code)
     long kbeg = 0, kend = a.K;
     if (a.klimit == HDM_KLIM_BY_M) kend = min((long) a.K, (long) (tm + 1) * HDM_TILE);
     if (a.klimit == HDM_KLIM_BY_N) kend = min((long) a.K, (long) (tn + 1) * HDM_TILE);
@@ -611,7 +613,7 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
     // VAR & 128: timing-only ablation (wrong results): every tile stages rows 0..127, so all operand traffic hits in L2
     long ldb = a.ldb;
     if (ROLE == HDM_ROLE_CONG1 && a.b_sky) {
-        // A_L in skyline storage (hdm_common.h): tile column tn reads panel tn, a plain K-major matrix of leading dimension
+        // A_L in skyline storage (gemm_geom.h): tile column tn reads panel tn, a plain K-major matrix of leading dimension
         // N - 128 tn whose element (row 128 tn, k 128 tn) sits at the panel's start -- the pointer is moved back so that
         // the stager's absolute (row, k) arithmetic lands there
         ldb = a.N - 128L * tn;
@@ -631,7 +633,7 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
     // launcher verifies (hdm_launch_gemm: operand spans); a generic launch -- Cholesky updates, the small products of the
     // rank-one path on buffers of a few KB -- takes the masked loop below, whose epilogue knows about diagonal tiles.  A
     // generic diagonal tile on this path once read 16 KB past a 2 KB operand: a device fault.)
-    if (!symdiag && a.lower_only && tm == tn) {   // workgroup-uniform: diagonal tile, 36-cell scheme
+    if (!symdiag && a.lower_only && tm == tn) {   // workgroup-uniform: diagonal tile, 36-cell scheme (gemm_geom.h: hdm_tile_is_cell_diag)
         const int nst = (kt1 - kt0) * npass;
         const int rvd = (a.M - m0 + 15) >> 4;                      // valid sub-tile rows (= columns) of this tile
         if (rvd < 8) {                                             // the last, short diagonal tile: only its needed cells
@@ -658,7 +660,7 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
         }
         return;
     }
-    if (!symdiag && tm != tn && m0 + HDM_TILE > a.M && n0 + HDM_TILE <= a.N) {
+    if (!symdiag && tm != tn && m0 + HDM_TILE > a.M && n0 + HDM_TILE <= a.N) {   // (gemm_geom.h: hdm_tile_is_edge)
         // workgroup-uniform: bottom-edge tile below the diagonal, rv < 8 valid sub-tile rows
         const int nst = (kt1 - kt0) * npass;
         const int rv = (a.M - m0 + 15) >> 4;
@@ -689,9 +691,7 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
         //
         // Triangular operands.  In the congruence kernels the K block that lies on an operand's diagonal is half
         // zeros: for stage s (16 k's) of such a block whole 16-row sub-tiles of the operand are structurally zero
-        //   step 2 (both products, last K block, B side lower triangular): column sub-tiles < s are dead,
-        //   step 1, first K block (A_L on the B side: k >= column): column sub-tiles > s are dead,
-        //   step 1, last K block (Linv on the A side: k <= row): row sub-tiles < s are dead.
+        // (gemm_geom.h says which, block by block: the tables HDM_LIVE_*, from which the host counts the MFMAs too).
         // The stage body exists in variants that run only the live range [JLO..JHI] x [ILO..3] of a wave's 4 x 4
         // sub-tiles; with the interleaved ownership the live sub-tiles are spread evenly over the four waves.
         hdm_u4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;   // staging registers, named so they are never an alloca
@@ -713,7 +713,7 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
         // one stage that has a successor, on buffer CB: 48 MFMAs, barrier, next stage's first fragments + look-ahead loads, 16 MFMAs
 #define HDM_STAGE(CB, JLO, JHI, ILO, SW)                                                                             \
     {                                                                                                                \
-        constexpr int NK = ((JHI) - (JLO) + 1) * (4 - (ILO));   /* live MFMAs per k-step */                          \
+        constexpr int NK = hdm_live_per_kstep(HdmLive{JLO, JHI, ILO});   /* live MFMAs per k-step */                 \
         HDM_LDF(fa1, fb1, CB, 4)                                                                                     \
         HDM_MMA(fa0, fb0, JLO, JHI, ILO)                                                                             \
         HDM_LDF(fa0, fb0, CB, 8)                                                                                     \
@@ -773,9 +773,9 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
         if (nst > 0) { HDM_LDF(fa0, fb0, 0, 0) }
         // Stages come in PAIRS on buffers 0, 1 (HDM_RUN2): every K block is eight stages, so every stage sequence of the
         // congruence roles is even and the buffer index of a stage is a compile-time constant.
-#define HDM_RUN2(JLO, JHI, ILO) { HDM_STAGE(0, JLO, JHI, ILO, false) HDM_STAGE(1, JLO, JHI, ILO, false) }
-#define HDM_END2(JLO, JHI, ILO) { HDM_STAGE(0, JLO, JHI, ILO, false) HDM_LAST(1, JLO, JHI, ILO) }
-#define HDM_RUN2SW(JLO, JHI, ILO) { HDM_STAGE(0, JLO, JHI, ILO, false) HDM_STAGE(1, JLO, JHI, ILO, true) }
+#define HDM_RUN2(L) { HDM_STAGE(0, L.jlo, L.jhi, L.ilo, false) HDM_STAGE(1, L.jlo, L.jhi, L.ilo, false) }
+#define HDM_END2(L) { HDM_STAGE(0, L.jlo, L.jhi, L.ilo, false) HDM_LAST(1, L.jlo, L.jhi, L.ilo) }
+#define HDM_RUN2SW(L) { HDM_STAGE(0, L.jlo, L.jhi, L.ilo, false) HDM_STAGE(1, L.jlo, L.jhi, L.ilo, true) }
         // The stage sequence of a tile is straight-line: plain loops over the full stages, and the eight stages of a
         // diagonal K block unrolled with compile-time live ranges (stage s of such a block keeps sub-tiles s/2.. or
         // ..s/2 of the wave's four: with the interleaved ownership that bound is the same for every wave).  A
@@ -783,31 +783,31 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
         // make the register allocator spill 350-480 VGPRs.
         if constexpr (ROLE == HDM_ROLE_CONG2) {
             // (tm > tn, full 128-row tile: diagonal and bottom-edge tiles left through the cell paths above)
-            const int nfull = tn * 4;                       // stage PAIRS before the B operand's diagonal block, per product
+            const int nfull = tn * HDM_KBLOCK_PAIRS;        // stage PAIRS before the B operand's diagonal block, per product
             // (stage s issues the loads of stage s + 2: the first pair's last k block is requested in the sixth stage of its
             // diagonal block, and the stagers move on to the second pair right there)
-            for (int t = 0; t < nfull; ++t) HDM_RUN2(0, 3, 0)
-            HDM_RUN2(0, 3, 0) HDM_RUN2(1, 3, 0) HDM_RUN2SW(2, 3, 0) HDM_RUN2(3, 3, 0)
-            for (int t = 0; t < nfull; ++t) HDM_RUN2(0, 3, 0)
-            HDM_RUN2(0, 3, 0) HDM_RUN2(1, 3, 0) HDM_RUN2(2, 3, 0) HDM_END2(3, 3, 0)
+            for (int t = 0; t < nfull; ++t) HDM_RUN2(HDM_LIVE_FULL)
+            HDM_RUN2(HDM_LIVE_CONG2_LAST[0]) HDM_RUN2(HDM_LIVE_CONG2_LAST[1]) HDM_RUN2SW(HDM_LIVE_CONG2_LAST[2]) HDM_RUN2(HDM_LIVE_CONG2_LAST[3])
+            for (int t = 0; t < nfull; ++t) HDM_RUN2(HDM_LIVE_FULL)
+            HDM_RUN2(HDM_LIVE_CONG2_LAST[0]) HDM_RUN2(HDM_LIVE_CONG2_LAST[1]) HDM_RUN2(HDM_LIVE_CONG2_LAST[2]) HDM_END2(HDM_LIVE_CONG2_LAST[3])
         } else if constexpr (ROLE == HDM_ROLE_CONG2D) {
             // one product; in the last K block both operands are on their diagonal: stage s keeps row and column
             // sub-tiles >= s, i.e. the wave's own [s/2..3] x [s/2..3]: 60 of the block's 128 sub-tile products
-            const int nfull = tn * 4;
-            for (int t = 0; t < nfull; ++t) HDM_RUN2(0, 3, 0)
-            HDM_RUN2(0, 3, 0) HDM_RUN2(1, 3, 1) HDM_RUN2(2, 3, 2) HDM_END2(3, 3, 3)
+            const int nfull = tn * HDM_KBLOCK_PAIRS;
+            for (int t = 0; t < nfull; ++t) HDM_RUN2(HDM_LIVE_FULL)
+            HDM_RUN2(HDM_LIVE_CONG2D_LAST[0]) HDM_RUN2(HDM_LIVE_CONG2D_LAST[1]) HDM_RUN2(HDM_LIVE_CONG2D_LAST[2]) HDM_END2(HDM_LIVE_CONG2D_LAST[3])
         } else if constexpr (ROLE == HDM_ROLE_CONG1) {
             // first K block: A_L on the B side, live column sub-tiles <= s; last K block: Linv on the A side, rows >= s
-            HDM_RUN2(0, 0, 0) HDM_RUN2(0, 1, 0) HDM_RUN2(0, 2, 0) HDM_RUN2(0, 3, 0)
-            const int nmid = (tm - tn - 1) * 4;
-            for (int t = 0; t < nmid; ++t) HDM_RUN2(0, 3, 0)
-            HDM_RUN2(0, 3, 0) HDM_RUN2(0, 3, 1) HDM_RUN2(0, 3, 2) HDM_END2(0, 3, 3)
+            HDM_RUN2(HDM_LIVE_CONG1_FIRST[0]) HDM_RUN2(HDM_LIVE_CONG1_FIRST[1]) HDM_RUN2(HDM_LIVE_CONG1_FIRST[2]) HDM_RUN2(HDM_LIVE_CONG1_FIRST[3])
+            const int nmid = (tm - tn - 1) * HDM_KBLOCK_PAIRS;
+            for (int t = 0; t < nmid; ++t) HDM_RUN2(HDM_LIVE_FULL)
+            HDM_RUN2(HDM_LIVE_CONG1_LAST[0]) HDM_RUN2(HDM_LIVE_CONG1_LAST[1]) HDM_RUN2(HDM_LIVE_CONG1_LAST[2]) HDM_END2(HDM_LIVE_CONG1_LAST[3])
         } else {
             // any stage count (the Gram role's K splits): an odd count ends with a stage of zeros (SStager::load_nomask)
             if (nst > 0) {
                 const int npairs = (nst + 1) >> 1;
-                for (int t = 0; t + 1 < npairs; ++t) HDM_RUN2(0, 3, 0)
-                HDM_END2(0, 3, 0)
+                for (int t = 0; t + 1 < npairs; ++t) HDM_RUN2(HDM_LIVE_FULL)
+                HDM_END2(HDM_LIVE_FULL)
             }
         }
 #undef HDM_RUN2
@@ -919,7 +919,7 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
                 if (si < sj || bi >= a.nblk) continue;   // wave-uniform
                 const double *x = smem + (si * (si + 1) / 2 + sj) * 256;
                 const double sc = (bi == bj) ? 1.0 : rt2;
-                const long sub = (long) bj * a.nblk - (long) bj * (bj - 1) / 2 + (bi - bj);
+                const long sub = hdm_blk_sub(bi, bj, a.nblk);
                 double *q = lane_base + sub * 16 * rs16;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -942,7 +942,7 @@ __device__ __forceinline__ void hdm_gemm_tile(const HdmGemmDev &p, const int z, 
                 const int bj = (n0 >> 4) + 2 * j + wn;
                 if (bi < bj || bi >= a.nblk) continue;  // (bj <= bi < nblk), wave-uniform
                 const double sc = (bi == bj) ? 1.0 : rt2;
-                const long sub = (long) bj * a.nblk - (long) bj * (bj - 1) / 2 + (bi - bj);
+                const long sub = hdm_blk_sub(bi, bj, a.nblk);
                 double *q = lane_base + sub * 16 * rs16;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

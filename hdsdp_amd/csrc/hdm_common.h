@@ -22,30 +22,9 @@ static inline size_t hdm_operand_pad(long ld) { return (size_t) 128 * (size_t) (
 hipError_t hdm_malloc(void **p, size_t bytes);   // alloc.cpp
 #include "devbuf.h"
 
-#define HDM_TILE 128          // workgroup tile edge of the fp64 MFMA GEMM family
-#define HDM_BK 16             // k-depth of one LDS stage
-#define HDM_SUB 16            // MFMA sub-tile edge (v_mfma_f64_16x16x4_f64)
+#include "gemm_geom.h"   // HDM_TILE / HDM_BK / HDM_SUB, HdmKLimit / HdmEpilogue / HdmRole, skyline storage, and the family's geometry
 
 typedef double hdm_d4 __attribute__((ext_vector_type(4)));
-
-// "Skyline" storage of a matrix in A_L form (strict lower triangle + half the diagonal; the constraint matrices and the
-// objective as the congruence reads them): only the 128-column panels from their diagonal block downwards are stored --
-// panel t holds rows 128 t .. n-1 of columns 128 t .. 128 t + 127 as a plain column-major (n - 128 t) x 128 matrix, the
-// panels follow each other.  53 % of the square at n = 2000 (34 GB instead of 64 GB for 2000 matrices); inside a panel
-// every column is contiguous and 128-byte aligned (n is a multiple of 16), so tile loads stay full lines, and the one
-// GEMM operand that reads A_L (congruence step 1, B side: rows = columns of panel tn, k = rows from the panel's top)
-// sees panel tn as an ordinary K-major matrix with leading dimension n - 128 tn.  The strict upper triangle of each
-// panel's top block is stored and stays zero.
-__host__ __device__ inline long hdm_sky_panel(int t, int n) { return 128L * ((long) t * n - 64L * t * (t - 1)); }   // start of panel t
-__host__ __device__ inline long hdm_sky_off(int i, int j, int n) {   // element (i, j), i >= 128 * (j / 128)
-    const int t = j >> 7;
-    return hdm_sky_panel(t, n) + (long) (j & 127) * (n - 128 * t) + (i - 128 * t);
-}
-__host__ __device__ inline long hdm_sky_size(int n) {                // elements of one matrix
-    const int t = (n + 127) / 128 - 1;
-    const long w = n - 128L * t;
-    return hdm_sky_panel(t, n) + w * w;
-}
 
 #define HDM_HIP_CHECK(expr)                                                                     \
     do {                                                                                        \
@@ -80,19 +59,6 @@ static inline long hdm_roundup(long x, long q) { return (x + q - 1) / q * q; }
 //   M-major ("N"): element (i,k) at X[i + k*ld]  (rows contiguous: a column-major M x K matrix)
 //   K-major ("T"): element (i,k) at X[i*ld + k]  (k contiguous: the transpose is column-major)
 // ---------------------------------------------------------------------------------------------
-enum HdmKLimit { HDM_KLIM_NONE = 0, HDM_KLIM_BY_M = 1, HDM_KLIM_BY_N = 2, HDM_KLIM_BAND = 3 };  // BAND: k in [tn*128, (tm+1)*128)
-enum HdmEpilogue {
-    HDM_EPI_STORE = 0,    // C = alpha*acc + beta*C, column-major
-    HDM_EPI_BLOCKED = 1,  // congruence output: 16x16-blocked lower triangle, sqrt(2) off-diagonal blocks
-    HDM_EPI_SLAB = 2      // split-K partial sums into slab[blockIdx.z]
-};
-
-// kernel roles: a distinct kernel symbol per role so that rocprofv3 --stats separates the hot-path
-// launches (congruence step 1/2, Gram) from the small Cholesky/TRTRI helper GEMMs
-// HDM_ROLE_CONG2D is internal to the launcher: a role-2 launch is issued as two kernels, the full diagonal tiles (computed
-// as P + P^T from one product, gemm_tile.h) and everything else; callers never ask for it
-enum HdmRole { HDM_ROLE_GENERIC = 0, HDM_ROLE_CONG1 = 1, HDM_ROLE_CONG2 = 2, HDM_ROLE_GRAM = 3, HDM_ROLE_CONG2D = 4, HDM_NROLES = 5 };
-
 struct HdmGemmArgs {
     const double *A, *B;
     double *C;

@@ -47,7 +47,7 @@ __global__ void mi_psig_norms_final_kernel(const double *__restrict__ part, int 
 __global__ void mi_psig_srow_kernel(double *__restrict__ dst, long row_stride, long row, int nblk, int n, const double *__restrict__ sig) {
     const int b = blockIdx.x;
     const int c = threadIdx.x >> 4, r = threadIdx.x & 15;
-    const long sub = (long) b * nblk - (long) b * (b - 1) / 2;
+    const long sub = hdm_blk_col_start(b, nblk);
     const long pb = sub * 16 + c;
     const int gi = b * 16 + c;
     dst[(pb * row_stride + row) * 16 + r] = (r == c && gi < n) ? sig[gi] : 0.0;

@@ -77,7 +77,7 @@ __device__ __forceinline__ void write_low_tile(const Src &src, double *__restric
     const int tx = threadIdx.x, ty = threadIdx.y;
     for (int jj = ty; jj < 32; jj += 8) {
         const int i = ti * 32 + tx, j = tj * 32 + jj;
-        if (i < ld && j < ld && i >= (j & ~127)) {      // skyline storage (hdm_common.h): nothing above a panel's top block
+        if (i < ld && j < ld && i >= (j & ~127)) {      // skyline storage (gemm_geom.h): nothing above a panel's top block
             double v = 0.0;
             if (i < n && j < n && i >= j) v = (i == j) ? 0.5 * src(i, j) : src(i, j);
             dst[hdm_sky_off(i, j, (int) ld)] = v;
@@ -177,7 +177,7 @@ __global__ void hdm_blocked_eye_kernel(double *__restrict__ dst, long row_stride
     // diagonal sub-blocks (bj == bi) of the "S row": At = L^-1 S L^-T = I (zero in the padding)
     int b = blockIdx.x;  // sub-block index along the diagonal
     int c = threadIdx.x >> 4, r = threadIdx.x & 15;
-    long sub = (long) b * nblk - (long) b * (b - 1) / 2;
+    long sub = hdm_blk_col_start(b, nblk);
     long pb = sub * 16 + c;
     int g = b * 16 + c;
     dst[(pb * row_stride + row) * 16 + r] = (r == c && g < n) ? 1.0 : 0.0;

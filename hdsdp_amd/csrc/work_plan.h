@@ -18,7 +18,7 @@ struct HdmLayout {
     long npb_loc;    // p-blocks per rank (K range of the local Gram part)
     int Lr;          // rows per segment of the Gram operand (local rows + 3 augmented, padded)
     long R;          // world * Lr: rows of the segment-ordered Gram matrix
-    long astride;    // elements per constraint matrix in skyline storage (hdm_common.h)
+    long astride;    // elements per constraint matrix in skyline storage (gemm_geom.h)
 };
 // `maxloc`: the most rows any rank owns -- ceil(m / world), or on one device the rows that are not zero on the block (the
 // caller's choice: cone_alloc_common)

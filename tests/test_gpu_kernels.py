@@ -516,3 +516,21 @@ def test_sweeps_from_the_zero_suppressed_copy_give_the_same_bits(case):
     assert got[0][1] == got[1][1] and got[0][2] == got[1][2]
     assert np.array_equal(got[0][3], got[1][3])
     assert np.max(np.abs(got[0][4] - got[1][4])) <= 1e-12 * np.max(np.abs(got[0][4]))
+
+
+@pytest.mark.parametrize("n", [128, 144, 384, 464])
+def test_schur_build_reports_and_computes_what_the_parent_commit_did(n):
+    """One HKKTBuildUp with kernel timing on, at the smallest blocks that reach every tile class of the GEMM family (128: one full
+    diagonal tile; 144: a short diagonal tile and a bottom edge with one valid sub-tile row, run as four; 384: a step-1 tile with
+    a middle K block; 464: all of these and five valid sub-tile rows): the algorithmic flops, the issued flops and the launch
+    count of every role, and M itself, are bit for bit what the commit before csrc/gemm_geom.h gave for the same call
+    (tests/golden/gemm_geom_parent.json, "device" section; tools/gemm_geom_fixture.py records it)."""
+    import json
+    import os
+    from tools.gemm_geom_fixture import device_record
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_geom_parent.json")) as f:
+        want = json.load(f)["device"][str(n)]
+    got = device_record(n, want["m"])
+    for role, (g, w) in enumerate(zip(got["roles"], want["roles"])):
+        assert g == w, f"n={n} role {role}: [flops, issued, launches] {g}, the parent's {w}"
+    assert got["M"] == want["M"]
