@@ -11,8 +11,10 @@
 //   * small blocks (n16 <= 256): the whole test is ONE single-workgroup launch (hdm_lanczos_whole_kernel), Ritz problems included;
 //   * large blocks: the steps between two Ritz checks are one launch of co-resident workgroups (hdm_lanczos_group_kernel) that
 //     returns the (alpha_k, beta_k) pairs through mapped pinned memory; the tridiagonal (k+1) x (k+1) Ritz problem is solved on
-//     the host by implicit QL (tridiag_eig; no LAPACK dependency), cyclic Jacobi being the way out if it does not converge;
+//     the host by implicit QL (lanczos_host.h: tridiag_eig; no LAPACK dependency), cyclic Jacobi being the way out if it does not converge;
 //   * the launch-per-product forms behind HDM_LANCZOS_WHOLE / _FUSED / _BIG / _GROUP = 0 remain as tested fallbacks.
+// The constants, the acceptance rule, the mailbox layout and the rule that picks a form are stated in lanczos_rule.h; the loop of
+// HLanczosSolve is hdm_lz_drive (lanczos_host.h), which the launch-per-group forms run over LzDeviceBackend below.
 // The start vector reproduces glibc's srand()/rand() stream (TYPE_3 additive feedback generator) without touching
 // the process-wide libc state, so the device run starts from the reference's own vector.
 #include "lanczos.h"
@@ -26,32 +28,20 @@
 
 namespace {
 
-// ---- glibc random_r TYPE_3 (r[i] = r[i-3] + r[i-31]), as srand(seed) / rand() use it -------------------------------
-struct GlibcRand {
-    int f, b;   // front / rear indices of the 31-word state
-    int32_t st[31];
-    void seed(unsigned int s) {
-        if (s == 0) s = 1;
-        st[0] = (int32_t) s;
-        long word = (int32_t) s;
-        for (int i = 1; i < 31; ++i) {
-            long hi = word / 127773, lo = word % 127773;
-            word = 16807 * lo - 2836 * hi;
-            if (word < 0) word += 2147483647;
-            st[i] = (int32_t) word;
-        }
-        f = 3; b = 0;
-        for (int i = 0; i < 310; ++i) (void) next();
-    }
-    int next() {
-        uint32_t v = (uint32_t) st[f] + (uint32_t) st[b];
-        st[f] = (int32_t) v;
-        int out = (int) (v >> 1);
-        if (++f >= 31) f = 0;
-        if (++b >= 31) b = 0;
-        return out;
-    }
-};
+// Sum of one value per thread over a 1024-thread workgroup in a fixed order: a shuffle tree per wave, then the 16 wave sums added
+// by thread 0 in wave order; every thread gets the sum.  red: 16 doubles of LDS, bc: one.
+// (hdm_resnorm_kernel keeps the same sum written out: only its thread 0 needs the result.)
+__device__ __forceinline__ double lz_wg_sum(double s, double *red, double *bc) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (tid == 0) { double t = 0.0; for (int q = 0; q < 16; ++q) t += red[q]; *bc = t; }
+    __syncthreads();
+    const double r = *bc;
+    __syncthreads();
+    return r;
+}
 
 // single workgroup: three-term recurrence + normalisation of one Lanczos step (hdsdp_lanczos.c:199-218)
 //   w -= hprev * Vprev ;  alp = -<w, Vk> ;  w += alp * Vk ;  nrm = |w| ;  Vnext = vnext = w / nrm  (if nrm > 0)
@@ -64,17 +54,8 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_step_kernel(const double *__
                                                                 double *__restrict__ vnext, int n, double *__restrict__ out) {
     __shared__ double red[16];
     __shared__ double bc;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    auto reduce = [&](double s) {
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (tid == 0) { double t = 0.0; for (int q = 0; q < 16; ++q) t += red[q]; bc = t; }
-        __syncthreads();
-        double r = bc;
-        __syncthreads();
-        return r;
-    };
+    const int tid = threadIdx.x;
+    auto reduce = [&](double s) { return lz_wg_sum(s, red, &bc); };
     const double hprev = Vprev ? *hprev_dev : 0.0;
     double s = 0.0;
     for (int i = tid; i < n; i += 1024) {
@@ -99,6 +80,49 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_step_kernel(const double *__
     if (tid == 0) { out[0] = alp; out[1] = nrm; }
 }
 
+// w = Linv ( -dS ( Linv^T sv ) ) with both matrices read from global memory (L2), for a 1024-thread workgroup and n <= LZ_FUSED_MAX:
+// element tid of the result (0 beyond n).  sv must be in place and visible; st1, st2, part are scratch (part may be reused
+// after the caller's next __syncthreads).
+__device__ __forceinline__ double lz_apply_global(const double *__restrict__ Linv, long ldl, const double *__restrict__ dS, long ldd, int n,
+                                                  const double *sv, double *st1, double *st2, double (*part)[LZ_FUSED_MAX]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // t1 = Linv^T v: one wavefront per column (contiguous reads), rows above the diagonal skipped
+    for (int j = wave; j < n; j += 16) {
+        const double *col = Linv + (long) j * ldl;
+        double a = 0.0;
+        for (int i = (j & ~63) + lane; i < n; i += 64) a += ((i < j) ? 0.0 : col[i]) * sv[i];
+        for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+        if (lane == 0) st1[j] = a;
+    }
+    __syncthreads();
+    // t2 = -dS t1 (dS symmetric: column dots again)
+    for (int j = wave; j < n; j += 16) {
+        const double *col = dS + (long) j * ldd;
+        double a = 0.0;
+        for (int i = lane; i < n; i += 64) a += col[i] * st1[i];
+        for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+        if (lane == 0) st2[j] = -a;
+    }
+    __syncthreads();
+    // w = Linv t2: rows across lanes (coalesced), four column chunks summed in order
+    {
+        const int i = tid & (LZ_FUSED_MAX - 1), c = tid >> 8;
+        const int cw = (n + 3) / 4, j0 = c * cw, j1 = min(n, j0 + cw), jend = min(j1, i + 1);
+        double a0 = 0.0, a1 = 0.0;
+        if (i < n) {
+            int j = j0;
+            for (; j + 1 < jend; j += 2) {
+                a0 += Linv[i + (long) j * ldl] * st2[j];
+                a1 += Linv[i + (long) (j + 1) * ldl] * st2[j + 1];
+            }
+            if (j < jend) a0 += Linv[i + (long) j * ldl] * st2[j];
+        }
+        part[c][i] = a0 + a1;
+    }
+    __syncthreads();
+    return (tid < n) ? ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid] : 0.0;
+}
+
 // Small blocks (n16 <= 256): up to three whole Lanczos steps -- operator application and recurrence -- in ONE single-workgroup
 // launch.  The reference checks its Ritz values every third step (checkFreq, hdsdp_lanczos.c:187-189) and the host needs
 // nothing but (alpha_k, beta_k) in between, so a group of steps is one launch and one synchronisation instead of five
@@ -106,68 +130,22 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_step_kernel(const double *__
 // half of what the reference's driver spends below the C ABI on mcp100 / gpp100.  The matrices (<= 512 KB each) are read
 // from L2; vectors live in LDS.  Sums are taken in a fixed order.  out: (alpha, beta) per step, then the number of steps done
 // (a zero norm ends the group early, as it ends the reference's loop).
-#define LZ_FUSED_MAX 256
-#define LZ_NCHUNK 32       // column chunks of the operator's last product (partial sums, reduced in chunk order)
 __global__ __launch_bounds__(1024) void hdm_lanczos_fused_kernel(const double *__restrict__ Linv, long ldl,
                                                                  const double *__restrict__ dS, long ldd, int n,
                                                                  double *__restrict__ V, long ldv, int k0, int nsteps, double hprev,
                                                                  double *__restrict__ blk, double *__restrict__ out) {
     __shared__ double sv[LZ_FUSED_MAX], st1[LZ_FUSED_MAX], st2[LZ_FUSED_MAX], part[4][LZ_FUSED_MAX], red[16];
     __shared__ double bc;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    auto reduce = [&](double s) {
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (tid == 0) { double t = 0.0; for (int q = 0; q < 16; ++q) t += red[q]; bc = t; }
-        __syncthreads();
-        const double r = bc;
-        __syncthreads();
-        return r;
-    };
+    const int tid = threadIdx.x;
+    auto reduce = [&](double s) { return lz_wg_sum(s, red, &bc); };
     int done = 0;
     for (int s = 0; s < nsteps; ++s) {
         const int k = k0 + s;
         if (tid < n) sv[tid] = V[tid + (long) k * ldv];
         __syncthreads();
-        // t1 = Linv^T v: one wavefront per column (contiguous reads), rows above the diagonal skipped
-        for (int j = wave; j < n; j += 16) {
-            const double *col = Linv + (long) j * ldl;
-            double a = 0.0;
-            for (int i = (j & ~63) + lane; i < n; i += 64) a += ((i < j) ? 0.0 : col[i]) * sv[i];
-            for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-            if (lane == 0) st1[j] = a;
-        }
-        __syncthreads();
-        // t2 = -dS t1 (dS symmetric: column dots again)
-        for (int j = wave; j < n; j += 16) {
-            const double *col = dS + (long) j * ldd;
-            double a = 0.0;
-            for (int i = lane; i < n; i += 64) a += col[i] * st1[i];
-            for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-            if (lane == 0) st2[j] = -a;
-        }
-        __syncthreads();
-        // w = Linv t2: rows across lanes (coalesced), four column chunks summed in order
-        {
-            const int i = tid & (LZ_FUSED_MAX - 1), c = tid >> 8;
-            const int cw = (n + 3) / 4, j0 = c * cw, j1 = min(n, j0 + cw), jend = min(j1, i + 1);
-            double a0 = 0.0, a1 = 0.0;
-            if (i < n) {
-                int j = j0;
-                for (; j + 1 < jend; j += 2) {
-                    a0 += Linv[i + (long) j * ldl] * st2[j];
-                    a1 += Linv[i + (long) (j + 1) * ldl] * st2[j + 1];
-                }
-                if (j < jend) a0 += Linv[i + (long) j * ldl] * st2[j];
-            }
-            part[c][i] = a0 + a1;
-        }
-        __syncthreads();
-        // the three-term recurrence and the normalisation (hdsdp_lanczos.c:199-218): thread i keeps element i
-        double x = 0.0, vk = 0.0;
+        // the operator, then the three-term recurrence and the normalisation (hdsdp_lanczos.c:199-218): thread i keeps element i
+        double x = lz_apply_global(Linv, ldl, dS, ldd, n, sv, st1, st2, part), vk = 0.0;
         if (tid < n) {
-            x = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
             vk = sv[tid];
             if (k > 0) x -= hprev * V[tid + (long) (k - 1) * ldv];
         }
@@ -202,7 +180,6 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_fused_kernel(const double *_
 // spin); the host launches this form only where the grid is co-resident by construction (one workgroup per CU, nothing else
 // on the device) and falls back to the launch-per-product form for the rest of the object's life if a wait ever runs out.
 // ---------------------------------------------------------------------------------------------------------------------
-#define LZG_WG 256
 struct LzgArgs {
     const double *Linv; long ldl; const double *LinvT; long ldt; const double *dS; long ldd;
     int n; double *V; long ldv; int k0, nsteps; double hprev;
@@ -461,8 +438,6 @@ __global__ __launch_bounds__(256) void hdm_transpose_kernel(const double *__rest
 // RESIDENT = true (n16 <= 128): the two matrices are first packed into LDS (lower triangles, column by column: 2 x 66 KB at
 // n16 = 128) and the 30-50 operator applications of a test read them there; from global memory every application is three
 // dependent passes of L2 round trips -- 12 us each at n = 100, 0.42 ms per ratio test on mcp100.
-#define LZ_MD 30
-#define LZ_RESIDENT_MAX 128
 template <bool RESIDENT>
 __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *__restrict__ Linv, long ldl, const double *__restrict__ dS,
                                                                  long ldd, int n, double *__restrict__ V, long ldv,
@@ -481,16 +456,7 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *_
         }
         __syncthreads();
     }
-    auto reduce = [&](double s) {
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (tid == 0) { double t = 0.0; for (int q = 0; q < 16; ++q) t += red[q]; bc = t; }
-        __syncthreads();
-        const double r = bc;
-        __syncthreads();
-        return r;
-    };
+    auto reduce = [&](double s) { return lz_wg_sum(s, red, &bc); };
     // w = Linv ( -dS ( Linv^T sv ) ): element tid of the result (0 beyond n); sv must be in place and visible
     auto apply = [&]() -> double {
         if (RESIDENT) {
@@ -550,45 +516,13 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *_
             __syncthreads();
             return xr;
         }
-        for (int j = wave; j < n; j += 16) {
-            const double *col = Linv + (long) j * ldl;
-            double a = 0.0;
-            for (int i = (j & ~63) + lane; i < n; i += 64) a += ((i < j) ? 0.0 : col[i]) * sv[i];
-            for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-            if (lane == 0) st1[j] = a;
-        }
-        __syncthreads();
-        for (int j = wave; j < n; j += 16) {
-            const double *col = dS + (long) j * ldd;
-            double a = 0.0;
-            for (int i = lane; i < n; i += 64) a += col[i] * st1[i];
-            for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-            if (lane == 0) st2[j] = -a;
-        }
-        __syncthreads();
-        {
-            const int i = tid & (LZ_FUSED_MAX - 1), c = tid >> 8;
-            const int cw = (n + 3) / 4, j0 = c * cw, j1 = min(n, j0 + cw), jend = min(j1, i + 1);
-            double a0 = 0.0, a1 = 0.0;
-            if (i < n) {
-                int j = j0;
-                for (; j + 1 < jend; j += 2) {
-                    a0 += Linv[i + (long) j * ldl] * st2[j];
-                    a1 += Linv[i + (long) (j + 1) * ldl] * st2[j + 1];
-                }
-                if (j < jend) a0 += Linv[i + (long) j * ldl] * st2[j];
-            }
-            part[c][i] = a0 + a1;
-        }
-        __syncthreads();
-        double x = 0.0;
-        if (tid < n) x = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+        const double x = lz_apply_global(Linv, ldl, dS, ldd, n, sv, st1, st2, part);
         __syncthreads();
         return x;
     };
     // ---- start vector (:166-181), normalised into V[:, 0]
     double v0 = 0.0;
-    if (tid < n) v0 = fresh ? start[tid] : warm[tid] + 1e-03 * start[tid];
+    if (tid < n) v0 = fresh ? start[tid] : warm[tid] + LZ_WARM_WEIGHT * start[tid];
     {
         const double nr = sqrt(reduce(v0 * v0));
         const double inv = nr > 0.0 ? 1.0 / nr : 0.0;
@@ -597,10 +531,9 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *_
     if (tid < LZ_MD + 2) { hd[tid] = 0.0; he[tid] = 0.0; }
     __threadfence_block();
     __syncthreads();
-    const int md = LZ_MD, checkFreq = 3;
     double step = 0.0, hprev = 0.0;
     int k = 0, status = 0;
-    for (k = 0; k < md; ++k) {
+    for (k = 0; k < LZ_MD; ++k) {
         if (tid < n) sv[tid] = V[tid + (long) k * ldv];
         __syncthreads();
         double x = apply();
@@ -617,7 +550,7 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *_
         hprev = (nrm > 0.0) ? nrm : 0.0;
         __threadfence_block();
         __syncthreads();
-        if (!((k + 1) % checkFreq == 0 || k > md - 1 || nrm == 0.0)) continue;
+        if (!hdm_lz_check_due(k, nrm)) continue;
         // ---- Ritz values of the leading kp x kp tridiagonal matrix: implicit QL with eigenvectors, wave 0
         const int kp = k + 1;
         if (wave == 0) {
@@ -710,8 +643,7 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *_
         __threadfence_block();
         __syncthreads();
         const double eig1 = sh_eig1, eig2 = sh_eig2;
-        const double resiVal = fabs(he[k] * y1[k]);
-        if (resiVal < 1e-04 || k >= md - 1) {
+        if (hdm_lz_residuals_due(fabs(he[k] * y1[k]), k)) {
             // z1 = V y1 ; z2 = Op z1 ; warm start <- z2 ; resiVal1 = | z2 - eig1 z1 |
             double z = 0.0;
             if (tid < n) for (int c = 0; c < kp; ++c) z += V[tid + (long) c * ldv] * y1[c];
@@ -729,17 +661,10 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *_
             w = apply();
             d = (tid < n) ? w - eig1 * z : 0.0;
             const double r2 = sqrt(reduce(d * d));
-            const double resiDiff = eig1 - eig2 - r2;
-            double gam = (resiDiff > 0) ? resiDiff : 1e-16;
-            const double sq = r1 * r1 / gam;
-            gam = r1 < sq ? r1 : sq;
-            if (gam < 1e-03 || gam + eig1 <= 0.5) {
-                step = (gam + eig1 <= 0.0) ? INFINITY : 1.0 / (gam + eig1);
-                break;
-            } else {
-                if (nrm == 0.0) { status = 1; break; }
-                step = 1.0 / (gam + eig1);
-            }
+            const HdmLzAccept a = hdm_lz_accept(eig1, eig2, r1, r2, nrm);
+            if (a.verdict == LZ_FAILED) { status = 1; break; }
+            step = a.step;
+            if (a.verdict == LZ_ACCEPTED) break;
         }
     }
     if (tid == 0) { out[0] = step; out[1] = (double) k; out[2] = (double) status; }
@@ -776,7 +701,7 @@ __global__ __launch_bounds__(1024) void hdm_resnorm_kernel(const double *__restr
 __global__ __launch_bounds__(1024) void hdm_warm_start_kernel(double *__restrict__ out, const double *__restrict__ warm,
                                                               const double *__restrict__ startd, int n, int n16, int fresh) {
     for (int i = threadIdx.x; i < n16; i += 1024)
-        out[i] = (i >= n) ? 0.0 : (fresh ? startd[i] : __dadd_rn(warm[i], __dmul_rn(1e-03, startd[i])));
+        out[i] = (i >= n) ? 0.0 : (fresh ? startd[i] : __dadd_rn(warm[i], __dmul_rn(LZ_WARM_WEIGHT, startd[i])));
 }
 
 // v <- v / |v| into the block's column 0 and into V[:, 0]   (single workgroup)
@@ -784,15 +709,11 @@ __global__ __launch_bounds__(1024) void hdm_normalize_kernel(const double *__res
                                                              double *__restrict__ blk, int n) {
     __shared__ double red[16];
     __shared__ double bc;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     double s = 0.0;
     for (int i = tid; i < n; i += 1024) s += v[i] * v[i];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    if (tid == 0) { double t = 0.0; for (int q = 0; q < 16; ++q) t += red[q]; bc = sqrt(t); }
-    __syncthreads();
-    const double inv = bc > 0.0 ? 1.0 / bc : 0.0;
+    const double nr = sqrt(lz_wg_sum(s, red, &bc));
+    const double inv = nr > 0.0 ? 1.0 / nr : 0.0;
     for (int i = tid; i < n; i += 1024) { double x = v[i] * inv; V0[i] = x; blk[i] = x; }
 }
 
@@ -849,126 +770,7 @@ __global__ void hdm_mirror_lower_kernel(double *A, long ld, int n) {
     if (i > j) A[j + (long) i * ld] = A[i + (long) j * ld];
 }
 
-// cyclic Jacobi for a small dense symmetric matrix (column-major k x k); eigenvalues ascending in d, vectors in Y
-void jacobi_eig(int k, std::vector<double> A, std::vector<double> &d, std::vector<double> &Y) {
-    Y.assign((size_t) k * k, 0.0);
-    for (int i = 0; i < k; ++i) Y[(size_t) i * k + i] = 1.0;
-    auto a = [&](int i, int j) -> double & { return A[(size_t) j * k + i]; };
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < k; ++p)
-            for (int q = p + 1; q < k; ++q) off += a(p, q) * a(p, q);
-        if (off < 1e-300) break;
-        for (int p = 0; p < k; ++p)
-            for (int q = p + 1; q < k; ++q) {
-                const double apq = a(p, q);
-                if (fabs(apq) < 1e-300) continue;
-                const double theta = (a(q, q) - a(p, p)) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int r = 0; r < k; ++r) {
-                    const double arp = a(r, p), arq = a(r, q);
-                    a(r, p) = c * arp - s * arq;
-                    a(r, q) = s * arp + c * arq;
-                }
-                for (int r = 0; r < k; ++r) {
-                    const double apr = a(p, r), aqr = a(q, r);
-                    a(p, r) = c * apr - s * aqr;
-                    a(q, r) = s * apr + c * aqr;
-                }
-                for (int r = 0; r < k; ++r) {
-                    const double yrp = Y[(size_t) p * k + r], yrq = Y[(size_t) q * k + r];
-                    Y[(size_t) p * k + r] = c * yrp - s * yrq;
-                    Y[(size_t) q * k + r] = s * yrp + c * yrq;
-                }
-            }
-    }
-    d.resize(k);
-    for (int i = 0; i < k; ++i) d[i] = a(i, i);
-    // ascending selection sort of (value, vector)
-    for (int i = 0; i < k; ++i) {
-        int mn = i;
-        for (int j = i + 1; j < k; ++j) if (d[j] < d[mn]) mn = j;
-        if (mn != i) {
-            std::swap(d[i], d[mn]);
-            for (int r = 0; r < k; ++r) std::swap(Y[(size_t) i * k + r], Y[(size_t) mn * k + r]);
-        }
-    }
-}
-
-// The Ritz matrix of a Lanczos run is TRIDIAGONAL: implicit QL with Wilkinson shifts (the EISPACK tql2 recurrence) instead of the
-// cyclic Jacobi above, which took 1.1 ms at k = 30 and 3.7 ms over the ten checks of a 30-step test on a host core -- three
-// times the device time of those steps once they ran in one launch per group.  U: the symmetric k x k matrix (column-major; only
-// its diagonal and first subdiagonal are read).  Eigenvalues ascending in d, vectors in the columns of Y.  Returns false if an
-// eigenvalue does not converge in 60 sweeps (the caller then takes the Jacobi route).
-bool tridiag_eig(int k, const std::vector<double> &U, std::vector<double> &d, std::vector<double> &Y) {
-    std::vector<double> e(k, 0.0);
-    d.resize(k);
-    for (int i = 0; i < k; ++i) d[i] = U[(size_t) i * k + i];
-    for (int i = 0; i + 1 < k; ++i) e[i] = U[(size_t) i * k + i + 1];       // T(i + 1, i)
-    Y.assign((size_t) k * k, 0.0);
-    for (int i = 0; i < k; ++i) Y[(size_t) i * k + i] = 1.0;
-    for (int l = 0; l < k; ++l) {
-        int iter = 0, m;
-        do {
-            for (m = l; m < k - 1; ++m) {
-                const double dd = fabs(d[m]) + fabs(d[m + 1]);
-                if (fabs(e[m]) + dd == dd) break;
-            }
-            if (m != l) {
-                if (iter++ == 60) return false;
-                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
-                double r = hypot(g, 1.0);
-                g = d[m] - d[l] + e[l] / (g + copysign(r, g));
-                double sn = 1.0, cs = 1.0, p = 0.0;
-                int i;
-                for (i = m - 1; i >= l; --i) {
-                    double f = sn * e[i];
-                    const double b = cs * e[i];
-                    e[i + 1] = (r = hypot(f, g));
-                    if (r == 0.0) { d[i + 1] -= p; e[m] = 0.0; break; }
-                    sn = f / r; cs = g / r;
-                    g = d[i + 1] - p;
-                    r = (d[i] - g) * sn + 2.0 * cs * b;
-                    d[i + 1] = g + (p = sn * r);
-                    g = cs * r - b;
-                    double *yi = &Y[(size_t) i * k], *yi1 = &Y[(size_t) (i + 1) * k];
-                    for (int q = 0; q < k; ++q) {
-                        f = yi1[q];
-                        yi1[q] = sn * yi[q] + cs * f;
-                        yi[q] = cs * yi[q] - sn * f;
-                    }
-                }
-                if (r == 0.0 && i >= l) continue;
-                d[l] -= p; e[l] = g; e[m] = 0.0;
-            }
-        } while (m != l);
-    }
-    for (int i = 0; i < k; ++i) {                 // ascending selection sort of (value, vector)
-        int mn = i;
-        for (int j = i + 1; j < k; ++j) if (d[j] < d[mn]) mn = j;
-        if (mn != i) {
-            std::swap(d[i], d[mn]);
-            for (int r = 0; r < k; ++r) std::swap(Y[(size_t) i * k + r], Y[(size_t) mn * k + r]);
-        }
-    }
-    return true;
-}
-
 }  // namespace
-
-void hdm_lanczos_start_vector(int n, double *p) {
-    // HLanczosIPrepare (hdsdp_lanczos.c:33-42): srand(n); per entry srand(rand()); sqrt(sqrt(rand() % 1627)) * (rand() % 2 - 0.5)
-    // (the reference re-seeds the one libc generator inside the loop, so a single generator object follows it)
-    GlibcRand g;
-    g.seed((unsigned int) n);
-    for (int i = 0; i < n; ++i) {
-        g.seed((unsigned int) g.next());
-        const int a = g.next() % 1627;
-        const int b = g.next() % 2;
-        p[i] = sqrt(sqrt((double) a)) * ((double) b - 0.5);
-    }
-}
 
 // A <- scale * ( sym(A) + diag_add * I )   (n x n, column-major): the two symmetrisation passes of the primal recovery
 __global__ void hdm_sym_scale_kernel(double *A, long ld, int n, double diag_add, double scale) {
@@ -1028,7 +830,7 @@ int HdmLanczos::init(int n_) {
     n = n_;
     n16 = (n + 15) / 16 * 16;
     const size_t blk = sizeof(double) * (size_t) n16 * 8;
-    HDM_HIP_CHECK(V.alloc((size_t) n16 * (maxdim + 1)));
+    HDM_HIP_CHECK(V.alloc((size_t) n16 * (LZ_MD + 1)));
     HDM_HIP_CHECK(bv.alloc(blk / sizeof(double)));
     HDM_HIP_CHECK(b1.alloc(blk / sizeof(double)));
     HDM_HIP_CHECK(b2.alloc(blk / sizeof(double)));
@@ -1039,9 +841,9 @@ int HdmLanczos::init(int n_) {
     // the scalars that travel between host and device -- (alpha, beta) pairs, Ritz coefficients, residual norms -- live in one
     // block of mapped pinned host memory: the kernels write their results straight into it and the host reads them after its
     // synchronisation (a copy into pageable memory per group of steps cost more than the group's kernels at n = 2000)
-    HDM_HIP_CHECK(scal_h.alloc(128, hipHostMallocMapped));
-    memset(scal_h.get(), 0, sizeof(double) * 128);
-    HDM_HIP_CHECK(part.alloc(32 * (size_t) n16));
+    HDM_HIP_CHECK(scal_h.alloc(LZ_MB_SIZE, hipHostMallocMapped));
+    memset(scal_h.get(), 0, sizeof(double) * LZ_MB_SIZE);
+    HDM_HIP_CHECK(part.alloc(LZ_NCHUNK * (size_t) n16));
     for (double *b : {bv.get(), b1.get(), b2.get(), bw.get(), bz.get()}) HDM_HIP_CHECK(hdm_memset_sync(b, 0, blk));
     HDM_HIP_CHECK(hdm_memset_sync(warm.get(), 0, sizeof(double) * (size_t) n16));
     HDM_HIP_CHECK(hdm_memset_sync(tmp.get(), 0, sizeof(double) * (size_t) n16));
@@ -1052,6 +854,11 @@ int HdmLanczos::init(int n_) {
         for (int i = 0; i < n; ++i) sp[i] = start[i];
         HDM_HIP_CHECK(startd.alloc((size_t) n16));
         HDM_HIP_CHECK(hipMemcpy(startd.get(), sp.data(), sizeof(double) * (size_t) n16, hipMemcpyHostToDevice));
+    }
+    {   // the co-resident form runs one workgroup per compute unit (hdm_lz_form)
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+        (void) hipGetLastError();
     }
     nComputed = 0;
     return 0;
@@ -1073,201 +880,168 @@ int HdmLanczos::apply(const double *Linv, long ldl, const double *dS, long ldd, 
     return 0;
 }
 
-int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, hipStream_t s, double *maxStep, int *steps) {
-    static const bool whole_env = [] { const char *e = getenv("HDM_LANCZOS_WHOLE"); return !(e && atoi(e) == 0); }();   // 0: the multi-launch forms (A/B, tests)
-    if (whole_env && n16 <= LZ_FUSED_MAX && maxdim == LZ_MD) {
-        // small block: the whole test in one launch (hdm_lanczos_whole_kernel); three doubles come back
-        if (n16 <= LZ_RESIDENT_MAX) {
-            const size_t dyn = sizeof(double) * (size_t) n16 * (n16 + 1);      // two packed triangles
-            static thread_local int configured_dev = -1;
-            int dev = 0;
-            HDM_HIP_CHECK(hipGetDevice(&dev));
-            if (configured_dev != dev) {
-                HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_lanczos_whole_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int) (sizeof(double) * LZ_RESIDENT_MAX * (LZ_RESIDENT_MAX + 1))));
-                configured_dev = dev;
+namespace {
+
+// the one-launch forms (hdm_lanczos_whole_kernel): three doubles come back through the mailbox
+int lz_solve_whole(HdmLanczos &z, HdmLzForm form, const double *Linv, long ldl, const double *dS, long ldd, hipStream_t s, double *maxStep,
+                   int *steps) {
+    const int n16 = z.n16, fresh = z.nComputed == 0 ? 1 : 0;
+    if (form == LZ_FORM_WHOLE_RESIDENT) {
+        const size_t dyn = sizeof(double) * (size_t) n16 * (n16 + 1);      // two packed triangles
+        static thread_local int configured_dev = -1;
+        int dev = 0;
+        HDM_HIP_CHECK(hipGetDevice(&dev));
+        if (configured_dev != dev) {
+            HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_lanczos_whole_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int) (sizeof(double) * LZ_RESIDENT_MAX * (LZ_RESIDENT_MAX + 1))));
+            configured_dev = dev;
+        }
+        hipLaunchKernelGGL(hdm_lanczos_whole_kernel<true>, dim3(1), dim3(1024), dyn, s, Linv, ldl, dS, ldd, n16, z.V.get(), (long) n16,
+                           z.startd.get(), z.warm.get(), fresh, z.scal_h.dev() + LZ_MB_WHOLE);
+    } else {
+        hipLaunchKernelGGL(hdm_lanczos_whole_kernel<false>, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, z.V.get(), (long) n16,
+                           z.startd.get(), z.warm.get(), fresh, z.scal_h.dev() + LZ_MB_WHOLE);
+    }
+    HDM_HIP_CHECK(hipGetLastError());
+    HDM_HIP_CHECK(hipStreamSynchronize(s));
+    const double *r = z.scal_h.get() + LZ_MB_WHOLE;      // step, Lanczos steps done, status
+    if (r[2] != 0.0) return 1;
+    z.nComputed += 1;
+    if (maxStep) *maxStep = r[0];
+    if (steps) *steps = (int) r[1];
+    return 0;
+}
+
+// What hdm_lz_drive (lanczos_host.h) runs on the device.  The start vector and the residuals are the same launches in every
+// form; a group of steps is one launch (fused, co-resident) or four per step (queued, stepwise).
+constexpr int LZ_RC_RETRY = 2;     // a grid-wide wait ran out: the object has given the co-resident form up, the test starts over
+struct LzDeviceBackend {
+    HdmLanczos &z;
+    HdmLzForm form;
+    const double *Linv; long ldl; const double *dS; long ldd;
+    hipStream_t s;
+    double *dbg;                   // HDSDP_MI355X_RATIO_DEBUG=2: the co-resident kernel's phase ticks
+    bool grouped() const { return form == LZ_FORM_GROUP8 || form == LZ_FORM_GROUP16; }
+
+    // fresh, or the previous Ritz image + 1e-3 * the same pseudo-random vector (:166-181), made on the device
+    int start() {
+        const int n16 = z.n16;
+        hipLaunchKernelGGL(hdm_warm_start_kernel, dim3(1), dim3(1024), 0, s, z.tmp.get(), z.warm.get(), z.startd.get(), z.n, n16, z.nComputed == 0 ? 1 : 0);
+        HDM_HIP_CHECK(hipMemsetAsync(z.V.get(), 0, sizeof(double) * (size_t) n16 * (LZ_MD + 1), s));
+        hipLaunchKernelGGL(hdm_normalize_kernel, dim3(1), dim3(1024), 0, s, z.tmp.get(), z.V.get(), z.bv.get(), n16);
+        HDM_HIP_CHECK(hipGetLastError());
+        if (!grouped()) return 0;
+        // the co-resident form: its barrier words (never reset: epochs only grow) and the transposed copy of Linv
+        if (dbg) HDM_HIP_CHECK(hipMemsetAsync(dbg, 0, sizeof(double) * 16, s));
+        HDM_HIP_CHECK(z.LT.reserve((size_t) n16 * n16));
+        if (!z.gsync) {
+            HDM_HIP_CHECK(z.gsync.alloc((64 + LZG_WG)));
+            HDM_HIP_CHECK(hipMemsetAsync(z.gsync.get(), 0, sizeof(unsigned) * (64 + LZG_WG), s));
+            z.sync_epoch = 0;
+        }
+        hipLaunchKernelGGL(hdm_transpose_kernel, dim3((n16 + 31) / 32, (n16 + 31) / 32), dim3(256), 0, s, Linv, ldl, z.LT.get(), (long) n16, n16);
+        HDM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+
+    int steps(int k, int g, double hprev, double *pairs) {
+        const int n16 = z.n16;
+        double *mb = z.scal_h.get(), *mb_dev = z.scal_h.dev();
+        if (form == LZ_FORM_STEPWISE && g > 1) {     // a synchronisation per step; a zero norm ends the test at its step
+            for (int q = 0; q < g; ++q) {
+                if (int rc = steps(k + q, 1, q > 0 ? pairs[2 * q - 1] : hprev, pairs + 2 * q)) return rc;
+                if (!(pairs[2 * q + 1] > 0.0)) break;
             }
-            hipLaunchKernelGGL(hdm_lanczos_whole_kernel<true>, dim3(1), dim3(1024), dyn, s, Linv, ldl, dS, ldd, n16, V.get(), (long) n16, startd.get(),
-                               warm.get(), nComputed == 0 ? 1 : 0, scal_h.dev() + 60);
+            return 0;
+        }
+        if (form == LZ_FORM_FUSED) {
+            hipLaunchKernelGGL(hdm_lanczos_fused_kernel, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, z.V.get(), (long) n16, k, g, hprev,
+                               z.bv.get(), mb_dev + LZ_MB_GROUP);
+        } else if (grouped()) {
+            LzgArgs a = {};
+            a.epoch0 = z.sync_epoch; z.sync_epoch += 3u * (unsigned) g;
+            mb[LZ_MB_GROUP + 2 * g + 1] = 0.0;                                   // give-up word of this launch
+            a.Linv = Linv; a.ldl = ldl; a.LinvT = z.LT.get(); a.ldt = n16; a.dS = dS; a.ldd = ldd; a.n = n16; a.V = z.V.get(); a.ldv = n16;
+            a.k0 = k; a.nsteps = g; a.hprev = hprev; a.blk = z.bv.get(); a.t1 = z.b1.get(); a.t2 = z.b2.get(); a.xw = z.b1.get() + n16;     // (the vector blocks are n16 x 8: column 1 of b1 is free)
+            a.out = mb_dev + LZ_MB_GROUP; a.sync = z.gsync.get(); a.dbg = dbg;
+            const int wgs = hdm_lz_group_wgs(z.cus);
+            if (form == LZ_FORM_GROUP8) hipLaunchKernelGGL(hdm_lanczos_group_kernel<8>, dim3(wgs), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(hdm_lanczos_group_kernel<16>, dim3(wgs), dim3(256), 0, s, a);
         } else {
-            hipLaunchKernelGGL(hdm_lanczos_whole_kernel<false>, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, V.get(), (long) n16, startd.get(),
-                               warm.get(), nComputed == 0 ? 1 : 0, scal_h.dev() + 60);
+            // four launches per step (three products and the recurrence, which takes the previous step's norm from device
+            // memory), queued back to back.  A zero norm inside a group ends the reference's loop at that step: the driver
+            // stops there too and what the later steps of the group computed is never looked at.
+            mb[LZ_MB_CARRY] = hprev;
+            for (int q = 0; q < g; ++q) {
+                const int kk = k + q;
+                if (z.apply(Linv, ldl, dS, ldd, z.bv.get(), nullptr, s)) return 1;
+                hipLaunchKernelGGL(hdm_lanczos_step_kernel, dim3(1), dim3(1024), 0, s, z.part.get(), LZ_NCHUNK, z.bw.get(),
+                                   kk > 0 ? z.V.get() + (size_t) (kk - 1) * n16 : nullptr,
+                                   q > 0 ? mb_dev + LZ_MB_GROUP + 2 * (q - 1) + 1 : mb_dev + LZ_MB_CARRY,
+                                   z.V.get() + (size_t) kk * n16, z.V.get() + (size_t) (kk + 1) * n16, z.bv.get(), n16, mb_dev + LZ_MB_GROUP + 2 * q);
+            }
         }
         HDM_HIP_CHECK(hipGetLastError());
         HDM_HIP_CHECK(hipStreamSynchronize(s));
-        const double r[3] = {scal_h.get()[60], scal_h.get()[61], scal_h.get()[62]};
-        if (r[2] != 0.0) return 1;
-        nComputed += 1;
-        if (maxStep) *maxStep = r[0];
-        if (steps) *steps = (int) r[1];
+        for (int q = 0; q < 2 * g; ++q) pairs[q] = mb[LZ_MB_GROUP + q];
+        if (grouped() && mb[LZ_MB_GROUP + 2 * g + 1] != 0.0) {
+            HDM_HIP_CHECK(hipMemsetAsync(z.gsync.get(), 0, sizeof(unsigned) * (64 + LZG_WG), s));
+            // a grid-wide wait ran out (the workgroups were not all resident): this object goes back to a launch per
+            // product for good, and this test starts over -- nothing of it has left the object yet
+            fprintf(stderr, "[hdsdp_mi355x] lanczos: grid-wide wait timed out, falling back to one launch per product\n");
+            z.big_ok = false;
+            return LZ_RC_RETRY;
+        }
         return 0;
     }
-    const int md = maxdim, nh = md + 1;
-    std::vector<double> H((size_t) nh * nh, 0.0);
-    auto Hm = [&](int i, int j) -> double & { return H[(size_t) j * nh + i]; };
-    // starting vector: fresh, or the previous Ritz image + 1e-3 * the same pseudo-random vector (:166-181), made on the device
-    hipLaunchKernelGGL(hdm_warm_start_kernel, dim3(1), dim3(1024), 0, s, tmp.get(), warm.get(), startd.get(), n, n16, nComputed == 0 ? 1 : 0);
-    HDM_HIP_CHECK(hipMemsetAsync(V.get(), 0, sizeof(double) * (size_t) n16 * (md + 1), s));
-    hipLaunchKernelGGL(hdm_normalize_kernel, dim3(1), dim3(1024), 0, s, tmp.get(), V.get(), bv.get(), n16);
-    HDM_HIP_CHECK(hipGetLastError());
 
-    int checkFreq = md / 5;
-    if (checkFreq > 3) checkFreq = 3;
-    double step = 0.0;
-    int k = 0;
-    double hs[2] = {0.0, 0.0};
-    std::vector<double> d, Y;
-    static const bool fuse_env = [] { const char *e = getenv("HDM_LANCZOS_FUSED"); return !(e && atoi(e) == 0); }();
-    const bool fused = fuse_env && n16 <= LZ_FUSED_MAX && checkFreq >= 1;
-    static const bool group_env = [] { const char *e = getenv("HDM_LANCZOS_GROUP"); return !(e && atoi(e) == 0); }();   // 0: one synchronisation per step (A/B)
-    // large blocks: the steps of a group in one launch of co-resident workgroups (hdm_lanczos_group_kernel); 0: a launch per product
-    static const bool big_env = [] { const char *e = getenv("HDM_LANCZOS_BIG"); return !(e && atoi(e) == 0); }();
-    bool big = big_env && big_ok && !fused && n16 > LZ_FUSED_MAX && n16 <= 4096 && checkFreq >= 1 && !hdm_flow_shared_device();
-    if (big) {
-        if (big_wg == 0) {
-            int dev = 0, cus = 0;
-            big_wg = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-                         ? std::min(LZG_WG, cus) : -1;
-            (void) hipGetLastError();
-        }
-        if (big_wg <= 0 || (n16 + big_wg - 1) / big_wg > 16) big = false;
-    }
-    static const bool dbg2 = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e) >= 2; }();
-    if (big) {
-        if (dbg2) HDM_HIP_CHECK(hipMemsetAsync(bz.get() + 4 * (size_t) n16, 0, sizeof(double) * 16, s));
-        HDM_HIP_CHECK(LT.reserve((size_t) n16 * n16));
-        if (!gsync) {
-            HDM_HIP_CHECK(gsync.alloc((64 + LZG_WG)));
-            HDM_HIP_CHECK(hipMemsetAsync(gsync.get(), 0, sizeof(unsigned) * (64 + LZG_WG), s));
-            sync_epoch = 0;
-        }
-        hipLaunchKernelGGL(hdm_transpose_kernel, dim3((n16 + 31) / 32, (n16 + 31) / 32), dim3(256), 0, s, Linv, ldl, LT.get(), (long) n16, n16);
+    // z1 = V y1 ; z2 = Op z1 ; warm start <- z2 ; r1 = | z2 - eig1 z1 |
+    // z2' = V y2 ; r2 = | Op z2' - eig1 z2' |   (the reference uses eig1 here too, :262-266)
+    // (both coefficient vectors go into the mailbox, everything is queued, one synchronisation; after the second apply() the
+    // vector block bv still holds v_{k+1}: the recurrence can continue)
+    int residuals(int kp, const double *y1, const double *y2, double eig1, double *r1, double *r2) {
+        const int n16 = z.n16;
+        double *mb = z.scal_h.get(), *mb_dev = z.scal_h.dev();
+        for (int r = 0; r < kp; ++r) { mb[LZ_MB_Y1 + r] = y1[r]; mb[LZ_MB_Y2 + r] = y2[r]; }
+        hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, z.V.get(), (long) n16, kp, mb_dev + LZ_MB_Y1, z.bz.get(), n16);
+        if (z.apply(Linv, ldl, dS, ldd, z.bz.get(), z.bw.get(), s)) return 1;
+        HDM_HIP_CHECK(hipMemcpyAsync(z.warm.get(), z.bw.get(), sizeof(double) * n16, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, z.bw.get(), z.bz.get(), eig1, n16, mb_dev + LZ_MB_R1);
+        hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, z.V.get(), (long) n16, kp, mb_dev + LZ_MB_Y2, z.bz.get(), n16);
+        if (z.apply(Linv, ldl, dS, ldd, z.bz.get(), z.bw.get(), s)) return 1;
+        hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, z.bw.get(), z.bz.get(), eig1, n16, mb_dev + LZ_MB_R2);
         HDM_HIP_CHECK(hipGetLastError());
+        HDM_HIP_CHECK(hipStreamSynchronize(s));
+        *r1 = mb[LZ_MB_R1]; *r2 = mb[LZ_MB_R2];
+        return 0;
     }
-    double grp[2 * 8 + 1] = {0.0};               // (alpha, beta) of the current group of steps, fused form
-    int grp_k0 = -1, grp_n = 0;
-    for (k = 0; k < md; ++k) {
-        const double hprev = (k > 0) ? Hm(k, k - 1) : 0.0;
-        if (fused) {
-            if (grp_k0 < 0 || k >= grp_k0 + grp_n) {       // next group: as many steps as lie before the next Ritz check
-                grp_k0 = k;
-                grp_n = std::min(std::min(checkFreq - (k % checkFreq), md - k), 8);
-                hipLaunchKernelGGL(hdm_lanczos_fused_kernel, dim3(1), dim3(1024), 0, s, Linv, ldl, dS, ldd, n16, V.get(), (long) n16, k, grp_n,
-                                   hprev, bv.get(), scal_h.dev() + 44);
-                HDM_HIP_CHECK(hipGetLastError());
-                HDM_HIP_CHECK(hipStreamSynchronize(s));
-                for (int q = 0; q < 2 * grp_n + 1; ++q) grp[q] = scal_h.get()[44 + q];   // (scal + 8 .. + 39, + 64 .. + 95: Ritz coefficients)
-            }
-            hs[0] = grp[2 * (k - grp_k0)]; hs[1] = grp[2 * (k - grp_k0) + 1];
-        } else if (big) {
-            if (grp_k0 < 0 || k >= grp_k0 + grp_n) {
-                grp_k0 = k;
-                grp_n = std::min(std::min(checkFreq - (k % checkFreq), md - k), 8);
-                LzgArgs a = {};
-                a.epoch0 = sync_epoch; sync_epoch += 3u * (unsigned) grp_n;     // (the barrier words are never reset: epochs only grow)
-                scal_h.get()[44 + 2 * grp_n + 1] = 0.0;                               // give-up word of this launch
-                a.Linv = Linv; a.ldl = ldl; a.LinvT = LT.get(); a.ldt = n16; a.dS = dS; a.ldd = ldd; a.n = n16; a.V = V.get(); a.ldv = n16;
-                a.k0 = k; a.nsteps = grp_n; a.hprev = hprev; a.blk = bv.get(); a.t1 = b1.get(); a.t2 = b2.get(); a.xw = b1.get() + n16;     // (the vector blocks are n16 x 8: column 1 of b1 is free)
-                a.out = scal_h.dev() + 44; a.sync = gsync.get(); a.dbg = dbg2 ? bz.get() + 4 * (size_t) n16 : nullptr;
-                if (n16 <= 2048) hipLaunchKernelGGL(hdm_lanczos_group_kernel<8>, dim3(big_wg), dim3(256), 0, s, a);
-                else hipLaunchKernelGGL(hdm_lanczos_group_kernel<16>, dim3(big_wg), dim3(256), 0, s, a);
-                HDM_HIP_CHECK(hipGetLastError());
-                HDM_HIP_CHECK(hipStreamSynchronize(s));
-                for (int q = 0; q < 2 * grp_n + 1; ++q) grp[q] = scal_h.get()[44 + q];
-                if (scal_h.get()[44 + 2 * grp_n + 1] != 0.0) {
-                    HDM_HIP_CHECK(hipMemsetAsync(gsync.get(), 0, sizeof(unsigned) * (64 + LZG_WG), s));
-                    // a grid-wide wait ran out (the workgroups were not all resident): this object goes back to a launch per
-                    // product for good, and this test starts over -- nothing of it has left the object yet
-                    fprintf(stderr, "[hdsdp_mi355x] lanczos: grid-wide wait timed out, falling back to one launch per product\n");
-                    big_ok = false;
-                    return solve(Linv, ldl, dS, ldd, s, maxStep, steps);
-                }
-            }
-            hs[0] = grp[2 * (k - grp_k0)]; hs[1] = grp[2 * (k - grp_k0) + 1];
-        } else {
-            // large blocks: the steps up to the next Ritz check are queued back to back (4 launches each: three products and
-            // the recurrence, which takes the previous step's norm from device memory); one copy and one synchronisation
-            // per group.  A zero norm inside a group ends the reference's loop at that step: the host stops there too and
-            // what the later steps of the group computed is never looked at.
-            if (grp_k0 < 0 || k >= grp_k0 + grp_n) {
-                grp_k0 = k;
-                grp_n = group_env ? std::min(std::min(checkFreq - (k % checkFreq), md - k), 8) : 1;
-                for (int q = 0; q < grp_n; ++q) {
-                    const int kk = k + q;
-                    if (apply(Linv, ldl, dS, ldd, bv.get(), nullptr, s)) return 1;
-                    hipLaunchKernelGGL(hdm_lanczos_step_kernel, dim3(1), dim3(1024), 0, s, part.get(), LZ_NCHUNK, bw.get(),
-                                       kk > 0 ? V.get() + (size_t) (kk - 1) * n16 : nullptr,
-                                       q > 0 ? scal_h.dev() + 44 + 2 * (q - 1) + 1 : scal_h.dev() + 43,
-                                       V.get() + (size_t) kk * n16, V.get() + (size_t) (kk + 1) * n16, bv.get(), n16, scal_h.dev() + 44 + 2 * q);
-                }
-                HDM_HIP_CHECK(hipGetLastError());
-                HDM_HIP_CHECK(hipStreamSynchronize(s));
-                for (int q = 0; q < 2 * grp_n; ++q) grp[q] = scal_h.get()[44 + q];
-                // the last norm of this group is the next group's hprev: keep it where the next group's first step reads it
-                scal_h.get()[43] = scal_h.get()[44 + 2 * (grp_n - 1) + 1];
-            }
-            hs[0] = grp[2 * (k - grp_k0)]; hs[1] = grp[2 * (k - grp_k0) + 1];
-        }
-        const double vAlp = hs[0], normPres = hs[1];
-        Hm(k, k) = -vAlp;
-        if (normPres > 0.0) Hm(k + 1, k) = Hm(k, k + 1) = normPres;
+};
 
-        if ((k + 1) % checkFreq == 0 || k > md - 1 || normPres == 0.0) {
-            const int kp = k + 1;
-            std::vector<double> U((size_t) kp * kp);
-            for (int j = 0; j < kp; ++j)
-                for (int i = 0; i < kp; ++i) U[(size_t) j * kp + i] = 0.5 * (Hm(i, j) + Hm(j, i));
-            if (!tridiag_eig(kp, U, d, Y)) jacobi_eig(kp, U, d, Y);
-            const double eig1 = d[kp - 1], eig2 = kp > 1 ? d[kp - 2] : d[kp - 1];
-            // (sign convention as in the single-launch form: largest-magnitude component positive)
-            for (int col : {kp - 1, kp > 1 ? kp - 2 : kp - 1}) {
-                double *yc = &Y[(size_t) col * kp], big = 0.0;
-                for (int r = 0; r < kp; ++r) if (fabs(yc[r]) > fabs(big)) big = yc[r];
-                if (big < 0.0) for (int r = 0; r < kp; ++r) yc[r] = -yc[r];
-            }
-            const double *y1 = &Y[(size_t) (kp - 1) * kp], *y2 = kp > 1 ? &Y[(size_t) (kp - 2) * kp] : y1;
-            const double resiVal = fabs(Hm(kp, k) * y1[k]);
-            if (resiVal < 1e-04 || k >= md - 1) {
-                // z1 = V y1 ; z2 = Op z1 ; warm start <- z2 ; resiVal1 = | z2 - eig1 z1 |
-                // z2' = V y2 ; resiVal2 = | Op z2' - eig1 z2' |   (the reference uses eig1 here too, :262-266)
-                // (both coefficient vectors go into the mapped block, everything is queued, one synchronisation)
-                for (int r = 0; r < kp; ++r) { scal_h.get()[8 + r] = y1[r]; scal_h.get()[64 + r] = y2[r]; }
-                hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, V.get(), (long) n16, kp, scal_h.dev() + 8, bz.get(), n16);
-                if (apply(Linv, ldl, dS, ldd, bz.get(), bw.get(), s)) return 1;
-                HDM_HIP_CHECK(hipMemcpyAsync(warm.get(), bw.get(), sizeof(double) * n16, hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, bw.get(), bz.get(), eig1, n16, scal_h.dev() + 2);
-                hipLaunchKernelGGL(hdm_lincomb_kernel, dim3(1), dim3(1024), 0, s, V.get(), (long) n16, kp, scal_h.dev() + 64, bz.get(), n16);
-                if (apply(Linv, ldl, dS, ldd, bz.get(), bw.get(), s)) return 1;
-                hipLaunchKernelGGL(hdm_resnorm_kernel, dim3(1), dim3(1024), 0, s, bw.get(), bz.get(), eig1, n16, scal_h.dev() + 3);
-                HDM_HIP_CHECK(hipGetLastError());
-                HDM_HIP_CHECK(hipStreamSynchronize(s));
-                const double r12[2] = {scal_h.get()[2], scal_h.get()[3]};
-                // after the second apply() the vector block bv still holds v_{k+1}: the recurrence can continue
-                const double resiVal1 = r12[0], resiVal2 = r12[1];
-                const double resiDiff = eig1 - eig2 - resiVal2;
-                double gam = (resiDiff > 0) ? resiDiff : 1e-16;
-                const double sq = resiVal1 * resiVal1 / gam;
-                gam = resiVal1 < sq ? resiVal1 : sq;
-                if (gam < 1e-03 || gam + eig1 <= 0.5) {
-                    step = (gam + eig1 <= 0.0) ? INFINITY : 1.0 / (gam + eig1);
-                    break;
-                } else {
-                    if (normPres == 0.0) return 1;
-                    step = 1.0 / (gam + eig1);
-                }
-            }
+}  // namespace
+
+int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, hipStream_t s, double *maxStep, int *steps) {
+    static const bool dbg2 = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e) >= 2; }();
+    for (;;) {
+        const HdmLzForm form = hdm_lz_form(n16, hdm_lz_switches(), big_ok, hdm_flow_shared_device(), cus);
+        if (form == LZ_FORM_WHOLE_RESIDENT || form == LZ_FORM_WHOLE_GLOBAL) return lz_solve_whole(*this, form, Linv, ldl, dS, ldd, s, maxStep, steps);
+        LzDeviceBackend be = {*this, form, Linv, ldl, dS, ldd, s, nullptr};
+        if (dbg2 && be.grouped()) be.dbg = bz.get() + 4 * (size_t) n16;
+        double step = 0.0;
+        int k = 0;
+        const int rc = hdm_lz_drive(be, &step, &k);
+        if (rc == LZ_RC_RETRY) continue;             // (big_ok is cleared: the form rule answers "queued" now)
+        if (rc) return 1;
+        if (be.dbg) {
+            double t[10];
+            HDM_HIP_CHECK(hipMemcpy(t, be.dbg, sizeof(t), hipMemcpyDeviceToHost));
+            fprintf(stderr, "[hdsdp_mi355x ratio] group kernel, workgroup 0, us: Linv^T v %.0f | wait %.0f | dS t1 %.0f | wait %.0f | Linv t2 + x %.0f | wait %.0f | "
+                            "alpha, norm, v_{k+1} %.0f\n", t[0] / 100, t[1] / 100, t[2] / 100, t[3] / 100, t[4] / 100, t[5] / 100, t[6] / 100);
         }
+        nComputed += 1;
+        if (maxStep) *maxStep = step;
+        if (steps) *steps = k;
+        return 0;
     }
-    if (big && dbg2) {
-        double t[10];
-        HDM_HIP_CHECK(hipMemcpy(t, bz.get() + 4 * (size_t) n16, sizeof(t), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[hdsdp_mi355x ratio] group kernel, workgroup 0, us: Linv^T v %.0f | wait %.0f | dS t1 %.0f | wait %.0f | Linv t2 + x %.0f | wait %.0f | "
-                        "alpha, norm, v_{k+1} %.0f\n", t[0] / 100, t[1] / 100, t[2] / 100, t[3] / 100, t[4] / 100, t[5] / 100, t[6] / 100);
-    }
-    nComputed += 1;
-    if (maxStep) *maxStep = step;
-    if (steps) *steps = k;
-    return 0;
 }
 
 // one kernel of this translation unit (= one code object): what the preload thread asks the runtime about (engine.hip: preload_modules)
