@@ -34,7 +34,7 @@ EXPORTS = [
     "HMiConeCheckIsInterior", "HMiConeGetLogBarrier", "HMiConeRatioTest", "HMiLanczosStartVector", "HMiConeGetPrimal", "HMiConeCheckIsInteriorExpert",
     "HMiConeAddStepToBufferAndCheck", "HMiConeReduceResi", "HMiConeSetPerturb", "HMiConeGetCoeffNorm", "HMiConeGetObjNorm",
     "HMiConeScalByConstant", "HMiConeComputeATimesXpy", "HMiConeComputeXDotS", "HMiConeComputeTraceCX", "HMiConeGetDual", "HMiConeGetPresolve", "HMiConeDetectFeature", "HMiConeGetDualMatrix",
-    "HMiConeGetTraces", "HMiConeGetPath", "HMiConeSweepInfo", "HMiConeGetStreaming", "HMiConeUseSweepCopy", "HMiKKTSetHostMirror", "HMiConeSetExchange", "HMiConeSetExchangePieces", "HMiConeGetExchangeStats", "HMiConeGetPrimalRoute", "HMiConeGetPrimalProfile", "HMiConeGetBuildProfile", "HMiConeBuildPrimalXSXDirection",
+    "HMiConeGetTraces", "HMiConeGetPath", "HMiConeGetDirectRows", "HMiConeSweepInfo", "HMiConeGetStreaming", "HMiConeUseSweepCopy", "HMiKKTSetHostMirror", "HMiConeSetExchange", "HMiConeSetExchangePieces", "HMiConeGetExchangeStats", "HMiConeGetPrimalRoute", "HMiConeGetPrimalProfile", "HMiConeGetBuildProfile", "HMiConeBuildPrimalXSXDirection",
     "HMiConeGetExchangeBuffers", "HMiConeSetExchangeBuffers", "HMiKKTDeviceMatrix", "HMiKKTGetRows", "HMiKKTGetDiagTarget", "HMiKKTGetMatrixTraffic", "HMiDeviceInit",
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiGetAssembleCounts", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
@@ -150,6 +150,7 @@ def load_library():
         "HMiConeGetDualMatrix": (C.c_int, [vp, dp]),
         "HMiConeGetTraces": (C.c_int, [vp, dp]),
         "HMiConeGetPath": (C.c_int, [vp]),
+        "HMiConeGetDirectRows": (None, [vp, ip, ip, ip, ip]),
         "HMiConeSweepInfo": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "HMiConeGetStreaming": (C.c_int, [vp, ip]),
         "HMiConeUseSweepCopy": (C.c_int, [vp, C.c_int]),
@@ -582,6 +583,13 @@ class SDPCone:
     @property
     def path(self):
         return load_library().HMiConeGetPath(self._h)
+
+    def direct_rows(self):
+        """(direct rows, rank-one ones among them, congruence rows, kmax) of a congruence + Gram block whose low-rank rows are
+        built without the congruence (HMiConeGetDirectRows); all zero for a cone without the form"""
+        v = [C.c_int(0) for _ in range(4)]
+        load_library().HMiConeGetDirectRows(self._h, *[C.byref(x) for x in v])
+        return tuple(int(x.value) for x in v)
 
     def use_sweep_copy(self, on):
         _check(load_library().HMiConeUseSweepCopy(self._h, int(bool(on))), "HMiConeUseSweepCopy")

@@ -21,6 +21,7 @@
 #include "dual_state.h"
 #include "kkt_store.h"
 #include "schur.h"
+#include "direct_rows.h"
 #include "lanczos.h"
 #include "lu.h"
 #include "small.h"

@@ -178,6 +178,14 @@ hdsdp_retcode HMiConeGetTraces(hdsdp_cone *cone, double *trA) {
     return HDSDP_RETCODE_OK;
 }
 int HMiConeGetPath(hdsdp_cone *cone) { const MiCone *c = cone_data(cone); return c ? c->path : -1; }
+void HMiConeGetDirectRows(hdsdp_cone *cone, int *nDirect, int *nRankOne, int *nCongruence, int *kmax) {
+    const MiCone *c = (cone && cone->coneBuildSchur == cone_build_schur) ? (const MiCone *) cone->coneData : nullptr;
+    const bool on = c && c->dr_n > 0;
+    if (nDirect) *nDirect = on ? c->dr_n : 0;
+    if (nRankOne) *nRankOne = on ? c->dr_r1 : 0;
+    if (nCongruence) *nCongruence = on ? c->mloc - c->dr_n : 0;
+    if (kmax) *kmax = on ? c->dr_kmax : 0;
+}
 int HMiConeUseSweepCopy(hdsdp_cone *cone, int on) {
     MiCone *c = cone_data(cone);
     if (!c || ensure_ctx()) return 1;

@@ -562,6 +562,25 @@ hdsdp_retcode corrector_components(MiCone *c, HdmChol &ch, MiKKTPriv *pv, int m)
     return HDSDP_RETCODE_OK;
 }
 
+// The direct rows of the cone (direct_rows.h): local rows [mloc - dr_n, mloc) of the transformed-row buffer from their terms.
+// U = Linv [a_j] for the rank-one ones is the call build_r1_path makes: the generic role, whose every tile runs the masked loop
+// (DESIGN section 4 records what an unmasked generic tile once did).  With a factor override `ch` is the primal factor object.
+hdsdp_retcode direct_rows_build(MiCone *c, HdmChol &ch) {
+    if (c->dr_r1 > 0) {
+        HdmGemmArgs u = {};
+        u.A = ch.Linv.get(); u.lda = ch.npad; u.B = c->dr_fac.get(); u.ldb = c->n16; u.b_kmajor = 1; u.C = c->dr_U.get(); u.ldc = c->n16;
+        u.M = c->n16; u.N = c->dr_r1_16; u.K = c->n16; u.batch = 1; u.alpha = 1.0; u.klimit = HDM_KLIM_BY_M; u.epilogue = HDM_EPI_STORE;
+        RC(hdm_launch_gemm(u, g.stream));
+    }
+    HdmDirectArgs a = {};
+    a.dst = c->AhatLoc; a.row_stride = c->Lr; a.row0 = c->mloc - c->dr_n; a.nrows = c->dr_n; a.nblk = c->nblk; a.n = c->n;
+    a.terms = c->dr_terms.get(); a.row_ptr = c->dr_ptr.get();
+    a.Linv = ch.Linv.get(); a.ldl = ch.npad; a.U = c->dr_U.get(); a.ldu = c->n16;
+    a.dst_span = (long) hdm_exchange_doubles(cone_layout(c)); a.linv_span = (long) ch.npad * ch.npad; a.u_span = (long) c->dr_U.count();
+    a.max_lcol = c->dr_max_lcol; a.nu = c->dr_r1;
+    return hdm_direct_rows(a, g.stream) ? HDSDP_RETCODE_FAILED : HDSDP_RETCODE_OK;
+}
+
 hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKKT, HdmChol *chOverride) {
     MiLin *l = (MiLin *) c->dualFactor->chol;
     HdmChol &ch = chOverride ? *chOverride : l->ch;
@@ -600,7 +619,8 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
             if (!A) return HDSDP_RETCODE_FAILED;
             RC(congruence_rows(c, ch, A, c->astride, c->astride * (long) c->Bs + opad, nb, q0));
         }
-    } else if (!staged) RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc, 0));
+    } else if (!staged) RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc - c->dr_n, 0));
+    if (c->dr_n > 0) RC(direct_rows_build(c, ch));   // (one device, resident rows: never staged, never streamed)
     if (c->rank == 0) {
         // "I row": A = I => T = Linv, At = Linv Linv^T.  Reuse step 2 with T := Linv.
         HdmGemmArgs k2 = {};

@@ -20,7 +20,16 @@ struct MiCone {
     int path = PATH_GEMM;
     bool synthetic = false;
     MiBlockData blk;           // presolve results (empty rows for synthetic)
-    std::vector<int> own;      // global indices of the owned constraints
+    std::vector<int> own;      // global indices of the owned constraints, in local order: ascending, unless the cone has direct rows
+    // Direct rows (direct_rows.h): local rows [mloc - dr_n, mloc) are written into the transformed-row buffer from their
+    // terms, without the congruence; the local order is then congruence rows (ascending), direct rows (ascending).
+    std::vector<int> own_asc;  // `own` ascending, for the pattern protocol (the same vector's order for a cone without direct rows)
+    int dr_n = 0, dr_r1 = 0, dr_kmax = 0;   // direct rows, the rank-one ones among them, the kmax in force (0: the form is off)
+    int dr_max_lcol = -1;      // largest column of the factor inverse a term names
+    HdmBuf<HdmDirectTerm> dr_terms;   // the term table, row d's terms at [dr_ptr[d], dr_ptr[d + 1])
+    HdmBuf<long> dr_ptr;
+    HdmBuf<double> dr_fac, dr_U;      // n16 x dr_r1_16: the rank-one direct rows' factors (K-major, zero-padded), and L^-1 times them
+    int dr_r1_16 = 0;
     // device data
     HdmBuf<double> Afull;      // mloc x (n16 x n16) constraint matrices in A_L form: strict lower + half diagonal
     HdmZs zs; int zs_state = 0; // zero-suppressed copy of Afull for the S / dS sweeps (schur.h); 0 = not looked at, 1 = in use, -1 = not built
@@ -196,6 +205,7 @@ int cone_alloc_common(MiCone *c) {
     for (int i = c->rank; i < c->m; i += c->world)
         if (!compact || c->blk.rows[i].type != MI_COEFF_ZERO) c->own.push_back(i);
     c->mloc = (int) c->own.size();
+    c->own_asc = c->own;
     const HdmLayout L = hdm_layout(c->n, c->world, compact ? c->mloc : (c->m + c->world - 1) / c->world);   // work_plan.h
     c->n16 = L.n16; c->nblk = L.nblk; c->npb = L.npb; c->npb_loc = L.npb_loc; c->Lr = L.Lr; c->R = L.R; c->astride = L.astride;
     const size_t n2 = (size_t) c->n16 * c->n16, nn = sizeof(double) * n2;
@@ -301,18 +311,19 @@ int cone_kkt_rows(const MiCone *c) {
 int64_t cone_getsymnnz(void *cd) { MiCone *c = (MiCone *) cd; const int64_t k = cone_kkt_rows(c); return k * k; }
 // the two pattern queries of HKKTAllocSparseKKT (hdsdp_schur.c:46-139), with the protocol of the reference's sparse SDP
 // cone (sdpSparseConeAddSymNnzImpl / sdpSparseConeGetSymMapping, hdsdp_conic_sdp.c:2086-2170): columns are visited in
-// order; in the column of its next row the block marks that row and all its later ones.  The positions handed back in
+// order; in the column of its next row the block marks that row and all its later ones (the rows in ascending order: own_asc --
+// a cone with direct rows keeps `own` in another).  The positions handed back in
 // the second call are not kept: the engine's builders write a dense device matrix at global (row, column) indices and
 // the operator gathers the pattern's entries from it.
 void cone_add_sym_nz(void *cd, int iCol, int *schurMatCol) {
     MiCone *c = (MiCone *) cd;
-    if (c->kkt_counted >= c->mloc || c->own[c->kkt_counted] != iCol) return;
-    for (int e = c->kkt_counted; e < c->mloc; ++e) schurMatCol[c->own[e]] = 1;
+    if (c->kkt_counted >= c->mloc || c->own_asc[c->kkt_counted] != iCol) return;
+    for (int e = c->kkt_counted; e < c->mloc; ++e) schurMatCol[c->own_asc[e]] = 1;
 }
 void cone_get_kkt_map(void *cd, int iCol, int *schurMatCol) {
     (void) schurMatCol;
     MiCone *c = (MiCone *) cd;
-    if (c->kkt_counted < c->mloc && c->own[c->kkt_counted] == iCol) c->kkt_counted += 1;
+    if (c->kkt_counted < c->mloc && c->own_asc[c->kkt_counted] == iCol) c->kkt_counted += 1;
 }
 
 // The A_L forms of the owned rows q0 .. q0 + count - 1 on the device (stride c->astride): the resident storage, or -- streamed

@@ -202,6 +202,62 @@ static int natural_path(const MiBlockData &blk, int nRow, int nCol, int world) {
     return path;
 }
 
+// Direct rows (direct_rows.h): decided here, once, before the rows are uploaded -- the rule and the partition are the header's;
+// what stays here is the switch, the new local order (own, rows_own and the first mloc entries of rows_seg: everything uploaded
+// after this call follows it) and the device copies of the term table and of the rank-one rows' factors.
+// HDSDP_MI355X_DIRECT_ROWS: unset = the rule; 0 = off; k > 0 = on whatever the size, kmax = k.
+static_assert(HDM_DR_ZERO == MI_COEFF_ZERO && HDM_DR_SPARSE == MI_COEFF_SPARSE && HDM_DR_DENSE == MI_COEFF_DENSE &&
+              HDM_DR_SPR1 == MI_COEFF_SPR1 && HDM_DR_DSR1 == MI_COEFF_DSR1 && HDM_DR_PATH_GEMM == PATH_GEMM,
+              "direct_rows.h restates the classes of coeff.h and the path numbers");
+static int cone_plan_direct_rows(MiCone *c, int natural, bool force_gemm, bool force_path, bool streamed) {
+    int sw = -1;
+    if (const char *e = getenv("HDSDP_MI355X_DIRECT_ROWS")) sw = std::max(0, atoi(e));
+    const HdmDirectRule rule = hdm_direct_rule(c->world, c->synthetic, streamed, natural, force_gemm, force_path, c->n, c->n16, sw);
+    if (!rule.on || c->mloc == 0 || (int) c->blk.rows.size() != c->m) return 0;
+    std::vector<int> type((size_t) c->m);
+    std::vector<long> stored((size_t) c->m);
+    for (int i = 0; i < c->m; ++i) { type[i] = c->blk.rows[i].type; stored[i] = (long) c->blk.rows[i].idx.size(); }
+    const HdmDirectPlan p = hdm_direct_partition(type, stored, rule);
+    if (p.nDirect == 0 || (int) p.order.size() != c->mloc) return 0;
+    c->own = p.order;
+    c->dr_n = p.nDirect; c->dr_r1 = p.nRankOne; c->dr_kmax = rule.kmax;
+    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->rows_seg.get(), c->own.data(), sizeof(int) * (size_t) c->mloc));
+    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->rows_own.get(), c->own.data(), sizeof(int) * (size_t) c->mloc));
+    std::vector<HdmDirectTerm> terms;
+    std::vector<long> ptr(1, 0L);
+    terms.reserve((size_t) p.nterms);
+    c->dr_r1_16 = (int) hdm_roundup(std::max(1, p.nRankOne), 16);
+    std::vector<double> fac((size_t) c->n16 * c->dr_r1_16, 0.0);   // K-major, zero-padded to n16
+    int slot = 0;
+    for (int q = p.nCongruence; q < c->mloc; ++q) {
+        const MiCoeff &co = c->blk.rows[c->own[q]];
+        const bool r1 = hdm_direct_is_r1(co.type);
+        hdm_direct_terms(co.type, c->n, co.idx, co.val, co.sign, slot, terms);
+        if (r1) {
+            for (int r = 0; r < c->n; ++r) fac[(size_t) slot * c->n16 + r] = co.factor[r];
+            slot += 1;
+        }
+        ptr.push_back((long) terms.size());
+    }
+    c->dr_max_lcol = -1;
+    for (const HdmDirectTerm &t : terms) {
+        if ((t.x < 0) != (t.y < 0) || t.x >= c->n || t.y >= c->n || -1 - t.x >= slot || -1 - t.y >= slot) {
+            fprintf(stderr, "[hdsdp_mi355x] direct rows: a term names a vector outside the block\n");
+            return 1;
+        }
+        c->dr_max_lcol = std::max(c->dr_max_lcol, std::max(t.x, t.y));
+    }
+    HDM_HIP_CHECK(c->dr_terms.alloc(std::max<size_t>(1, terms.size())));
+    HDM_HIP_CHECK(c->dr_ptr.alloc(ptr.size()));
+    HDM_HIP_CHECK(c->dr_fac.alloc(fac.size()));
+    HDM_HIP_CHECK(c->dr_U.alloc(fac.size()));
+    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->dr_terms.get(), terms.data(), sizeof(HdmDirectTerm) * terms.size()));
+    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->dr_ptr.get(), ptr.data(), sizeof(long) * ptr.size()));
+    HDM_HIP_CHECK(hdm_memcpy_h2d_sync(c->dr_fac.get(), fac.data(), sizeof(double) * fac.size()));
+    HDM_HIP_CHECK(hdm_memset_sync(c->dr_U.get(), 0, sizeof(double) * fac.size()));
+    return 0;
+}
+
 // the device data of one SDP block for rank `rank` of `world` on the calling thread's context, from the block's presolved
 // host data.  A shard of a sharded block (world > 1) copies the entries of its own rows only (the others keep class, counts
 // and trace): W shards of one block together hold one more copy of the data, not W.  With `take` the source is moved from.
@@ -229,7 +285,8 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
     if (cone_alloc_common(c)) return HDSDP_RETCODE_MEMORY;
     c->trA.assign((size_t) nRow, 0.0);
     for (int i = 0; i < nRow; ++i) c->trA[i] = c->blk.rows[i].trace;
-    c->path = natural_path(c->blk, nRow, nCol, world);
+    const int natural = natural_path(c->blk, nRow, nCol, world);
+    c->path = natural;
     const char *force = getenv("HDSDP_MI355X_FORCE_GEMM");
     if (force && atoi(force)) c->path = PATH_GEMM;
     const char *forcesp = getenv("HDSDP_MI355X_FORCE_PATH");
@@ -239,6 +296,7 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
         CreateTimer t_(1);
         // (rows too many to stay resident beside the work buffers -- congruence + Gram path only -- live in the compressed copy)
         const bool stream = (c->path == PATH_GEMM) && cone_wants_streaming(c);
+        if (cone_plan_direct_rows(c, natural, force && atoi(force), forcesp != nullptr, stream)) return HDSDP_RETCODE_MEMORY;
         if (stream ? upload_streamed_rows(c) : upload_dense_rows(c)) return HDSDP_RETCODE_MEMORY;   // the dense forms also feed the S assembly
     }
     if (c->path == PATH_R1) {

@@ -2,12 +2,24 @@
 #pragma once
 #include "hdm_common.h"
 #include "bsparse.h"
+#include "direct_rows.h"
 #include <functional>
 
 int hdm_unpack_sym(const double *packed, long pstride, double *full, long fstride, int n, int ld, int batch, hipStream_t s);
 int hdm_synth_fill(double *full, long fstride, int n, int ld, int c0, int batch, hipStream_t s);
 int hdm_synth_obj(double *C, int n, int ld, int m, hipStream_t s);
 int hdm_blocked_eye(double *dst, long row_stride, long row, int nblk, int n, hipStream_t s);
+// The direct rows of a block (direct_rows.h) into the blocked congruence layout: local rows row0 .. row0 + nrows - 1 of dst, every
+// 128-byte line of them, zeros included.  terms / row_ptr: the term table (device), row d's terms at [row_ptr[d], row_ptr[d + 1]).
+// The spans (elements readable / writable from the three pointers), max_lcol (largest column of Linv a term names, -1: none) and
+// nu (columns of U the terms may name) are what the launcher checks the launch against before it runs.
+struct HdmDirectArgs {
+    double *dst; long row_stride, row0; int nrows, nblk, n;
+    const HdmDirectTerm *terms; const long *row_ptr;
+    const double *Linv; long ldl; const double *U; long ldu;
+    long dst_span, linv_span, u_span; int max_lcol, nu;
+};
+int hdm_direct_rows(const HdmDirectArgs &a, hipStream_t s);
 int hdm_slab_reduce(const double *slabs, long slab_stride, int nsplit, double *out, long total, long R, hipStream_t s);
 int hdm_extract(const double *G, long ldg, long R, long pI, const int *rows_seg, const HdmMatView &Mv, double *asinv,
                 double *asinvrd, double *asinvc, double *scal, double Rd, int hsd, hipStream_t s);

@@ -5,6 +5,7 @@
 //                               LDS tile transpose so both triangles are written coalesced
 //   * hdm_synth_kernel          SURVEY.md 8(d) splitmix64 generator evaluated counter-based on device
 //   * hdm_blocked_eye_kernel    identity in the 16x16-blocked congruence layout (the "S row")
+//   * hdm_direct_rows_kernel    low-rank constraint rows straight into that layout (direct_rows.h)
 //   * hdm_slab_reduce_kernel    split-K slab reduction of the Gram GEMM (deterministic order)
 //   * hdm_extract_kernel        scatter Gram rows/cols into M, ASinv, ASinvRdSinv, ASinvCSinv, scalars
 //   * hdm_sym_combine_kernel    S = tau*C - sum_i y_i A_i - Rd*I  (hdsdp_conic_sdp.c:343-402), lower part
@@ -181,6 +182,60 @@ __global__ void hdm_blocked_eye_kernel(double *__restrict__ dst, long row_stride
     long pb = sub * 16 + c;
     int g = b * 16 + c;
     dst[(pb * row_stride + row) * 16 + r] = (r == c && g < n) ? 1.0 : 0.0;
+}
+
+// The direct rows of a block (direct_rows.h): transformed row d at matrix position (16 bi + r, 16 bj + c) is the sum of its terms,
+// c (x_r y_s + y_r x_s), in table order; it goes to dst[((16 sub + c) row_stride + row0 + d) 16 + r], times sqrt(2) off the block
+// diagonal as the HDM_EPI_BLOCKED epilogue has it (gemm_tile.h), an exact zero at or beyond n.  HBM-write bound.
+// One workgroup = one 16 x 16 sub-block of 16 consecutive direct rows; lane (row, r) holds the 16 values of its matrix row in
+// registers and stores them p-block by p-block, so that for a fixed p-block a wave writes four adjacent 128-byte lines.  The
+// terms run in chunks of HDM_DR_TCH: a row's x / y slices over the sub-block's columns are staged in LDS (each lane loads one
+// entry, all 16 lanes of the row read all of them), its slices over the sub-block's rows stay in registers.
+constexpr int HDM_DR_TCH = 8;
+constexpr int HDM_DR_LDS_ROW = HDM_DR_TCH * 16 + 2;   // (+2: the four rows of a wave read from different banks)
+__global__ __launch_bounds__(256) void hdm_direct_rows_kernel(HdmDirectArgs a) {
+    __shared__ double sx[16 * HDM_DR_LDS_ROW], sy[16 * HDM_DR_LDS_ROW];
+    const int rl = threadIdx.x >> 4, r = threadIdx.x & 15;
+    const long sub = blockIdx.x;
+    const int bj = hdm_blk_col_of(sub, a.nblk), bi = bj + (int) (sub - hdm_blk_col_start(bj, a.nblk));
+    const long d0 = (long) blockIdx.y * 16, d = d0 + rl;
+    const bool live = d < a.nrows;
+    const long t0 = live ? a.row_ptr[d] : 0, t1 = live ? a.row_ptr[d + 1] : 0;
+    long kgroup = 0;   // the longest row of the group: the barriers below are reached by every lane
+    for (int q = 0; q < 16; ++q) {
+        const long k = (d0 + q < a.nrows) ? a.row_ptr[d0 + q + 1] - a.row_ptr[d0 + q] : 0;
+        kgroup = k > kgroup ? k : kgroup;
+    }
+    const long gi = 16L * bi + r, gj0 = 16L * bj;
+    double *mx = sx + rl * HDM_DR_LDS_ROW, *my = sy + rl * HDM_DR_LDS_ROW;
+    double acc[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) acc[c] = 0.0;
+    for (long e0 = 0; e0 < kgroup; e0 += HDM_DR_TCH) {
+        __syncthreads();
+        for (int t = 0; t < HDM_DR_TCH; ++t) {
+            const long e = t0 + e0 + t;
+            if (e >= t1) break;
+            const HdmDirectTerm tm = a.terms[e];
+            mx[t * 16 + r] = hdm_direct_vec(tm.x, gj0 + r, a.Linv, a.ldl, a.U, a.ldu);
+            my[t * 16 + r] = hdm_direct_vec(tm.y, gj0 + r, a.Linv, a.ldl, a.U, a.ldu);
+        }
+        __syncthreads();
+        for (int t = 0; t < HDM_DR_TCH; ++t) {
+            const long e = t0 + e0 + t;
+            if (e >= t1) break;
+            const HdmDirectTerm tm = a.terms[e];
+            const double xr = hdm_direct_vec(tm.x, gi, a.Linv, a.ldl, a.U, a.ldu);
+            const double yr = hdm_direct_vec(tm.y, gi, a.Linv, a.ldl, a.U, a.ldu);
+#pragma unroll
+            for (int c = 0; c < 16; ++c) acc[c] = hdm_direct_fma(acc[c], tm.c, xr, my[t * 16 + c], yr, mx[t * 16 + c]);
+        }
+    }
+    if (!live) return;
+    const double sc = (bi == bj) ? 1.0 : 1.4142135623730951;
+    double *q = a.dst + (sub * 16 * a.row_stride + a.row0 + d) * 16 + r;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) q[(long) c * a.row_stride * 16] = (gi < a.n && gj0 + c < a.n) ? sc * acc[c] : 0.0;
 }
 
 // out = sum over the split-K slabs, in slab order (deterministic).  The Gram launch writes lower 128-tiles only, so
@@ -827,6 +882,28 @@ int hdm_synth_obj(double *C, int n, int ld, int m, hipStream_t s) {
 
 int hdm_blocked_eye(double *dst, long row_stride, long row, int nblk, int n, hipStream_t s) {
     hipLaunchKernelGGL(hdm_blocked_eye_kernel, dim3(nblk), dim3(256), 0, s, dst, row_stride, row, nblk, n);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Bounds of a direct-rows launch, checked here before it runs.  Stores: the last line written is that of local row
+// row0 + nrows - 1 in p-block 16 nsub - 1, i.e. element ((16 nsub - 1) row_stride + row0 + nrows - 1) 16 + 15 of dst.  Loads: entry
+// i <= 16 nblk - 1 of column v <= max_lcol of Linv (element i + v ldl) or of column j < nu of U (element i + j ldu); the terms and
+// row_ptr are the cone's own table, whose vector indices were held to max_lcol and nu when it was made.
+int hdm_direct_rows(const HdmDirectArgs &a, hipStream_t s) {
+    if (a.nrows <= 0) return 0;
+    const long n16 = 16L * a.nblk, nsub = (long) a.nblk * (a.nblk + 1) / 2, groups = (a.nrows + 15L) / 16;
+    const long dst_need = ((16 * nsub - 1) * a.row_stride + a.row0 + a.nrows - 1) * 16 + 16;
+    const long linv_need = a.max_lcol >= 0 ? (long) a.max_lcol * a.ldl + n16 : 0;
+    const long u_need = a.nu > 0 ? (long) (a.nu - 1) * a.ldu + n16 : 0;
+    if (a.row0 < 0 || a.row0 + a.nrows > a.row_stride || a.n > n16 || a.max_lcol >= a.n || a.ldl < n16 || a.ldu < n16 ||
+        dst_need > a.dst_span || linv_need > a.linv_span || u_need > a.u_span || groups > 65535 || nsub > 2147483647L) {
+        fprintf(stderr, "[hdsdp_mi355x] direct rows: the launch needs %ld / %ld / %ld elements of the row buffer, the factor inverse and "
+                        "the transformed factors, the caller vouches for %ld / %ld / %ld: launch refused\n",
+                dst_need, linv_need, u_need, a.dst_span, a.linv_span, a.u_span);
+        return 1;
+    }
+    hipLaunchKernelGGL(hdm_direct_rows_kernel, dim3((unsigned) nsub, (unsigned) groups), dim3(256), 0, s, a);
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

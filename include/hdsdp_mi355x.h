@@ -316,6 +316,13 @@ hdsdp_retcode HMiConeGetDualMatrix(hdsdp_cone *cone, double *S);
 hdsdp_retcode HMiConeGetTraces(hdsdp_cone *cone, double *trA);
 /* which device path the cone's builder uses: 0 = dense congruence + Gram (MFMA), 1 = rank-one */
 int HMiConeGetPath(hdsdp_cone *cone);
+/* Direct rows (csrc/direct_rows.h): on the congruence + Gram path of one device, rows of rank one and
+ * triplet rows of at most *kmax entries are written into the transformed-row buffer in closed form, without the congruence;
+ * the block's other non-zero rows are its congruence rows.  *nDirect such rows, *nRankOne of them rank one, *nCongruence others,
+ * *kmax the entry limit in force.  All zero for a cone without the form (sharded, synthetic, streamed, forced path, below the size
+ * floor, no eligible row, switched off) and for a group cone; HMiConeGetPath still answers 0 for a block with direct rows.
+ * Each output may be NULL.  HDSDP_MI355X_DIRECT_ROWS in the table below. */
+void HMiConeGetDirectRows(hdsdp_cone *cone, int *nDirect, int *nRankOne, int *nCongruence, int *kmax);
 /* the zero-suppressed copy of the constraint data the S / dS sweeps read (csrc/schur.h: HdmZs): returns 1 and the number of
  * stored values / of skyline positions it stands for when the cone has built one, 0 when its sweeps read the dense storage */
 int HMiConeSweepInfo(hdsdp_cone *cone, int64_t *values, int64_t *positions);
@@ -516,6 +523,9 @@ void HMiSDPAFree(HMiSDPA **pp);
  *  HDSDP_MI355X_ZS                by cost   0 / 1 / 2: zero-suppressed copy for the S / dS sweeps (schur.h) test_gpu_switches.py
  *  HDSDP_MI355X_PRIMAL_SIGNED     1         KKT_TYPE_PRIMAL with an indefinite X: signed factor + signed  test_gpu_primal_signed.py
  *                                           Gram correction (route 1); 0: row-by-row fallback / refusal
+ *  HDSDP_MI355X_DIRECT_ROWS      by size   rank-one and short triplet rows of a congruence + Gram block   test_gpu_direct_rows.py
+ *                                           built without the congruence (direct_rows.h); 0: off; k > 0: on
+ *                                           whatever the size, up to k entries per row.  Read at cone creation
  *  HDSDP_MI355X_STREAM_A          by memory 0 / 1: synthetic constraint data resident / regenerated per     test_gpu_streamed.py
  *                                           batch (MiCone::streamed)
  *  HDSDP_MI355X_DEVICE_M          0         1: HKKTInit turns the host mirror of M off when no cone of    test_gpu_device_m.py
