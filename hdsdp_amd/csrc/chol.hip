@@ -670,75 +670,6 @@ int HdmChol::set_reverse_inverse(hipStream_t s) {
     return 0;
 }
 
-// Blocked LDL' without pivoting, in the clothing of the blocked Cholesky above (KKT_TYPE_PRIMAL with an indefinite registered
-// matrix, engine_build.h: build_primal).  Per block column k: the SIGNED register sweep factors the diagonal block as
-// F_kk S_k F_kk^T and inverts F_kk (sweep128.h; S_k = the pivots' signs, F_kk with a positive diagonal); the panel is
-// Q = A_ik inv(F_kk)^T (the same product as the Cholesky panel), F_ik = Q S_k; the trailing update is
-// A22 -= F_ik S_k F_jk^T = F_ik Q^T -- the Cholesky update's product with Q kept aside in Z as its second operand.  Same
-// kernels as enqueue_factor apart from the sweep's flavour and one scaling pass per panel; dense only (no envelope), eager only.
-static int hdm_k128_launch(bool update, const double *A, long lda, const double *B, long ldb, double *C, long ldc, int rows,
-                           hipStream_t s);
-int HdmChol::factor_signed(hipStream_t s, int *info_host, int *nneg_host) {
-    if (!sgn.get()) {
-        HDM_HIP_CHECK(sgn.alloc((size_t) npad));
-        HDM_HIP_CHECK(sinfo_dev.alloc(2));
-        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_potrf_diag_sweep_signed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          DIAG_SWEEP_LDS_DOUBLES * (int) sizeof(double)));
-    }
-    if (!Z.get() && nblk > 1) HDM_HIP_CHECK(Z.alloc((size_t) npad * NB));
-    hipLaunchKernelGGL(hdm_zero_words_kernel, dim3(1), dim3(64), 0, s, sinfo_dev.get(), 2);
-    HDM_HIP_CHECK(hipGetLastError());
-    const long ld = npad;
-    static const bool k128 = [] { const char *e = getenv("HDM_CHOL_K128"); return !(e && atoi(e) == 0); }();
-    for (int k = 0; k < nblk; ++k) {
-        double *Akk = L.get() + (long) k * NB * (ld + 1);
-        hipLaunchKernelGGL(hdm_potrf_diag_sweep_signed_kernel, dim3(1), dim3(SM_T), DIAG_SWEEP_LDS_DOUBLES * sizeof(double), s, Akk, ld,
-                           Dinv.get() + (long) k * NB * NB, sinfo_dev.get(), k * NB, std::max(1, std::min(NB, n - k * NB)), sgn.get() + (long) k * NB);
-        HDM_HIP_CHECK(hipGetLastError());
-        const int rows = npad - (k + 1) * NB;
-        if (rows <= 0) break;
-        double *P = Akk + NB;
-        if (k128 && rows % 64 == 0 && ld < (1L << 20)) {
-            if (hdm_k128_launch(false, P, ld, Dinv.get() + (long) k * NB * NB, NB, P, ld, rows, s)) return 1;
-        } else {
-            HdmGemmArgs g = {};
-            g.A = P; g.lda = ld; g.B = Dinv.get() + (long) k * NB * NB; g.ldb = NB; g.C = P; g.ldc = ld;
-            g.M = rows; g.N = NB; g.K = NB; g.batch = 1; g.alpha = 1.0; g.beta = 0.0; g.epilogue = HDM_EPI_STORE;
-            if (hdm_launch_gemm(g, s)) return 1;
-        }
-        const long tot = (long) rows * NB;
-        hipLaunchKernelGGL(hdm_signed_panel_kernel, dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, s, P, ld, Z.get(), (long) npad,
-                           (const double *) (sgn.get() + (long) k * NB), rows);
-        HDM_HIP_CHECK(hipGetLastError());
-        if (k128 && rows % 64 == 0 && ld < (1L << 20)) {
-            if (hdm_k128_launch(true, P, ld, Z.get(), (long) npad, Akk + (long) NB * (ld + 1), ld, rows, s)) return 1;
-        } else {
-            HdmGemmArgs u = {};
-            u.A = P; u.lda = ld; u.B = Z.get(); u.ldb = npad; u.C = Akk + (long) NB * (ld + 1); u.ldc = ld;
-            u.M = rows; u.N = rows; u.K = NB; u.batch = 1; u.alpha = -1.0; u.beta = 1.0;
-            u.lower_only = 1; u.epilogue = HDM_EPI_STORE;
-            if (hdm_launch_gemm(u, s)) return 1;
-        }
-    }
-    int info[2] = {0, 0};
-    HDM_HIP_CHECK(hipMemcpyAsync(info, sinfo_dev.get(), sizeof(int) * 2, hipMemcpyDeviceToHost, s));
-    HDM_HIP_CHECK(hipStreamSynchronize(s));
-    if (info[0] > n) info[0] = 0;
-    if (info_host) *info_host = info[0];
-    if (nneg_host) *nneg_host = info[1];
-    factored = (info[0] == 0);
-    have_inv = false;
-    logdet_ok = false;
-    return 0;
-}
-
-int HdmChol::reverse_signs(double *sig_dev, hipStream_t s) {
-    if (!sgn.get() || !factored) return 1;
-    hipLaunchKernelGGL(hdm_reverse_signs_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, (const double *) sgn.get(), sig_dev, n, npad);
-    HDM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
 // capture `body` (launches on stream s with fixed arguments) into an executable graph; nullptr if that is not possible
 template <class F> static hipGraphExec_t hdm_capture(hipStream_t s, F body) {
     hipGraph_t graph = nullptr;
@@ -872,6 +803,23 @@ static int hdm_k128_launch(bool update, const double *A, long lda, const double 
     return 0;
 }
 
+// The two GEMMs of a block column of the blocked factorisations: through the K = 128 kernel above where it applies (rows a
+// multiple of 64, a leading dimension its offsets cover, HDM_CHOL_K128 not 0), as the plain product of the GEMM family otherwise.
+static bool hdm_chol_k128(int rows, long ld) {
+    static const bool k128 = [] { const char *e = getenv("HDM_CHOL_K128"); return !(e && atoi(e) == 0); }();
+    return k128 && rows % 64 == 0 && ld < (1L << 20);
+}
+// panel product, in place: P <- P * Dinv_k
+static int hdm_chol_panel(double *P, long ld, const double *Dk, int rows, hipStream_t s) {
+    if (hdm_chol_k128(rows, ld)) return hdm_k128_launch(false, P, ld, Dk, NB, P, ld, rows, s);
+    return hdm_launch_gemm(hdm_gemm_product(P, ld, rows, NB, NB, 1.0, hdm_mmajor(P, ld), hdm_mmajor(Dk, NB)), s);
+}
+// trailing update, lower only: A22 -= P * Q^T   (Q = P: the Cholesky factor; Q = Z: the signed factor)
+static int hdm_chol_update(double *A22, long ld, const double *P, const double *Q, long ldq, int rows, hipStream_t s) {
+    if (hdm_chol_k128(rows, ld)) return hdm_k128_launch(true, P, ld, Q, ldq, A22, ld, rows, s);
+    return hdm_launch_gemm(hdm_gemm_product(A22, ld, rows, rows, NB, -1.0, hdm_mmajor(P, ld), hdm_mmajor(Q, ldq), 1.0, hdm_lower()), s);
+}
+
 __global__ void hdm_zero_word_kernel(int *p) { *p = 0; }
 
 int HdmChol::enqueue_factor(hipStream_t s) {
@@ -896,23 +844,60 @@ int HdmChol::enqueue_factor(hipStream_t s) {
         const int rows = env_colh.empty() ? npad - (k + 1) * NB : (env_colh[k] - k) * NB;
         if (rows <= 0) continue;
         double *P = Akk + NB;  // panel below the diagonal block
-        static const bool k128 = [] { const char *e = getenv("HDM_CHOL_K128"); return !(e && atoi(e) == 0); }();
-        if (k128 && rows % 64 == 0 && ld < (1L << 20)) {
-            if (hdm_k128_launch(false, P, ld, Dinv.get() + (long) k * NB * NB, NB, P, ld, rows, s)) return 1;
-            if (hdm_k128_launch(true, P, ld, P, ld, Akk + (long) NB * (ld + 1), ld, rows, s)) return 1;
-            continue;
-        }
-        HdmGemmArgs g = {};
-        g.A = P; g.lda = ld; g.B = Dinv.get() + (long) k * NB * NB; g.ldb = NB; g.C = P; g.ldc = ld;
-        g.M = rows; g.N = NB; g.K = NB; g.batch = 1; g.alpha = 1.0; g.beta = 0.0;
-        g.epilogue = HDM_EPI_STORE;
-        if (hdm_launch_gemm(g, s)) return 1;
-        HdmGemmArgs u = {};
-        u.A = P; u.lda = ld; u.B = P; u.ldb = ld; u.C = Akk + (long) NB * (ld + 1); u.ldc = ld;
-        u.M = rows; u.N = rows; u.K = NB; u.batch = 1; u.alpha = -1.0; u.beta = 1.0;
-        u.lower_only = 1; u.epilogue = HDM_EPI_STORE;
-        if (hdm_launch_gemm(u, s)) return 1;
+        if (hdm_chol_panel(P, ld, Dinv.get() + (long) k * NB * NB, rows, s)) return 1;
+        if (hdm_chol_update(Akk + (long) NB * (ld + 1), ld, P, P, ld, rows, s)) return 1;
     }
+    return 0;
+}
+
+// Blocked LDL' without pivoting, in the clothing of the blocked Cholesky above (KKT_TYPE_PRIMAL with an indefinite registered
+// matrix, engine_build.h: build_primal).  Per block column k: the SIGNED register sweep factors the diagonal block as
+// F_kk S_k F_kk^T and inverts F_kk (sweep128.h; S_k = the pivots' signs, F_kk with a positive diagonal); the panel is
+// Q = A_ik inv(F_kk)^T (the same product as the Cholesky panel), F_ik = Q S_k; the trailing update is
+// A22 -= F_ik S_k F_jk^T = F_ik Q^T -- the Cholesky update's product with Q kept aside in Z as its second operand.  Same
+// kernels as enqueue_factor apart from the sweep's flavour and one scaling pass per panel; dense only (no envelope), eager only.
+int HdmChol::factor_signed(hipStream_t s, int *info_host, int *nneg_host) {
+    if (!sgn.get()) {
+        HDM_HIP_CHECK(sgn.alloc((size_t) npad));
+        HDM_HIP_CHECK(sinfo_dev.alloc(2));
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_potrf_diag_sweep_signed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          DIAG_SWEEP_LDS_DOUBLES * (int) sizeof(double)));
+    }
+    if (!Z.get() && nblk > 1) HDM_HIP_CHECK(Z.alloc((size_t) npad * NB));
+    hipLaunchKernelGGL(hdm_zero_words_kernel, dim3(1), dim3(64), 0, s, sinfo_dev.get(), 2);
+    HDM_HIP_CHECK(hipGetLastError());
+    const long ld = npad;
+    for (int k = 0; k < nblk; ++k) {
+        double *Akk = L.get() + (long) k * NB * (ld + 1);
+        hipLaunchKernelGGL(hdm_potrf_diag_sweep_signed_kernel, dim3(1), dim3(SM_T), DIAG_SWEEP_LDS_DOUBLES * sizeof(double), s, Akk, ld,
+                           Dinv.get() + (long) k * NB * NB, sinfo_dev.get(), k * NB, std::max(1, std::min(NB, n - k * NB)), sgn.get() + (long) k * NB);
+        HDM_HIP_CHECK(hipGetLastError());
+        const int rows = npad - (k + 1) * NB;
+        if (rows <= 0) break;
+        double *P = Akk + NB;
+        if (hdm_chol_panel(P, ld, Dinv.get() + (long) k * NB * NB, rows, s)) return 1;
+        const long tot = (long) rows * NB;
+        hipLaunchKernelGGL(hdm_signed_panel_kernel, dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, s, P, ld, Z.get(), (long) npad,
+                           (const double *) (sgn.get() + (long) k * NB), rows);
+        HDM_HIP_CHECK(hipGetLastError());
+        if (hdm_chol_update(Akk + (long) NB * (ld + 1), ld, P, Z.get(), npad, rows, s)) return 1;
+    }
+    int info[2] = {0, 0};
+    HDM_HIP_CHECK(hipMemcpyAsync(info, sinfo_dev.get(), sizeof(int) * 2, hipMemcpyDeviceToHost, s));
+    HDM_HIP_CHECK(hipStreamSynchronize(s));
+    if (info[0] > n) info[0] = 0;
+    if (info_host) *info_host = info[0];
+    if (nneg_host) *nneg_host = info[1];
+    factored = (info[0] == 0);
+    have_inv = false;
+    logdet_ok = false;
+    return 0;
+}
+
+int HdmChol::reverse_signs(double *sig_dev, hipStream_t s) {
+    if (!sgn.get() || !factored) return 1;
+    hipLaunchKernelGGL(hdm_reverse_signs_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, (const double *) sgn.get(), sig_dev, n, npad);
+    HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -936,19 +921,13 @@ int HdmChol::invert_factor(hipStream_t s) {
         for (long sz = NB; sz < npad; sz *= 2) {
             const int pairs = (int) (npad / (2 * sz));
             const long pstride = 2 * sz * (ld + 1);
-            HdmGemmArgs g = {};   // T = C * A^-1   (B operand element (j,k) = A^-1(k,j): K-major)
-            g.A = L.get() + sz; g.lda = ld; g.strideA = pstride;
-            g.B = Linv.get(); g.ldb = ld; g.b_kmajor = 1; g.strideB = pstride;
-            g.C = Zd.get() + sz; g.ldc = ld; g.strideC = pstride;
-            g.M = (int) sz; g.N = (int) sz; g.K = (int) sz; g.batch = pairs; g.alpha = 1.0; g.epilogue = HDM_EPI_STORE;
-            if (hdm_launch_gemm(g, s)) return 1;
-            HdmGemmArgs h = {};   // X = -B^-1 * T   (B^-1 lower triangular: K loop cut by the row tile)
-            h.A = Linv.get() + sz * (ld + 1); h.lda = ld; h.strideA = pstride;
-            h.B = Zd.get() + sz; h.ldb = ld; h.b_kmajor = 1; h.strideB = pstride;
-            h.C = Linv.get() + sz; h.ldc = ld; h.strideC = pstride;
-            h.M = (int) sz; h.N = (int) sz; h.K = (int) sz; h.batch = pairs; h.alpha = -1.0;
-            h.klimit = HDM_KLIM_BY_M; h.epilogue = HDM_EPI_STORE;
-            if (hdm_launch_gemm(h, s)) return 1;
+            const int m = (int) sz;
+            // T = C * A^-1   (B operand element (j,k) = A^-1(k,j): K-major)
+            if (hdm_launch_gemm(hdm_gemm_product(Zd.get() + sz, ld, m, m, m, 1.0, hdm_mmajor(L.get() + sz, ld, pstride), hdm_kmajor(Linv.get(), ld, pstride),
+                                                 0.0, hdm_batched(pairs, pstride)), s)) return 1;
+            // X = -B^-1 * T   (B^-1 lower triangular: K loop cut by the row tile)
+            if (hdm_launch_gemm(hdm_gemm_product(Linv.get() + sz, ld, m, m, m, -1.0, hdm_mmajor(Linv.get() + sz * (ld + 1), ld, pstride),
+                                                 hdm_kmajor(Zd.get() + sz, ld, pstride), 0.0, hdm_klimit(HDM_KLIM_BY_M).batched(pairs, pstride)), s)) return 1;
         }
         have_inv = true;
         return 0;
@@ -961,15 +940,11 @@ int HdmChol::invert_factor(hipStream_t s) {
         const int rows = npad - (k + 1) * NB;
         if (rows <= 0) continue;
         const double *P = L.get() + (long) k * NB * (ld + 1) + NB;
-        HdmGemmArgs g = {};  // Z = P * Dinv_k   (B operand K-major: Bop[j,kk] = Dinv_k[kk + j*NB])
-        g.A = P; g.lda = ld; g.B = Dinv.get() + (long) k * NB * NB; g.ldb = NB; g.b_kmajor = 1;
-        g.C = Z.get(); g.ldc = npad; g.M = rows; g.N = NB; g.K = NB; g.batch = 1; g.alpha = 1.0; g.epilogue = HDM_EPI_STORE;
-        if (hdm_launch_gemm(g, s)) return 1;
-        HdmGemmArgs h = {};  // X = -W * Z, W lower triangular => K loop cut by the row tile
-        h.A = Linv.get() + (long) (k + 1) * NB * (ld + 1); h.lda = ld; h.B = Z.get(); h.ldb = npad; h.b_kmajor = 1;
-        h.C = Xkk + NB; h.ldc = ld; h.M = rows; h.N = NB; h.K = rows; h.batch = 1; h.alpha = -1.0;
-        h.klimit = HDM_KLIM_BY_M; h.epilogue = HDM_EPI_STORE;
-        if (hdm_launch_gemm(h, s)) return 1;
+        // Z = P * Dinv_k   (B operand K-major: Bop[j,kk] = Dinv_k[kk + j*NB])
+        if (hdm_launch_gemm(hdm_gemm_product(Z.get(), npad, rows, NB, NB, 1.0, hdm_mmajor(P, ld), hdm_kmajor(Dinv.get() + (long) k * NB * NB, NB)), s)) return 1;
+        // X = -W * Z, W lower triangular => K loop cut by the row tile
+        if (hdm_launch_gemm(hdm_gemm_product(Xkk + NB, ld, rows, NB, rows, -1.0, hdm_mmajor(Linv.get() + (long) (k + 1) * NB * (ld + 1), ld),
+                                             hdm_kmajor(Z.get(), npad), 0.0, hdm_klimit(HDM_KLIM_BY_M)), s)) return 1;
     }
     have_inv = true;
     return 0;
@@ -1112,11 +1087,8 @@ int HdmChol::solve_host(const double *rhs, double *sol, int nrhs, int which, hip
 int HdmChol::inverse_full(double *out_dev, long ldo, hipStream_t s) {
     // out = Linv^T * Linv  (full symmetric npad x npad); dpotri + HUtilMatSymmetrize equivalent
     if (invert_factor(s)) return 1;
-    HdmGemmArgs g = {};
-    g.A = Linv.get(); g.lda = npad; g.a_kmajor = 1; g.B = Linv.get(); g.ldb = npad; g.b_kmajor = 1;
-    g.C = out_dev; g.ldc = ldo; g.M = npad; g.N = npad; g.K = npad; g.batch = 1; g.alpha = 1.0;
-    g.epilogue = HDM_EPI_STORE;
-    return hdm_launch_gemm(g, s);
+    const HdmOperand Lt = hdm_kmajor(Linv.get(), npad);
+    return hdm_launch_gemm(hdm_gemm_product(out_dev, ldo, npad, npad, npad, 1.0, Lt, Lt), s);
 }
 
 // one kernel of this translation unit (= one code object): what the preload thread asks the runtime about (engine.hip: preload_modules)

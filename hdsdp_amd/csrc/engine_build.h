@@ -5,43 +5,17 @@
 // phase 0: both steps; 1: step 1 only; 2: step 2 only (count <= Bc, T still holds step 1's output), optionally only the
 // output tiles of the tile columns in `colmask` -- the multi-GPU build runs step 2 by packed-index range so that the
 // finished ranges can leave for the other ranks while the rest is still being computed
-// `asrc_span`: elements readable from Asrc (the buffer's operand slack included), for the launcher's check of the
-// unmasked tile loads
-int congruence_rows(MiCone *c, HdmChol &ch, const double *Asrc, long astride, long asrc_span, int count, long row0,
-                    int phase = 0, unsigned long long colmask = 0) {
-    // rows row0 .. row0+count-1 of AhatLoc  <-  blocked( Linv * A * Linv^T ),  A = A_L + A_L^T given in A_L form:
-    //   step 1  U  = Linv * A_L                 (lower x lower = lower triangular: k in [col tile, row tile], n^3/3)
-    //   step 2  At = U * Linv^T + Linv * U^T    (SYR2K form, lower tiles, k <= col tile, 2n^3/3)
-    // i.e. n^3 flops per constraint instead of the 4/3 n^3 of (Linv A) Linv^T, and half the intermediate traffic.
-    const long nn = (long) c->n16 * c->n16;
-    const double n3 = (double) c->n * c->n * c->n;
+// `src_rows`: skyline matrices the buffer behind Asrc holds (its span for the launcher's check is hdm_afull_span of them)
+int congruence_rows(MiCone *c, HdmChol &ch, const double *Asrc, long src_rows, int count, long row0, int phase = 0,
+                    unsigned long long colmask = 0) {
+    // rows row0 .. row0+count-1 of AhatLoc  <-  blocked( Linv * A * Linv^T ): step 1 into T, step 2 from there (gemm_calls.h)
+    const HdmLayout L = cone_layout(c);
     for (int b0 = 0; b0 < count; b0 += c->Bc) {
         const int nb = std::min(c->Bc, count - b0);
-        HdmGemmArgs k1 = {};
-        k1.A = ch.Linv.get(); k1.lda = ch.npad; k1.strideA = 0;
-        k1.B = Asrc + (long) b0 * astride; k1.ldb = c->n16; k1.strideB = astride; k1.b_kmajor = 1; k1.b_sky = 1;
-        k1.C = c->T.get(); k1.ldc = c->n16; k1.strideC = nn;
-        k1.M = c->n16; k1.N = c->n16; k1.K = c->n16; k1.batch = nb; k1.alpha = 1.0;
-        k1.klimit = HDM_KLIM_BAND; k1.lower_only = 1; k1.epilogue = HDM_EPI_STORE; k1.role = HDM_ROLE_CONG1;
-        k1.flops = (double) nb * n3 / 3.0;
-        const long linv_span = (long) ch.npad * ch.npad;
-        const long t_span = nn * c->Bc + (long) (hdm_operand_pad(c->n16) / sizeof(double));
-        k1.spanA = linv_span; k1.spanB = asrc_span - (long) b0 * astride;
-        if (phase != 2 && c->shared_ts && hdm_zero_diag_upper(c->T.get(), nn, c->n16, nb, g.stream)) return 1;
-        if (phase != 2 && hdm_launch_gemm(k1, g.stream)) return 1;
+        if (phase != 2 && c->shared_ts && hdm_zero_diag_upper(c->T.get(), (long) c->n16 * c->n16, c->n16, nb, g.stream)) return 1;
+        if (phase != 2 && hdm_launch_gemm(hdm_cong_step1(L, c->n, ch.Linv.get(), ch.npad, Asrc, src_rows, b0, nb, c->T.get()), g.stream)) return 1;
         if (phase == 1) continue;
-        HdmGemmArgs k2 = {};
-        k2.A = c->T.get(); k2.lda = c->n16; k2.strideA = nn;
-        k2.B = ch.Linv.get(); k2.ldb = ch.npad; k2.strideB = 0;
-        k2.A2 = ch.Linv.get(); k2.lda2 = ch.npad; k2.strideA2 = 0;
-        k2.B2 = c->T.get(); k2.ldb2 = c->n16; k2.strideB2 = nn;
-        k2.C = c->AhatLoc; k2.M = c->n16; k2.N = c->n16; k2.K = c->n16; k2.batch = nb; k2.alpha = 1.0;
-        k2.klimit = HDM_KLIM_BY_N; k2.lower_only = 1; k2.epilogue = HDM_EPI_BLOCKED;
-        k2.blk_row_stride = c->Lr; k2.blk_row0 = row0 + b0; k2.nblk = c->nblk; k2.role = HDM_ROLE_CONG2;
-        k2.tile_col_mask = colmask;
-        k2.spanA = t_span; k2.spanB = linv_span; k2.spanA2 = linv_span; k2.spanB2 = t_span;
-        k2.flops = (double) nb * n3 * 2.0 / 3.0 * hdm_cong2_mask_share(hdm_ntiles(c->n16), colmask);
-        if (hdm_launch_gemm(k2, g.stream)) return 1;
+        if (hdm_launch_gemm(hdm_cong_step2(L, c->n, c->Bc, ch.Linv.get(), ch.npad, c->T.get(), nb, c->AhatLoc, row0 + b0, colmask), g.stream)) return 1;
     }
     return 0;
 }
@@ -49,24 +23,8 @@ int congruence_rows(MiCone *c, HdmChol &ch, const double *Asrc, long astride, lo
 // Gram partial sums of the K splits [z0, z0 + nz): slabs slab0.. <- (or +=, `accumulate`) Ahat * Ahat^T over their share of this
 // rank's p-range.  slab0 < 0: slab z0 (one slab per split)
 int gram_splits(MiCone *c, int z0, int nz, int slab0 = -1, bool accumulate = false) {
-    HdmGemmArgs gq = {};
-    gq.A = c->AhatAll; gq.B = c->AhatAll; gq.a_kmajor = 1; gq.b_kmajor = 1;
-    gq.lda = 16; gq.ldb = 16; gq.a_kblk = (long) c->Lr * 16; gq.b_kblk = (long) c->Lr * 16;
-    if (c->world > 1) { gq.seg_rows = c->Lr; gq.seg_extra = c->npb_loc * c->Lr * 16 - (long) c->Lr * 16; }
-    gq.ldc = c->R; gq.M = (int) c->R; gq.N = (int) c->R; gq.K = (int) (c->npb_loc * 16);
-    gq.lower_only = 1; gq.epilogue = HDM_EPI_SLAB; gq.batch = nz;
-    const long chunk = (c->npb_loc + c->nsplit - 1) / c->nsplit;
-    gq.k_chunk = chunk * 16; gq.slab_stride = c->R * c->R; gq.alpha = 1.0; gq.role = HDM_ROLE_GRAM;
-    gq.k_base = (long) z0 * gq.k_chunk;
-    gq.spanA = gq.spanB = (long) hdm_exchange_doubles(cone_layout(c)) + HDM_OPERAND_PAD_DOUBLES;
-    gq.C = c->slabs + (long) (slab0 < 0 ? z0 : slab0) * gq.slab_stride;
-    gq.beta = accumulate ? 1.0 : 0.0;
-    gq.queue_global = c->gram_queue_global ? 1 : 0;
-    {   // (m+3)(m+4)/2 inner products of length n(n+1)/2 (this rank's share), 2 flops each
-        const double rows = (double) c->m + 3.0;
-        gq.flops = rows * (rows + 1.0) * 0.5 * ((double) c->n * (c->n + 1) * 0.5) * 2.0 / c->world * ((double) nz / c->nsplit);
-    }
-    return hdm_launch_gemm(gq, g.stream);
+    double *slab = c->slabs + (long) (slab0 < 0 ? z0 : slab0) * c->R * c->R;
+    return hdm_launch_gemm(hdm_gram_splits(cone_layout(c), c->n, c->m, c->nsplit, z0, nz, c->AhatAll, slab, accumulate, c->gram_queue_global), g.stream);
 }
 
 // the K splits [z0, z0 + nz) in groups of nslab, launch after launch on the engine stream, every group accumulating into the slabs
@@ -105,12 +63,7 @@ int exchange_pieces(const MiCone *c) {
     return P;
 }
 // p-blocks [lo, hi) of every destination's chunk that piece k of P carries
-void piece_range(const MiCone *c, int k, int P, long *lo, long *hi) {
-    const long chunk = (c->npb_loc + c->nsplit - 1) / c->nsplit;   // p-blocks per split
-    const int zper = c->nsplit / P;
-    *lo = std::min<long>(c->npb_loc, (long) k * zper * chunk);
-    *hi = (k == P - 1) ? c->npb_loc : std::min<long>(c->npb_loc, (long) (k + 1) * zper * chunk);
-}
+void piece_range(const MiCone *c, int k, int P, long *lo, long *hi) { hdm_piece_range(cone_layout(c), c->nsplit, k, P, lo, hi); }
 // Tile columns of congruence step 2 whose output piece k needs.  P-block q belongs to the 16 x 16 sub-block q / 16 of the
 // blocked lower triangle, sub-blocks are numbered column by column (gemm_geom.h: hdm_blk_col_of), and tile
 // column tn produces the sub-block columns 8 tn .. 8 tn + 7: a range of p-blocks is a range of tile columns.
@@ -258,18 +211,8 @@ int signed_correction(MiCone *c) {
                            (const double *) c->AhatAll, seg_stride, c->Lr, R, (const int *) (c->pcols.get() + j0), nc, nc16, pb0, c->pgat.get());
         if (hipGetLastError() != hipSuccess) rc = 1;
         rc |= mark();
-        HdmGemmArgs gq = {};
-        gq.A = c->pgat.get(); gq.B = c->pgat.get(); gq.a_kmajor = 1; gq.b_kmajor = 1;
-        gq.lda = 16; gq.ldb = 16; gq.a_kblk = R * 16; gq.b_kblk = R * 16;
-        gq.ldc = R; gq.M = (int) R; gq.N = (int) R; gq.K = (int) nc16;
-        gq.lower_only = 1; gq.epilogue = HDM_EPI_SLAB; gq.batch = nz;
-        gq.k_chunk = (nc16 / 16 + nz - 1) / nz * 16; gq.k_base = 0; gq.slab_stride = R * R;
-        gq.alpha = alpha; gq.beta = (j0 == 0) ? 0.0 : 1.0; gq.role = HDM_ROLE_GRAM;
-        gq.queue_global = c->gram_queue_global ? 1 : 0;
-        gq.spanA = gq.spanB = (long) c->pgat.count();
-        gq.C = c->slabs;
-        gq.flops = (double) R * (R + 1) * 0.5 * (double) nc * 2.0;
-        if (!rc && hdm_launch_gemm(gq, g.stream)) rc = 1;
+        if (!rc && hdm_launch_gemm(hdm_gram_gathered(R, nc, nc16, nz, alpha, j0 != 0, c->pgat.get(), (long) c->pgat.count(), c->slabs,
+                                                     c->gram_queue_global), g.stream)) rc = 1;
     }
     rc |= mark();
     if (!rc) {
@@ -323,12 +266,11 @@ hdsdp_retcode build_primal_general(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, con
     HdmBuf<double> row, ALsq;   // freed on every way out
     HIP_RC(row.alloc((size_t) m));
     HIP_RC(ALsq.alloc((size_t) c->n16 * c->n16, hdm_operand_pad(c->n16)));
-    HdmGemmArgs q = {};
-    q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE; q.ldc = ldx;
+    const int n16 = c->n16;
+    const HdmOperand Xm = hdm_mmajor(c->Xup.get(), ldx), Xk = hdm_kmajor(c->Xup.get(), ldx);
     // vectors: ASinv_i = <A_i, X>, ASinvRdSinv_i = Rd <A_i, X^2>   (Pr2 <- X X^T)
-    q.A = c->Xup.get(); q.lda = ldx; q.B = c->Xup.get(); q.ldb = ldx; q.C = c->Pr2.get();
     hdsdp_retcode rc = HDSDP_RETCODE_OK;
-    if (hdm_launch_gemm(q, g.stream) ||
+    if (hdm_launch_gemm(hdm_gemm_product(c->Pr2.get(), ldx, n16, n16, n16, 1.0, Xm, Xm), g.stream) ||
         cone_sym_dot2(c, c->Xup.get(), c->Pr2.get(), ldx, pv->vecs.get(), pv->vecs.get() + m, 2.0, 2.0 * c->Rd))
         rc = HDSDP_RETCODE_FAILED;
     for (int qi = 0; qi < c->mloc && rc == HDSDP_RETCODE_OK; ++qi) {
@@ -338,14 +280,11 @@ hdsdp_retcode build_primal_general(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, con
         if (!Arow || hdm_sky_to_square(Arow, ALsq.get(), c->n16, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
         const double *AL = ALsq.get();
         // Pr1 = X A_L            (B operand element (j, k) = A_L(k, j): K-major)
-        q.A = c->Xup.get(); q.lda = ldx; q.a_kmajor = 0; q.B = AL; q.ldb = c->n16; q.b_kmajor = 1; q.C = c->Pr1.get(); q.beta = 0.0;
-        if (hdm_launch_gemm(q, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
+        if (hdm_launch_gemm(hdm_gemm_product(c->Pr1.get(), ldx, n16, n16, n16, 1.0, Xm, hdm_kmajor(AL, n16)), g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
         // Pr1 += X A_L^T         (B operand element (j, k) = A_L(j, k): M-major)
-        q.b_kmajor = 0; q.beta = 1.0;
-        if (hdm_launch_gemm(q, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
+        if (hdm_launch_gemm(hdm_gemm_product(c->Pr1.get(), ldx, n16, n16, n16, 1.0, Xm, hdm_mmajor(AL, n16), 1.0), g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
         // Pr2 = Pr1 X            (B operand element (j, k) = X(k, j): K-major)
-        q.A = c->Pr1.get(); q.lda = ldx; q.B = c->Xup.get(); q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr2.get(); q.beta = 0.0;
-        if (hdm_launch_gemm(q, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
+        if (hdm_launch_gemm(hdm_gemm_product(c->Pr2.get(), ldx, n16, n16, n16, 1.0, hdm_mmajor(c->Pr1.get(), ldx), Xk), g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
         if (hipMemsetAsync(row.get(), 0, sizeof(double) * (size_t) m, g.stream) != hipSuccess ||
             cone_sym_dot2(c, c->Pr2.get(), nullptr, ldx, row.get(), row.get(), 2.0, 0.0)) { rc = HDSDP_RETCODE_FAILED; break; }
         hipLaunchKernelGGL(mi_put_row_kernel, dim3((m + 255) / 256), dim3(256), 0, g.stream, Mview, c->own[qi], row.get(), m);
@@ -394,10 +333,7 @@ int primal_signed_factor(MiCone *c, HdmChol &ch, const double *Xr, const double 
     hipLaunchKernelGGL(mi_psig_rowscale_kernel, dim3((unsigned) ((np * np + 255) / 256)), dim3(256), 0, g.stream,
                        (const double *) ch.Linv.get(), (const double *) c->psig.get(), c->Pr1.get(), np, (int) np);
     HIP_RC(hipGetLastError());
-    HdmGemmArgs q = {};
-    q.A = ch.Linv.get(); q.lda = np; q.a_kmajor = 1; q.B = c->Pr1.get(); q.ldb = np; q.b_kmajor = 1; q.C = c->Pr2.get(); q.ldc = np;
-    q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE;
-    RC(hdm_launch_gemm(q, g.stream));
+    RC(hdm_launch_gemm(hdm_gemm_product(c->Pr2.get(), np, c->n16, c->n16, c->n16, 1.0, hdm_kmajor(ch.Linv.get(), np), hdm_kmajor(c->Pr1.get(), np)), g.stream));
     hipLaunchKernelGGL(mi_psig_norms_kernel, dim3(MI_PSIG_BLOCKS), dim3(256), 0, g.stream, (const double *) c->Pr2.get(), (const double *) c->Xup.get(),
                        (const double *) ch.Linv.get(), np, c->n, c->pchk.get());
     hipLaunchKernelGGL(mi_psig_norms_final_kernel, dim3(1), dim3(64), 0, g.stream, (const double *) c->pchk.get(), MI_PSIG_BLOCKS,
@@ -538,10 +474,8 @@ hdsdp_retcode corrector_components(MiCone *c, HdmChol &ch, MiKKTPriv *pv, int m)
     RC(ch.inverse_full(c->Xinv.get(), ch.npad, g.stream));
     const double *Y = nullptr;
     if (c->Rd != 0.0) {
-        HdmGemmArgs q = {};  // Y = X * X^T = S^-2
-        q.A = c->Xinv.get(); q.lda = ch.npad; q.B = c->Xinv.get(); q.ldb = ch.npad; q.C = c->Yinv.get(); q.ldc = ch.npad;
-        q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE;
-        RC(hdm_launch_gemm(q, g.stream));
+        const HdmOperand X = hdm_mmajor(c->Xinv.get(), ch.npad);   // Y = X * X^T = S^-2
+        RC(hdm_launch_gemm(hdm_gemm_product(c->Yinv.get(), ch.npad, c->n16, c->n16, c->n16, 1.0, X, X), g.stream));
         Y = c->Yinv.get();
     }
     // A is stored in A_L form: <A, X> = 2 <A_L, X>
@@ -567,16 +501,14 @@ hdsdp_retcode corrector_components(MiCone *c, HdmChol &ch, MiKKTPriv *pv, int m)
 // (DESIGN section 4 records what an unmasked generic tile once did).  With a factor override `ch` is the primal factor object.
 hdsdp_retcode direct_rows_build(MiCone *c, HdmChol &ch) {
     if (c->dr_r1 > 0) {
-        HdmGemmArgs u = {};
-        u.A = ch.Linv.get(); u.lda = ch.npad; u.B = c->dr_fac.get(); u.ldb = c->n16; u.b_kmajor = 1; u.C = c->dr_U.get(); u.ldc = c->n16;
-        u.M = c->n16; u.N = c->dr_r1_16; u.K = c->n16; u.batch = 1; u.alpha = 1.0; u.klimit = HDM_KLIM_BY_M; u.epilogue = HDM_EPI_STORE;
-        RC(hdm_launch_gemm(u, g.stream));
+        RC(hdm_launch_gemm(hdm_gemm_product(c->dr_U.get(), c->n16, c->n16, c->dr_r1_16, c->n16, 1.0, hdm_mmajor(ch.Linv.get(), ch.npad),
+                                            hdm_kmajor(c->dr_fac.get(), c->n16), 0.0, hdm_klimit(HDM_KLIM_BY_M)), g.stream));
     }
     HdmDirectArgs a = {};
     a.dst = c->AhatLoc; a.row_stride = c->Lr; a.row0 = c->mloc - c->dr_n; a.nrows = c->dr_n; a.nblk = c->nblk; a.n = c->n;
     a.terms = c->dr_terms.get(); a.row_ptr = c->dr_ptr.get();
     a.Linv = ch.Linv.get(); a.ldl = ch.npad; a.U = c->dr_U.get(); a.ldu = c->n16;
-    a.dst_span = (long) hdm_exchange_doubles(cone_layout(c)); a.linv_span = (long) ch.npad * ch.npad; a.u_span = (long) c->dr_U.count();
+    a.dst_span = (long) hdm_exchange_doubles(cone_layout(c)); a.linv_span = hdm_linv_span(ch.npad); a.u_span = (long) c->dr_U.count();
     a.max_lcol = c->dr_max_lcol; a.nu = c->dr_r1;
     return hdm_direct_rows(a, g.stream) ? HDSDP_RETCODE_FAILED : HDSDP_RETCODE_OK;
 }
@@ -598,8 +530,7 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
     HIP_RC(hipEventRecord(g.ev[0], g.stream));
     RC(ch.invert_factor(g.stream));
     HIP_RC(hipEventRecord(g.ev[1], g.stream));
-    const long opad = (long) (hdm_operand_pad(c->n16) / sizeof(double));       // slack behind Afull / CL / T (allocation sites)
-    const long afull_span = c->astride * std::max(1, c->mloc) + opad;
+    const long afull_rows = std::max(1, c->mloc);   // matrices behind Afull (allocation sites)
     // Multi-GPU: run step 2 of the owned rows by packed-index range, in the order of the exchange pieces, so that a piece
     // crosses the links while the later ranges are still being computed (at two ranks the all-to-all moves 8 GB per
     // rank over a single link, more than the Gram product alone can hide).  Needs the piecewise exchange hooks, all
@@ -617,35 +548,30 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
             const int nb = std::min(c->Bs, c->mloc - q0);
             const double *A = cone_rows(c, q0, nb);
             if (!A) return HDSDP_RETCODE_FAILED;
-            RC(congruence_rows(c, ch, A, c->astride, c->astride * (long) c->Bs + opad, nb, q0));
+            RC(congruence_rows(c, ch, A, c->Bs, nb, q0));
         }
-    } else if (!staged) RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc - c->dr_n, 0));
+    } else if (!staged) RC(congruence_rows(c, ch, c->Afull.get(), afull_rows, c->mloc - c->dr_n, 0));
     if (c->dr_n > 0) RC(direct_rows_build(c, ch));   // (one device, resident rows: never staged, never streamed)
     if (c->rank == 0) {
         // "I row": A = I => T = Linv, At = Linv Linv^T.  Reuse step 2 with T := Linv.
-        HdmGemmArgs k2 = {};
-        k2.A = ch.Linv.get(); k2.lda = ch.npad; k2.B = ch.Linv.get(); k2.ldb = ch.npad; k2.C = c->AhatLoc;
-        k2.M = c->n16; k2.N = c->n16; k2.K = c->n16; k2.batch = 1; k2.alpha = 1.0;
-        k2.klimit = HDM_KLIM_BY_N; k2.lower_only = 1; k2.epilogue = HDM_EPI_BLOCKED;
-        k2.blk_row_stride = c->Lr; k2.blk_row0 = c->mloc; k2.nblk = c->nblk;
-        RC(hdm_launch_gemm(k2, g.stream));
+        RC(hdm_launch_gemm(hdm_cong_irow(cone_layout(c), ch.Linv.get(), ch.npad, c->AhatLoc, c->mloc), g.stream));
         if (typeKKT == KKT_TYPE_HOMOGENEOUS) {
             if (!c->CL.get()) {
                 HIP_RC(c->CL.alloc((size_t) c->astride, hdm_operand_pad(c->n16)));
                 HIP_RC(hipMemsetAsync(c->CL.get(), 0, sizeof(double) * (size_t) c->astride, g.stream));
                 RC(hdm_lower_half(c->Cfull.get(), c->CL.get(), c->n, c->n16, g.stream));
             }
-            RC(congruence_rows(c, ch, c->CL.get(), c->astride, c->astride + opad, 1, c->mloc + 2));
+            RC(congruence_rows(c, ch, c->CL.get(), 1, 1, c->mloc + 2));
         }
     }
     if (staged) {
-        RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc, 0, 1));
+        RC(congruence_rows(c, ch, c->Afull.get(), afull_rows, c->mloc, 0, 1));
         if (prof_record(c->pe_s1, g.stream)) return HDSDP_RETCODE_FAILED;
         const unsigned long long all = (NT >= 64) ? ~0ULL : ((1ULL << NT) - 1);
         unsigned long long done = 0;
         for (int k = 0; k < P; ++k) {
             unsigned long long mk = (k == P - 1 ? all : piece_tile_cols(c, k, P)) & all & ~done;
-            if (mk) { RC(congruence_rows(c, ch, c->Afull.get(), c->astride, afull_span, c->mloc, 0, 2, mk)); c->last_staged += 1; }
+            if (mk) { RC(congruence_rows(c, ch, c->Afull.get(), afull_rows, c->mloc, 0, 2, mk)); c->last_staged += 1; }
             done |= mk;
             if (!c->piece_ev[k]) HIP_RC(hipEventCreateWithFlags(&c->piece_ev[k], hipEventDisableTiming));
             HIP_RC(hipEventRecord(c->piece_ev[k], g.stream));

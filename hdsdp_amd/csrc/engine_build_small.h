@@ -18,15 +18,12 @@ hdsdp_retcode build_r1_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKK
     const int n16 = c->n16, m16 = c->mloc16;
     RC(ch.invert_factor(g.stream));
     TRACE_STEP("r1 step 1");
-    HdmGemmArgs u = {};  // U = Linv * Avec
-    u.A = ch.Linv.get(); u.lda = ch.npad; u.B = c->Avec.get(); u.ldb = n16; u.b_kmajor = 1; u.C = c->U.get(); u.ldc = n16;
-    u.M = n16; u.N = m16; u.K = n16; u.batch = 1; u.alpha = 1.0; u.klimit = HDM_KLIM_BY_M; u.epilogue = HDM_EPI_STORE;
-    RC(hdm_launch_gemm(u, g.stream));
+    const HdmOperand Linv = hdm_mmajor(ch.Linv.get(), ch.npad), LinvT = hdm_kmajor(ch.Linv.get(), ch.npad), Ut = hdm_kmajor(c->U.get(), n16);
+    // U = Linv * Avec
+    RC(hdm_launch_gemm(hdm_gemm_product(c->U.get(), n16, n16, m16, n16, 1.0, Linv, hdm_kmajor(c->Avec.get(), n16), 0.0, hdm_klimit(HDM_KLIM_BY_M)), g.stream));
     TRACE_STEP("r1 step 2");
-    HdmGemmArgs v = {};  // V = Linv^T * U = S^-1 * Avec
-    v.A = ch.Linv.get(); v.lda = ch.npad; v.a_kmajor = 1; v.B = c->U.get(); v.ldb = n16; v.b_kmajor = 1; v.C = c->V.get(); v.ldc = n16;
-    v.M = n16; v.N = m16; v.K = n16; v.batch = 1; v.alpha = 1.0; v.epilogue = HDM_EPI_STORE;
-    RC(hdm_launch_gemm(v, g.stream));
+    // V = Linv^T * U = S^-1 * Avec
+    RC(hdm_launch_gemm(hdm_gemm_product(c->V.get(), n16, n16, m16, n16, 1.0, LinvT, Ut), g.stream));
     TRACE_STEP("r1 step 3");
     if (typeKKT == KKT_TYPE_CORRECTOR) {
         // ASinv_i = s_i a_i' S^-1 a_i = s_i <u_i,u_i>; ASinvRdSinv_i = Rd s_i |v_i|^2
@@ -36,10 +33,8 @@ hdsdp_retcode build_r1_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKK
         if (c->Rd != 0.0) RC(hdm_r1_colnorm(c->V.get(), n16, n16, c->sgn.get(), c->rows_own.get(), c->mloc, c->Rd, pv->vecs.get() + m, g.stream));
         return HDSDP_RETCODE_OK;
     }
-    HdmGemmArgs gq = {};  // Gr1 = U^T U
-    gq.A = c->U.get(); gq.lda = n16; gq.a_kmajor = 1; gq.B = c->U.get(); gq.ldb = n16; gq.b_kmajor = 1; gq.C = c->Gr1.get(); gq.ldc = m16;
-    gq.M = m16; gq.N = m16; gq.K = n16; gq.batch = 1; gq.alpha = 1.0; gq.lower_only = 1; gq.epilogue = HDM_EPI_STORE;
-    RC(hdm_launch_gemm(gq, g.stream));
+    // Gr1 = U^T U
+    RC(hdm_launch_gemm(hdm_gemm_product(c->Gr1.get(), m16, m16, m16, n16, 1.0, Ut, Ut, 0.0, hdm_lower()), g.stream));
     TRACE_STEP("r1 step 5");
     RC(hdm_r1_hadamard(c->Gr1.get(), m16, c->sgn.get(), c->rows_own.get(), c->mloc, kkt_view(kkt), pv->vecs.get(), g.stream));
     TRACE_STEP("r1 step 6");
@@ -54,20 +49,14 @@ hdsdp_retcode build_r1_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKK
     if (typeKKT == KKT_TYPE_HOMOGENEOUS && c->rank == 0) {
         // Ct = Linv C Linv^T (full);  ASinvCSinv_i = s_i u_i' Ct u_i;  CSinv = tr Ct; CSinvCSinv = |Ct|_F^2;
         // CSinvRdSinv = Rd <Ct, Linv Linv^T>
-        HdmGemmArgs k1 = {};
-        k1.A = ch.Linv.get(); k1.lda = ch.npad; k1.B = c->Cfull.get(); k1.ldb = n16; k1.C = c->W.get(); k1.ldc = n16;
-        k1.M = n16; k1.N = n16; k1.K = n16; k1.batch = 1; k1.alpha = 1.0; k1.klimit = HDM_KLIM_BY_M;
-        RC(hdm_launch_gemm(k1, g.stream));
+        // W = Linv * C   (C symmetric)
+        RC(hdm_launch_gemm(hdm_gemm_product(c->W.get(), n16, n16, n16, n16, 1.0, Linv, hdm_mmajor(c->Cfull.get(), n16), 0.0, hdm_klimit(HDM_KLIM_BY_M)), g.stream));
     TRACE_STEP("r1 step 9");
-        HdmGemmArgs k2 = {};
-        k2.A = c->W.get(); k2.lda = n16; k2.B = ch.Linv.get(); k2.ldb = ch.npad; k2.C = c->Ct.get(); k2.ldc = n16;
-        k2.M = n16; k2.N = n16; k2.K = n16; k2.batch = 1; k2.alpha = 1.0; k2.klimit = HDM_KLIM_BY_N;
-        RC(hdm_launch_gemm(k2, g.stream));
+        // Ct = W * Linv^T
+        RC(hdm_launch_gemm(hdm_gemm_product(c->Ct.get(), n16, n16, n16, n16, 1.0, hdm_mmajor(c->W.get(), n16), Linv, 0.0, hdm_klimit(HDM_KLIM_BY_N)), g.stream));
     TRACE_STEP("r1 step 10");
-        HdmGemmArgs w = {};  // W = Ct * U
-        w.A = c->Ct.get(); w.lda = n16; w.B = c->U.get(); w.ldb = n16; w.b_kmajor = 1; w.C = c->W.get(); w.ldc = n16;
-        w.M = n16; w.N = m16; w.K = n16; w.batch = 1; w.alpha = 1.0;
-        RC(hdm_launch_gemm(w, g.stream));
+        // W = Ct * U
+        RC(hdm_launch_gemm(hdm_gemm_product(c->W.get(), n16, n16, m16, n16, 1.0, hdm_mmajor(c->Ct.get(), n16), Ut), g.stream));
     TRACE_STEP("r1 step 11");
         hipLaunchKernelGGL(mi_col_dot_kernel, dim3((c->mloc + 3) / 4), dim3(256), 0, g.stream, c->U.get(), c->W.get(), (long) n16,
                            n16, c->sgn.get(), c->rows_own.get(), c->mloc, pv->vecs.get() + 2 * m);
@@ -79,10 +68,8 @@ hdsdp_retcode build_r1_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKK
                            c->n, 0, 1.0, pv->vecs.get() + 3 * m + 2);
     TRACE_STEP("r1 step 14");
         if (c->Rd != 0.0) {
-            HdmGemmArgs q = {};  // Xinv := Linv Linv^T
-            q.A = ch.Linv.get(); q.lda = ch.npad; q.B = ch.Linv.get(); q.ldb = ch.npad; q.C = c->Xinv.get(); q.ldc = n16;
-            q.M = n16; q.N = n16; q.K = n16; q.batch = 1; q.alpha = 1.0;
-            RC(hdm_launch_gemm(q, g.stream));
+            // Xinv := Linv Linv^T
+            RC(hdm_launch_gemm(hdm_gemm_product(c->Xinv.get(), n16, n16, n16, n16, 1.0, Linv, Linv), g.stream));
     TRACE_STEP("r1 step 15");
             hipLaunchKernelGGL(mi_mat_dot_kernel, dim3(1), dim3(256), 0, g.stream, c->Ct.get(), (long) n16, c->Xinv.get(),
                                (long) n16, c->n, 0, c->Rd, pv->vecs.get() + 3 * m + 3);
@@ -100,13 +87,13 @@ hdsdp_retcode build_sparse_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int ty
     HdmChol &ch = l->ch;
     const int m = kkt->nRow;
     const long ldx = ch.npad;
+    const int n16 = c->n16;
+    const HdmOperand X = hdm_mmajor(c->Xinv.get(), ldx);
     RC(ch.inverse_full(c->Xinv.get(), ldx, g.stream));
     RC(hdm_sparse_dot(c->sp_rp.get(), c->sp_ti.get(), c->sp_tj.get(), c->sp_tv.get(), c->Xinv.get(), ldx, c->mloc, c->rows_own.get(), 1.0, pv->vecs.get(), g.stream));
     if (c->Rd != 0.0) {
-        HdmGemmArgs q = {};  // Y = X X^T = S^-2
-        q.A = c->Xinv.get(); q.lda = ldx; q.B = c->Xinv.get(); q.ldb = ldx; q.C = c->Yinv.get(); q.ldc = ldx;
-        q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE;
-        RC(hdm_launch_gemm(q, g.stream));
+        // Y = X X^T = S^-2
+        RC(hdm_launch_gemm(hdm_gemm_product(c->Yinv.get(), ldx, n16, n16, n16, 1.0, X, X), g.stream));
         RC(hdm_sparse_dot(c->sp_rp.get(), c->sp_ti.get(), c->sp_tj.get(), c->sp_tv.get(), c->Yinv.get(), ldx, c->mloc, c->rows_own.get(), c->Rd,
                           pv->vecs.get() + m, g.stream));
     }
@@ -116,14 +103,9 @@ hdsdp_retcode build_sparse_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int ty
                            pv->vecs.get() + 3 * m);
     RC(hdm_sparse_pairs(c->sp_rp.get(), c->sp_ti.get(), c->sp_tj.get(), c->sp_tv.get(), c->Xinv.get(), ldx, c->mloc, c->rows_own.get(), kkt_view(kkt), g.stream));
     if (typeKKT == KKT_TYPE_HOMOGENEOUS) {
-        HdmGemmArgs w = {};  // W = X C,  Ct = W X = X C X
-        w.A = c->Xinv.get(); w.lda = ldx; w.B = c->Cfull.get(); w.ldb = c->n16; w.C = c->W.get(); w.ldc = ldx;
-        w.M = c->n16; w.N = c->n16; w.K = c->n16; w.batch = 1; w.alpha = 1.0; w.epilogue = HDM_EPI_STORE;
-        RC(hdm_launch_gemm(w, g.stream));
-        HdmGemmArgs x = {};
-        x.A = c->W.get(); x.lda = ldx; x.B = c->Xinv.get(); x.ldb = ldx; x.C = c->Ct.get(); x.ldc = ldx;
-        x.M = c->n16; x.N = c->n16; x.K = c->n16; x.batch = 1; x.alpha = 1.0; x.epilogue = HDM_EPI_STORE;
-        RC(hdm_launch_gemm(x, g.stream));
+        // W = X C,  Ct = W X = X C X
+        RC(hdm_launch_gemm(hdm_gemm_product(c->W.get(), ldx, n16, n16, n16, 1.0, X, hdm_mmajor(c->Cfull.get(), n16)), g.stream));
+        RC(hdm_launch_gemm(hdm_gemm_product(c->Ct.get(), ldx, n16, n16, n16, 1.0, hdm_mmajor(c->W.get(), ldx), X), g.stream));
         RC(hdm_sparse_dot(c->sp_rp.get(), c->sp_ti.get(), c->sp_tj.get(), c->sp_tv.get(), c->Ct.get(), ldx, c->mloc, c->rows_own.get(), 1.0,
                           pv->vecs.get() + 2 * m, g.stream));
         hipLaunchKernelGGL(mi_mat_dot_kernel, dim3(1), dim3(256), 0, g.stream, c->Cfull.get(), (long) c->n16, c->Xinv.get(), ldx, c->n,

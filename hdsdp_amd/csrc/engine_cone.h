@@ -870,14 +870,12 @@ void cone_build_primal_dir(void *cd, void *kktv, double *X, double *XSX, int iDu
     if (hipMemcpy2DAsync(c->Pr1.get(), sizeof(double) * ldx, D, sizeof(double) * c->n16, sizeof(double) * n, n,
                          hipMemcpyDeviceToDevice, g.stream) != hipSuccess) return;
     if (hdm_mirror_lower(c->Pr1.get(), ldx, n, g.stream)) return;
-    HdmGemmArgs q = {};
-    q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE; q.ldc = ldx;
+    const int n16 = c->n16;
+    const HdmOperand Xt = hdm_kmajor(c->Xup.get(), ldx);
     // T = D X   (B operand element (j, k) = X(k, j): K-major)
-    q.A = c->Pr1.get(); q.lda = ldx; q.a_kmajor = 0; q.B = c->Xup.get(); q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr2.get();
-    if (hdm_launch_gemm(q, g.stream)) return;
+    if (hdm_launch_gemm(hdm_gemm_product(c->Pr2.get(), ldx, n16, n16, n16, 1.0, hdm_mmajor(c->Pr1.get(), ldx), Xt), g.stream)) return;
     // P = X^T T   (A operand element (i, k) = X(k, i): K-major; B operand element (j, k) = T(k, j): K-major)
-    q.A = c->Xup.get(); q.lda = ldx; q.a_kmajor = 1; q.B = c->Pr2.get(); q.ldb = ldx; q.b_kmajor = 1; q.C = c->Pr1.get();
-    if (hdm_launch_gemm(q, g.stream)) return;
+    if (hdm_launch_gemm(hdm_gemm_product(c->Pr1.get(), ldx, n16, n16, n16, 1.0, Xt, hdm_kmajor(c->Pr2.get(), ldx)), g.stream)) return;
     std::vector<double> h((size_t) n * n);
     if (hipMemcpy2DAsync(h.data(), sizeof(double) * n, c->Pr1.get(), sizeof(double) * ldx, sizeof(double) * n, n,
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess) return;
@@ -975,21 +973,18 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
     const size_t np2 = sizeof(double) * (size_t) ch.npad * ch.npad;
     if (c->Pr1.reserve(np2 / sizeof(double)) != hipSuccess) return fail("out of memory");
     if (c->Pr2.reserve(np2 / sizeof(double)) != hipSuccess) return fail("out of memory");
-    HdmGemmArgs q = {};
-    q.M = c->n16; q.N = c->n16; q.K = c->n16; q.batch = 1; q.alpha = 1.0; q.epilogue = HDM_EPI_STORE; q.ldc = ch.npad;
+    const int n16 = c->n16;
+    const long np = ch.npad;
+    const HdmOperand W = hdm_mmajor(ch.Linv.get(), np), Wt = hdm_kmajor(ch.Linv.get(), np);
     // T1 = W dS          (W = Linv)
-    q.A = ch.Linv.get(); q.lda = ch.npad; q.a_kmajor = 0; q.B = c->dS.get(); q.ldb = c->n16; q.b_kmajor = 0; q.C = c->Pr1.get();
-    if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
+    if (hdm_launch_gemm(hdm_gemm_product(c->Pr1.get(), np, n16, n16, n16, 1.0, W, hdm_mmajor(c->dS.get(), n16)), g.stream)) return fail("gemm");
     // Z = T1 W^T
-    q.A = c->Pr1.get(); q.lda = ch.npad; q.a_kmajor = 0; q.B = ch.Linv.get(); q.ldb = ch.npad; q.b_kmajor = 0; q.C = c->Pr2.get();
-    if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
+    if (hdm_launch_gemm(hdm_gemm_product(c->Pr2.get(), np, n16, n16, n16, 1.0, hdm_mmajor(c->Pr1.get(), np), W), g.stream)) return fail("gemm");
     if (hdm_sym_scale(c->Pr2.get(), ch.npad, c->n16, 1.0, 1.0, g.stream)) return fail("sym");
     // T2 = W^T Z
-    q.A = ch.Linv.get(); q.lda = ch.npad; q.a_kmajor = 1; q.B = c->Pr2.get(); q.ldb = ch.npad; q.b_kmajor = 0; q.C = c->Pr1.get();
-    if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
+    if (hdm_launch_gemm(hdm_gemm_product(c->Pr1.get(), np, n16, n16, n16, 1.0, Wt, hdm_mmajor(c->Pr2.get(), np)), g.stream)) return fail("gemm");
     // X = T2 W
-    q.A = c->Pr1.get(); q.lda = ch.npad; q.a_kmajor = 0; q.B = ch.Linv.get(); q.ldb = ch.npad; q.b_kmajor = 1; q.C = c->Pr2.get();
-    if (hdm_launch_gemm(q, g.stream)) return fail("gemm");
+    if (hdm_launch_gemm(hdm_gemm_product(c->Pr2.get(), np, n16, n16, n16, 1.0, hdm_mmajor(c->Pr1.get(), np), Wt), g.stream)) return fail("gemm");
     if (hdm_sym_scale(c->Pr2.get(), ch.npad, n, 0.0, dBarrierMu, g.stream)) return fail("sym");
     if (hipMemcpy2DAsync(X, sizeof(double) * n, c->Pr2.get(), sizeof(double) * ch.npad, sizeof(double) * n, n,
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess) return fail("copy");

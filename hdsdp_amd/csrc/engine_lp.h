@@ -107,7 +107,7 @@ int lp_build_pairs(MiLPCone *c) {
 
 int lp_build_dense_buffer(MiLPCone *c) {
     if (c->W) return 0;
-    c->wspan = (long) (c->kc / 16) * c->mpad * 16 + HDM_OPERAND_PAD_DOUBLES;
+    c->wspan = hdm_lp_span(c->kc, c->mpad);
     if (c->W.alloc((size_t) c->wspan) != hipSuccess) return 1;
     return hdm_memset_sync(c->W.get(), 0, sizeof(double) * (size_t) c->wspan) != hipSuccess;
 }
@@ -238,15 +238,7 @@ hdsdp_retcode lp_build_schur(void *cd, int iCone, void *kktv, int typeKKT) {   /
         hipLaunchKernelGGL(lp_scatter_kernel, dim3((kv + 255) / 256), dim3(256), 0, g.stream, c0, kv, (const int *) c->d_cbeg.get(),
                            (const int *) c->d_cidx.get(), (const double *) c->d_cval.get(), (const double *) c->d_d.get(), ldb, c->W.get());
         HIP_RC(hipGetLastError());
-        HdmGemmArgs q = {};
-        q.A = c->W.get(); q.B = c->W.get(); q.a_kmajor = 1; q.b_kmajor = 1;
-        q.lda = 16; q.ldb = 16; q.a_kblk = ldb; q.b_kblk = ldb;
-        q.spanA = q.spanB = c->wspan;
-        q.C = l->Mdev.get(); q.ldc = ldm;
-        q.M = m16; q.N = m16; q.K = kp; q.batch = 1;
-        q.lower_only = 1; q.epilogue = HDM_EPI_STORE; q.alpha = 1.0; q.beta = 1.0; q.role = HDM_ROLE_GRAM;
-        q.flops = (double) c->m * (c->m + 1) * (double) kv;     // lower triangle, 2 flops a term
-        RC(hdm_launch_gemm(q, g.stream));
+        RC(hdm_launch_gemm(hdm_gram_lp(c->m, m16, c->mpad, c->kc, kv, kp, c->W.get(), l->Mdev.get(), ldm), g.stream));
     }
     return HDSDP_RETCODE_OK;
 }

@@ -111,6 +111,8 @@ static double issued_mfma_flops(const HdmGemmArgs &a, int subset) {
     return (double) hdm_launch_mfmas(tile_geom(a), subset) * 2048.0 * ((a.epilogue == HDM_EPI_SLAB) ? 1.0 : (double) a.batch);
 }
 
+// (tests/gemm_calls_driver.cpp restates tile_geom and the argument checks below for the host-only test of the call forms:
+// change them together)
 int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream) {
     if (args.M <= 0 || args.N <= 0 || args.batch <= 0) return 0;
     if ((args.M % 8) || (args.N % 8) || (args.K % HDM_BK)) {

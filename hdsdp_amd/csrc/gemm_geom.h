@@ -21,6 +21,8 @@
 #define HDM_BK 16             // k-depth of one LDS stage
 #define HDM_SUB 16            // MFMA sub-tile edge (v_mfma_f64_16x16x4_f64)
 
+static inline long hdm_roundup(long x, long q) { return (x + q - 1) / q * q; }
+
 enum HdmKLimit { HDM_KLIM_NONE = 0, HDM_KLIM_BY_M = 1, HDM_KLIM_BY_N = 2, HDM_KLIM_BAND = 3 };  // BAND: k in [tn*128, (tm+1)*128)
 enum HdmEpilogue {
     HDM_EPI_STORE = 0,    // C = alpha*acc + beta*C, column-major

@@ -1,13 +1,6 @@
 // hdm_common.h -- shared declarations for the MI355X (gfx950) HDSDP Schur engine.
 // Internal header (C++/HIP). The public C ABI lives in include/hdsdp_mi355x.h.
 #pragma once
-#include <cstddef>
-// Slack (bytes) appended to every device buffer that the role 1-3 GEMM kernels read as an operand: their staging loads
-// carry no row mask (gemm_tile.h, SStager::load_nomask), so the last tile of the last matrix in a buffer may read up
-// to 127 rows past its end.  `ld` = elements between consecutive rows (K-major) or 1 (M-major).
-static inline size_t hdm_operand_pad(long ld) { return (size_t) 128 * (size_t) (ld < 16 ? 16 : ld) * 8 + 4096; }
-#define HDM_OPERAND_PAD_DOUBLES 8192   /* the same slack for the [p-block][row][16] congruence output, in doubles */
-
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -23,6 +16,7 @@ hipError_t hdm_malloc(void **p, size_t bytes);   // alloc.cpp
 #include "devbuf.h"
 
 #include "gemm_geom.h"   // HDM_TILE / HDM_BK / HDM_SUB, HdmKLimit / HdmEpilogue / HdmRole, skyline storage, and the family's geometry
+#include "gemm_calls.h"  // HdmGemmArgs and its call forms; with work_plan.h: the layout, the operand slack and the spans
 
 typedef double hdm_d4 __attribute__((ext_vector_type(4)));
 
@@ -50,54 +44,7 @@ static inline hipError_t hdm_memcpy_h2d_sync(void *dst, const void *src, size_t 
     return hipDeviceSynchronize();
 }
 
-static inline long hdm_roundup(long x, long q) { return (x + q - 1) / q * q; }
-
-// ---------------------------------------------------------------------------------------------
-// GEMM family (gemm_f64.hip).  Everything is column-major fp64.
-//   C[M x N] = alpha * A[M x K] * B[N x K]^T + beta * C
-// Operand storage is selected per operand:
-//   M-major ("N"): element (i,k) at X[i + k*ld]  (rows contiguous: a column-major M x K matrix)
-//   K-major ("T"): element (i,k) at X[i*ld + k]  (k contiguous: the transpose is column-major)
-// ---------------------------------------------------------------------------------------------
-struct HdmGemmArgs {
-    const double *A, *B;
-    double *C;
-    // optional second product accumulated into the same tile (SYR2K form): C = alpha (A B^T + A2 B2^T) + beta C,
-    // same shapes, storage classes and K range as the first pair; A2 == nullptr: single product
-    const double *A2, *B2;
-    long lda2, ldb2, strideA2, strideB2;
-    int b_sky;        // congruence step 1: the B operand is a batch of skyline-stored A_L matrices (N = their dimension)
-    // roles 1-3 (unmasked tile loads): elements readable from each operand pointer, slack included; checked at launch
-    long spanA, spanB, spanA2, spanB2;
-    long lda, ldb, ldc;
-    long strideA, strideB, strideC;  // batch strides (elements) along blockIdx.z (batch) -- 0 = shared
-    int M, N, K;
-    int a_kmajor, b_kmajor;
-    long a_kblk, b_kblk;  // K-major operands: elements between consecutive 16-deep k blocks (16 for a plain matrix)
-    // K-major operands may be cut into row segments (one per source rank after the multi-GPU transpose):
-    // element offset += (row / seg_rows) * seg_extra.  seg_rows == 0: one segment.
-    long seg_rows, seg_extra;
-    int klimit;       // HdmKLimit: triangular operand => shorter K loop for early tiles
-    int lower_only;   // only tiles with tile_m >= tile_n are computed (C symmetric / lower)
-    unsigned long long tile_col_mask;  // != 0: only tile columns whose bit is set are computed (N <= 64 tiles; multi-GPU
-                                       // builds run congruence step 2 by packed-index range, see engine.hip)
-    int epilogue;     // HdmEpilogue
-    int batch;        // number of batch entries (grid z for STORE/BLOCKED), or #K-splits for SLAB
-    int queue_global; // persistent launches: ONE job queue for the whole chip, batch entry (K split) by batch entry in order,
-                      // instead of one queue per XCD over the entries x, x + 8, ... (gemm_tile.h: hdm_gemm_persist_kernel)
-    double alpha, beta;
-    int role;         // HdmRole
-    double flops;     // algorithmic flops of this launch (valid data only), for the live roofline
-    // BLOCKED epilogue: destination chunk layout  dst[((blk*16 + c_local) * rowStride + row) * 16 + r_local]
-    long blk_row_stride;  // = m_pad (number of constraint rows per 16-wide p-block)
-    long blk_row0;        // constraint row of batch entry 0
-    int nblk;             // n/16: sub-blocks per matrix edge
-    // SLAB epilogue / split-K
-    long k_chunk;         // K range per split (multiple of HDM_BK)
-    long k_base;          // first k of split 0 (a launch may cover a sub-range of the splits; C then points at its first slab)
-    long slab_stride;     // elements between slabs
-};
-
+// the GEMM family (gemm_f64.hip): its argument block and the call forms that fill it are gemm_calls.h's
 int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream);
 // while a stream capture is recording the launches (chol.hip), the launcher must not record timing events
 void hdm_gemm_capture_mode(int on);

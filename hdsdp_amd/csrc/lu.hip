@@ -303,12 +303,9 @@ int HdmLu::factor(hipStream_t s, int *info_host) {
         if (rem <= 0) break;
         hipLaunchKernelGGL(hdm_lu_trsm_kernel, dim3((rem + 255) / 256), dim3(256), 0, s, Ad, ld, nn, j0);
         HDM_HIP_CHECK(hipGetLastError());
-        HdmGemmArgs g = {};    // A22 -= L21 * U12   (B operand element (j,k) = U12(k,j): K-major)
-        g.A = Ad + (j0 + LNB) + (long) j0 * ld; g.lda = ld;
-        g.B = Ad + j0 + (long) (j0 + LNB) * ld; g.ldb = ld; g.b_kmajor = 1;
-        g.C = Ad + (long) (j0 + LNB) * (ld + 1); g.ldc = ld;
-        g.M = rem; g.N = rem; g.K = LNB; g.batch = 1; g.alpha = -1.0; g.beta = 1.0; g.epilogue = HDM_EPI_STORE;
-        if (hdm_launch_gemm(g, s)) return 1;
+        // A22 -= L21 * U12   (B operand element (j,k) = U12(k,j): K-major)
+        if (hdm_launch_gemm(hdm_gemm_product(Ad + (long) (j0 + LNB) * (ld + 1), ld, rem, rem, LNB, -1.0, hdm_mmajor(Ad + (j0 + LNB) + (long) j0 * ld, ld),
+                                             hdm_kmajor(Ad + j0 + (long) (j0 + LNB) * ld, ld), 1.0), s)) return 1;
     }
     int info = 0;
     std::vector<int> hp(npad), hperm(npad);

@@ -121,11 +121,8 @@ extern "C" {
 int HMiGemmNT(const double *A, int64_t lda, int aKMajor, const double *B, int64_t ldb, int bKMajor, double *C,
               int64_t ldc, int M, int N, int K, double alpha, double beta, int kLimit, int lowerOnly) {
     if (ensure_ctx()) return 1;
-    HdmGemmArgs q = {};
-    q.A = A; q.lda = lda; q.a_kmajor = aKMajor; q.B = B; q.ldb = ldb; q.b_kmajor = bKMajor; q.C = C; q.ldc = ldc;
-    q.M = M; q.N = N; q.K = K; q.alpha = alpha; q.beta = beta; q.klimit = kLimit; q.lower_only = lowerOnly;
-    q.batch = 1; q.epilogue = HDM_EPI_STORE;
-    if (hdm_launch_gemm(q, g.stream)) return 1;
+    if (hdm_launch_gemm(hdm_gemm_product(C, ldc, M, N, K, alpha, hdm_operand(A, lda, aKMajor), hdm_operand(B, ldb, bKMajor), beta, hdm_klimit(kLimit).lower(lowerOnly)),
+                        g.stream)) return 1;
     HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
     return 0;
 }

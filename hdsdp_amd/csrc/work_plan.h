@@ -4,10 +4,11 @@
 // what this header says (engine_cone.h: cone_alloc_common, cone_alloc_gemm_work; engine_create.h: cone_alloc_batch), and
 // HMiWorkPlanQuery hands the same numbers to callers without a device (hdsdp_amd/dist.py: ShardPlan.hbm_bytes).
 #pragma once
-#include "hdm_common.h"
+#include "gemm_geom.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 
 // ---- layout ---------------------------------------------------------------------------------
@@ -39,6 +40,22 @@ static inline long hdm_rows_of_rank(int m, int world, int rank) { return rank < 
 // it not counted); one device reads the Gram operand where the congruence wrote it, a sharded block has a send and a receive side.
 static inline size_t hdm_exchange_doubles(const HdmLayout &L) { return (size_t) L.world * L.npb_loc * L.Lr * 16; }
 static inline size_t hdm_exchange_bytes(const HdmLayout &L) { return sizeof(double) * hdm_exchange_doubles(L) * (L.world == 1 ? 1 : 2); }
+
+// ---- operand slack and spans ------------------------------------------------------------------
+// Slack (bytes) appended to every device buffer that the role 1-3 GEMM kernels read as an operand: their staging loads
+// carry no row mask (gemm_tile.h, SStager::load_nomask), so the last tile of the last matrix in a buffer may read up
+// to 127 rows past its end.  `ld` = elements between consecutive rows (K-major) or 1 (M-major).
+static inline size_t hdm_operand_pad(long ld) { return (size_t) 128 * (size_t) (ld < 16 ? 16 : ld) * 8 + 4096; }
+#define HDM_OPERAND_PAD_DOUBLES 8192   /* the same slack for the [p-block][row][16] congruence output, in doubles */
+// Elements readable from the start of each operand buffer of the Schur build, slack included -- what a role launch vouches for
+// (gemm_calls.h), never more than the allocation: the intermediates T of `Bc` matrices, the factor inverse (npad x npad), a
+// buffer of `rows` skyline matrices (Afull, a regenerated batch, CL), an exchange buffer, the LP cone's dense buffer.
+static inline long hdm_t_span(const HdmLayout &L, long Bc) { return (long) L.n16 * L.n16 * Bc + (long) (hdm_operand_pad(L.n16) / sizeof(double)); }
+static inline long hdm_linv_span(long npad) { return npad * npad; }
+static inline long hdm_afull_span(const HdmLayout &L, long rows) { return L.astride * rows + (long) (hdm_operand_pad(L.n16) / sizeof(double)); }
+static inline long hdm_exchange_span(const HdmLayout &L) { return (long) hdm_exchange_doubles(L) + HDM_OPERAND_PAD_DOUBLES; }
+// the LP cone's dense buffer W: [kc / 16][mpad][16] doubles (engine_lp.h: lp_build_dense_buffer)
+static inline long hdm_lp_span(int kc, int mpad) { return (long) (kc / 16) * mpad * 16 + HDM_OPERAND_PAD_DOUBLES; }
 
 // ---- knobs ----------------------------------------------------------------------------------
 // The A/B and test switches of the plan (include/hdsdp_mi355x.h lists them), as the environment states them NOW: the engine

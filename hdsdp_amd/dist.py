@@ -141,7 +141,7 @@ class Exchange:
         self.plan = ShardPlan(cone.n, cone.m, self.world)
         count = self.plan.chunk * self.world
         # torch owns the exchange buffers so RCCL sees registered allocations; the engine's Gram kernel reads them
-        # with unmasked tile loads, hence the slack behind the payload (hdm_common.h: HDM_OPERAND_PAD_DOUBLES)
+        # with unmasked tile loads, hence the slack behind the payload (work_plan.h: HDM_OPERAND_PAD_DOUBLES)
         pad = 8192
         self._send_full = torch.zeros(count + pad, dtype=torch.float64, device="cuda")
         self._recv_full = torch.zeros(count + pad, dtype=torch.float64, device="cuda") if self.world > 1 else self._send_full
