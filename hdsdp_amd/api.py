@@ -39,7 +39,7 @@ EXPORTS = [
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiGetAssembleCounts", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
-    "HMiWorkPlanQuery", "HMiConeGetWorkPlan",
+    "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
 ]
 
@@ -201,6 +201,10 @@ def load_library():
         "HMiRcmOrder": (C.c_int, [C.c_int, ip, ip, ip]),
         "HMiWorkPlanQuery": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
         "HMiConeGetWorkPlan": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
+        "HMiKKTSetGroupedBuild": (C.c_int, [kp, C.c_int]),
+        "HMiKKTGetGroupedBuild": (C.c_int, [kp, ip, ip, ip]),
+        "HMiGroupedPlanQuery": (C.c_int, [C.c_int, C.c_int, ip, ip, ip, ip, C.POINTER(C.c_int64), ip, ip, ip, ip, ip, C.POINTER(C.c_int64), ip, ip, ip,
+                                          C.POINTER(C.c_int64), ip, ip]),
         "HMiPresolveCSC": (C.c_int, [C.c_int, C.c_int, ip, ip, dp, ip, ip, ip, ip, ip, ip]),
         "HMiReadSDPA": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "HMiSDPAGetDims": (None, [vp, ip, ip, ip]),
@@ -298,6 +302,39 @@ def work_plan(n, m, world=1, rank=0):
     if load_library().HMiWorkPlanQuery(n, m, world, rank, out, len(out)) != len(out):
         raise HDSDPError(f"HMiWorkPlanQuery refused n={n} m={m} world={world} rank={rank}")
     return dict(zip(WORK_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def grouped_plan(m, cones):
+    """the grouped Schur build's plan (csrc/grouped_plan.h through HMiGroupedPlanQuery) for an operator of m rows whose cones are
+    given as (n, rows) or (n, rows, kind_ok): block dimension, global rows owned in local order, and whether the cone is of the
+    kind the engine groups at all (default True).  Host arithmetic; needs no GPU.  Returns a dict: cones (grouped), n_eligible,
+    eligible / slot_of (per cone), jobs (slot, q0, q1, first), the destinations of M (m_row >= m_col) with their contributors as a
+    CSR (m_ptr, m_slot, m_idx), the same for the vectors' rows (v_row, v_ptr, v_slot, v_idx), staging_doubles"""
+    lib = load_library()
+    nc = len(cones)
+    dims = np.asarray([int(c[0]) for c in cones], dtype=np.int32).reshape(nc)
+    kind = np.asarray([1 if (len(c) < 3 or c[2]) else 0 for c in cones], dtype=np.int32).reshape(nc)
+    rows = [np.asarray(c[1], dtype=np.int32).reshape(-1) for c in cones]
+    beg = np.zeros(nc + 1, dtype=np.int32)
+    beg[1:] = np.cumsum([r.size for r in rows])
+    allrows = np.ascontiguousarray(np.concatenate(rows + [np.zeros(1, dtype=np.int32)]), dtype=np.int32)
+    counts = (C.c_int64 * 8)()
+    el, slot = np.zeros(max(1, nc), dtype=np.int32), np.zeros(max(1, nc), dtype=np.int32)
+    head = (int(m), nc, _iptr(dims), _iptr(kind), _iptr(beg), _iptr(allrows), counts, _iptr(el), _iptr(slot))
+    if lib.HMiGroupedPlanQuery(*head, *([None] * 10)) != 8:
+        raise HDSDPError("HMiGroupedPlanQuery refused the operator")
+    ng, nj, nm, nmc, nv, nvc = (int(counts[i]) for i in range(6))
+    iz = lambda k: np.zeros(max(1, k), dtype=np.int32)        # noqa: E731
+    lz = lambda k: np.zeros(max(1, k), dtype=np.int64)        # noqa: E731
+    jobs, mr, mcl, mp, ms, mi, vr, vp_, vs, vi = iz(4 * nj), iz(nm), iz(nm), lz(nm + 1), iz(nmc), iz(nmc), iz(nv), lz(nv + 1), iz(nvc), iz(nvc)
+    lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))     # noqa: E731
+    if lib.HMiGroupedPlanQuery(*head, _iptr(jobs), _iptr(mr), _iptr(mcl), lp(mp), _iptr(ms), _iptr(mi), _iptr(vr), lp(vp_), _iptr(vs),
+                               _iptr(vi)) != 8:
+        raise HDSDPError("HMiGroupedPlanQuery refused the operator")
+    return {"cones": ng, "n_eligible": int(counts[7]), "eligible": el[:nc].astype(bool), "slot_of": slot[:nc].copy(),
+            "jobs": jobs[:4 * nj].reshape(nj, 4), "m_row": mr[:nm], "m_col": mcl[:nm], "m_ptr": mp[:nm + 1], "m_slot": ms[:nmc],
+            "m_idx": mi[:nmc], "v_row": vr[:nv], "v_ptr": vp_[:nv + 1], "v_slot": vs[:nvc], "v_idx": vi[:nvc],
+            "staging_doubles": int(counts[6])}
 
 
 def assemble_counts():
@@ -820,6 +857,17 @@ class KKT:
         """HMiKKTSetHostMirror: 1 = the host copy of M is refreshed after every build; 0 = M stays on the device and kktDiag[]
         points into the diagonal channel (refused, with a stderr line, while a host cone sits in the operator)"""
         load_library().HMiKKTSetHostMirror(self._k, 1 if on else 0)
+
+    def set_grouped_build(self, on):
+        """HMiKKTSetGroupedBuild: all eligible small SDP cones of the operator are built in one pass of three launches
+        (csrc/grouped_plan.h has the rule); returns the number of cones that will be grouped (0: off, or fewer than two eligible)"""
+        return int(load_library().HMiKKTSetGroupedBuild(self._k, 1 if on else 0))
+
+    def grouped_build_info(self):
+        """HMiKKTGetGroupedBuild: dict(cones, jobs, launches) of the last build's grouped pass (all 0: it did not run)"""
+        c, j, l = C.c_int(0), C.c_int(0), C.c_int(0)
+        load_library().HMiKKTGetGroupedBuild(self._k, C.byref(c), C.byref(j), C.byref(l))
+        return {"cones": c.value, "jobs": j.value, "launches": l.value}
 
     def diag_target(self):
         """HMiKKTGetDiagTarget: 0 = kktDiag[] points into kktMatElem, 1 = into the diagonal channel"""

@@ -135,6 +135,7 @@ int ensure_ctx() {
 
 namespace {
 #include "engine_build_small.h"
+#include "engine_grouped.h"
 }  // namespace
 
 // =============================================================================================

@@ -220,6 +220,36 @@ int HMiWorkPlanQuery(int n, int m, int world, int rank, int64_t *out, int cap) {
     memcpy(out, v, sizeof(v));
     return 17;
 }
+// the grouped build's plan (grouped_plan.h) for an operator described by arrays -- host only, no context, no device
+int HMiGroupedPlanQuery(int nRow, int nCones, const int *dims, const int *kindOk, const int *rowBeg, const int *rows, int64_t *counts,
+                        int *eligible, int *slotOf, int *jobs, int *mRow, int *mCol, int64_t *mPtr, int *mSlot, int *mIdx, int *vRow,
+                        int64_t *vPtr, int *vSlot, int *vIdx) {
+    if (nRow < 0 || nCones < 0 || !dims || !kindOk || !rowBeg || !counts || rowBeg[0] != 0) return -1;
+    std::vector<HdmGroupedCone> cs((size_t) nCones);
+    for (int k = 0; k < nCones; ++k) {
+        if (rowBeg[k + 1] < rowBeg[k] || (rowBeg[k + 1] > rowBeg[k] && !rows)) return -1;
+        for (int q = rowBeg[k]; q < rowBeg[k + 1]; ++q) if (rows[q] < 0 || rows[q] >= nRow) return -1;
+        cs[(size_t) k].n = dims[k]; cs[(size_t) k].mloc = rowBeg[k + 1] - rowBeg[k];
+        cs[(size_t) k].rows = rows ? rows + rowBeg[k] : nullptr; cs[(size_t) k].kind_ok = kindOk[k] != 0;
+    }
+    const HdmGroupedPlan p = hdm_grouped_plan(nRow, cs);
+    int nel = 0;
+    for (int k = 0; k < nCones; ++k) {
+        const int e = hdm_grouped_eligible(cs[(size_t) k]) ? 1 : 0;
+        nel += e;
+        if (eligible) eligible[k] = e;
+        if (slotOf) slotOf[k] = p.slot_of[(size_t) k];
+    }
+    const int64_t v[8] = {(int64_t) p.cones.size(), (int64_t) p.jobs.size(), (int64_t) p.m_row.size(), (int64_t) p.m_slot.size(),
+                          (int64_t) p.v_row.size(), (int64_t) p.v_slot.size(), (int64_t) (p.x_doubles + p.g_doubles + p.v_doubles), nel};
+    memcpy(counts, v, sizeof(v));
+    if (jobs) for (size_t j = 0; j < p.jobs.size(); ++j) { jobs[4 * j] = p.jobs[j].slot; jobs[4 * j + 1] = p.jobs[j].q0; jobs[4 * j + 2] = p.jobs[j].q1; jobs[4 * j + 3] = p.jobs[j].first; }
+    auto put = [](int *dst, const std::vector<int> &src) { if (dst && !src.empty()) memcpy(dst, src.data(), sizeof(int) * src.size()); };
+    put(mRow, p.m_row); put(mCol, p.m_col); put(mSlot, p.m_slot); put(mIdx, p.m_idx); put(vRow, p.v_row); put(vSlot, p.v_slot); put(vIdx, p.v_idx);
+    if (mPtr) for (size_t e = 0; e < p.m_ptr.size(); ++e) mPtr[e] = p.m_ptr[e];
+    if (vPtr) for (size_t e = 0; e < p.v_ptr.size(); ++e) vPtr[e] = p.v_ptr[e];
+    return 8;
+}
 int HMiConeGetWorkPlan(hdsdp_cone *cone, int64_t *out, int cap) {
     const MiCone *c = cone_data(cone);
     if (!c || !out || cap < 7) return -1;

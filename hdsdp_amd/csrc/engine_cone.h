@@ -144,7 +144,30 @@ struct MiCone {
     } small;
 };
 
+// The grouped Schur build of an operator (grouped_plan.h: rule and plan; engine_grouped.h performs it).
+// Decided at HKKTInit: which cones are eligible (`desc`, `n_eligible`).  The job and contributor lists (`plan`: empty unless at
+// least two cones are eligible), their device copies and the staging buffers are made when the switch is first turned on, so an
+// operator that never uses the pass pays for none of them.
+struct MiGrouped {
+    bool on = false;                 // HMiKKTSetGroupedBuild / HDSDP_MI355X_GROUPED_BUILD
+    std::vector<HdmGroupedCone> desc;   // the operator's cones as the rule sees them (rows: the cones' own vectors, not owned)
+    int n_eligible = 0;
+    bool planned = false;
+    HdmGroupedPlan plan;
+    bool dev_ready = false;
+    int max_n16 = 0;
+    HdmPinned<HdmGroupedConeDev> cones_host;   // refreshed per build (Rd moves), uploaded from here
+    HdmBuf<HdmGroupedConeDev> cones_dev;
+    HdmBuf<HdmGroupedJob> jobs;
+    HdmBuf<int> m_row, m_col, m_slot, m_idx, v_row, v_slot, v_idx;
+    HdmBuf<long> m_ptr, v_ptr;
+    HdmBuf<double> X, G, V;          // staging: S^-1 per cone, packed local Gram matrices, local vectors + scalars
+    int last_cones = 0, last_jobs = 0, last_launches = 0;   // the last build (HMiKKTGetGroupedBuild)
+    bool used() const { return on && plan.used(); }
+};
+
 struct MiKKTPriv {
+    MiGrouped grp;
     // how M is stored, what state it is in and where the last factorised matrix came from (kkt_store.h); the operator's linear
     // system (MiLin::st) points here
     HdmKktState st;

@@ -368,6 +368,13 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     rc = kkt_init_device_common(HKKT, pv);
     if (rc != HDSDP_RETCODE_OK) return rc;
     if (sw.device_m) kkt_apply_device_m(HKKT, pv);
+    // the grouped Schur build (engine_grouped.h): eligibility is decided for every operator, the pass is used when the switch is on
+    grouped_init_plan(HKKT, pv);
+    static const bool grouped_env = [] { const char *e = getenv("HDSDP_MI355X_GROUPED_BUILD"); return e && atoi(e) != 0; }();
+    if (grouped_env) {
+        const int k = grouped_set(HKKT, pv, 1);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_BUILD=1: %d of %d cone(s) are built in one grouped pass\n", k, nCones);
+    }
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
 }
@@ -503,14 +510,25 @@ static hdsdp_retcode kkt_pull(hdsdp_kkt *HKKT, int typeKKT) {
     return HDSDP_RETCODE_OK;
 }
 
-hdsdp_retcode HKKTBuildUp(hdsdp_kkt *HKKT, int typeKKT) {
-    StatScope stat_(typeKKT == KKT_TYPE_CORRECTOR ? ST_BUILD_CORR : ST_BUILD_M, __func__);
+// HKKTBuildUp and HKKTBuildUpFixed: clean, then the cones in order -- the grouped cones of the operator (engine_grouped.h; none
+// unless the switch is on) all at once, where the first of them sits, every other cone through its own slot -- then the pull.
+static hdsdp_retcode kkt_build_cones(hdsdp_kkt *HKKT, int typeKKT, bool fixed, int kktStrategy) {
     hdsdp_retcode rc = kkt_clean(HKKT, typeKKT);
     if (rc != HDSDP_RETCODE_OK) return rc;
+    MiKKTPriv *pv = priv_of(HKKT);
+    const bool grouped = pv->grp.used() && typeKKT != KKT_TYPE_PRIMAL;
+    pv->grp.last_cones = pv->grp.last_jobs = pv->grp.last_launches = 0;
+    bool grouped_done = false;
     for (int i = 0; i < HKKT->nCones; ++i) {
         hdsdp_cone *c = HKKT->cones[i];
-        rc = c->coneBuildSchur(c->coneData, c->iCone, HKKT, typeKKT);  // == HConeBuildSchurComplement
-        if (stat_trace()) {
+        if (grouped && pv->grp.plan.slot_of[(size_t) i] >= 0) {
+            if (grouped_done) continue;
+            grouped_done = true;
+            rc = grouped_build(HKKT, pv, typeKKT);
+        }
+        else if (fixed) rc = c->coneBuildSchurFixed(c->coneData, c->iCone, HKKT, typeKKT, kktStrategy);
+        else rc = c->coneBuildSchur(c->coneData, c->iCone, HKKT, typeKKT);  // == HConeBuildSchurComplement
+        if (!fixed && stat_trace()) {
             const hipError_t e = hipDeviceSynchronize();
             fprintf(stderr, "[hdsdp_mi355x trace]   build type %d, cone %d of %d -> rc %d, %s\n", typeKKT, i, HKKT->nCones, (int) rc,
                     e == hipSuccess ? "ok" : hipGetErrorName(e));
@@ -518,6 +536,11 @@ hdsdp_retcode HKKTBuildUp(hdsdp_kkt *HKKT, int typeKKT) {
         if (rc != HDSDP_RETCODE_OK) return rc;
     }
     return kkt_pull(HKKT, typeKKT);
+}
+
+hdsdp_retcode HKKTBuildUp(hdsdp_kkt *HKKT, int typeKKT) {
+    StatScope stat_(typeKKT == KKT_TYPE_CORRECTOR ? ST_BUILD_CORR : ST_BUILD_M, __func__);
+    return kkt_build_cones(HKKT, typeKKT, false, 0);
 }
 
 hdsdp_retcode HKKTBuildUpExtraCone(hdsdp_kkt *HKKT, hdsdp_cone *cone, int typeKKT) {
@@ -528,14 +551,7 @@ hdsdp_retcode HKKTBuildUpExtraCone(hdsdp_kkt *HKKT, hdsdp_cone *cone, int typeKK
 
 hdsdp_retcode HKKTBuildUpFixed(hdsdp_kkt *HKKT, int typeKKT, int kktStrategy) {
     StatScope stat_(typeKKT == KKT_TYPE_CORRECTOR ? ST_BUILD_CORR : ST_BUILD_M, __func__);
-    hdsdp_retcode rc = kkt_clean(HKKT, typeKKT);
-    if (rc != HDSDP_RETCODE_OK) return rc;
-    for (int i = 0; i < HKKT->nCones; ++i) {
-        hdsdp_cone *c = HKKT->cones[i];
-        rc = c->coneBuildSchurFixed(c->coneData, c->iCone, HKKT, typeKKT, kktStrategy);
-        if (rc != HDSDP_RETCODE_OK) return rc;
-    }
-    return kkt_pull(HKKT, typeKKT);
+    return kkt_build_cones(HKKT, typeKKT, true, kktStrategy);
 }
 
 void HKKTExport(hdsdp_kkt *HKKT, double *dKKTASinvVec, double *dKKTASinvRdSinvVec, double *dKKTASinvCSinvVec,
@@ -668,6 +684,14 @@ void HMiKKTSetHostMirror(hdsdp_kkt *HKKT, int mirrorM) {
     }
     pv->st.mirror_switched(mirrorM != 0);
     kkt_point_diag(HKKT, pv);
+}
+int HMiKKTSetGroupedBuild(hdsdp_kkt *HKKT, int on) { return grouped_set(HKKT, priv_of(HKKT), on); }
+int HMiKKTGetGroupedBuild(hdsdp_kkt *HKKT, int *cones, int *jobs, int *launches) {
+    const MiGrouped &gr = priv_of(HKKT)->grp;
+    if (cones) *cones = gr.last_cones;
+    if (jobs) *jobs = gr.last_jobs;
+    if (launches) *launches = gr.last_launches;
+    return gr.last_cones > 0 ? 1 : 0;
 }
 int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
     MiKKTPriv *pv = priv_of(HKKT);

@@ -1,8 +1,10 @@
 // small.h -- the fused single-launch Phase-A pass for small rank-one blocks (small.hip)
 #pragma once
 #include "hdm_common.h"
+#include "bsparse.h"
+#include "grouped_plan.h"
 
-#define SMALL_P 128        // padded dimension: n, m <= 128
+#define SMALL_P 128       // padded dimension: n, m <= 128
 #define SMALL_SPMAX 8      // a rank-one factor with more entries than this is treated as dense
 #define SMALL_NDENSE 4     // at most this many dense factors per block
 
@@ -45,3 +47,33 @@ int hdm_small_check(const HdmSmallCheckArgs &args, hipStream_t s);
 
 size_t hdm_small_lds_bytes();
 int hdm_small_phase_a(const HdmSmallArgs &args, hipStream_t s);
+
+// ---- the grouped Schur build: every eligible small SDP block of an operator in three launches (grouped_plan.h has the rule and
+// the plan, DESIGN.md section 17 the whole story) -------------------------------------------------------------------------
+struct HdmGroupedConeDev {              // one grouped cone as the kernels see it
+    int n, n16, mloc, pad;
+    const double *W;                    // 128 x 128 triangular inverse of the dual factor (HdmChol::Dinv of a one-block factor)
+    const double *A;                    // mloc matrices in A_L form, column-major n16 x n16 each
+    const double *C;                    // objective, full symmetric, ld n16
+    double Rd;
+    long xoff, goff, voff;              // this cone's places in the three staging buffers (doubles)
+};
+struct HdmGroupedArgs {
+    const HdmGroupedConeDev *cones; int ncones;
+    const HdmGroupedJob *jobs; int njobs;
+    int max_n16;                        // the largest n16 among the cones (sizes the jobs' LDS)
+    int typeKKT;                        // KKT_TYPE_INFEASIBLE 0, _CORRECTOR 1, _HOMOGENEOUS 2
+    double *X, *G, *V;                  // staging: S^-1 per cone; packed local lower Gram; ASinv, ASinvRdSinv, ASinvCSinv (mloc each) + 4 scalars
+};
+struct HdmGroupedScatterArgs {
+    const HdmGroupedConeDev *cones; int ncones;
+    long nM; const int *m_row, *m_col; const long *m_ptr; const int *m_slot, *m_idx;   // destinations of M and their contributors (CSR)
+    int nV; const int *v_row; const long *v_ptr; const int *v_slot, *v_idx;           // rows of the m-vectors and theirs
+    const double *G, *V;
+    double *vecs; int m;                // the operator's accumulators: ASinv[m], ASinvRdSinv[m], ASinvCSinv[m], scal[4]
+    int typeKKT;
+};
+size_t hdm_grouped_lds_bytes(int n16);
+int hdm_grouped_inverses(const HdmGroupedArgs &a, hipStream_t s);                               // launch 1: one workgroup per cone
+int hdm_grouped_jobs(const HdmGroupedArgs &a, hipStream_t s);                                   // launch 2: one workgroup per job
+int hdm_grouped_scatter(const HdmGroupedScatterArgs &a, const HdmMatView &Mv, hipStream_t s);   // launch 3: one thread per destination

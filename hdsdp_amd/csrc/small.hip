@@ -413,5 +413,207 @@ int hdm_small_phase_a(const HdmSmallArgs &args, hipStream_t s) {
     return 0;
 }
 
+// ---- the grouped Schur build (see small.h, grouped_plan.h) ----------------------------------------------
+// Three launches for all grouped cones of an operator, whatever their number: plain independent workgroups, no workgroup waits
+// for another one, nothing is accumulated with atomics -- every staging word has one writer, every destination one adder.
+#define GR_T 256
+#define GR_W (GR_T / 64)
+typedef double gr_c4 __attribute__((ext_vector_type(4)));
+
+// Launch 1.  X = S^-1 = W'W from the triangular inverse W = L^-1 the cone's factor object holds (row k of W is zero right of column
+// k, and the padding of the 128-block is the identity: only rows below n enter).  Full symmetric n16 x n16, zero in the padding.
+__global__ __launch_bounds__(GR_T) void hdm_grouped_inverse_kernel(HdmGroupedArgs a) {
+    __shared__ double Wl[HDM_GROUPED_MAX_N * (HDM_GROUPED_MAX_N + 1)];   // W(k, i) at k + 65 i
+    const HdmGroupedConeDev c = a.cones[blockIdx.x];
+    const int n = c.n, n16 = c.n16, tid = threadIdx.x;
+    constexpr int ldw = HDM_GROUPED_MAX_N + 1;
+    for (int e = tid; e < n * n; e += GR_T) {
+        const int k = e % n, i = e / n;
+        Wl[k + i * ldw] = (k >= i) ? c.W[k + (long) i * SMALL_P] : 0.0;
+    }
+    __syncthreads();
+    double *X = a.X + c.xoff;
+    for (int e = tid; e < n16 * n16; e += GR_T) {
+        const int i = e % n16, j = e / n16;
+        if (i < j) continue;
+        double v = 0.0;
+        if (i < n)
+            for (int k = i; k < n; ++k) v += Wl[k + i * ldw] * Wl[k + j * ldw];
+        X[i + (long) j * n16] = v;
+        X[j + (long) i * n16] = v;
+    }
+}
+
+// out(j, i) = sum_k P(i, k) Q(k, j) on the fp64 MFMA, every operand from LDS: P's element (i, k) is read at Pl[i + k ld], Q's
+// element (k, j) at Ql[j + k ld] -- both fragments are sixteen consecutive doubles per k -- and the 16 x 16 result tile (lane l,
+// register r: row (l >> 4) + 4 r, column l & 15) is stored transposed, which makes its stores consecutive as well.  The callers
+// choose P and Q among symmetric matrices and transposes so that what lands in `out` is the column-major product they want.
+__device__ __forceinline__ void gr_product(const double *Pl, const double *Ql, double *out, int nb, int ld, int wave, int lane) {
+    const int l15 = lane & 15, lq = lane >> 4;
+    for (int t = wave; t < nb * nb; t += GR_W) {
+        const int ti = t % nb, tj = t / nb;
+        const double *pa = Pl + ti * 16 + l15 + lq * ld, *pb = Ql + tj * 16 + l15 + lq * ld;
+        gr_c4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < 4 * nb; ++k) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[4 * k * ld], pb[4 * k * ld], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[tj * 16 + l15 + (ti * 16 + lq + 4 * r) * ld] = acc[r];
+    }
+}
+
+__device__ __forceinline__ double gr_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// The symmetric matrix in Al (a constraint matrix, or the objective) against X: T = X Al, B = T X, and the three sums
+// s[0] = <Al, X>, s[1] = <T, X> = <Al, X^2>, s[2] = <B, C>; thread 0 returns with them.  Products and sums the build type or a zero Rd
+// does not ask for are skipped (their sums come back as 0).  Ends behind a barrier: B and Al stay valid until the caller's next one.
+__device__ __forceinline__ void gr_row(const double *Xl, const double *Al, double *Tl, double *Bl, const double *C, double *red,
+                                       int n16, bool needT, bool needB, bool needC, double (&s)[3]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nb = n16 >> 4, nn = n16 * n16;
+    if (needT) gr_product(Al, Xl, Tl, nb, n16, wave, lane);      // (Al X)(i, j) stored at j + i ld: column-major X Al
+    __syncthreads();
+    if (needB) gr_product(Xl, Tl, Bl, nb, n16, wave, lane);      // Q(k, j) = T(j, k): (X T')(i, j) = (X Al X)(i, j) stored at j + i ld
+    __syncthreads();
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+    for (int e = tid; e < nn; e += GR_T) {
+        const double x = Xl[e];
+        p0 += Al[e] * x;
+        if (needT) p1 += Tl[e] * x;
+        if (needC) p2 += Bl[e] * C[e];
+    }
+    p0 = gr_wave_sum(p0); p1 = gr_wave_sum(p1); p2 = gr_wave_sum(p2);
+    if (lane == 0) { red[wave * 3] = p0; red[wave * 3 + 1] = p1; red[wave * 3 + 2] = p2; }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = (red[k] + red[3 + k]) + (red[6 + k] + red[9 + k]);
+    __syncthreads();
+}
+
+// Launch 2.  One workgroup per job (grouped_plan.h): X in LDS, then row after row of the job.  Writes staging only: the local vectors
+// of its rows, column q of the cone's local lower Gram, and -- the cone's first job -- the four scalars.
+__global__ __launch_bounds__(GR_T) void hdm_grouped_jobs_kernel(HdmGroupedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const HdmGroupedJob job = a.jobs[blockIdx.x];
+    const HdmGroupedConeDev c = a.cones[job.slot];
+    const int n16 = c.n16, nn = n16 * n16, mloc = c.mloc;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double *Xl = sm, *Al = sm + nn, *Tl = sm + 2 * nn, *Bl = sm + 3 * nn, *red = sm + 4 * nn;
+    const bool corrector = a.typeKKT == 1, hsd = a.typeKKT == 2, rd = c.Rd != 0.0;
+    const double *X = a.X + c.xoff;
+    double *V = a.V + c.voff, *G = a.G + c.goff;
+    for (int e = tid; e < nn; e += GR_T) Xl[e] = X[e];
+    double s[3];
+    if (job.first) {
+        // TraceSinv (Rd != 0), and under HSD the objective as one more row: CSinv = <C, X>, CSinvCSinv = <X C X, C>, CSinvRdSinv = Rd <C, X^2>
+        double sc[4] = {0.0, 0.0, 0.0, 0.0};
+        if (hsd) {
+            for (int e = tid; e < nn; e += GR_T) Al[e] = c.C[e];
+            __syncthreads();
+            gr_row(Xl, Al, Tl, Bl, c.C, red, n16, true, true, true, s);
+            sc[1] = s[0]; sc[2] = s[2];
+            if (rd) sc[3] = c.Rd * s[1];
+        } else __syncthreads();
+        if (tid == 0) {
+            if (rd && !corrector)
+                for (int i = 0; i < c.n; ++i) sc[0] += Xl[i + i * n16];
+            for (int k = 0; k < 4; ++k) V[3 * mloc + k] = sc[k];
+        }
+    }
+    for (int q = job.q0; q < job.q1; ++q) {
+        __syncthreads();                                   // the previous row's images are done with
+        const double *AL = c.A + (long) q * nn;            // (n16 <= 64: the skyline storage of an A_L form is the plain square)
+        for (int e = tid; e < nn; e += GR_T) {
+            const int i = e % n16, j = e / n16;
+            if (i < j) continue;
+            const double v = AL[e];
+            if (i == j) Al[e] = 2.0 * v;                   // A_L form: half the diagonal is stored
+            else { Al[e] = v; Al[j + i * n16] = v; }
+        }
+        __syncthreads();
+        gr_row(Xl, Al, Tl, Bl, c.C, red, n16, rd || !corrector, !corrector, hsd, s);
+        if (tid == 0) {
+            V[q] = s[0];
+            V[mloc + q] = rd ? c.Rd * s[1] : 0.0;
+            V[2 * mloc + q] = hsd ? s[2] : 0.0;
+        }
+        if (corrector) continue;
+        // column q of the local Gram: <B_q, A_p> = sum over the stored triangle of A_L,p (i, j) (B(i, j) + B(j, i)), one wave per p
+        for (int p = q + wave; p < mloc; p += GR_W) {
+            const double *AP = c.A + (long) p * nn;
+            double acc = 0.0;
+            for (int e = lane; e < nn; e += 64) {
+                const int i = e % n16, j = e / n16;
+                if (i >= j) acc += AP[e] * (Bl[e] + Bl[j + i * n16]);
+            }
+            acc = gr_wave_sum(acc);
+            if (lane == 0) G[hdm_grouped_gidx(p, q, mloc)] = acc;
+        }
+    }
+}
+
+// Launch 3.  One thread per destination: an entry of M's lower triangle, a row of the m-vectors, or (the last thread) the four
+// scalars.  It sums its contributors in list order -- ascending cone order -- and adds the sum where the per-cone builders add
+// theirs.  A corrector build has no M: its threads start behind M's destinations.
+__global__ __launch_bounds__(GR_T) void hdm_grouped_scatter_kernel(HdmGroupedScatterArgs a, HdmMatView Mv) {
+    const bool corrector = a.typeKKT == 1, hsd = a.typeKKT == 2;
+    const long t = (long) blockIdx.x * GR_T + threadIdx.x + (corrector ? a.nM : 0L);
+    if (t < a.nM) {
+        double acc = 0.0;
+        for (long k = a.m_ptr[t]; k < a.m_ptr[t + 1]; ++k) acc += a.G[a.cones[a.m_slot[k]].goff + a.m_idx[k]];
+        *hdm_mat_at(Mv, a.m_row[t], a.m_col[t]) += acc;
+    } else if (t < a.nM + a.nV) {
+        const long r = t - a.nM;
+        for (int v = 0; v < (hsd ? 3 : 2); ++v) {
+            double acc = 0.0;
+            for (long k = a.v_ptr[r]; k < a.v_ptr[r + 1]; ++k) {
+                const HdmGroupedConeDev &c = a.cones[a.v_slot[k]];
+                acc += a.V[c.voff + (long) v * c.mloc + a.v_idx[k]];
+            }
+            a.vecs[(long) v * a.m + a.v_row[r]] += acc;
+        }
+    } else if (t == a.nM + a.nV) {
+        for (int k = 0; k < 4; ++k) {
+            double acc = 0.0;
+            for (int s = 0; s < a.ncones; ++s) acc += a.V[a.cones[s].voff + 3L * a.cones[s].mloc + k];
+            a.vecs[3L * a.m + k] += acc;
+        }
+    }
+}
+
+size_t hdm_grouped_lds_bytes(int n16) { return sizeof(double) * (4 * (size_t) n16 * n16 + 3 * GR_W + 4); }
+
+int hdm_grouped_inverses(const HdmGroupedArgs &a, hipStream_t s) {
+    if (a.ncones < 1 || a.max_n16 > HDM_GROUPED_MAX_N) return 1;
+    hipLaunchKernelGGL(hdm_grouped_inverse_kernel, dim3(a.ncones), dim3(GR_T), 0, s, a);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int hdm_grouped_jobs(const HdmGroupedArgs &a, hipStream_t s) {
+    if (a.njobs < 1 || a.max_n16 < 16 || a.max_n16 > HDM_GROUPED_MAX_N || (a.max_n16 & 15) || a.typeKKT < 0 || a.typeKKT > 2) return 1;
+    const size_t lds = hdm_grouped_lds_bytes(a.max_n16);
+    if (lds > 160 * 1024) return 1;
+    static thread_local int configured_dev = -1;
+    int dev = 0;
+    HDM_HIP_CHECK(hipGetDevice(&dev));
+    if (configured_dev != dev) {
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_grouped_jobs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        configured_dev = dev;
+    }
+    hipLaunchKernelGGL(hdm_grouped_jobs_kernel, dim3(a.njobs), dim3(GR_T), lds, s, a);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int hdm_grouped_scatter(const HdmGroupedScatterArgs &a, const HdmMatView &Mv, hipStream_t s) {
+    if (a.ncones < 1 || a.typeKKT < 0 || a.typeKKT > 2) return 1;
+    const long threads = (a.typeKKT == 1 ? 0L : a.nM) + a.nV + 1;
+    hipLaunchKernelGGL(hdm_grouped_scatter_kernel, dim3((unsigned) ((threads + GR_T - 1) / GR_T)), dim3(GR_T), 0, s, a, Mv);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // one kernel of this translation unit (= one code object): what the preload thread asks the runtime about (engine.hip: preload_modules)
 const void *hdm_module_handle_small() { return (const void *) hdm_small_phase_a_kernel; }

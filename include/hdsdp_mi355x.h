@@ -352,6 +352,30 @@ int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT);
 /* bytes of M (and of the channel) moved between host and device since HKKTInit: the mirror's copy after a build, its upload
  * for a factorisation, the channel's uploads, rows read by HMiKKTGetRows.  The operator's vectors and scalars are not counted. */
 void HMiKKTGetMatrixTraffic(hdsdp_kkt *HKKT, int64_t *bytesToHost, int64_t *bytesToDevice);
+/* The grouped Schur build (csrc/grouped_plan.h, csrc/small.hip).  An SDP with many small blocks spends its
+ * Schur builds on launch latency: the per-cone builders issue 4 to 16 launches per block.  With the switch on, every eligible
+ * cone of the operator -- an engine SDP cone on one device, not synthetic, not streamed, constraint data resident, n <= 64 and
+ * mloc * n16 * n16 <= 2^19 -- is built in ONE pass of three launches (inverses, row jobs, ordered scatter), whatever the number of
+ * cones, provided at least two cones are eligible; every other cone goes through its own slot as before, and KKT_TYPE_PRIMAL builds
+ * never group.  Off by default.  The cones' factor objects are read and left as they are.
+ * HMiKKTSetGroupedBuild: after HKKTInit; returns the number of cones that will be grouped (0: off, or fewer than two eligible).
+ * HMiKKTGetGroupedBuild: the last HKKTBuildUp / HKKTBuildUpFixed -- cones grouped, jobs (workgroups of the second launch), kernel
+ * launches the grouped pass issued (the clean's memsets and the pull's copies are not counted); returns 1 if the pass ran, else 0.
+ * HMiGroupedPlanQuery: the plan for an operator described by arrays; host arithmetic only, opens no context, works without a
+ * device.  Cone k has dimension dims[k], owns the global rows rows[rowBeg[k] .. rowBeg[k + 1]) (its local order) and kindOk[k] says
+ * whether it is a cone of the kind above (what only the engine can know); the dimension and data bounds are applied here.
+ * counts (8): [0] grouped cones [1] jobs [2] destinations in M's lower triangle [3] their contributors [4] rows of the m-vectors
+ * touched [5] their contributors [6] doubles of staging memory [7] eligible cones.  Every other output may be NULL; sized by a
+ * first call: eligible, slotOf (nCones: 0 / 1; position among the grouped cones or -1), jobs (4 per job: slot, first row, end row,
+ * 1 = the cone's first job, which also computes its scalars), the destinations of M (mRow >= mCol) with their contributors as a CSR
+ * (mPtr: [2] + 1 entries; mSlot, mIdx: slot and index into the cone's local lower Gram, packed by columns) and the same for the
+ * vectors' rows (vIdx: the cone's local row).  Contributors of a destination are listed in ascending cone order: that is the order
+ * the scatter sums them in.  Returns 8, or -1 for a bad argument. */
+int HMiKKTSetGroupedBuild(hdsdp_kkt *HKKT, int on);
+int HMiKKTGetGroupedBuild(hdsdp_kkt *HKKT, int *cones, int *jobs, int *launches);
+int HMiGroupedPlanQuery(int nRow, int nCones, const int *dims, const int *kindOk, const int *rowBeg, const int *rows, int64_t *counts,
+                        int *eligible, int *slotOf, int *jobs, int *mRow, int *mCol, int64_t *mPtr, int *mSlot, int *mIdx, int *vRow,
+                        int64_t *vPtr, int *vSlot, int *vIdx);
 /* multi-GPU (world > 1): constraint rows are sharded (row i on rank i % world).  Each rank congruence-
  * transforms its own rows, a transpose (all-to-all) re-shards the transformed data from "by constraint"
  * to "by packed-index range", each rank forms the Gram partial sum over its range, and an all-reduce
@@ -530,6 +554,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           batch (MiCone::streamed)
  *  HDSDP_MI355X_DEVICE_M          0         1: HKKTInit turns the host mirror of M off when no cone of    test_gpu_device_m.py
  *                                           cones[] is a host cone (diagonal channel); else one stderr line
+ *  HDSDP_MI355X_GROUPED_BUILD     0         1: HKKTInit turns the grouped Schur build on (all eligible    test_gpu_grouped_build.py
+ *                                           small SDP cones of an operator in three launches)
  *  -- the next six are the work plan's knobs: all read in csrc/work_plan.h (hdm_knobs_from_env), per allocation; HMiWorkPlanQuery sees them too --
  *  HDM_TCAP_GIB                   32        GiB of congruence intermediates per launch group              test_gpu_switches.py, test_gpu_group.py
  *  HDM_BC                         1024      constraints per congruence launch (upper bound)               test_gpu_switches.py
