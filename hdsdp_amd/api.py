@@ -39,6 +39,7 @@ EXPORTS = [
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiGetAssembleCounts", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
+    "HMiGemmRoleLayout", "HMiGemmRoleSpan", "HMiCongStep1", "HMiCongStep2", "HMiCongIRow", "HMiGramSplits", "HMiGramGathered", "HMiGramLp",
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
 ]
@@ -189,6 +190,15 @@ def load_library():
         "HMiGetStageTimes": (None, [dp, C.c_int]),
         "HMiGemmNT": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, C.c_int,
                                 C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]),
+        "HMiGemmRoleLayout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+        "HMiGemmRoleSpan": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+        "HMiCongStep1": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64]),
+        "HMiCongStep2": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64,
+                                   C.c_uint64]),
+        "HMiCongIRow": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64]),
+        "HMiGramSplits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int]),
+        "HMiGramGathered": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int, vp, C.c_int64, vp, C.c_int64, C.c_int]),
+        "HMiGramLp": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, C.c_int64]),
         "HMiPotrf": (C.c_int, [vp, C.c_int, C.c_int64, ip]),
         "HMiMfmaPeakProbe": (C.c_double, [C.c_int]),
         "HMiDiagBlockProbe": (C.c_double, [C.c_int, C.c_int]),
@@ -302,6 +312,28 @@ def work_plan(n, m, world=1, rank=0):
     if load_library().HMiWorkPlanQuery(n, m, world, rank, out, len(out)) != len(out):
         raise HDSDPError(f"HMiWorkPlanQuery refused n={n} m={m} world={world} rank={rank}")
     return dict(zip(WORK_PLAN_FIELDS, (int(v) for v in out)))
+
+
+GEMM_ROLE_LAYOUT_FIELDS = ("n16", "nblk", "npb", "npb_loc", "Lr", "R", "astride")
+SPAN_T, SPAN_LINV, SPAN_AFULL, SPAN_EXCHANGE, SPAN_LP = range(5)
+
+
+def gemm_role_layout(n, world=1, maxloc=0):
+    """the layout numbers of a dense block (csrc/work_plan.h: hdm_layout through HMiGemmRoleLayout); needs no GPU"""
+    out = (C.c_int64 * len(GEMM_ROLE_LAYOUT_FIELDS))()
+    if load_library().HMiGemmRoleLayout(n, world, maxloc, out, len(out)) != len(out):
+        raise HDSDPError(f"HMiGemmRoleLayout refused n={n} world={world} maxloc={maxloc}")
+    return dict(zip(GEMM_ROLE_LAYOUT_FIELDS, (int(v) for v in out)))
+
+
+def gemm_role_span(which, n=16, world=1, maxloc=0, a0=0, a1=0):
+    """doubles an operand buffer of the Schur build's GEMM launches is vouched to hold, slack included (HMiGemmRoleSpan:
+    SPAN_T of a0 matrices, SPAN_LINV of leading dimension a0, SPAN_AFULL of a0 skyline matrices, SPAN_EXCHANGE, SPAN_LP of
+    kc = a0 and mpad = a1); needs no GPU"""
+    v = int(load_library().HMiGemmRoleSpan(which, n, world, maxloc, a0, a1))
+    if v < 0:
+        raise HDSDPError(f"HMiGemmRoleSpan refused which={which} n={n} world={world} maxloc={maxloc} a0={a0} a1={a1}")
+    return v
 
 
 def grouped_plan(m, cones):

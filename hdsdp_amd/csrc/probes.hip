@@ -127,6 +127,87 @@ int HMiGemmNT(const double *A, int64_t lda, int aKMajor, const double *B, int64_
     return 0;
 }
 
+// The call forms of a dense block's Schur build (gemm_calls.h), one launch each on the caller's device buffers.  The caller
+// says how many doubles every buffer holds; an entry refuses (returns 1, launches nothing) when an operand buffer is smaller
+// than the span its form vouches for or the destination smaller than what the form writes, so that no argument a test can
+// write makes a kernel read or write outside an allocation (the launcher checks the unmasked loads' reach against the span).
+// Each is one form followed by hdm_launch_gemm and a synchronise: no field is assigned here.
+namespace {
+int run_form(const HdmGemmArgs &a) {
+    if (ensure_ctx()) return 1;
+    if (hdm_launch_gemm(a, g.stream)) return 1;
+    HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
+    return 0;
+}
+bool layout_args_ok(int n, int world, int maxloc) { return n >= 1 && n <= (1 << 15) && world >= 1 && world <= 64 && maxloc >= 0 && maxloc <= (1 << 20); }
+// doubles of a blocked congruence destination: every p-block of the triangle, Lr constraint rows of 16 each
+long blocked_doubles(const HdmLayout &L) { return L.npb * L.Lr * 16; }
+bool linv_ok(const HdmLayout &L, int64_t ldl, int64_t linv_len) { return ldl >= hdm_roundup(L.n16, HDM_TILE) && ldl <= (1 << 20) && linv_len >= hdm_linv_span(ldl); }
+}  // namespace
+
+int HMiGemmRoleLayout(int n, int world, int maxloc, int64_t *out, int cap) {
+    if (!out || cap < 7 || !layout_args_ok(n, world, maxloc)) return -7;
+    const HdmLayout L = hdm_layout(n, world, maxloc);
+    const int64_t v[7] = {L.n16, L.nblk, L.npb, L.npb_loc, L.Lr, L.R, L.astride};
+    std::copy(v, v + 7, out);
+    return 7;
+}
+int64_t HMiGemmRoleSpan(int which, int n, int world, int maxloc, int64_t a0, int64_t a1) {
+    if (!layout_args_ok(n, world, maxloc) || a0 < 0 || a1 < 0 || a0 > (1 << 20) || a1 > (1 << 20)) return -1;
+    const HdmLayout L = hdm_layout(n, world, maxloc);
+    switch (which) {
+        case 0: return hdm_t_span(L, a0);
+        case 1: return hdm_linv_span(a0);
+        case 2: return hdm_afull_span(L, a0);
+        case 3: return hdm_exchange_span(L);
+        case 4: return hdm_lp_span((int) a0, (int) a1);
+        default: return -1;
+    }
+}
+int HMiCongStep1(int n, int world, int maxloc, const double *Linv, int64_t linv_len, int64_t ldl, const double *Asrc, int64_t asrc_len,
+                 int64_t src_rows, int64_t b0, int nb, double *T, int64_t t_len) {
+    if (!layout_args_ok(n, world, maxloc) || !Linv || !Asrc || !T) return 1;
+    const HdmLayout L = hdm_layout(n, world, maxloc);
+    if (!linv_ok(L, ldl, linv_len) || nb < 1 || b0 < 0 || src_rows < b0 + nb || asrc_len < hdm_afull_span(L, src_rows) ||
+        t_len < (int64_t) nb * L.n16 * L.n16) return 1;
+    return run_form(hdm_cong_step1(L, n, Linv, ldl, Asrc, src_rows, b0, nb, T));
+}
+int HMiCongStep2(int n, int world, int maxloc, int64_t Bc, const double *Linv, int64_t linv_len, int64_t ldl, const double *T, int64_t t_len,
+                 int nb, double *dst, int64_t dst_len, int64_t blk_row0, uint64_t colmask) {
+    if (!layout_args_ok(n, world, maxloc) || !Linv || !T || !dst) return 1;
+    const HdmLayout L = hdm_layout(n, world, maxloc);
+    if (!linv_ok(L, ldl, linv_len) || nb < 1 || Bc < nb || t_len < hdm_t_span(L, Bc) || blk_row0 < 0 || blk_row0 + nb > L.Lr ||
+        dst_len < blocked_doubles(L)) return 1;
+    return run_form(hdm_cong_step2(L, n, Bc, Linv, ldl, T, nb, dst, blk_row0, colmask));
+}
+int HMiCongIRow(int n, int world, int maxloc, const double *Linv, int64_t linv_len, int64_t ldl, double *dst, int64_t dst_len, int64_t blk_row0) {
+    if (!layout_args_ok(n, world, maxloc) || !Linv || !dst) return 1;
+    const HdmLayout L = hdm_layout(n, world, maxloc);
+    if (!linv_ok(L, ldl, linv_len) || blk_row0 < 0 || blk_row0 >= L.Lr || dst_len < blocked_doubles(L)) return 1;
+    return run_form(hdm_cong_irow(L, Linv, ldl, dst, blk_row0));
+}
+int HMiGramSplits(int n, int world, int maxloc, int m, int64_t nsplit, int z0, int nz, const double *Ahat, int64_t ahat_len, double *slab,
+                  int64_t slab_len, int accumulate, int queue_global) {
+    if (!layout_args_ok(n, world, maxloc) || !Ahat || !slab) return 1;
+    const HdmLayout L = hdm_layout(n, world, maxloc);
+    if (nsplit < 1 || nsplit > L.npb_loc || z0 < 0 || nz < 1 || z0 + (int64_t) nz > nsplit || ahat_len < hdm_exchange_span(L) ||
+        slab_len < (int64_t) nz * L.R * L.R) return 1;
+    return run_form(hdm_gram_splits(L, n, m, nsplit, z0, nz, Ahat, slab, accumulate != 0, queue_global != 0));
+}
+int HMiGramGathered(int64_t R, int64_t nc, int nz, double alpha, int accumulate, const double *gat, int64_t gat_len, double *slabs,
+                    int64_t slabs_len, int queue_global) {
+    if (!gat || !slabs || R < 8 || R > (1 << 20) || (R % 8) || nc < 1 || nc > (1 << 24) || nz < 1 || nz > 4096) return 1;
+    const long nc16 = hdm_roundup(nc, 16);
+    if (gat_len < nc16 * R || slabs_len < (int64_t) nz * R * R) return 1;
+    return run_form(hdm_gram_gathered(R, nc, nc16, nz, alpha, accumulate != 0, gat, gat_len, slabs, queue_global != 0));
+}
+int HMiGramLp(int m, int mpad, int kc, int kv, const double *W, int64_t w_len, double *M, int64_t m_len, int64_t ldm) {
+    if (!W || !M || m < 1 || mpad < 1 || mpad > (1 << 20) || kc < 16 || (kc % 16) || kv < 1 || kv > kc) return 1;
+    const int m16 = (int) hdm_roundup(m, 16), kp = (int) hdm_roundup(kv, 16);
+    if (m16 > mpad || w_len < hdm_lp_span(kc, mpad) || ldm < m16 || m_len < (int64_t) (m16 - 1) * ldm + m16) return 1;
+    return run_form(hdm_gram_lp(m, m16, mpad, kc, kv, kp, W, M, ldm));
+}
+
 // blocked Cholesky + solve of a host matrix (lower triangle, column-major, leading dimension n) whose structural zeros are
 // described by a block envelope: first[i] = first 128-block column with an entry in block row i (NULL = dense)
 int HMiCholEnvelopeSolve(const double *A_host, int n, const int *first, const double *b, double *x, double *L_host, int *info) {

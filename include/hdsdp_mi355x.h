@@ -641,6 +641,29 @@ void HMiSetDebugBuffer(void *dev, int role);
 /* raw kernels (device pointers) exported for unit tests and micro-benchmarks */
 int HMiGemmNT(const double *A, int64_t lda, int aKMajor, const double *B, int64_t ldb, int bKMajor, double *C,
               int64_t ldc, int M, int N, int K, double alpha, double beta, int kLimit, int lowerOnly);
+/* The call forms of a dense block's Schur build (csrc/gemm_calls.h: hdm_cong_step1, hdm_cong_step2, hdm_cong_irow, hdm_gram_splits,
+ * hdm_gram_gathered, hdm_gram_lp), ONE launch each on the caller's device buffers, for tests/test_gpu_gemm_roles.py.  (n, world,
+ * maxloc) name the block's layout as csrc/work_plan.h: hdm_layout takes them.  Every buffer comes with the number of doubles it
+ * holds: an entry returns 1 and launches nothing when an operand buffer is smaller than the span its form vouches for, or the
+ * destination smaller than what the form writes (T: nb n16^2; a blocked destination: npb Lr 16; slabs: nz R^2; the LP matrix:
+ * (m16 - 1) ldm + m16), or a row range leaves its buffer.  Returns 0 after the launch has completed.
+ * HMiGemmRoleLayout (host only): out (cap >= 7) = [0] n16 [1] nblk [2] npb [3] npb_loc [4] Lr [5] R [6] elements per skyline matrix;
+ * returns 7, or -7 for a bad argument.
+ * HMiGemmRoleSpan (host only): the doubles a form vouches for: which = 0 the intermediates T of a0 matrices, 1 the factor inverse
+ * of leading dimension a0, 2 a buffer of a0 skyline matrices, 3 an exchange buffer, 4 the LP cone's dense buffer (kc = a0,
+ * mpad = a1); -1 for a bad argument. */
+int HMiGemmRoleLayout(int n, int world, int maxloc, int64_t *out, int cap);
+int64_t HMiGemmRoleSpan(int which, int n, int world, int maxloc, int64_t a0, int64_t a1);
+int HMiCongStep1(int n, int world, int maxloc, const double *Linv, int64_t linv_len, int64_t ldl, const double *Asrc, int64_t asrc_len,
+                 int64_t src_rows, int64_t b0, int nb, double *T, int64_t t_len);
+int HMiCongStep2(int n, int world, int maxloc, int64_t Bc, const double *Linv, int64_t linv_len, int64_t ldl, const double *T, int64_t t_len,
+                 int nb, double *dst, int64_t dst_len, int64_t blk_row0, uint64_t colmask);
+int HMiCongIRow(int n, int world, int maxloc, const double *Linv, int64_t linv_len, int64_t ldl, double *dst, int64_t dst_len, int64_t blk_row0);
+int HMiGramSplits(int n, int world, int maxloc, int m, int64_t nsplit, int z0, int nz, const double *Ahat, int64_t ahat_len, double *slab,
+                  int64_t slab_len, int accumulate, int queue_global);
+int HMiGramGathered(int64_t R, int64_t nc, int nz, double alpha, int accumulate, const double *gat, int64_t gat_len, double *slabs,
+                    int64_t slabs_len, int queue_global);
+int HMiGramLp(int m, int mpad, int kc, int kv, const double *W, int64_t w_len, double *M, int64_t m_len, int64_t ldm);
 int HMiPotrf(double *A_dev, int n, int64_t lda, int *info);  /* in place, lower */
 /* blocked Cholesky + one solve of a host matrix (lower triangle, column-major, ld = n) with a block envelope: first[i] = first
    128-block column with an entry in block row i, NULL = dense; L_host (n x n) receives the factor if not NULL */

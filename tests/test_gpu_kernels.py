@@ -64,6 +64,76 @@ def test_gemm_triangular_k_limits():
     assert np.all(got[~msk] == 0.0)  # lower_only leaves the strict upper part untouched
 
 
+# the generic masked loop at the edges HMiGemmNT reaches, against an extended-precision product.  Every element is held to the a-priori
+# bound (K + 4) 2^-53 (|alpha| |A| |B|^T + |beta| |C|)_ij, K = the k values the launch sums for that element (tests/
+# test_gpu_gemm_roles.py derives it); whatever the launch does not own -- the rows between M and ldc, the strict upper part of
+# a lower-only product -- keeps the bits of a NaN with a payload; the operands' padding up to their leading dimension is NaN.
+_EDGE_CASES = [
+    # M, N, K, akm, bkm, ld padding (A, B, C), beta, kLimit, lowerOnly
+    (200, 136, 48, 0, 0, (0, 0, 24), -0.5, 0, 0),          # ldc > M
+    (200, 136, 48, 1, 1, (0, 0, 24), -0.5, 0, 0),
+    (200, 136, 48, 0, 1, (8, 16, 0), -0.5, 0, 0),          # leading dimensions larger than the operands
+    (200, 136, 48, 1, 0, (16, 8, 40), -0.5, 0, 0),
+    (264, 264, 272, 1, 0, (0, 0, 0), -0.5, 1, 0),          # kLimit by the row tile on a K-major (lower triangular) A
+    (264, 264, 272, 1, 1, (16, 0, 8), 0.0, 1, 0),
+    (264, 264, 272, 0, 1, (0, 0, 0), -0.5, 2, 1),          # kLimit by the column tile on a K-major (lower triangular) B, lower only
+    (264, 264, 272, 1, 1, (0, 16, 8), 0.0, 2, 1),
+    (200, 136, 48, 0, 0, (0, 0, 8), 0.0, 0, 0),            # beta = 0 over a C of NaNs: an overwrite, not a multiply
+    (200, 136, 48, 1, 1, (0, 0, 0), 0.0, 0, 0),
+    (136, 72, 16, 0, 0, (0, 0, 0), -0.5, 0, 0),            # M, N = 8 mod 16
+    (136, 72, 16, 1, 1, (0, 0, 8), 0.0, 0, 0),
+    (8, 8, 16, 0, 0, (0, 0, 0), -0.5, 0, 0),
+    (8, 8, 16, 1, 1, (0, 0, 8), 0.0, 0, 1),
+]
+
+
+@pytest.mark.parametrize("M,N,K,akm,bkm,pads,beta,klim,lower", _EDGE_CASES)
+def test_gemm_nt_generic_loop_edges(M, N, K, akm, bkm, pads, beta, klim, lower):
+    import xprec_ref as xr
+    if not xr.HAVE_LD:
+        pytest.skip(xr.NO_LD_REASON)
+    from hdsdp_amd import api
+    lib = api.load_library()
+    rng = np.random.default_rng(M * 1000 + N + K + akm * 7 + bkm * 13 + klim * 31 + sum(pads))
+    alpha, LD, u = 1.5, np.longdouble, 2.0 ** -53
+    sent_bits = np.uint64(0x7FF85EED0BADC0DE)
+    A, B, C0 = rng.standard_normal((M, K)), rng.standard_normal((N, K)), rng.standard_normal((M, N))
+    if klim == 1:
+        A = np.tril(A)
+    if klim == 2:
+        B = np.tril(B)
+
+    def operand(X, kmajor, pad):
+        rows, ld = (X.shape[0], K + pad) if kmajor else (K, X.shape[0] + pad)
+        buf = np.full((rows, ld), np.nan)
+        buf[:, :ld - pad] = X if kmajor else X.T
+        return buf, ld
+
+    bufA, lda = operand(A, akm, pads[0])
+    bufB, ldb = operand(B, bkm, pads[1])
+    ldc = M + pads[2]
+    i, j = np.meshgrid(np.arange(M), np.arange(N), indexing="ij")
+    own = (i >= j) if lower else np.ones((M, N), dtype=bool)
+    bufC = np.full((N, ldc), sent_bits, dtype=np.uint64).view(np.float64)
+    if beta != 0.0:
+        bufC[:, :M] = np.where(own, C0, bufC[:, :M].T).T
+    dA, dB, dC = _dev(bufA), _dev(bufB), _dev(bufC)
+    assert lib.HMiGemmNT(dA.data_ptr(), lda, akm, dB.data_ptr(), ldb, bkm, dC.data_ptr(), ldc, M, N, K, alpha, beta, klim, lower) == 0
+    out = dC.cpu().numpy()
+    got = out[:, :M].T
+    ref = alpha * xr.mm(A, B.T) + (LD(beta) * C0.astype(LD) if beta != 0.0 else 0)
+    ksum = np.minimum(K, (i // 128 + 1) * 128) if klim == 1 else np.minimum(K, (j // 128 + 1) * 128) if klim == 2 else np.full((M, N), K)
+    bound = (ksum + 4) * u * (alpha * (np.abs(A) @ np.abs(B).T) + abs(beta) * np.abs(C0))
+    assert np.all(np.isfinite(got[own]))
+    err = np.abs(got.astype(LD) - ref)
+    assert np.all(err[own] <= bound[own]), f"worst error / bound {float(np.max(err[own] / bound[own])):.3g}"
+    print(f"\ngeneric loop M={M} N={N} K={K} akm={akm} bkm={bkm} pads={pads} beta={beta} kLimit={klim} lower={lower}: error / bound "
+          f"{float(np.max(err[own] / bound[own])):.3f}")
+    untouched = np.ones((N, ldc), dtype=bool)
+    untouched[:, :M] = ~own.T
+    assert np.all(out.view(np.uint64)[untouched] == sent_bits), "the launch wrote outside the elements it owns"
+
+
 @pytest.mark.parametrize("n", [50, 128, 300, 400, 517, 1000])
 def test_dense_direct_linsys(n):
     """HFpLinsys* dense-direct surface vs LAPACK semantics (linalg/hdsdp_linsolver.c:1082-1260); 1, 2, 3, 4, 5 and 8
