@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from chain_operator import CHAIN_M, banded_chain, block_with_rows as _block_with_rows
 from util import golden_schur_dense, primal_X, KKT_TOL, RATIO_TOL, check_close, kkt_err, load_golden, lower_mask, y_of
 
 pytestmark = pytest.mark.gpu
@@ -1033,21 +1034,6 @@ def test_fused_phase_a_refuses_what_it_cannot_do():
         cone.destroy()
 
 
-def _block_with_rows(n, m, keep):
-    """a block of the synthetic family on which only the constraints in `keep` have data (CSC, column 0 = C)"""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-    import oracle_py
-    beg0, idx0, val0, _ = oracle_py.synth_csc(n, m)
-    beg, idx, val = [0], [], []
-    for col in range(m + 1):
-        lo, hi = int(beg0[col]), int(beg0[col + 1])
-        if col == 0 or (col - 1) in keep:
-            idx += [int(v) for v in idx0[lo:hi]]; val += [float(v) for v in val0[lo:hi]]
-        beg.append(len(idx))
-    return np.array(beg, dtype=np.int32), np.array(idx, dtype=np.int32), np.array(val)
-
-
 @pytest.mark.parametrize("nblocks,per,expect_sparse", [(12, 7, False), (12, 3, True)])
 def test_sparse_operator_decision_and_its_dense_way_back(nblocks, per, expect_sparse):
     """HKKTInit's two-stage rule (interface/hdsdp_schur.c:229-238, :104-108) on blocks that are each sparse candidates
@@ -1344,29 +1330,11 @@ def test_sparse_operator_with_a_banded_pattern_over_several_blocks_of_M(scramble
     keeps inside the factor object (P M P' is factored, right-hand sides and solutions are permuted).  M against the oracle's
     block-by-block sum, the solve against LAPACK on that sum, and twice -- the second factorisation replays the captured
     launch chain"""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-    import oracle_py
     from hdsdp_amd import api
-    nblocks, m = 50, 408
-    Rd, tau = -30.0, 1.0
-    y = 0.02 * np.cos(np.arange(m) + 0.3)
-    cones, Mref = [], np.zeros((m, m))
-    renum = np.random.default_rng(7).permutation(m) if scrambled else np.arange(m)
+    m = CHAIN_M
+    cones = []
     try:
-        for b in range(nblocks):
-            n = 10 + (b % 3)
-            keep = sorted(int(renum[k]) for k in range(8 * b, 8 * b + 16))
-            beg, idx, val = _block_with_rows(n, m, keep)
-            blk = oracle_py.Block(n, m, beg, idx, val)
-            Lf, info = blk.factor(blk.assemble_S(tau, y, Rd))
-            assert info == 0
-            Mref += blk.kkt_build(blk.inverse(Lf), Rd, 0)["M"]
-            blk.close()
-            c = api.SDPCone.from_csc(n, m, beg, idx, val, iCone=b)
-            c.set_start(Rd)
-            assert c.check_is_interior(tau, y)
-            cones.append(c)
+        Mref = banded_chain(scrambled, cones)
         kkt = api.KKT(m, cones)
         assert kkt.is_sparse
         A = np.triu(Mref) + np.triu(Mref, 1).T
