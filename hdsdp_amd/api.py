@@ -41,12 +41,48 @@ EXPORTS = [
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
     "HMiGemmRoleLayout", "HMiGemmRoleSpan", "HMiCongStep1", "HMiCongStep2", "HMiCongIRow", "HMiGramSplits", "HMiGramGathered", "HMiGramLp",
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
+    "HMiLinsysSetRefine", "HMiLinsysGetRefine", "HMiLinsysRefineBytes", "HMiKKTSetRefine", "HMiSymResidualProbe",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
 ]
 
 
 class HDSDPError(RuntimeError):
     pass
+
+
+# status of a refined solve (csrc/refine_rule.h: HdmRefineStatus)
+REFINE_OFF, REFINE_CONVERGED, REFINE_STAGNATED, REFINE_MAXSTEPS, REFINE_NUMERICAL, REFINE_NO_MATRIX, REFINE_NOT_AVAILABLE = range(7)
+REFINE_STATUS_NAMES = ("OFF", "CONVERGED", "STAGNATED", "MAXSTEPS", "NUMERICAL", "NO_MATRIX", "NOT_AVAILABLE")
+
+
+def _refine_stats(h):
+    """HMiLinsysGetRefine + HMiLinsysRefineBytes of a linear-system handle as a dict"""
+    lib = load_library()
+    st, steps = C.c_int(0), C.c_int(0)
+    r0, r1, tol = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    solves, total = C.c_int64(0), C.c_int64(0)
+    cap = lib.HMiLinsysGetRefine(h, C.byref(st), C.byref(steps), C.byref(r0), C.byref(r1), C.byref(tol), C.byref(solves), C.byref(total))
+    if cap < 0:
+        raise HDSDPError("HMiLinsysGetRefine failed")
+    return {"cap": int(cap), "status": st.value, "status_name": REFINE_STATUS_NAMES[st.value], "steps": steps.value, "resid0": r0.value,
+            "resid": r1.value, "tol": tol.value, "solves": solves.value, "total_steps": total.value,
+            "device_bytes": int(lib.HMiLinsysRefineBytes(h))}
+
+
+def sym_residual(M, x, b, n=None, ld=None):
+    """HMiSymResidualProbe: (r, |r|_2^2) with r = b - M x from the refined solve's residual kernel.  M: the (n, ld) C-order array
+    that IS the column-major ld x n matrix (M[j, i] = element (row i, column j)); lower triangle valid, everything else -- the
+    upper triangle, rows >= n -- goes to the device as it is and must not be read"""
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    n = M.shape[0] if n is None else n
+    ld = M.shape[1] if ld is None else ld
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if M.size < ld * n or x.size < n or b.size < n:
+        raise ValueError("sym_residual: an array is smaller than n and ld say")
+    r, nrm = np.zeros(n), C.c_double(0.0)
+    _check(load_library().HMiSymResidualProbe(int(n), _dptr(M), int(ld), _dptr(x), _dptr(b), _dptr(r), C.byref(nrm)), "HMiSymResidualProbe")
+    return r, nrm.value
 
 
 class hdsdp_kkt(C.Structure):  # interface/def_hdsdp_schur.h:32-68
@@ -213,6 +249,11 @@ def load_library():
         "HMiConeGetWorkPlan": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "HMiKKTSetGroupedBuild": (C.c_int, [kp, C.c_int]),
         "HMiKKTGetGroupedBuild": (C.c_int, [kp, ip, ip, ip]),
+        "HMiLinsysSetRefine": (C.c_int, [vp, C.c_int]),
+        "HMiLinsysGetRefine": (C.c_int, [vp, ip, ip, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "HMiLinsysRefineBytes": (C.c_int64, [vp]),
+        "HMiKKTSetRefine": (C.c_int, [kp, C.c_int]),
+        "HMiSymResidualProbe": (C.c_int, [C.c_int, dp, C.c_long, dp, dp, dp, dp]),
         "HMiGroupedPlanQuery": (C.c_int, [C.c_int, C.c_int, ip, ip, ip, ip, C.POINTER(C.c_int64), ip, ip, ip, ip, ip, C.POINTER(C.c_int64), ip, ip, ip,
                                           C.POINTER(C.c_int64), ip, ip]),
         "HMiPresolveCSC": (C.c_int, [C.c_int, C.c_int, ip, ip, dp, ip, ip, ip, ip, ip, ip]),
@@ -890,6 +931,21 @@ class KKT:
         points into the diagonal channel (refused, with a stderr line, while a host cone sits in the operator)"""
         load_library().HMiKKTSetHostMirror(self._k, 1 if on else 0)
 
+    def set_refine(self, max_steps):
+        """HMiKKTSetRefine: HKKTSolve iterates on the true residual, at most max_steps corrections (0: off, the default; clamped
+        to 8).  Turn it on before factorize(): the residual reads the matrix the factor was made from."""
+        _check(load_library().HMiKKTSetRefine(self._k, int(max_steps)), "HMiKKTSetRefine")
+
+    def set_param(self, relTol=0.0, absTol=0.0, maxIter=-1):
+        """HFpLinsysSetParam on the operator's linear system (HKKTInit sets 5e-12 / 1e-12 for m <= 5000): the refined solve's
+        tolerances"""
+        load_library().HFpLinsysSetParam(self._k.contents.kktM, float(relTol), float(absTol), -1, int(maxIter), -1)
+
+    def refine_stats(self):
+        """the operator's linear system: dict(cap, status, status_name, steps, resid0, resid, tol, solves, total_steps, device_bytes)
+        of the last solve and the running totals"""
+        return _refine_stats(self._k.contents.kktM)
+
     def set_grouped_build(self, on):
         """HMiKKTSetGroupedBuild: all eligible small SDP cones of the operator are built in one pass of three launches
         (csrc/grouped_plan.h has the rule); returns the number of cones that will be grouped (0: off, or fewer than two eligible)"""
@@ -995,11 +1051,28 @@ class LinSys:
         nrhs = 1 if rhs.ndim == 1 else rhs.shape[0]  # C-order (nrhs, n) == column-major n x nrhs
         return rhs, nrhs
 
-    def solve(self, rhs):
+    def solve(self, rhs, inplace=False):
         rhs, nrhs = self._rhs(rhs)
+        if inplace:                  # solVec == NULL: the solution replaces the right-hand side
+            _check(load_library().HFpLinsysSolve(self._h, nrhs, _dptr(rhs), None), "HFpLinsysSolve")
+            return rhs
         sol = np.zeros_like(rhs)
         _check(load_library().HFpLinsysSolve(self._h, nrhs, _dptr(rhs), _dptr(sol)), "HFpLinsysSolve")
         return sol
+
+    def set_param(self, relTol=0.0, absTol=0.0, maxIter=-1):
+        """HFpLinsysSetParam: the tolerances of the refined solve (values <= 0: the reference's 1e-6)"""
+        load_library().HFpLinsysSetParam(self._h, float(relTol), float(absTol), -1, int(maxIter), -1)
+
+    def set_refine(self, max_steps):
+        """HMiLinsysSetRefine: solve() iterates on the true residual, at most max_steps corrections (0: off, the default; clamped
+        to 8).  Turn it on before numeric(): the residual reads a device copy of the matrix taken then."""
+        _check(load_library().HMiLinsysSetRefine(self._h, int(max_steps)), "HMiLinsysSetRefine")
+
+    def refine_stats(self):
+        """dict(cap, status, status_name, steps, resid0, resid, tol, solves, total_steps, device_bytes) of the last solve and the
+        running totals"""
+        return _refine_stats(self._h)
 
     def fsolve(self, rhs):
         rhs, nrhs = self._rhs(rhs)

@@ -60,6 +60,9 @@ struct HdmChol {
     int enqueue_factor(hipStream_t s);
     int enqueue_solve(double *b_dev, double *x_dev, int nrhs, long ldv, int which, hipStream_t s);
     int solve_host(const double *rhs, double *sol, int nrhs, int which, hipStream_t s);
+    // after the synchronisation that follows solve_device: did a workgroup of the single-launch substitution give up waiting?
+    // Then its result is to be thrown away; later solves use per-block launches.  (Reads and clears the give-up word.)
+    bool flow_gave_up();
     int inverse_full(double *out_dev, long ldo, hipStream_t s);
 };
 

@@ -1051,6 +1051,20 @@ static bool hdm_flow_fail_once() {
     return false;
 }
 
+bool HdmChol::flow_gave_up() {
+    bool gave_up = flow_pending && flow_err && *(volatile int *) flow_err.get() != 0;
+    if (flow_pending && hdm_flow_fail_once()) gave_up = true;
+    flow_pending = false;
+    if (gave_up) {
+        // a workgroup of the single-launch substitution gave up waiting (it would mean the workgroups were not
+        // co-resident): per-block launches from now on
+        fprintf(stderr, "[hdsdp_mi355x] single-launch substitution timed out; using per-block launches\n");
+        flow_ok = false;
+        if (flow_err) *flow_err.get() = 0;
+    }
+    return gave_up;
+}
+
 int HdmChol::solve_host(const double *rhs, double *sol, int nrhs, int which, hipStream_t s) {
     // nrhs columns of length n (column-major, ld = n) on the host.  `sol` may be `rhs` (the reference solves in place
     // almost everywhere, hdsdp_algo.c:452-454): a chunk's solution goes through a host staging buffer and reaches `sol`
@@ -1067,15 +1081,7 @@ int HdmChol::solve_host(const double *rhs, double *sol, int nrhs, int which, hip
         HDM_HIP_CHECK(hipMemcpy2DAsync(host_stage.data(), sizeof(double) * n, x, sizeof(double) * npad,
                                        sizeof(double) * n, nc, hipMemcpyDeviceToHost, s));
         HDM_HIP_CHECK(hipStreamSynchronize(s));
-        bool gave_up = flow_pending && flow_err && *(volatile int *) flow_err.get() != 0;
-        if (flow_pending && hdm_flow_fail_once()) gave_up = true;
-        flow_pending = false;
-        if (gave_up) {
-            // a workgroup of the single-launch substitution gave up waiting (it would mean the workgroups were not
-            // co-resident): per-block launches from now on, and this chunk again from the untouched right-hand side
-            fprintf(stderr, "[hdsdp_mi355x] single-launch substitution timed out; using per-block launches\n");
-            flow_ok = false;
-            if (flow_err) *flow_err.get() = 0;
+        if (flow_gave_up()) {       // this chunk again from the untouched right-hand side
             c0 -= chunk;
             continue;
         }

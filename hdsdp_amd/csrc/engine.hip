@@ -24,6 +24,7 @@
 #include "direct_rows.h"
 #include "lanczos.h"
 #include "lu.h"
+#include "refine.h"
 #include "small.h"
 #include "bsparse.h"
 #include <algorithm>
@@ -90,7 +91,8 @@ void preload_modules(int dev) {
             if (hipSetDevice(dev) != hipSuccess) return;
             const void *handles[] = {hdm_module_handle_small(), hdm_module_handle_chol(), hdm_module_handle_schur(),
                                      hdm_module_handle_lanczos(), hdm_module_handle_gemm_f64(), hdm_module_handle_lu(),
-                                     hdm_module_handle_bsparse(), hdm_module_handle_gemm_persist(), (const void *) mi_scale_kernel};
+                                     hdm_module_handle_bsparse(), hdm_module_handle_gemm_persist(), hdm_module_handle_refine(),
+                                     (const void *) mi_scale_kernel};
             for (const void *h : handles) { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, h); }
         });
         atexit(preload_join);

@@ -51,8 +51,8 @@ hdsdp_retcode HFpLinsysCreate(hdsdp_linsys_fp **pHLin, int nCol, linsys_type Lty
     if (!pHLin) return HDSDP_RETCODE_FAILED;
     switch (Ltype) {
         case HDSDP_LINSYS_DENSE_DIRECT:
-        case HDSDP_LINSYS_DENSE_ITERATIVE:  // Schur system: solved by a direct blocked Cholesky here (stricter
-            break;                          // than the reference's PCG to 1e-12, hdsdp_linsolver.c:1446-1588)
+        case HDSDP_LINSYS_DENSE_ITERATIVE:  // Schur system: a direct blocked Cholesky in place of the reference's PCG to 1e-12
+            break;                          // (hdsdp_linsolver.c:1446-1588); HMiLinsysSetRefine iterates on the true residual
         case HDSDP_LINSYS_SPARSE_DIRECT:    // sparse dual matrix: CSC in, dense factorisation on the device (see MiLin)
             break;
         default:
@@ -73,8 +73,33 @@ hdsdp_retcode HFpLinsysCreate(hdsdp_linsys_fp **pHLin, int nCol, linsys_type Lty
 void HFpLinsysSetParam(hdsdp_linsys_fp *HLin, double relTol, double absTol, int nThreads, int maxIter, int nRestartFreq) {
     (void) nThreads; (void) nRestartFreq;
     MiLin *l = (MiLin *) HLin->chol;
-    l->relTol = relTol; l->absTol = absTol; l->maxIter = maxIter;  // recorded; the direct solve needs none
+    // the refined solve's tolerance (refine_rule.h: hdm_refine_tol; values <= 0 take the reference's defaults); the direct solve
+    // itself needs none, and maxIter is recorded only: the step cap is HMiLinsysSetRefine's
+    l->relTol = relTol; l->absTol = absTol; l->maxIter = maxIter;
 }
+// the refined solve (refine_rule.h): 0 = off (the default), else the step cap, clamped to 8
+int HMiLinsysSetRefine(hdsdp_linsys_fp *HLin, int maxSteps) {
+    if (!HLin || !HLin->chol) return 1;
+    MiLin *l = (MiLin *) HLin->chol;
+    l->st->refine_set(maxSteps);
+    if (l->st->refine() == 0) { l->rf.release(); l->rf.unrefined(HDM_REFINE_OFF); }
+    return 0;
+}
+int HMiLinsysGetRefine(hdsdp_linsys_fp *HLin, int *status, int *steps, double *resid0, double *resid, double *tol, int64_t *solves,
+                       int64_t *totalSteps) {
+    if (!HLin || !HLin->chol) return -1;
+    const MiLin *l = (const MiLin *) HLin->chol;
+    if (status) *status = l->rf.status;
+    if (steps) *steps = l->rf.steps;
+    if (resid0) *resid0 = l->rf.resid0;
+    if (resid) *resid = l->rf.resid;
+    if (tol) *tol = l->rf.tol;
+    if (solves) *solves = l->rf.solves;
+    if (totalSteps) *totalSteps = l->rf.total_steps;
+    return l->st->refine();
+}
+int64_t HMiLinsysRefineBytes(hdsdp_linsys_fp *HLin) { return (HLin && HLin->chol) ? ((const MiLin *) HLin->chol)->rf.bytes() : 0; }
+int HMiKKTSetRefine(hdsdp_kkt *HKKT, int maxSteps) { return (HKKT && HKKT->kktM) ? HMiLinsysSetRefine(HKKT->kktM, maxSteps) : 1; }
 hdsdp_retcode HFpLinsysSymbolic(hdsdp_linsys_fp *HLin, int *colMatBeg, int *colMatIdx) {
     return HLin->cholSymbolic(HLin->chol, colMatBeg, colMatIdx);
 }
@@ -250,6 +275,17 @@ static hdsdp_retcode kkt_init_envelope(MiKKTPriv *pv, MiLin *lm, const HdmKktSwi
     return lm->ch.set_envelope(nat.first.data()) ? HDSDP_RETCODE_FAILED : HDSDP_RETCODE_OK;
 }
 
+// The Schur system's tolerances: what the refined solve (refine_rule.h) iterates to.  The reference sets them on its dense
+// (iterative) Schur system only; a sparse operator's refined solve is held to the same accuracy here.
+static void kkt_set_accuracy(hdsdp_kkt *HKKT) {
+    const int nRow = HKKT->nRow;
+    double acc = 1e-12;  // KKT_ACCURACY (hdsdp.h:27); loosened for big systems exactly as hdsdp_schur.c:21-35
+    int iters = -1;
+    if (nRow > 20000) { acc *= 100.0; iters = 500; } else if (nRow > 15000) { acc *= 50.0; iters = 450; }
+    else if (nRow > 5000) { acc *= 5.0; iters = 120; }
+    HFpLinsysSetParam(HKKT->kktM, 5.0 * acc, acc, -1, iters, -1);
+}
+
 // Storage of a sparse operator: the host CSC, and on the device the TILE form (bsparse.h) when it pays -- the rows are reordered
 // (dense rows last, reverse Cuthill-McKee for the rest), and matrix and factor exist only as the 128 x 128 tiles inside the block
 // pattern of the Cholesky factor: O(tiles of L) memory, a level-scheduled left-looking factorisation.  Taken when those tiles
@@ -277,6 +313,7 @@ static hdsdp_retcode kkt_init_sparse_storage(hdsdp_kkt *HKKT, MiKKTPriv *pv, con
     if (rc != HDSDP_RETCODE_OK) return rc;
     rc = HFpLinsysSymbolic(HKKT->kktM, HKKT->kktMatBeg, HKKT->kktMatIdx);
     if (rc != HDSDP_RETCODE_OK) return rc;
+    kkt_set_accuracy(HKKT);
     // the pattern as (row, column) pairs on the device
     pv->nnz = (long) nnz;
     if (pv->sp_rows.alloc(std::max<size_t>(1, nnz)) != hipSuccess ||
@@ -303,11 +340,7 @@ static hdsdp_retcode kkt_init_dense_storage(hdsdp_kkt *HKKT) {
     memset(HKKT->kktMatElem, 0, sizeof(double) * (size_t) nRow * nRow);
     hdsdp_retcode rc = HFpLinsysCreate(&HKKT->kktM, nRow, HDSDP_LINSYS_DENSE_ITERATIVE);
     if (rc != HDSDP_RETCODE_OK) return rc;
-    double acc = 1e-12;  // KKT_ACCURACY (hdsdp.h:27); loosened for big systems exactly as hdsdp_schur.c:21-35
-    int iters = -1;
-    if (nRow > 20000) { acc *= 100.0; iters = 500; } else if (nRow > 15000) { acc *= 50.0; iters = 450; }
-    else if (nRow > 5000) { acc *= 5.0; iters = 120; }
-    HFpLinsysSetParam(HKKT->kktM, 5.0 * acc, acc, -1, iters, -1);
+    kkt_set_accuracy(HKKT);
     for (int i = 0; i < nRow; ++i) HKKT->kktDiag[i] = &HKKT->kktMatElem[i + (size_t) i * nRow];
     return HDSDP_RETCODE_OK;
 }
@@ -374,6 +407,13 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     if (grouped_env) {
         const int k = grouped_set(HKKT, pv, 1);
         fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_BUILD=1: %d of %d cone(s) are built in one grouped pass\n", k, nCones);
+    }
+    // HDSDP_MI355X_REFINE=k: an unchanged driver's Schur solves are refined with at most k steps (HMiKKTSetRefine)
+    if (const char *e = getenv("HDSDP_MI355X_REFINE")) {
+        if (atoi(e) > 0) {
+            (void) HMiKKTSetRefine(HKKT, atoi(e));
+            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_REFINE=%d: Schur solves are refined, at most %d step(s)\n", atoi(e), pv->st.refine());
+        }
     }
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
@@ -585,7 +625,10 @@ static hdsdp_retcode kkt_load(hdsdp_kkt *HKKT, MiKKTPriv *pv, MiLin *l, const Hd
     switch (plan.load) {
     case HDM_KKT_LOAD_STAGED: case HDM_KKT_LOAD_PIVOTED: break;
     case HDM_KKT_LOAD_TILES: RC(l->bsp->load_M(g.stream)); break;
-    case HDM_KKT_LOAD_HOST: RC(l->ch.load_host(HKKT->kktMatElem, HKKT->nRow, g.stream)); break;
+    case HDM_KKT_LOAD_HOST:
+        RC(l->ch.load_host(HKKT->kktMatElem, HKKT->nRow, g.stream));
+        RC(lin_refine_keep_image(l, l->ch.L.get(), l->ch.npad));
+        break;
     case HDM_KKT_LOAD_DEVICE: RC(l->ch.load_device(l->Mdev.get(), l->ch.npad, g.stream)); break;
     case HDM_KKT_LOAD_PERMUTED:
         if (plan.gather) kkt_csc_gather(pv, dense_view(l->Mdev.get(), l->ch.npad));

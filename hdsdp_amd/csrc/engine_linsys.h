@@ -3,6 +3,7 @@
 // and the engine's thread-local context `g`); split out of a 3 300-line file in round 3, nothing else changed.
 // Whether a system is switched to the pivoted solver and where its last factorised matrix came from is HdmKktState's
 // (kkt_store.h, with the table of how the Schur operator's matrix reaches the factor): lin_factor_indef reads the source from it.
+// The refined solve (lin_solve_refined: refine_rule.h's loop on refine.hip's residual) asks the same state what its residual reads.
 // =============================================================================================
 // linear-system objects
 // =============================================================================================
@@ -36,6 +37,22 @@ struct MiLin {
     bool csc_in = false;
     std::vector<int> cscBeg, cscIdx;
     std::vector<double> dense;
+    // the refined solve (refine_rule.h, refine.hip).  Whether it is on and what its residual reads is the
+    // state's (kkt_store.h: hdm_kkt_refine_source); everything here is allocated at the first use and freed when it goes off.
+    struct Refine {
+        HdmSymRes res;
+        HdmBuf<double> Mcopy;      // npad x npad: the loaded image of a host matrix, as the factorisation saw it
+        HdmBuf<double> v;          // 5 npad + 8: right-hand side, iterate, previous iterate, unrefined solution, residual; |r|^2
+        HdmBuf<int> perm;          // device copy of MiLin::perm
+        std::vector<double> stage; // the returned iterate on its way to the caller
+        // the last solve and the running totals (HMiLinsysGetRefine)
+        int status = HDM_REFINE_OFF, steps = 0;
+        double resid0 = 0.0, resid = 0.0, tol = 0.0;
+        int64_t solves = 0, total_steps = 0;
+        void unrefined(HdmRefineStatus why) { status = why; steps = 0; resid0 = resid = tol = 0.0; }
+        void release() { res.part.reset(); res.npart.reset(); Mcopy.reset(); v.reset(); perm.reset(); stage.clear(); stage.shrink_to_fit(); }
+        int64_t bytes() const { return (int64_t) (res.bytes() + sizeof(double) * (Mcopy.count() + v.count()) + sizeof(int) * perm.count()); }
+    } rf;
 };
 
 hdsdp_retcode lin_create(void **pchol, int nCol) {
@@ -71,8 +88,19 @@ const double *lin_densify(MiLin *l, const int *colMatBeg, const int *colMatIdx, 
     return l->dense.data();
 }
 
+// the loaded image of a host matrix (n x n of `img`, on the device) is kept for the refined solve's residual: asked for by the
+// state after the load and before the factorisation overwrites it
+hdsdp_retcode lin_refine_keep_image(MiLin *l, const double *img, long ldimg) {
+    if (!l->st->refine_wants_copy()) return HDSDP_RETCODE_OK;
+    const size_t npad = (size_t) l->ch.npad;
+    if (l->rf.Mcopy.reserve(npad * npad) != hipSuccess) return HDSDP_RETCODE_MEMORY;
+    HIP_RC(hipMemcpy2DAsync(l->rf.Mcopy.get(), sizeof(double) * npad, img, sizeof(double) * (size_t) ldimg, sizeof(double) * (size_t) l->n,
+                            (size_t) l->n, hipMemcpyDeviceToDevice, g.stream));
+    return HDSDP_RETCODE_OK;
+}
 hdsdp_retcode lin_factor_host(MiLin *l, const double *A, int *info) {
     RC(l->ch.load_host(A, l->n, g.stream));
+    RC(lin_refine_keep_image(l, l->ch.L.get(), l->ch.npad));
     RC(l->ch.factor(g.stream, info));
     return HDSDP_RETCODE_OK;
 }
@@ -83,7 +111,10 @@ hdsdp_retcode lin_factor_indef(MiLin *l) {
         if (l->lu->init(l->n)) { l->lu.reset(); return HDSDP_RETCODE_MEMORY; }
     }
     if (l->st->src_dev()) RC(l->lu->load_device_lower(l->st->src_dev(), l->st->src_ld(), g.stream));
-    else if (l->st->src_host()) RC(l->lu->load_host_lower(l->st->src_host(), l->st->src_ld(), g.stream));
+    else if (l->st->src_host()) {
+        RC(l->lu->load_host_lower(l->st->src_host(), l->st->src_ld(), g.stream));
+        RC(lin_refine_keep_image(l, l->lu->A.get(), l->lu->npad));
+    }
     else return HDSDP_RETCODE_FAILED;
     int info = 0;
     RC(l->lu->factor(g.stream, &info));
@@ -145,9 +176,104 @@ void lin_bsolve(void *chol, int nRhs, double *rhs, double *sol) {
         (sol ? sol : rhs)[0] = NAN;
     }
 }
+// ---- the refined solve: refine_rule.h's loop on the device ----
+// d = M^-1 v through the factor's own substitution path (HdmChol::solve_device, or the pivoted solver's once switched), from and
+// to vectors in the driver's order: x <- d, or x <- x + d.  A permuted factor's right-hand side and solution are permuted here.
+static hdsdp_retcode lin_refine_apply(MiLin *l, const HdmRefineSource &src, const double *v, double *x, bool add) {
+    const int n = l->n;
+    if (src.pivoted) {
+        HdmLu &lu = *l->lu;
+        double *b = lu.vec.get(), *d = lu.vec.get() + 2L * lu.npad;
+        RC(hdm_refine_scatter(b, v, nullptr, n, g.stream));
+        RC(lu.solve_device(b, d, 1, lu.npad, g.stream));
+        RC(hdm_refine_gather(x, d, nullptr, n, add ? 1 : 0, g.stream));
+        return HDSDP_RETCODE_OK;
+    }
+    HdmChol &c = l->ch;
+    double *b = c.vec.get(), *d = c.vec.get() + 2L * c.npad;
+    const int *perm = src.permute ? l->rf.perm.get() : nullptr;
+    HIP_RC(hipMemsetAsync(c.vec.get(), 0, sizeof(double) * 4L * c.npad, g.stream));
+    RC(hdm_refine_scatter(b, v, perm, n, g.stream));
+    RC(c.solve_device(b, d, 1, c.npad, 0, g.stream));
+    RC(hdm_refine_gather(x, d, perm, n, add ? 1 : 0, g.stream));
+    return HDSDP_RETCODE_OK;
+}
+// one right-hand side.  The caller's vectors are read once, at the start, and written once, at the end: in-place solves are safe,
+// and after a give-up of the single-launch substitution the whole solve starts again from the right-hand side on the device.
+static hdsdp_retcode lin_solve_refined_column(MiLin *l, const HdmRefineSource &src, const double *M, long ldm, const double *rhs, double *out) {
+    const int n = l->n;
+    const long npad = l->ch.npad;
+    MiLin::Refine &rf = l->rf;
+    double *B = rf.v.get(), *X = B + npad, *XP = B + 2 * npad, *X0 = B + 3 * npad, *R = B + 4 * npad, *nrm = B + 5 * npad;
+    double bnorm2 = 0.0;
+    for (int i = 0; i < n; ++i) bnorm2 += rhs[i] * rhs[i];
+    const double tol = hdm_refine_tol(l->relTol, l->absTol, std::sqrt(bnorm2));
+    HIP_RC(hipMemcpyAsync(B, rhs, sizeof(double) * (size_t) n, hipMemcpyHostToDevice, g.stream));
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        HdmRefineLoop loop(l->st->refine(), tol);
+        bool gave_up = false;
+        double norm2 = 0.0;
+        // the residual of X and its squared norm on the host; gave_up: the substitution before it has to be thrown away
+        auto residual = [&]() -> hdsdp_retcode {
+            RC(rf.res.run(M, ldm, n, X, B, R, nrm, g.stream));
+            HIP_RC(hipMemcpyAsync(&norm2, nrm, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+            HIP_RC(hipStreamSynchronize(g.stream));
+            gave_up = !src.pivoted && l->ch.flow_gave_up();
+            return HDSDP_RETCODE_OK;
+        };
+        RC(lin_refine_apply(l, src, B, X, false));
+        RC(residual());
+        bool more = !gave_up && loop.first(norm2);
+        while (more) {
+            HIP_RC(hipMemcpyAsync(XP, X, sizeof(double) * (size_t) n, hipMemcpyDeviceToDevice, g.stream));
+            if (loop.solves == 0) HIP_RC(hipMemcpyAsync(X0, X, sizeof(double) * (size_t) n, hipMemcpyDeviceToDevice, g.stream));
+            RC(lin_refine_apply(l, src, R, X, true));
+            RC(residual());
+            more = !gave_up && loop.next(norm2);
+        }
+        if (gave_up) continue;      // (flow_gave_up switched the object to per-block launches: the second attempt cannot give up)
+        const double *pick = loop.keep == HDM_REFINE_KEEP_CURRENT ? X : loop.keep == HDM_REFINE_KEEP_PREVIOUS ? XP : loop.solves > 0 ? X0 : X;
+        rf.stage.resize((size_t) n);
+        HIP_RC(hipMemcpyAsync(rf.stage.data(), pick, sizeof(double) * (size_t) n, hipMemcpyDeviceToHost, g.stream));
+        HIP_RC(hipStreamSynchronize(g.stream));
+        memcpy(out, rf.stage.data(), sizeof(double) * (size_t) n);
+        rf.status = loop.status; rf.steps = loop.steps; rf.resid0 = loop.resid0; rf.resid = loop.resid; rf.tol = tol;
+        rf.solves += 1; rf.total_steps += loop.solves;
+        return HDSDP_RETCODE_OK;
+    }
+    return HDSDP_RETCODE_FAILED;
+}
+// nRhs columns one after another; false in *refined: the state has no matrix for the residual and the solve runs as it always did
+static hdsdp_retcode lin_solve_refined(MiLin *l, int nRhs, double *rhs, double *sol, bool *refined) {
+    *refined = false;
+    if (l->st->refine() == 0) { l->rf.unrefined(HDM_REFINE_OFF); return HDSDP_RETCODE_OK; }
+    const HdmRefineSource src = hdm_kkt_refine_source(*l->st);
+    const bool factored = src.pivoted ? (l->lu && l->lu->factored) : l->ch.factored;
+    if (src.matrix == HDM_REFINE_MAT_NONE || l->bsp || !factored) {
+        l->rf.unrefined(src.matrix == HDM_REFINE_MAT_NONE ? src.why_none : HDM_REFINE_NO_MATRIX);
+        return HDSDP_RETCODE_OK;
+    }
+    const double *M = src.matrix == HDM_REFINE_MAT_COPY ? l->rf.Mcopy.get() : l->st->src_dev();
+    const long ldm = src.matrix == HDM_REFINE_MAT_COPY ? (long) l->ch.npad : l->st->src_ld();
+    if (!M) { l->rf.unrefined(HDM_REFINE_NO_MATRIX); return HDSDP_RETCODE_OK; }
+    MiLin::Refine &rf = l->rf;
+    if (rf.v.reserve(5 * (size_t) l->ch.npad + 8) != hipSuccess || rf.res.reserve(l->n)) return HDSDP_RETCODE_MEMORY;
+    if (src.permute && !rf.perm) {
+        if (rf.perm.alloc((size_t) l->n) != hipSuccess) return HDSDP_RETCODE_MEMORY;
+        HIP_RC(hdm_memcpy_h2d_sync(rf.perm.get(), l->perm.data(), sizeof(int) * (size_t) l->n));
+    }
+    *refined = true;
+    for (int r = 0; r < nRhs; ++r)
+        RC(lin_solve_refined_column(l, src, M, ldm, rhs + (size_t) r * l->n, (sol ? sol : rhs) + (size_t) r * l->n));
+    return HDSDP_RETCODE_OK;
+}
+
 // :1198-1225 dpotrs
 hdsdp_retcode lin_solve(void *chol, int nRhs, double *rhs, double *sol) {
     MiLin *l = (MiLin *) chol;
+    bool refined = false;
+    RC(lin_solve_refined(l, nRhs, rhs, sol, &refined));
+    if (refined) return HDSDP_RETCODE_OK;
     if (l->st->indef()) {                              // :1761-1780 dsytrs
         if (!l->lu || !l->lu->factored) return HDSDP_RETCODE_FAILED;
         RC(l->lu->solve_host(rhs, sol ? sol : rhs, nRhs, g.stream));

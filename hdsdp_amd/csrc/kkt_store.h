@@ -1,10 +1,12 @@
 // kkt_store.h -- how the Schur operator's matrix M is stored, what state it is in, and how it reaches the factor.
 // HKKTInit decides the storage once (sparse or dense host matrix, tile store or dense device matrix, block envelope, order);
 // from then on every writer of M names what it did through one of HdmKktState's transitions, and HKKTFactorize asks
-// hdm_kkt_load_plan what to do, performs it and commits it.
+// hdm_kkt_load_plan what to do, performs it and commits it.  What is left of the factorised matrix afterwards -- what the residual
+// of a refined solve may read -- is hdm_kkt_refine_source's answer, from the same state (the table is at the end of this file).
 // Pure host arithmetic: no HIP call, no engine state.  The engine performs these rules (engine_kkt.h, engine_linsys.h, and
 // HMiKKTPhaseA in engine_api.h); tests/test_kkt_store_cpu.py compiles this header alone.
 #pragma once
+#include "refine_rule.h"
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -132,22 +134,35 @@ class HdmKktState {
     // not owned: where the last factorised matrix came from (lower triangle valid)
     const double *srcHost = nullptr, *srcDev = nullptr;
     long srcLd = 0;
+    // the refined solve (refine_rule.h): the step cap (0 = off) and what is left of the matrix the factor was made from
+    int refine_ = 0;
+    HdmKktSource fact_src_ = HDM_KKT_SRC_NONE;   // where the factorised matrix came from
+    bool fact_copy_ = false;                     // host source: refinement was on then, so a device copy of the loaded image exists
+    bool fact_dev_intact_ = false;               // device source: no build has overwritten the device matrix since
     friend HdmKktLoadPlan hdm_kkt_load_plan(const HdmKktState &);
+    friend struct HdmRefineSource hdm_kkt_refine_source(const HdmKktState &);
+    void factorised_from(HdmKktSource src) {
+        fact_src_ = src; fact_copy_ = (src == HDM_KKT_SRC_HOST_M && refine_ > 0); fact_dev_intact_ = (src == HDM_KKT_SRC_DEVICE_M);
+    }
 
 public:
     HdmKktForm form() const { return form_; }
     bool mirror() const { return mirror_; }       bool permuted() const { return permuted_; }   bool indef() const { return indef_; }
     bool m_valid() const { return m_valid_; }     bool chan_folded() const { return chan_folded_; }
     const double *src_host() const { return srcHost; }   const double *src_dev() const { return srcDev; }   long src_ld() const { return srcLd; }
+    int refine() const { return refine_; }
+    // the loaded image of a host matrix is to be copied on the device before it is factorised (asked after commit / host_matrix_given)
+    bool refine_wants_copy() const { return fact_src_ == HDM_KKT_SRC_HOST_M && fact_copy_; }
 
     // Transitions, named for what happened.
     // HKKTInit decided the storage: a fresh device matrix and factor object.  The mirror keeps what it was told.
     void storage_decided(HdmKktForm form, bool permuted) {
         form_ = form; permuted_ = permuted; indef_ = false; m_valid_ = chan_folded_ = false;
         srcHost = srcDev = nullptr; srcLd = 0;
+        factorised_from(HDM_KKT_SRC_NONE);
     }
     // a build of type t started: it zeroes M and the channel, unless it is a corrector build, which touches neither
-    void build_started(bool corrector) { if (!corrector) chan_folded_ = false; }
+    void build_started(bool corrector) { if (!corrector) { chan_folded_ = false; fact_dev_intact_ = false; } }
     // a build of type t finished: the device matrix holds its result (a corrector build leaves what was there)
     void build_finished(bool corrector) { if (!corrector) m_valid_ = true; }
     // the channel was uploaded and added to the device matrix's diagonal (HKKTRegularize, or staging)
@@ -155,13 +170,18 @@ public:
     // the host CSC was scattered into the zeroed device matrix, which is thereby the matrix to be factored
     void csc_scattered() { m_valid_ = true; }
     // the fused small pass (HMiKKTPhaseA) wrote M and its factor in one launch
-    void small_pass_done(const double *Mdev, long ld) { m_valid_ = true; srcHost = nullptr; srcDev = Mdev; srcLd = ld; }
+    void small_pass_done(const double *Mdev, long ld) {
+        m_valid_ = true; srcHost = nullptr; srcDev = Mdev; srcLd = ld;
+        factorised_from(HDM_KKT_SRC_DEVICE_M);
+    }
     // the mirror was switched (HMiKKTSetHostMirror): kkt_point_diag and the plan read it, nothing else changes
     void mirror_switched(bool on) { mirror_ = on; }
     // the solver was switched to the pivoted one (lin_switch_indefinite)
     void switched_to_pivoted() { indef_ = true; }
     // a host matrix was handed over for factorisation (HFpLinsysNumeric on a linear system that is no operator's)
-    void host_matrix_given(const double *A, long ld) { srcHost = A; srcDev = nullptr; srcLd = ld; }
+    void host_matrix_given(const double *A, long ld) { srcHost = A; srcDev = nullptr; srcLd = ld; factorised_from(HDM_KKT_SRC_HOST_M); }
+    // refinement was switched (HMiLinsysSetRefine): 0 = off, else the step cap.  What was factorised before keeps what it has.
+    void refine_set(int maxSteps) { refine_ = hdm_refine_clamp(maxSteps); if (refine_ == 0) fact_copy_ = false; }   // (off: the copy is freed)
 
     // staging of `plan` is done: record what it made of M and where the factorisation takes it from
     void commit(const HdmKktLoadPlan &plan, const double *Mhost, long ldHost, const double *Mdev, long ldDev) {
@@ -169,6 +189,7 @@ public:
         if (plan.stage == HDM_KKT_STAGE_CSC_TO_M) csc_scattered();
         if (plan.source == HDM_KKT_SRC_HOST_M) { srcHost = Mhost; srcDev = nullptr; srcLd = ldHost; }
         if (plan.source == HDM_KKT_SRC_DEVICE_M) { srcHost = nullptr; srcDev = Mdev; srcLd = ldDev; }
+        factorised_from(plan.source);
     }
 };
 
@@ -213,4 +234,39 @@ inline HdmKktLoadPlan hdm_kkt_load_plan(const HdmKktState &st) {
     else if (st.form_ == HDM_KKT_CSC && st.permuted_) { p.load = HDM_KKT_LOAD_PERMUTED; p.gather = !st.mirror_; }
     else p.load = HDM_KKT_LOAD_DEVICE;
     return p;
+}
+
+// ---- the refined solve's matrix -------------------------------------------------------------
+// What the residual b - M x of a refined solve (refine_rule.h) reads, from the state alone:
+//
+//  factorised source            | the residual reads                                | valid
+//  -----------------------------+---------------------------------------------------+-------------------------------------------
+//  device M (mirror off, or a   | that matrix in place: channel folded, CSC         | until the next build that is no corrector
+//  CSC scattered into it)       | scattered, regularised -- what the factor saw     | build starts (it zeroes M): then NO_MATRIX
+//  host M (dense with the       | a device copy of the loaded image, taken after    | until the next factorisation; exists only if
+//  mirror on, HFpLinsysNumeric) | the load and before the factorisation             | refinement was on then: else NO_MATRIX
+//  nothing factorised yet       | --                                                | NO_MATRIX
+//  tile form                    | --                                                | NOT_AVAILABLE
+//
+// Permuted CSC: the factor holds P M P', the residual's matrix is in the driver's order: right-hand sides and corrections are
+// permuted on the device (permute).  Once switched to the pivoted solver the factor is of the recorded source in the driver's
+// order: corrections are the pivoted solver's (pivoted), nothing is permuted.
+enum HdmRefineMatrix { HDM_REFINE_MAT_NONE = 0, HDM_REFINE_MAT_DEVICE_M, HDM_REFINE_MAT_COPY };
+struct HdmRefineSource {
+    HdmRefineMatrix matrix = HDM_REFINE_MAT_NONE;
+    HdmRefineStatus why_none = HDM_REFINE_OFF;     // matrix == NONE: the status of the (unrefined) solve
+    bool permute = false, pivoted = false;
+};
+inline HdmRefineSource hdm_kkt_refine_source(const HdmKktState &st) {
+    HdmRefineSource r;
+    if (st.refine_ == 0) return r;
+    if (st.form_ == HDM_KKT_TILES) { r.why_none = HDM_REFINE_NOT_AVAILABLE; return r; }
+    r.why_none = HDM_REFINE_NO_MATRIX;
+    if (st.fact_src_ == HDM_KKT_SRC_DEVICE_M && st.fact_dev_intact_) r.matrix = HDM_REFINE_MAT_DEVICE_M;
+    else if (st.fact_src_ == HDM_KKT_SRC_HOST_M && st.fact_copy_) r.matrix = HDM_REFINE_MAT_COPY;
+    else return r;
+    r.why_none = HDM_REFINE_OFF;
+    r.pivoted = st.indef_;
+    r.permute = st.permuted_ && !st.indef_;
+    return r;
 }

@@ -4,6 +4,7 @@
 #include "../../include/hdsdp_mi355x.h"
 #include "chol.h"
 #include "hdm_common.h"
+#include "refine.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -225,6 +226,24 @@ int HMiCholEnvelopeSolve(const double *A_host, int n, const int *first, const do
         rc = 0;
     } while (0);
     return rc;
+}
+
+// the refined solve's residual kernel (refine.hip) on host arrays: M goes up exactly as given -- ld x n doubles, whatever lies
+// above the diagonal and in rows >= n included -- and r = b - M x and |r|_2^2 come back
+int HMiSymResidualProbe(int n, const double *Mlower, long ld, const double *x, const double *b, double *r, double *norm2) {
+    if (n < 1 || ld < n || !Mlower || !x || !b || !r || !norm2 || ensure_ctx()) return 1;
+    HdmBuf<double> M, v;
+    HdmSymRes res;
+    if (M.alloc((size_t) ld * n) != hipSuccess || v.alloc(3 * (size_t) n + 1) != hipSuccess || res.reserve(n)) return 1;
+    double *xd = v.get(), *bd = xd + n, *rd = bd + n, *nd = rd + n;
+    if (hipMemcpyAsync(M.get(), Mlower, sizeof(double) * (size_t) ld * n, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+        hipMemcpyAsync(xd, x, sizeof(double) * (size_t) n, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+        hipMemcpyAsync(bd, b, sizeof(double) * (size_t) n, hipMemcpyHostToDevice, g.stream) != hipSuccess) return 1;
+    if (res.run(M.get(), ld, n, xd, bd, rd, nd, g.stream)) return 1;
+    if (hipMemcpyAsync(r, rd, sizeof(double) * (size_t) n, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+        hipMemcpyAsync(norm2, nd, sizeof(double), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+        hipStreamSynchronize(g.stream) != hipSuccess) return 1;
+    return 0;
 }
 
 // diagnostic: factorisation time (ms, HIP events, graph replay included) of an n x n matrix whose pattern is a band of

@@ -194,6 +194,28 @@ hdsdp_retcode HFpLinsysGetDiag(hdsdp_linsys_fp *HLin, double *diagElem);        
 void HFpLinsysInvert(hdsdp_linsys_fp *HLin, double *dFullMatrix, double *dAuxiMatrix);    /* :2119 */
 void HFpLinsysClear(hdsdp_linsys_fp *HLin);                                               /* :2126 */
 void HFpLinsysDestroy(hdsdp_linsys_fp **HLin);                                            /* :2138 */
+/* The refined solve (csrc/refine_rule.h, csrc/refine.hip).  HFpLinsysSolve on a DENSE_DIRECT, SPARSE_DIRECT or
+ * DENSE_ITERATIVE object (switched to the pivoted solver or not) then iterates on the true residual b - M x, formed on the
+ * device in twice the working precision: solve, residual, and while the residual's 2-norm is not below
+ *     tol = max(min(absTol, relTol |b|), 0.1 absTol)      (the reference's formula; HFpLinsysSetParam's values, 1e-6 where unset)
+ * a correction solve with the same factor, x <- x + d, the new residual.  Off by default, and with it off nothing changes.
+ * HMiLinsysSetRefine: maxSteps = 0 turns it off (and frees its device memory), anything above is the step cap, clamped to 8.
+ * The residual needs the matrix the factor was made from: turn refinement on BEFORE HFpLinsysNumeric / HKKTFactorize.
+ * HMiLinsysGetRefine: the last HFpLinsysSolve (its last right-hand side) and the running totals; returns the step cap (0: off).
+ *   status   0 OFF  1 CONVERGED  2 STAGNATED (the residual did not halve: the iterate with the smaller residual went back)
+ *            3 MAXSTEPS  4 NUMERICAL (a residual was not finite: the unrefined solution went back)  5 NO_MATRIX (the factorised
+ *            matrix is not at hand -- refinement was off when it was factorised, or a later build has overwritten the device
+ *            matrix: the solve ran unrefined)  6 NOT_AVAILABLE (the tile form of a sparse operator: the solve ran unrefined)
+ *   steps    corrections in the solution that went back;  resid0, resid: |b - M x|_2 before and after;  tol: as above
+ *   solves, totalSteps: refined right-hand sides and correction solves since the object was created
+ * Stopping short of tol is a status, not a failure: nothing switches solvers.  FSolve / BSolve are not refined.
+ * HMiLinsysRefineBytes: device memory the refined solve holds for this object (0 while it is off).
+ * HMiKKTSetRefine: the same switch on the operator's linear system (kktM). */
+int HMiLinsysSetRefine(hdsdp_linsys_fp *HLin, int maxSteps);
+int HMiLinsysGetRefine(hdsdp_linsys_fp *HLin, int *status, int *steps, double *resid0, double *resid, double *tol, int64_t *solves,
+                       int64_t *totalSteps);
+int64_t HMiLinsysRefineBytes(hdsdp_linsys_fp *HLin);
+int HMiKKTSetRefine(hdsdp_kkt *HKKT, int maxSteps);
 
 /* ==========  MI355X SDP cone: the reference's cone slots that feed the Schur path  ==========
  * HMiConeCreateSDP    = HUserDataSetConeData + HConeCreate/SetData/ProcData/PresolveData for one
@@ -556,6 +578,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           cones[] is a host cone (diagonal channel); else one stderr line
  *  HDSDP_MI355X_GROUPED_BUILD     0         1: HKKTInit turns the grouped Schur build on (all eligible    test_gpu_grouped_build.py
  *                                           small SDP cones of an operator in three launches)
+ *  HDSDP_MI355X_REFINE           0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on
+ *                                           steps (HMiKKTSetRefine)
  *  -- the next six are the work plan's knobs: all read in csrc/work_plan.h (hdm_knobs_from_env), per allocation; HMiWorkPlanQuery sees them too --
  *  HDM_TCAP_GIB                   32        GiB of congruence intermediates per launch group              test_gpu_switches.py, test_gpu_group.py
  *  HDM_BC                         1024      constraints per congruence launch (upper bound)               test_gpu_switches.py
@@ -691,6 +715,10 @@ int HMiKKTNegativePivots(hdsdp_kkt *HKKT);
    factorisation time, best of three */
 int HMiBspSolve(int m, const int *colBeg, const int *rowIdx, const double *val, const double *b, double *x, int *info, int *stats,
                 double *ms);
+/* the refined solve's residual kernel on host arrays: r = b - M x and |r|_2^2, every component accumulated in twice the working
+   precision and rounded once.  Mlower: ld x n column-major, lower triangle valid; it is uploaded exactly as given and nothing above
+   the diagonal or in rows >= n is read.  Deterministic: two calls give the same bits. */
+int HMiSymResidualProbe(int n, const double *Mlower, long ld, const double *x, const double *b, double *r, double *norm2);
 int HMiCholEnvelopeProbe(int n, int band, int reps, double *ms_dense, double *ms_env);   /* factorisation time of a block-banded matrix, dense vs on its envelope */
 double HMiDiagBlockProbe(int variant, int reps);   /* us per 128 x 128 diagonal-block kernel of the Cholesky (0: LDS panels, 1: register sweep) */
 double HMiMfmaPeakProbe(int iters);    /* measured fp64 MFMA TFLOP/s of a register-only loop */
