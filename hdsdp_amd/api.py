@@ -38,7 +38,7 @@ EXPORTS = [
     "HMiConeGetExchangeBuffers", "HMiConeSetExchangeBuffers", "HMiKKTDeviceMatrix", "HMiKKTGetRows", "HMiKKTGetDiagTarget", "HMiKKTGetMatrixTraffic", "HMiDeviceInit",
     "HMiSetDevices", "HMiSetDevicesEx", "HMiRcclGroupSelfTest", "HMiGetDeviceGroup", "HMiSetShardMinDim", "HMiConeGetShardCount", "HMiConeGetGroupTraffic", "HMiRcclSelfTest", "HMiGetCallStats", "HMiCallStatName", "HMiResetCallStats", "HMiGetAssembleCounts", "HMiKKTPhaseAEligible", "HMiKKTPhaseA",
     "HMiDeviceSynchronize", "HMiStream", "HMiVersion", "HMiGetStageTimes", "HMiGemmNT", "HMiPotrf",
-    "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
+    "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiBspSymbolic", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
     "HMiGemmRoleLayout", "HMiGemmRoleSpan", "HMiCongStep1", "HMiCongStep2", "HMiCongIRow", "HMiGramSplits", "HMiGramGathered", "HMiGramLp",
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
     "HMiLinsysSetRefine", "HMiLinsysGetRefine", "HMiLinsysRefineBytes", "HMiKKTSetRefine", "HMiSymResidualProbe",
@@ -245,6 +245,7 @@ def load_library():
         "HMiKKTNegativePivots": (C.c_int, [kp]),
         "HMiBspSolve": (C.c_int, [C.c_int, ip, ip, dp, dp, dp, ip, ip, dp]),
         "HMiRcmOrder": (C.c_int, [C.c_int, ip, ip, ip]),
+        "HMiBspSymbolic": (C.c_int, [C.c_int, ip, ip, C.c_double, ip, ip, ip, ip]),
         "HMiWorkPlanQuery": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
         "HMiConeGetWorkPlan": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "HMiKKTSetGroupedBuild": (C.c_int, [kp, C.c_int]),
@@ -303,6 +304,42 @@ def rccl_group_self_test(ids, timeout_ms=60000):
     lib = load_library()
     arr = (C.c_int * len(ids))(*ids)
     return int(lib.HMiRcclGroupSelfTest(len(ids), arr, int(timeout_ms)))
+
+
+def bsp_symbolic(m, beg, idx, max_fraction=1.0):
+    """HMiBspSymbolic (host only): (rc, perm, stats[5], blockPtr, blockRow) of the tile form's symbolic phase on a lower-triangular
+    CSC pattern; perm and the block pattern are None where rc != 0"""
+    lib = load_library()
+    ip = C.POINTER(C.c_int)
+    beg, idx = np.ascontiguousarray(beg, dtype=np.int32), np.ascontiguousarray(idx, dtype=np.int32)
+    perm, stats = np.zeros(m, dtype=np.int32), np.zeros(5, dtype=np.int32)
+    rc = lib.HMiBspSymbolic(m, beg.ctypes.data_as(ip), idx.ctypes.data_as(ip), float(max_fraction), perm.ctypes.data_as(ip),
+                            stats.ctypes.data_as(ip), None, None)
+    if rc != 0:
+        return rc, None, stats, None, None
+    bptr, brow = np.zeros(stats[0] + 1, dtype=np.int32), np.zeros(stats[1], dtype=np.int32)
+    rc = lib.HMiBspSymbolic(m, beg.ctypes.data_as(ip), idx.ctypes.data_as(ip), float(max_fraction), perm.ctypes.data_as(ip),
+                            stats.ctypes.data_as(ip), bptr.ctypes.data_as(ip), brow.ctypes.data_as(ip))
+    return rc, perm, stats, bptr, brow
+
+
+def chol_envelope_solve(A, first, b):
+    """HMiCholEnvelopeSolve: the blocked Cholesky of the symmetric matrix A (its lower triangle is read) on the block envelope
+    first[] (None = dense) and one solve.  Returns (x, L, info): L = the lower triangle of the factor, x and L None where
+    info != 0."""
+    lib = load_library()
+    A = np.asfortranarray(A, dtype=np.float64)
+    n = A.shape[0]
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    x, L, info = np.zeros(n), np.zeros((n, n), order="F"), C.c_int(-1)
+    fa = None if first is None else np.ascontiguousarray(first, dtype=np.int32)
+    rc = lib.HMiCholEnvelopeSolve(A.ctypes.data, n, None if fa is None else fa.ctypes.data_as(C.POINTER(C.c_int)), b.ctypes.data,
+                                  x.ctypes.data, L.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise HDSDPError("HMiCholEnvelopeSolve failed")
+    if info.value != 0:
+        return None, None, info.value
+    return x, np.tril(L), 0
 
 
 def device_group():

@@ -31,6 +31,15 @@ __device__ __forceinline__ double *hdm_mat_at(const HdmMatView &v, int r, int c)
     return v.base + ((long) t << 14) + (pr & 127) + ((pc & 127) << 7);
 }
 
+// what the symbolic phase leaves for the device part of HdmBsp::init to upload (host only)
+struct HdmBspLists {
+    int tail_rows = 0;                // rows sent behind the reverse Cuthill-McKee part (the dense tail)
+    std::vector<int> tmap, diag, cols_by_level;
+    std::vector<int> tgt, tgt_src_ptr, src_col;
+    std::vector<int2> src, pan;
+    std::vector<int> row_ptr, row_col, row_tile, col_ptr, col_row, col_tile;
+};
+
 struct HdmBsp {
     int m = 0, nb = 0, ntiles = 0, nlevels = 0;
     std::vector<int> perm;            // old -> new
@@ -59,6 +68,8 @@ struct HdmBsp {
     // symbolic phase from the lower-triangular CSC pattern (host).  Returns 0, or 1 when the tile form would not pay
     // (`max_fraction` of the dense lower triangle's tiles) or cannot be built.
     int init(int m, const int *beg, const int *idx, double max_fraction);
+    // the host part of init alone (no device call): m, nb, ntiles, nlevels, perm, bptr, brow, the level pointers and `ls`
+    int symbolic(int m, const int *beg, const int *idx, double max_fraction, HdmBspLists &ls);
     HdmMatView view_M() const;        // the accumulation store the builders write
     HdmMatView view_L() const;        // the factor store (values scattered from the host CSC land here)
     int zero_M(hipStream_t s);

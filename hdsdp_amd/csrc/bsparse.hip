@@ -197,9 +197,11 @@ template <class T> static int bs_upload(HdmBuf<T> &dev, const std::vector<T> &h)
     return 0;
 }
 
-int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
+// the pure host part: row order, block pattern of the factor, levels and every list the kernels walk.  No device call.
+int HdmBsp::symbolic(int m_, const int *beg, const int *idx, double max_fraction, HdmBspLists &ls) {
     m = m_;
     nb = (m + BT - 1) / BT;
+    ntiles = nlevels = 0;
     if (nb < 2 || (long) nb * nb > (1L << 26)) return 1;
     // ---- row order: rows that reach a large part of the matrix go last (an arrow's shaft: eliminated last they cause no fill),
     // reverse Cuthill-McKee for the others (neighbours end up in the same or in neighbouring tiles)
@@ -224,6 +226,7 @@ int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
     // (the reduced pattern is still lower triangular in its own numbering: `sub` is increasing)
     std::vector<int> sperm = ms > 0 ? hdm_rcm_order(ms, sbeg, sidx) : std::vector<int>();
     perm.assign(m, 0);
+    ls.tail_rows = m - ms;
     {
         int tail = ms;
         for (int v = 0; v < m; ++v) perm[v] = (sub[v] >= 0) ? sperm[sub[v]] : tail++;
@@ -252,14 +255,17 @@ int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
     for (int k = 0; k < nb; ++k) { brow.insert(brow.end(), col[k].begin(), col[k].end()); bptr[k + 1] = (int) brow.size(); }
     ntiles = (int) brow.size();
     if ((double) ntiles > max_fraction * (double) dense_tiles()) return 1;
-    std::vector<int> tmap((size_t) nb * nb, -1), diag(nb);
+    std::vector<int> &tmap = ls.tmap, &diag = ls.diag;
+    tmap.assign((size_t) nb * nb, -1);
+    diag.assign(nb, 0);
     for (int k = 0; k < nb; ++k)
         for (int q = bptr[k]; q < bptr[k + 1]; ++q) { tmap[(size_t) brow[q] + (size_t) k * nb] = q; if (brow[q] == k) diag[k] = q; }
     // ---- levels of the block elimination tree
     std::vector<int> level(nb, 0);
     for (int k = 0; k < nb; ++k) if (parent[k] >= 0) level[parent[k]] = std::max(level[parent[k]], level[k] + 1);
     nlevels = 1 + *std::max_element(level.begin(), level.end());
-    std::vector<int> cols_by_level(nb);
+    std::vector<int> &cols_by_level = ls.cols_by_level;
+    cols_by_level.resize(nb);
     std::iota(cols_by_level.begin(), cols_by_level.end(), 0);
     std::stable_sort(cols_by_level.begin(), cols_by_level.end(), [&](int a, int b) { return level[a] < level[b]; });
     lvl_ptr.assign(nlevels + 1, 0);
@@ -274,8 +280,9 @@ int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
                 if (t < 0) return 1;                          // cannot happen: the symbolic factorisation closed the pattern
                 srcs[t].push_back(make_int2(qa, qb));
             }
-    std::vector<int> h_tgt, h_tsp{0}, h_scol;
-    std::vector<int2> h_src, h_pan;
+    std::vector<int> &h_tgt = ls.tgt, &h_tsp = ls.tgt_src_ptr, &h_scol = ls.src_col;
+    std::vector<int2> &h_src = ls.src, &h_pan = ls.pan;
+    h_tgt.clear(); h_tsp.assign(1, 0); h_scol.clear(); h_src.clear(); h_pan.clear();
     std::vector<int> tile_col((size_t) ntiles);
     for (int k = 0; k < nb; ++k) for (int q = bptr[k]; q < bptr[k + 1]; ++q) tile_col[q] = k;
     lvl_tgt_ptr.assign(nlevels + 1, 0);
@@ -297,7 +304,8 @@ int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
         lvl_pan_ptr[l + 1] = (int) h_pan.size();
     }
     // ---- strictly lower tiles by block row and by block column (substitutions)
-    std::vector<int> rp(nb + 1, 0), rc, rt, cp(nb + 1, 0), cr, ct;
+    std::vector<int> &rp = ls.row_ptr, &rc = ls.row_col, &rt = ls.row_tile, &cp = ls.col_ptr, &cr = ls.col_row, &ct = ls.col_tile;
+    rp.assign(nb + 1, 0); cp.assign(nb + 1, 0); cr.clear(); ct.clear();
     for (int k = 0; k < nb; ++k)
         for (int q = bptr[k] + 1; q < bptr[k + 1]; ++q) rp[brow[q] + 1] += 1;
     for (int k = 0; k < nb; ++k) rp[k + 1] += rp[k];
@@ -311,11 +319,17 @@ int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
         for (int q = bptr[k] + 1; q < bptr[k + 1]; ++q) { cr.push_back(brow[q]); ct.push_back(q); }
         cp[k + 1] = (int) cr.size();
     }
-    // ---- device side
-    if (bs_upload(perm_dev, perm) || bs_upload(tilemap, tmap) || bs_upload(lvl_cols, cols_by_level) || bs_upload(tgt_tile, h_tgt) ||
-        bs_upload(tgt_src_ptr, h_tsp) || bs_upload(src, h_src) || bs_upload(src_col, h_scol) || bs_upload(pan, h_pan) || bs_upload(row_ptr, rp) ||
-        bs_upload(row_col, rc) || bs_upload(row_tile, rt) || bs_upload(col_ptr, cp) || bs_upload(col_row, cr) ||
-        bs_upload(col_tile, ct) || bs_upload(diag_tile, diag))
+    return 0;
+}
+
+// symbolic phase, then the device part: uploads of its lists, the tile stores, the diagonal sweep's set-up
+int HdmBsp::init(int m_, const int *beg, const int *idx, double max_fraction) {
+    HdmBspLists ls;
+    if (symbolic(m_, beg, idx, max_fraction, ls)) return 1;
+    if (bs_upload(perm_dev, perm) || bs_upload(tilemap, ls.tmap) || bs_upload(lvl_cols, ls.cols_by_level) || bs_upload(tgt_tile, ls.tgt) ||
+        bs_upload(tgt_src_ptr, ls.tgt_src_ptr) || bs_upload(src, ls.src) || bs_upload(src_col, ls.src_col) || bs_upload(pan, ls.pan) ||
+        bs_upload(row_ptr, ls.row_ptr) || bs_upload(row_col, ls.row_col) || bs_upload(row_tile, ls.row_tile) || bs_upload(col_ptr, ls.col_ptr) ||
+        bs_upload(col_row, ls.col_row) || bs_upload(col_tile, ls.col_tile) || bs_upload(diag_tile, ls.diag))
         return 1;
     const size_t tb = sizeof(double) * BTT * ((size_t) ntiles + 1);
     if (Mval.alloc(BTT * ((size_t) ntiles + 1)) != hipSuccess || Lval.alloc(BTT * ((size_t) ntiles + 1)) != hipSuccess ||

@@ -436,6 +436,23 @@ int HMiRcmOrder(int m, const int *colBeg, const int *rowIdx, int *perm) {
     return 0;
 }
 
+// host only (no device call): the tile form's symbolic phase (HdmBsp::symbolic) on a lower-triangular CSC pattern.  perm[old] = new;
+// stats[0..4] = block rows, tiles of the factor, levels, rows sent to the dense tail, update source pairs; blockPtr (nb + 1) and
+// blockRow (ntiles) = the factor's block pattern by block column, lower with the diagonal first.  Any output may be NULL: a first
+// call with blockPtr = blockRow = NULL sizes them through stats.  Returns what HdmBsp::init would for the pattern (1: no tile form).
+int HMiBspSymbolic(int m, const int *colBeg, const int *rowIdx, double maxFraction, int *perm, int *stats, int *blockPtr, int *blockRow) {
+    if (m <= 0 || !colBeg || !rowIdx) return 1;
+    HdmBsp bs;
+    HdmBspLists ls;
+    const int rc = bs.symbolic(m, colBeg, rowIdx, maxFraction, ls);
+    if (stats) { stats[0] = bs.nb; stats[1] = bs.ntiles; stats[2] = bs.nlevels; stats[3] = ls.tail_rows; stats[4] = (int) ls.src.size(); }
+    if (rc) return rc;
+    if (perm) for (int i = 0; i < m; ++i) perm[i] = bs.perm[i];
+    if (blockPtr) for (int k = 0; k <= bs.nb; ++k) blockPtr[k] = bs.bptr[k];
+    if (blockRow) for (int q = 0; q < bs.ntiles; ++q) blockRow[q] = bs.brow[q];
+    return 0;
+}
+
 // how the operator's matrix will be factored: *permuted = 1 if the factor object holds P M P' (reverse Cuthill-McKee order of
 // the sparse pattern), *fraction = blocks inside the pattern's block envelope / blocks of the dense lower triangle (1 = dense)
 int HMiKKTTileInfo(hdsdp_kkt *HKKT, int *tiles, int64_t *denseTiles, int *levels, int64_t *bytes) {

@@ -715,6 +715,12 @@ int HMiKKTNegativePivots(hdsdp_kkt *HKKT);
    factorisation time, best of three */
 int HMiBspSolve(int m, const int *colBeg, const int *rowIdx, const double *val, const double *b, double *x, int *info, int *stats,
                 double *ms);
+/* host only (no device call): the symbolic phase of that factorisation on a lower-triangular CSC pattern.  perm[old] = new;
+   stats[0..4] = block rows, tiles of the factor, levels, rows sent to the dense tail, update source pairs; blockPtr (block rows
+   + 1 entries) and blockRow (one per tile) = the factor's block pattern by block column, diagonal first.  Every output may be
+   NULL; a first call with blockPtr = blockRow = NULL sizes them through stats.  Returns 1 where HKKTInit would not take the tile
+   form (fewer than two block rows, or more tiles than maxFraction of the dense triangle's). */
+int HMiBspSymbolic(int m, const int *colBeg, const int *rowIdx, double maxFraction, int *perm, int *stats, int *blockPtr, int *blockRow);
 /* the refined solve's residual kernel on host arrays: r = b - M x and |r|_2^2, every component accumulated in twice the working
    precision and rounded once.  Mlower: ld x n column-major, lower triangle valid; it is uploaded exactly as given and nothing above
    the diagonal or in rows >= n is read.  Deterministic: two calls give the same bits. */
