@@ -42,6 +42,7 @@ EXPORTS = [
     "HMiGemmRoleLayout", "HMiGemmRoleSpan", "HMiCongStep1", "HMiCongStep2", "HMiCongIRow", "HMiGramSplits", "HMiGramGathered", "HMiGramLp",
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
     "HMiLinsysSetRefine", "HMiLinsysGetRefine", "HMiLinsysRefineBytes", "HMiKKTSetRefine", "HMiSymResidualProbe",
+    "HMiLinsysSetRefineTiles", "HMiLinsysGetRefineTiles", "HMiKKTSetRefineTiles", "HMiTileResidualProbe", "HMiBspRefinedSolve", "HMiBspRefineTimingProbe",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
 ]
 
@@ -83,6 +84,54 @@ def sym_residual(M, x, b, n=None, ld=None):
     r, nrm = np.zeros(n), C.c_double(0.0)
     _check(load_library().HMiSymResidualProbe(int(n), _dptr(M), int(ld), _dptr(x), _dptr(b), _dptr(r), C.byref(nrm)), "HMiSymResidualProbe")
     return r, nrm.value
+
+
+def tile_residual(m, beg, idx, val, x, b):
+    """HMiTileResidualProbe: (r, |r|_2^2) with r = b - M x from the tile form's residual kernel; M as the lower-triangular CSC
+    (beg, idx, val) HMiBspSolve takes, x, b and r in the caller's order.  The tile store's padding and spare tile are NaN."""
+    beg, idx = np.ascontiguousarray(beg, dtype=np.int32), np.ascontiguousarray(idx, dtype=np.int32)
+    val, x, b = (np.ascontiguousarray(a, dtype=np.float64) for a in (val, x, b))
+    if beg.size != m + 1 or idx.size < beg[m] or val.size < beg[m] or x.size < m or b.size < m:
+        raise ValueError("tile_residual: an array is smaller than m and the pattern say")
+    r, nrm = np.zeros(m), C.c_double(0.0)
+    _check(load_library().HMiTileResidualProbe(int(m), _iptr(beg), _iptr(idx), _dptr(val), _dptr(x), _dptr(b), _dptr(r), C.byref(nrm)),
+           "HMiTileResidualProbe")
+    return r, nrm.value
+
+
+def bsp_refined_solve(m, beg, idx, val, b, max_steps, relTol=0.0, absTol=0.0):
+    """HMiBspRefinedSolve: the tile-form factorisation of the CSC matrix and the production refined solve.  Returns (x, info, st):
+    st = dict(status, status_name, steps, resid0, resid, tol, block_rows, tiles, levels, negative); x is None where info != 0"""
+    beg, idx = np.ascontiguousarray(beg, dtype=np.int32), np.ascontiguousarray(idx, dtype=np.int32)
+    val, b = np.ascontiguousarray(val, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    if beg.size != m + 1 or idx.size < beg[m] or val.size < beg[m] or b.size < m:
+        raise ValueError("bsp_refined_solve: an array is smaller than m and the pattern say")
+    x, stats = np.zeros(m), np.zeros(4, dtype=np.int32)
+    info, status, steps = C.c_int(-1), C.c_int(0), C.c_int(0)
+    r0, r1, tol = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    _check(load_library().HMiBspRefinedSolve(int(m), _iptr(beg), _iptr(idx), _dptr(val), _dptr(b), _dptr(x), int(max_steps), float(relTol),
+                                             float(absTol), C.byref(info), C.byref(status), C.byref(steps), C.byref(r0), C.byref(r1),
+                                             C.byref(tol), _iptr(stats)), "HMiBspRefinedSolve")
+    st = {"status": status.value, "status_name": REFINE_STATUS_NAMES[status.value], "steps": steps.value, "resid0": r0.value,
+          "resid": r1.value, "tol": tol.value, "block_rows": int(stats[0]), "tiles": int(stats[1]), "levels": int(stats[2]),
+          "negative": int(stats[3])}
+    return (x if info.value == 0 else None), info.value, st
+
+
+def bsp_refine_timing(m, beg, idx, val, b, variants, warmup=3, reps=31):
+    """HMiBspRefineTimingProbe: one tile-form factorisation of the CSC matrix, then the variants -- (cap, relTol, absTol), cap < 0 =
+    the unrefined solve -- alternate solve by solve.  Returns (ms[variant, rep], corrections, status, resid0, resid, stats[4], work bytes)"""
+    beg, idx = np.ascontiguousarray(beg, dtype=np.int32), np.ascontiguousarray(idx, dtype=np.int32)
+    val, b = np.ascontiguousarray(val, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    nv = len(variants)
+    caps = np.array([v[0] for v in variants], dtype=np.int32)
+    rel, ab = np.array([float(v[1]) for v in variants]), np.array([float(v[2]) for v in variants])
+    ms, corr, status = np.zeros((nv, reps)), np.zeros(nv, dtype=np.int32), np.zeros(nv, dtype=np.int32)
+    resid, stats, work = np.zeros(2 * nv), np.zeros(4, dtype=np.int32), C.c_int64(0)
+    _check(load_library().HMiBspRefineTimingProbe(int(m), _iptr(beg), _iptr(idx), _dptr(val), _dptr(b), nv, _iptr(caps), _dptr(rel), _dptr(ab),
+                                                  int(warmup), int(reps), _dptr(ms), _iptr(corr), _iptr(status), _dptr(resid), _iptr(stats),
+                                                  C.byref(work)), "HMiBspRefineTimingProbe")
+    return ms, corr, status, resid[0::2].copy(), resid[1::2].copy(), stats, work.value
 
 
 class hdsdp_kkt(C.Structure):  # interface/def_hdsdp_schur.h:32-68
@@ -255,6 +304,12 @@ def load_library():
         "HMiLinsysRefineBytes": (C.c_int64, [vp]),
         "HMiKKTSetRefine": (C.c_int, [kp, C.c_int]),
         "HMiSymResidualProbe": (C.c_int, [C.c_int, dp, C.c_long, dp, dp, dp, dp]),
+        "HMiLinsysSetRefineTiles": (C.c_int, [vp, C.c_int]),
+        "HMiLinsysGetRefineTiles": (C.c_int, [vp]),
+        "HMiKKTSetRefineTiles": (C.c_int, [kp, C.c_int]),
+        "HMiTileResidualProbe": (C.c_int, [C.c_int, ip, ip, dp, dp, dp, dp, dp]),
+        "HMiBspRefineTimingProbe": (C.c_int, [C.c_int, ip, ip, dp, dp, C.c_int, ip, dp, dp, C.c_int, C.c_int, dp, ip, ip, dp, ip, C.POINTER(C.c_int64)]),
+        "HMiBspRefinedSolve": (C.c_int, [C.c_int, ip, ip, dp, dp, dp, C.c_int, C.c_double, C.c_double, ip, ip, ip, dp, dp, dp, ip]),
         "HMiGroupedPlanQuery": (C.c_int, [C.c_int, C.c_int, ip, ip, ip, ip, C.POINTER(C.c_int64), ip, ip, ip, ip, ip, C.POINTER(C.c_int64), ip, ip, ip,
                                           C.POINTER(C.c_int64), ip, ip]),
         "HMiPresolveCSC": (C.c_int, [C.c_int, C.c_int, ip, ip, dp, ip, ip, ip, ip, ip, ip]),
@@ -972,6 +1027,15 @@ class KKT:
         """HMiKKTSetRefine: HKKTSolve iterates on the true residual, at most max_steps corrections (0: off, the default; clamped
         to 8).  Turn it on before factorize(): the residual reads the matrix the factor was made from."""
         _check(load_library().HMiKKTSetRefine(self._k, int(max_steps)), "HMiKKTSetRefine")
+
+    def set_refine_tiles(self, on):
+        """HMiKKTSetRefineTiles: the tile form's own switch on top of set_refine's cap -- a tile operator is refined only with
+        both on before factorize(); off (the default) it answers NOT_AVAILABLE and holds no memory"""
+        _check(load_library().HMiKKTSetRefineTiles(self._k, 1 if on else 0), "HMiKKTSetRefineTiles")
+
+    def refine_tiles(self):
+        """HMiLinsysGetRefineTiles of the operator's linear system"""
+        return bool(load_library().HMiLinsysGetRefineTiles(self._k.contents.kktM))
 
     def set_param(self, relTol=0.0, absTol=0.0, maxIter=-1):
         """HFpLinsysSetParam on the operator's linear system (HKKTInit sets 5e-12 / 1e-12 for m <= 5000): the refined solve's

@@ -80,7 +80,8 @@ struct HdmBsp {
     // fails, linalg/hdsdp_linsolver.c:596-626), and so is this; for a positive definite matrix it IS the Cholesky factorisation,
     // bit for bit.  info = 0, or first zero / non-finite pivot + 1 (renumbered order); nneg = negative pivots.
     int factor(hipStream_t s, int *info, int *nneg = nullptr);
-    int solve_host(const double *rhs, double *sol, hipStream_t s);   // driver's numbering in and out
+    int solve_device(double *v, hipStream_t s);   // the level loops alone, in place: nb * 128 entries, renumbered order, padding zero
+    int solve_host(const double *rhs, double *sol, hipStream_t s);   // driver's numbering in and out, around solve_device
 };
 
 // reverse Cuthill-McKee order of a symmetric pattern given as its lower triangle in CSC form: perm[old] = new

@@ -385,19 +385,26 @@ int HdmBsp::factor(hipStream_t s, int *info_host, int *nneg_host) {
     return 0;
 }
 
+// the substitutions alone, in place on a device vector of nb * 128 entries in the renumbered order (padding zero)
+int HdmBsp::solve_device(double *v, hipStream_t s) {
+    if (!factored) return 1;
+    for (int l = 0; l < nlevels; ++l)
+        hipLaunchKernelGGL(bs_fwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval.get(), Winv.get(), lvl_cols.get(), row_ptr.get(), row_col.get(), row_tile.get(),
+                           v, lvl_ptr[l]);
+    for (int l = nlevels - 1; l >= 0; --l)
+        hipLaunchKernelGGL(bs_bwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval.get(), Winv.get(), lvl_cols.get(), col_ptr.get(), col_row.get(), col_tile.get(),
+                           v, lvl_ptr[l], sgn.get());
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int HdmBsp::solve_host(const double *rhs, double *sol, hipStream_t s) {
     if (!factored) return 1;
     HDM_HIP_CHECK(hipStreamSynchronize(s));                     // the staging buffer is free
     memset(hvec.get(), 0, sizeof(double) * BT * (size_t) nb);
     for (int i = 0; i < m; ++i) hvec.get()[perm[i]] = rhs[i];
     HDM_HIP_CHECK(hipMemcpyAsync(vec.get(), hvec.get(), sizeof(double) * BT * (size_t) nb, hipMemcpyHostToDevice, s));
-    for (int l = 0; l < nlevels; ++l)
-        hipLaunchKernelGGL(bs_fwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval.get(), Winv.get(), lvl_cols.get(), row_ptr.get(), row_col.get(), row_tile.get(),
-                           vec.get(), lvl_ptr[l]);
-    for (int l = nlevels - 1; l >= 0; --l)
-        hipLaunchKernelGGL(bs_bwd_kernel, dim3(lvl_ptr[l + 1] - lvl_ptr[l]), dim3(256), 0, s, Lval.get(), Winv.get(), lvl_cols.get(), col_ptr.get(), col_row.get(), col_tile.get(),
-                           vec.get(), lvl_ptr[l], sgn.get());
-    HDM_HIP_CHECK(hipGetLastError());
+    if (solve_device(vec.get(), s)) return 1;
     HDM_HIP_CHECK(hipMemcpyAsync(hvec.get(), vec.get(), sizeof(double) * BT * (size_t) nb, hipMemcpyDeviceToHost, s));
     HDM_HIP_CHECK(hipStreamSynchronize(s));
     for (int i = 0; i < m; ++i) sol[i] = hvec.get()[perm[i]];

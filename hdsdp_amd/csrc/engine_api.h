@@ -515,6 +515,114 @@ int HMiBspSolve(int m, const int *colBeg, const int *rowIdx, const double *val, 
     } while (0);
     return rc;
 }
+// the CSC values of a host matrix scattered into the accumulation store of a stand-alone tile object (what HMiBspSolve does)
+static int bsp_probe_scatter(HdmBsp &bs, int m, const int *colBeg, const int *rowIdx, const double *val) {
+    const long nnz = colBeg[m];
+    std::vector<int> cols((size_t) nnz);
+    for (int c = 0; c < m; ++c) for (int q = colBeg[c]; q < colBeg[c + 1]; ++q) cols[q] = c;
+    HdmBuf<int> rows_d, cols_d;
+    HdmBuf<double> vals_d;
+    if (rows_d.alloc(nnz) != hipSuccess || cols_d.alloc(nnz) != hipSuccess || vals_d.alloc(nnz) != hipSuccess) return 1;
+    if (hipMemcpy(rows_d.get(), rowIdx, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(cols_d.get(), cols.data(), sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(vals_d.get(), val, sizeof(double) * nnz, hipMemcpyHostToDevice) != hipSuccess) return 1;
+    hipLaunchKernelGGL(mi_csc_scatter_kernel, dim3((unsigned) ((nnz + 255) / 256)), dim3(256), 0, g.stream, bs.view_M(), rows_d.get(), cols_d.get(), nnz, vals_d.get());
+    return (hipGetLastError() != hipSuccess || hipStreamSynchronize(g.stream) != hipSuccess) ? 1 : 0;   // (the buffers go with this scope)
+}
+// The tile form's residual kernel (refine.hip: HdmBspRefine::residual) on a host matrix: r = b - M x and |r|_2^2 with x, b and r in
+// the driver's order.  Before the values are scattered, every padding row and column of the last block row and the whole trash tile
+// are filled with NaN: a kernel that read any of them would return it.
+int HMiTileResidualProbe(int m, const int *colBeg, const int *rowIdx, const double *val, const double *x, const double *b, double *r, double *norm2) {
+    if (m < 1 || !colBeg || !rowIdx || !val || !x || !b || !r || !norm2 || ensure_ctx()) return 1;
+    HdmBsp bs;
+    HdmBspRefine t;
+    if (bs.init(m, colBeg, rowIdx, 1.0) || bs.zero_M(g.stream) || hipStreamSynchronize(g.stream) != hipSuccess) return 1;
+    const int first_pad = m - (bs.nb - 1) * 128;               // rows (and, in the diagonal tile, columns) of the last block from here on
+    std::vector<double> img(16384);
+    for (int k = 0; k < bs.nb; ++k)
+        for (int q = bs.bptr[k]; q < bs.bptr[k + 1]; ++q) {
+            if (bs.brow[q] != bs.nb - 1 || first_pad >= 128) continue;
+            for (int c = 0; c < 128; ++c)
+                for (int i = 0; i < 128; ++i) img[(size_t) i + 128 * (size_t) c] = (i >= first_pad || (k == bs.nb - 1 && c >= first_pad)) ? NAN : 0.0;
+            if (hipMemcpy(bs.Mval.get() + ((size_t) q << 14), img.data(), sizeof(double) * 16384, hipMemcpyHostToDevice) != hipSuccess) return 1;
+        }
+    std::fill(img.begin(), img.end(), NAN);
+    if (hipMemcpy(bs.Mval.get() + ((size_t) bs.ntiles << 14), img.data(), sizeof(double) * 16384, hipMemcpyHostToDevice) != hipSuccess) return 1;
+    if (bsp_probe_scatter(bs, m, colBeg, rowIdx, val) || t.prepare(bs)) return 1;
+    double *B = t.vec(0), *X = t.vec(1), *R = t.vec(4), *T = t.vec(5), *nrm = t.vec(6);
+    if (hipMemsetAsync(B, 0, sizeof(double) * 2 * (size_t) t.len, g.stream) != hipSuccess ||
+        hipMemcpyAsync(T, b, sizeof(double) * (size_t) m, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+        hdm_refine_scatter(B, T, bs.perm_dev.get(), m, g.stream) ||
+        hipMemcpyAsync(T, x, sizeof(double) * (size_t) m, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
+        hdm_refine_scatter(X, T, bs.perm_dev.get(), m, g.stream)) return 1;
+    if (t.residual(bs.Mval.get(), X, B, R, nrm, g.stream) || hdm_refine_gather(T, R, bs.perm_dev.get(), m, 0, g.stream)) return 1;
+    if (hipMemcpyAsync(r, T, sizeof(double) * (size_t) m, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+        hipMemcpyAsync(norm2, nrm, sizeof(double), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+        hipStreamSynchronize(g.stream) != hipSuccess) return 1;
+    return 0;
+}
+// The production refined solve of the tile form on a host matrix: scatter, load_M, factor, then lin_refine_column over the
+// stand-alone object, its residual reading the accumulation store.  *info as HMiBspSolve; with a zero pivot nothing is solved.
+// status .. tol as HMiLinsysGetRefine reports them; stats[0..3] = block rows, tiles stored, levels, negative pivots.
+int HMiBspRefinedSolve(int m, const int *colBeg, const int *rowIdx, const double *val, const double *b, double *x, int maxSteps, double relTol,
+                       double absTol, int *info, int *status, int *steps, double *resid0, double *resid, double *tol, int *stats) {
+    if (m < 1 || !colBeg || !rowIdx || !val || !b || !x || ensure_ctx()) return 1;
+    HdmBsp bs;
+    HdmBspRefine t;
+    int inf = 0;
+    if (bs.init(m, colBeg, rowIdx, 1.0) || bsp_probe_scatter(bs, m, colBeg, rowIdx, val) || bs.load_M(g.stream) || bs.factor(g.stream, &inf)) return 1;
+    if (info) *info = inf;
+    if (stats) { stats[0] = bs.nb; stats[1] = bs.ntiles; stats[2] = bs.nlevels; stats[3] = bs.negative; }
+    if (inf != 0) return 0;
+    if (t.prepare(bs)) return 1;
+    HdmRefineStats rf;
+    LinRefineTiles form(bs, t, bs.Mval.get());
+    if (lin_refine_column(form, m, maxSteps, relTol, absTol, b, x, rf) != HDSDP_RETCODE_OK) return 1;
+    if (status) *status = rf.status;
+    if (steps) *steps = rf.steps;
+    if (resid0) *resid0 = rf.resid0;
+    if (resid) *resid = rf.resid;
+    if (tol) *tol = rf.tol;
+    return 0;
+}
+// What the tile form's refined solve costs beside the unrefined one (tools/refine_tiles_timing.py): one factorisation, then the
+// nVariants variants alternate solve by solve, warmup + reps rounds, host clock around each solve (every one ends in a stream
+// synchronisation).  Variant v: caps[v] < 0 = HdmBsp::solve_host, the unrefined solve; otherwise the refined solve with that cap
+// under relTols[v] / absTols[v].  ms[v * reps + r]; corrections[v] = correction solves over the timed rounds; status[v] and
+// resid[2 v], resid[2 v + 1] (|r_0|, |r|) of the last one; stats as HMiBspSolve; *workBytes = what the refined solve allocated.
+int HMiBspRefineTimingProbe(int m, const int *colBeg, const int *rowIdx, const double *val, const double *b, int nVariants, const int *caps,
+                            const double *relTols, const double *absTols, int warmup, int reps, double *ms, int *corrections, int *status,
+                            double *resid, int *stats, int64_t *workBytes) {
+    if (m < 1 || !colBeg || !rowIdx || !val || !b || nVariants < 1 || !caps || !relTols || !absTols || warmup < 0 || reps < 1 || !ms || ensure_ctx())
+        return 1;
+    HdmBsp bs;
+    HdmBspRefine t;
+    int inf = 0;
+    if (bs.init(m, colBeg, rowIdx, 1.0) || bsp_probe_scatter(bs, m, colBeg, rowIdx, val) || bs.load_M(g.stream) || bs.factor(g.stream, &inf)) return 1;
+    if (stats) { stats[0] = bs.nb; stats[1] = bs.ntiles; stats[2] = bs.nlevels; stats[3] = bs.negative; }
+    if (inf != 0 || t.prepare(bs)) return 1;
+    if (workBytes) *workBytes = (int64_t) t.bytes();
+    std::vector<double> x((size_t) m);
+    std::vector<HdmRefineStats> rf((size_t) nVariants);
+    if (corrections) std::fill(corrections, corrections + nVariants, 0);
+    LinRefineTiles form(bs, t, bs.Mval.get());
+    for (int r = -warmup; r < reps; ++r)
+        for (int v = 0; v < nVariants; ++v) {
+            const int64_t before = rf[(size_t) v].total_steps;
+            const auto t0 = std::chrono::steady_clock::now();
+            if (caps[v] < 0) { if (bs.solve_host(b, x.data(), g.stream)) return 1; }
+            else if (lin_refine_column(form, m, caps[v], relTols[v], absTols[v], b, x.data(), rf[(size_t) v]) != HDSDP_RETCODE_OK) return 1;
+            const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (r < 0) continue;
+            ms[(size_t) v * reps + r] = dt;
+            if (corrections) corrections[v] += (int) (rf[(size_t) v].total_steps - before);
+        }
+    for (int v = 0; v < nVariants; ++v) {
+        if (status) status[v] = rf[(size_t) v].status;
+        if (resid) { resid[2 * v] = rf[(size_t) v].resid0; resid[2 * v + 1] = rf[(size_t) v].resid; }
+    }
+    return 0;
+}
 void HMiKKTEnvelopeInfo(hdsdp_kkt *HKKT, int *permuted, double *fraction) {
     if (permuted) *permuted = 0;
     if (fraction) *fraction = 1.0;

@@ -100,6 +100,16 @@ int HMiLinsysGetRefine(hdsdp_linsys_fp *HLin, int *status, int *steps, double *r
 }
 int64_t HMiLinsysRefineBytes(hdsdp_linsys_fp *HLin) { return (HLin && HLin->chol) ? ((const MiLin *) HLin->chol)->rf.bytes() : 0; }
 int HMiKKTSetRefine(hdsdp_kkt *HKKT, int maxSteps) { return (HKKT && HKKT->kktM) ? HMiLinsysSetRefine(HKKT->kktM, maxSteps) : 1; }
+// the tile form's own switch on top of the step cap (kkt_store.h): a tile operator is refined only with both on before HKKTFactorize
+int HMiLinsysSetRefineTiles(hdsdp_linsys_fp *HLin, int on) {
+    if (!HLin || !HLin->chol) return 1;
+    MiLin *l = (MiLin *) HLin->chol;
+    l->st->refine_tiles_set(on != 0);
+    if (!on) l->rf.tiles.release();
+    return 0;
+}
+int HMiLinsysGetRefineTiles(hdsdp_linsys_fp *HLin) { return (HLin && HLin->chol) ? (((const MiLin *) HLin->chol)->st->refine_tiles() ? 1 : 0) : -1; }
+int HMiKKTSetRefineTiles(hdsdp_kkt *HKKT, int on) { return (HKKT && HKKT->kktM) ? HMiLinsysSetRefineTiles(HKKT->kktM, on) : 1; }
 hdsdp_retcode HFpLinsysSymbolic(hdsdp_linsys_fp *HLin, int *colMatBeg, int *colMatIdx) {
     return HLin->cholSymbolic(HLin->chol, colMatBeg, colMatIdx);
 }
@@ -415,6 +425,13 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
             fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_REFINE=%d: Schur solves are refined, at most %d step(s)\n", atoi(e), pv->st.refine());
         }
     }
+    // HDSDP_MI355X_REFINE_TILES=1: ... and a tile-form operator's too (HMiKKTSetRefineTiles; it needs the step cap above as well)
+    if (const char *e = getenv("HDSDP_MI355X_REFINE_TILES")) {
+        if (atoi(e) > 0) {
+            (void) HMiKKTSetRefineTiles(HKKT, 1);
+            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_REFINE_TILES=%d: the tile form of a sparse operator is refined too (step cap %d)\n", atoi(e), pv->st.refine());
+        }
+    }
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
 }
@@ -653,6 +670,8 @@ hdsdp_retcode HKKTFactorize(hdsdp_kkt *HKKT) {
     pv->bytes_h2d += plan.matrix_bytes(HKKT->nRow, pv->nnz);
     pv->st.commit(plan, HKKT->kktMatElem, HKKT->nRow, l->Mdev.get(), l->ch.npad);
     if (plan.load == HDM_KKT_LOAD_PIVOTED) return lin_factor_indef(l);     // switched earlier: stays switched (hdsdp_linsolver.c:1838)
+    // tile form, mirror on, refined: the scattered factor store is the only image of the factorised matrix on the device
+    if (pv->st.refine_wants_tile_copy() && l->rf.tiles.keep_copy(*l->bsp, g.stream)) return HDSDP_RETCODE_MEMORY;
     if (kkt_load(HKKT, pv, l, plan) != HDSDP_RETCODE_OK) return HDSDP_RETCODE_FAILED;
     // the tile form factors LDL' like the reference's sparse direct solver (linalg/hdsdp_linsolver.c:596-626 over external/qdldl.c):
     // an indefinite matrix factors and the solves go on with the signed factor; only a pivot that is exactly zero is a failure

@@ -3,10 +3,19 @@
 // and the engine's thread-local context `g`); split out of a 3 300-line file in round 3, nothing else changed.
 // Whether a system is switched to the pivoted solver and where its last factorised matrix came from is HdmKktState's
 // (kkt_store.h, with the table of how the Schur operator's matrix reaches the factor): lin_factor_indef reads the source from it.
-// The refined solve (lin_solve_refined: refine_rule.h's loop on refine.hip's residual) asks the same state what its residual reads.
+// The refined solve (lin_solve_refined: refine_rule.h's loop on refine.hip's residual) asks the same state what its residual reads;
+// lin_refine_column is that loop once, over what a storage form supplies (the dense forms, the tile form).
 // =============================================================================================
 // linear-system objects
 // =============================================================================================
+// the last refined solve and the running totals (HMiLinsysGetRefine)
+struct HdmRefineStats {
+    int status = HDM_REFINE_OFF, steps = 0;
+    double resid0 = 0.0, resid = 0.0, tol = 0.0;
+    int64_t solves = 0, total_steps = 0;
+    void unrefined(HdmRefineStatus why) { status = why; steps = 0; resid0 = resid = tol = 0.0; }
+};
+
 struct MiLin {
     int n = 0;
     linsys_type type = HDSDP_LINSYS_DENSE_DIRECT;
@@ -39,19 +48,15 @@ struct MiLin {
     std::vector<double> dense;
     // the refined solve (refine_rule.h, refine.hip).  Whether it is on and what its residual reads is the
     // state's (kkt_store.h: hdm_kkt_refine_source); everything here is allocated at the first use and freed when it goes off.
-    struct Refine {
+    struct Refine : HdmRefineStats {
         HdmSymRes res;
+        HdmBspRefine tiles;        // the tile form's part (refine.h): plan, slots, vectors, and the copy of the factor store
         HdmBuf<double> Mcopy;      // npad x npad: the loaded image of a host matrix, as the factorisation saw it
         HdmBuf<double> v;          // 5 npad + 8: right-hand side, iterate, previous iterate, unrefined solution, residual; |r|^2
         HdmBuf<int> perm;          // device copy of MiLin::perm
         std::vector<double> stage; // the returned iterate on its way to the caller
-        // the last solve and the running totals (HMiLinsysGetRefine)
-        int status = HDM_REFINE_OFF, steps = 0;
-        double resid0 = 0.0, resid = 0.0, tol = 0.0;
-        int64_t solves = 0, total_steps = 0;
-        void unrefined(HdmRefineStatus why) { status = why; steps = 0; resid0 = resid = tol = 0.0; }
-        void release() { res.part.reset(); res.npart.reset(); Mcopy.reset(); v.reset(); perm.reset(); stage.clear(); stage.shrink_to_fit(); }
-        int64_t bytes() const { return (int64_t) (res.bytes() + sizeof(double) * (Mcopy.count() + v.count()) + sizeof(int) * perm.count()); }
+        void release() { res.part.reset(); res.npart.reset(); Mcopy.reset(); v.reset(); perm.reset(); stage.clear(); stage.shrink_to_fit(); tiles.release(); }
+        int64_t bytes() const { return (int64_t) (res.bytes() + sizeof(double) * (Mcopy.count() + v.count()) + sizeof(int) * perm.count() + tiles.bytes()); }
     } rf;
 };
 
@@ -198,58 +203,133 @@ static hdsdp_retcode lin_refine_apply(MiLin *l, const HdmRefineSource &src, cons
     RC(hdm_refine_gather(x, d, perm, n, add ? 1 : 0, g.stream));
     return HDSDP_RETCODE_OK;
 }
-// one right-hand side.  The caller's vectors are read once, at the start, and written once, at the end: in-place solves are safe,
-// and after a give-up of the single-launch substitution the whole solve starts again from the right-hand side on the device.
-static hdsdp_retcode lin_solve_refined_column(MiLin *l, const HdmRefineSource &src, const double *M, long ldm, const double *rhs, double *out) {
-    const int n = l->n;
-    const long npad = l->ch.npad;
-    MiLin::Refine &rf = l->rf;
-    double *B = rf.v.get(), *X = B + npad, *XP = B + 2 * npad, *X0 = B + 3 * npad, *R = B + 4 * npad, *nrm = B + 5 * npad;
+// One right-hand side of a refined solve, over what a storage form supplies (`Form`):
+//   B, X, XP, X0, R, nrm   device vectors of `len` entries each (right-hand side, iterate, previous iterate, unrefined solution,
+//                          residual) and one double, in whatever order and padding the form's factor works in
+//   load(rhs)              the caller's right-hand side -> B          store(pick, out)   an iterate -> the caller's vector
+//   apply(v, x, add)       x <- M^-1 v, or x <- x + M^-1 v, through the factor's own substitution path
+//   residual()             R <- B - M X in twice the working precision, nrm <- |R|^2
+//   gave_up()              the substitution before the last residual has to be thrown away (asked after a synchronisation);
+//                          attempts: 2 where that can happen -- the whole solve then starts again from B -- else 1
+// The caller's vectors are read once, at the start, and written once, at the end: in-place solves are safe.
+template <class Form>
+static hdsdp_retcode lin_refine_column(Form &f, int n, int cap, double relTol, double absTol, const double *rhs, double *out, HdmRefineStats &rf) {
     double bnorm2 = 0.0;
     for (int i = 0; i < n; ++i) bnorm2 += rhs[i] * rhs[i];
-    const double tol = hdm_refine_tol(l->relTol, l->absTol, std::sqrt(bnorm2));
-    HIP_RC(hipMemcpyAsync(B, rhs, sizeof(double) * (size_t) n, hipMemcpyHostToDevice, g.stream));
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        HdmRefineLoop loop(l->st->refine(), tol);
+    const double tol = hdm_refine_tol(relTol, absTol, std::sqrt(bnorm2));
+    RC(f.load(rhs));
+    for (int attempt = 0; attempt < f.attempts; ++attempt) {
+        HdmRefineLoop loop(cap, tol);
         bool gave_up = false;
         double norm2 = 0.0;
-        // the residual of X and its squared norm on the host; gave_up: the substitution before it has to be thrown away
+        // the residual of X and its squared norm on the host
         auto residual = [&]() -> hdsdp_retcode {
-            RC(rf.res.run(M, ldm, n, X, B, R, nrm, g.stream));
-            HIP_RC(hipMemcpyAsync(&norm2, nrm, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+            RC(f.residual());
+            HIP_RC(hipMemcpyAsync(&norm2, f.nrm, sizeof(double), hipMemcpyDeviceToHost, g.stream));
             HIP_RC(hipStreamSynchronize(g.stream));
-            gave_up = !src.pivoted && l->ch.flow_gave_up();
+            gave_up = f.gave_up();
             return HDSDP_RETCODE_OK;
         };
-        RC(lin_refine_apply(l, src, B, X, false));
+        RC(f.apply(f.B, f.X, false));
         RC(residual());
         bool more = !gave_up && loop.first(norm2);
         while (more) {
-            HIP_RC(hipMemcpyAsync(XP, X, sizeof(double) * (size_t) n, hipMemcpyDeviceToDevice, g.stream));
-            if (loop.solves == 0) HIP_RC(hipMemcpyAsync(X0, X, sizeof(double) * (size_t) n, hipMemcpyDeviceToDevice, g.stream));
-            RC(lin_refine_apply(l, src, R, X, true));
+            HIP_RC(hipMemcpyAsync(f.XP, f.X, sizeof(double) * (size_t) f.len, hipMemcpyDeviceToDevice, g.stream));
+            if (loop.solves == 0) HIP_RC(hipMemcpyAsync(f.X0, f.X, sizeof(double) * (size_t) f.len, hipMemcpyDeviceToDevice, g.stream));
+            RC(f.apply(f.R, f.X, true));
             RC(residual());
             more = !gave_up && loop.next(norm2);
         }
         if (gave_up) continue;      // (flow_gave_up switched the object to per-block launches: the second attempt cannot give up)
-        const double *pick = loop.keep == HDM_REFINE_KEEP_CURRENT ? X : loop.keep == HDM_REFINE_KEEP_PREVIOUS ? XP : loop.solves > 0 ? X0 : X;
-        rf.stage.resize((size_t) n);
-        HIP_RC(hipMemcpyAsync(rf.stage.data(), pick, sizeof(double) * (size_t) n, hipMemcpyDeviceToHost, g.stream));
-        HIP_RC(hipStreamSynchronize(g.stream));
-        memcpy(out, rf.stage.data(), sizeof(double) * (size_t) n);
+        const double *pick = loop.keep == HDM_REFINE_KEEP_CURRENT ? f.X : loop.keep == HDM_REFINE_KEEP_PREVIOUS ? f.XP : loop.solves > 0 ? f.X0 : f.X;
+        RC(f.store(pick, out));
         rf.status = loop.status; rf.steps = loop.steps; rf.resid0 = loop.resid0; rf.resid = loop.resid; rf.tol = tol;
         rf.solves += 1; rf.total_steps += loop.solves;
         return HDSDP_RETCODE_OK;
     }
     return HDSDP_RETCODE_FAILED;
 }
+// the dense forms: vectors in the driver's order, the residual of a dense lower triangle (HdmSymRes), corrections through
+// lin_refine_apply; after a give-up of the single-launch substitution the whole solve starts again from the right-hand side
+struct LinRefineDense {
+    MiLin *l;
+    const HdmRefineSource &src;
+    const double *M;
+    long ldm, len;
+    double *B, *X, *XP, *X0, *R, *nrm;
+    int attempts = 2;
+    LinRefineDense(MiLin *l_, const HdmRefineSource &s, const double *M_, long ld) : l(l_), src(s), M(M_), ldm(ld), len(l_->n) {
+        const long npad = l->ch.npad;
+        B = l->rf.v.get(); X = B + npad; XP = B + 2 * npad; X0 = B + 3 * npad; R = B + 4 * npad; nrm = B + 5 * npad;
+    }
+    hdsdp_retcode load(const double *rhs) {
+        HIP_RC(hipMemcpyAsync(B, rhs, sizeof(double) * (size_t) l->n, hipMemcpyHostToDevice, g.stream));
+        return HDSDP_RETCODE_OK;
+    }
+    hdsdp_retcode apply(const double *v, double *x, bool add) { return lin_refine_apply(l, src, v, x, add); }
+    hdsdp_retcode residual() { RC(l->rf.res.run(M, ldm, l->n, X, B, R, nrm, g.stream)); return HDSDP_RETCODE_OK; }
+    bool gave_up() { return !src.pivoted && l->ch.flow_gave_up(); }
+    hdsdp_retcode store(const double *pick, double *out) {
+        std::vector<double> &stage = l->rf.stage;
+        stage.resize((size_t) l->n);
+        HIP_RC(hipMemcpyAsync(stage.data(), pick, sizeof(double) * (size_t) l->n, hipMemcpyDeviceToHost, g.stream));
+        HIP_RC(hipStreamSynchronize(g.stream));
+        memcpy(out, stage.data(), sizeof(double) * (size_t) l->n);
+        return HDSDP_RETCODE_OK;
+    }
+};
+// the tile form: every vector in the tile store's order (HdmBsp::perm_dev applied once on the way in and once on the way out,
+// padded to nb * 128), the residual of the tile store `mat`, corrections through HdmBsp::solve_device.  The level loops have no
+// give-up path.  Shared by the operator's linear system and HMiBspRefinedSolve.
+struct LinRefineTiles {
+    HdmBsp &bs;
+    HdmBspRefine &t;
+    const double *mat;      // the tile store the residual reads
+    long len;
+    double *B, *X, *XP, *X0, *R, *T, *nrm;
+    int attempts = 1;
+    LinRefineTiles(HdmBsp &bs_, HdmBspRefine &t_, const double *store_) : bs(bs_), t(t_), mat(store_), len(t_.len) {
+        B = t.vec(0); X = t.vec(1); XP = t.vec(2); X0 = t.vec(3); R = t.vec(4); T = t.vec(5); nrm = t.vec(6);
+    }
+    hdsdp_retcode load(const double *rhs) {
+        HIP_RC(hipMemsetAsync(B, 0, sizeof(double) * (size_t) len, g.stream));
+        HIP_RC(hipMemcpyAsync(T, rhs, sizeof(double) * (size_t) bs.m, hipMemcpyHostToDevice, g.stream));
+        RC(hdm_refine_scatter(B, T, bs.perm_dev.get(), bs.m, g.stream));
+        return HDSDP_RETCODE_OK;
+    }
+    hdsdp_retcode apply(const double *v, double *x, bool add) { RC(t.apply(bs, v, x, add, g.stream)); return HDSDP_RETCODE_OK; }
+    hdsdp_retcode residual() { RC(t.residual(mat, X, B, R, nrm, g.stream)); return HDSDP_RETCODE_OK; }
+    bool gave_up() { return false; }
+    hdsdp_retcode store(const double *pick, double *out) {
+        RC(hdm_refine_gather(T, pick, bs.perm_dev.get(), bs.m, 0, g.stream));
+        t.stage.resize((size_t) bs.m);
+        HIP_RC(hipMemcpyAsync(t.stage.data(), T, sizeof(double) * (size_t) bs.m, hipMemcpyDeviceToHost, g.stream));
+        HIP_RC(hipStreamSynchronize(g.stream));
+        memcpy(out, t.stage.data(), sizeof(double) * (size_t) bs.m);
+        return HDSDP_RETCODE_OK;
+    }
+};
 // nRhs columns one after another; false in *refined: the state has no matrix for the residual and the solve runs as it always did
 static hdsdp_retcode lin_solve_refined(MiLin *l, int nRhs, double *rhs, double *sol, bool *refined) {
     *refined = false;
     if (l->st->refine() == 0) { l->rf.unrefined(HDM_REFINE_OFF); return HDSDP_RETCODE_OK; }
     const HdmRefineSource src = hdm_kkt_refine_source(*l->st);
+    if (l->bsp) {
+        const bool tiles = src.matrix == HDM_REFINE_MAT_TILES_M || src.matrix == HDM_REFINE_MAT_TILES_COPY;
+        const double *store = src.matrix == HDM_REFINE_MAT_TILES_M ? l->bsp->Mval.get() : l->rf.tiles.copy.get();
+        if (!tiles || !l->bsp->factored || !store) {
+            l->rf.unrefined(src.matrix == HDM_REFINE_MAT_NONE ? src.why_none : HDM_REFINE_NO_MATRIX);
+            return HDSDP_RETCODE_OK;
+        }
+        if (l->rf.tiles.prepare(*l->bsp)) return HDSDP_RETCODE_MEMORY;
+        *refined = true;
+        LinRefineTiles form(*l->bsp, l->rf.tiles, store);
+        for (int r = 0; r < nRhs; ++r)
+            RC(lin_refine_column(form, l->n, l->st->refine(), l->relTol, l->absTol, rhs + (size_t) r * l->n, (sol ? sol : rhs) + (size_t) r * l->n, l->rf));
+        return HDSDP_RETCODE_OK;
+    }
     const bool factored = src.pivoted ? (l->lu && l->lu->factored) : l->ch.factored;
-    if (src.matrix == HDM_REFINE_MAT_NONE || l->bsp || !factored) {
+    if (src.matrix == HDM_REFINE_MAT_NONE || !factored) {
         l->rf.unrefined(src.matrix == HDM_REFINE_MAT_NONE ? src.why_none : HDM_REFINE_NO_MATRIX);
         return HDSDP_RETCODE_OK;
     }
@@ -263,8 +343,9 @@ static hdsdp_retcode lin_solve_refined(MiLin *l, int nRhs, double *rhs, double *
         HIP_RC(hdm_memcpy_h2d_sync(rf.perm.get(), l->perm.data(), sizeof(int) * (size_t) l->n));
     }
     *refined = true;
+    LinRefineDense form(l, src, M, ldm);
     for (int r = 0; r < nRhs; ++r)
-        RC(lin_solve_refined_column(l, src, M, ldm, rhs + (size_t) r * l->n, (sol ? sol : rhs) + (size_t) r * l->n));
+        RC(lin_refine_column(form, l->n, l->st->refine(), l->relTol, l->absTol, rhs + (size_t) r * l->n, (sol ? sol : rhs) + (size_t) r * l->n, rf));
     return HDSDP_RETCODE_OK;
 }
 

@@ -98,6 +98,8 @@ enum HdmKktStage {       // what HKKTFactorize does to M before the factor objec
     HDM_KKT_STAGE_CSC_TO_M         // zero the device matrix; upload the nnz host values; scatter them into it at (rows, cols)
 };
 enum HdmKktSource { HDM_KKT_SRC_NONE = 0, HDM_KKT_SRC_HOST_M, HDM_KKT_SRC_DEVICE_M };
+// tile form, refined (cap and tile switch on at HKKTFactorize): which tile store held the matrix the factor was made from
+enum HdmKktTileSource { HDM_KKT_TILE_SRC_NONE = 0, HDM_KKT_TILE_SRC_M_STORE, HDM_KKT_TILE_SRC_COPY };
 enum HdmKktLoad {
     HDM_KKT_LOAD_STAGED = 0,   // (done by staging)
     HDM_KKT_LOAD_TILES,        // HdmBsp::load_M: the accumulation store is copied into the factor store
@@ -139,10 +141,20 @@ class HdmKktState {
     HdmKktSource fact_src_ = HDM_KKT_SRC_NONE;   // where the factorised matrix came from
     bool fact_copy_ = false;                     // host source: refinement was on then, so a device copy of the loaded image exists
     bool fact_dev_intact_ = false;               // device source: no build has overwritten the device matrix since
+    // the tile form's refined solve has a switch of its own on top of the cap (HMiLinsysSetRefineTiles)
+    bool refine_tiles_ = false;
+    HdmKktTileSource fact_tile_ = HDM_KKT_TILE_SRC_NONE;   // accumulation store in place (with fact_dev_intact_), or a copy of the factor store
     friend HdmKktLoadPlan hdm_kkt_load_plan(const HdmKktState &);
     friend struct HdmRefineSource hdm_kkt_refine_source(const HdmKktState &);
     void factorised_from(HdmKktSource src) {
         fact_src_ = src; fact_copy_ = (src == HDM_KKT_SRC_HOST_M && refine_ > 0); fact_dev_intact_ = (src == HDM_KKT_SRC_DEVICE_M);
+        fact_tile_ = HDM_KKT_TILE_SRC_NONE;
+    }
+    // tile form: load_M copied the accumulation store (it stays as it is), or staging scattered the host CSC into the factor store
+    void tiles_factorised_from(HdmKktLoad load) {
+        if (form_ != HDM_KKT_TILES || refine_ == 0 || !refine_tiles_) return;
+        fact_tile_ = load == HDM_KKT_LOAD_TILES ? HDM_KKT_TILE_SRC_M_STORE : HDM_KKT_TILE_SRC_COPY;
+        fact_dev_intact_ = (fact_tile_ == HDM_KKT_TILE_SRC_M_STORE);
     }
 
 public:
@@ -153,6 +165,9 @@ public:
     int refine() const { return refine_; }
     // the loaded image of a host matrix is to be copied on the device before it is factorised (asked after commit / host_matrix_given)
     bool refine_wants_copy() const { return fact_src_ == HDM_KKT_SRC_HOST_M && fact_copy_; }
+    bool refine_tiles() const { return refine_tiles_; }
+    // tile form with the mirror on: the scattered factor store is to be copied before HdmBsp::factor overwrites it (asked after commit)
+    bool refine_wants_tile_copy() const { return fact_tile_ == HDM_KKT_TILE_SRC_COPY; }
 
     // Transitions, named for what happened.
     // HKKTInit decided the storage: a fresh device matrix and factor object.  The mirror keeps what it was told.
@@ -181,7 +196,12 @@ public:
     // a host matrix was handed over for factorisation (HFpLinsysNumeric on a linear system that is no operator's)
     void host_matrix_given(const double *A, long ld) { srcHost = A; srcDev = nullptr; srcLd = ld; factorised_from(HDM_KKT_SRC_HOST_M); }
     // refinement was switched (HMiLinsysSetRefine): 0 = off, else the step cap.  What was factorised before keeps what it has.
-    void refine_set(int maxSteps) { refine_ = hdm_refine_clamp(maxSteps); if (refine_ == 0) fact_copy_ = false; }   // (off: the copy is freed)
+    void refine_set(int maxSteps) {
+        refine_ = hdm_refine_clamp(maxSteps);
+        if (refine_ == 0) { fact_copy_ = false; drop_tile_copy(); }   // (off: the copies are freed)
+    }
+    // the tile form's own switch (HMiLinsysSetRefineTiles).  Off: the copy of the factor store is freed
+    void refine_tiles_set(bool on) { refine_tiles_ = on; if (!on) drop_tile_copy(); }
 
     // staging of `plan` is done: record what it made of M and where the factorisation takes it from
     void commit(const HdmKktLoadPlan &plan, const double *Mhost, long ldHost, const double *Mdev, long ldDev) {
@@ -190,7 +210,11 @@ public:
         if (plan.source == HDM_KKT_SRC_HOST_M) { srcHost = Mhost; srcDev = nullptr; srcLd = ldHost; }
         if (plan.source == HDM_KKT_SRC_DEVICE_M) { srcHost = nullptr; srcDev = Mdev; srcLd = ldDev; }
         factorised_from(plan.source);
+        tiles_factorised_from(plan.load);
     }
+
+private:
+    void drop_tile_copy() { if (fact_tile_ == HDM_KKT_TILE_SRC_COPY) fact_tile_ = HDM_KKT_TILE_SRC_NONE; }
 };
 
 // ---- the load rule --------------------------------------------------------------------------
@@ -246,12 +270,21 @@ inline HdmKktLoadPlan hdm_kkt_load_plan(const HdmKktState &st) {
 //  host M (dense with the       | a device copy of the loaded image, taken after    | until the next factorisation; exists only if
 //  mirror on, HFpLinsysNumeric) | the load and before the factorisation             | refinement was on then: else NO_MATRIX
 //  nothing factorised yet       | --                                                | NO_MATRIX
-//  tile form                    | --                                                | NOT_AVAILABLE
+//  tile form, its switch off   | --                                                | NOT_AVAILABLE
+//  tile form, mirror off        | the accumulation store HdmBsp::Mval in place:     | until the next build that is no corrector
+//  (cap and switch on at        | channel folded, regularised -- what load_M copied | build starts (it zeroes the store): then
+//  HKKTFactorize)               |                                                   | NO_MATRIX
+//  tile form, mirror on         | a device copy of the factor store (ntiles tiles), | until the next factorisation; exists only if
+//  (cap and switch on then)     | taken after the scatter and before the            | cap and switch were on then: else NO_MATRIX;
+//                               | factorisation overwrites it                       | freed when either goes off
 //
+// The tile form is refined only when the step cap AND its own switch (HMiLinsysSetRefineTiles / HDSDP_MI355X_REFINE_TILES) are on:
+// with the cap alone the answer stays NOT_AVAILABLE and nothing is recorded or allocated.  Its loop runs in the tile store's own
+// (permuted, padded) order, so nothing is permuted per step.
 // Permuted CSC: the factor holds P M P', the residual's matrix is in the driver's order: right-hand sides and corrections are
 // permuted on the device (permute).  Once switched to the pivoted solver the factor is of the recorded source in the driver's
 // order: corrections are the pivoted solver's (pivoted), nothing is permuted.
-enum HdmRefineMatrix { HDM_REFINE_MAT_NONE = 0, HDM_REFINE_MAT_DEVICE_M, HDM_REFINE_MAT_COPY };
+enum HdmRefineMatrix { HDM_REFINE_MAT_NONE = 0, HDM_REFINE_MAT_DEVICE_M, HDM_REFINE_MAT_COPY, HDM_REFINE_MAT_TILES_M, HDM_REFINE_MAT_TILES_COPY };
 struct HdmRefineSource {
     HdmRefineMatrix matrix = HDM_REFINE_MAT_NONE;
     HdmRefineStatus why_none = HDM_REFINE_OFF;     // matrix == NONE: the status of the (unrefined) solve
@@ -260,7 +293,15 @@ struct HdmRefineSource {
 inline HdmRefineSource hdm_kkt_refine_source(const HdmKktState &st) {
     HdmRefineSource r;
     if (st.refine_ == 0) return r;
-    if (st.form_ == HDM_KKT_TILES) { r.why_none = HDM_REFINE_NOT_AVAILABLE; return r; }
+    if (st.form_ == HDM_KKT_TILES) {
+        if (!st.refine_tiles_) { r.why_none = HDM_REFINE_NOT_AVAILABLE; return r; }
+        r.why_none = HDM_REFINE_NO_MATRIX;
+        if (st.fact_tile_ == HDM_KKT_TILE_SRC_M_STORE && st.fact_dev_intact_) r.matrix = HDM_REFINE_MAT_TILES_M;
+        else if (st.fact_tile_ == HDM_KKT_TILE_SRC_COPY) r.matrix = HDM_REFINE_MAT_TILES_COPY;
+        else return r;
+        r.why_none = HDM_REFINE_OFF;
+        return r;
+    }
     r.why_none = HDM_REFINE_NO_MATRIX;
     if (st.fact_src_ == HDM_KKT_SRC_DEVICE_M && st.fact_dev_intact_) r.matrix = HDM_REFINE_MAT_DEVICE_M;
     else if (st.fact_src_ == HDM_KKT_SRC_HOST_M && st.fact_copy_) r.matrix = HDM_REFINE_MAT_COPY;

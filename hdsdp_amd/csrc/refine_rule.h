@@ -22,7 +22,7 @@ enum HdmRefineStatus {
     HDM_REFINE_MAXSTEPS,
     HDM_REFINE_NUMERICAL,
     HDM_REFINE_NO_MATRIX,       // the factorised matrix is no longer (or was never) at hand: the solve ran unrefined
-    HDM_REFINE_NOT_AVAILABLE    // the storage form has no refined solve (tile form): the solve ran unrefined
+    HDM_REFINE_NOT_AVAILABLE    // the storage form's refined solve is not switched on (tile form, kkt_store.h): the solve ran unrefined
 };
 
 constexpr int HDM_REFINE_STEP_CAP = 8;

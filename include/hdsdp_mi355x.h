@@ -205,17 +205,27 @@ void HFpLinsysDestroy(hdsdp_linsys_fp **HLin);                                  
  *   status   0 OFF  1 CONVERGED  2 STAGNATED (the residual did not halve: the iterate with the smaller residual went back)
  *            3 MAXSTEPS  4 NUMERICAL (a residual was not finite: the unrefined solution went back)  5 NO_MATRIX (the factorised
  *            matrix is not at hand -- refinement was off when it was factorised, or a later build has overwritten the device
- *            matrix: the solve ran unrefined)  6 NOT_AVAILABLE (the tile form of a sparse operator: the solve ran unrefined)
+ *            matrix: the solve ran unrefined)  6 NOT_AVAILABLE (the tile form of a sparse operator without its own switch, below: the solve ran unrefined)
  *   steps    corrections in the solution that went back;  resid0, resid: |b - M x|_2 before and after;  tol: as above
  *   solves, totalSteps: refined right-hand sides and correction solves since the object was created
  * Stopping short of tol is a status, not a failure: nothing switches solvers.  FSolve / BSolve are not refined.
  * HMiLinsysRefineBytes: device memory the refined solve holds for this object (0 while it is off).
- * HMiKKTSetRefine: the same switch on the operator's linear system (kktM). */
+ * HMiKKTSetRefine: the same switch on the operator's linear system (kktM).
+ * The TILE form of a sparse operator (HMiKKTTileInfo) has a switch of its own on top of the cap: HMiLinsysSetRefineTiles /
+ * HMiKKTSetRefineTiles(.., 1).  With the cap on and this switch off (the default) a tile operator answers NOT_AVAILABLE, solves
+ * unrefined and holds no memory, as before; with both on BEFORE HKKTFactorize its solves are refined by the same loop, the
+ * residual formed from the tile store (the accumulation store in place with the host mirror off -- valid until the next build
+ * zeroes it, then NO_MATRIX -- or, with the mirror on, a device copy of the scattered factor store taken before the
+ * factorisation).  Switching it off frees what it allocated (HMiLinsysRefineBytes counts it).  HMiLinsysGetRefineTiles: 1 on,
+ * 0 off, -1 for a bad handle. */
 int HMiLinsysSetRefine(hdsdp_linsys_fp *HLin, int maxSteps);
 int HMiLinsysGetRefine(hdsdp_linsys_fp *HLin, int *status, int *steps, double *resid0, double *resid, double *tol, int64_t *solves,
                        int64_t *totalSteps);
 int64_t HMiLinsysRefineBytes(hdsdp_linsys_fp *HLin);
 int HMiKKTSetRefine(hdsdp_kkt *HKKT, int maxSteps);
+int HMiLinsysSetRefineTiles(hdsdp_linsys_fp *HLin, int on);
+int HMiLinsysGetRefineTiles(hdsdp_linsys_fp *HLin);
+int HMiKKTSetRefineTiles(hdsdp_kkt *HKKT, int on);
 
 /* ==========  MI355X SDP cone: the reference's cone slots that feed the Schur path  ==========
  * HMiConeCreateSDP    = HUserDataSetConeData + HConeCreate/SetData/ProcData/PresolveData for one
@@ -580,6 +590,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           small SDP cones of an operator in three launches)
  *  HDSDP_MI355X_REFINE           0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on
  *                                           steps (HMiKKTSetRefine)
+ *  HDSDP_MI355X_REFINE_TILES     0         1: HKKTInit turns the tile form's refined solve on as well    test_gpu_refine_tiles.py::test_the_environment_switches_refine_a_tile_operator
+ *                                           (HMiKKTSetRefineTiles; needs HDSDP_MI355X_REFINE=k too)
  *  -- the next six are the work plan's knobs: all read in csrc/work_plan.h (hdm_knobs_from_env), per allocation; HMiWorkPlanQuery sees them too --
  *  HDM_TCAP_GIB                   32        GiB of congruence intermediates per launch group              test_gpu_switches.py, test_gpu_group.py
  *  HDM_BC                         1024      constraints per congruence launch (upper bound)               test_gpu_switches.py
@@ -725,6 +737,24 @@ int HMiBspSymbolic(int m, const int *colBeg, const int *rowIdx, double maxFracti
    precision and rounded once.  Mlower: ld x n column-major, lower triangle valid; it is uploaded exactly as given and nothing above
    the diagonal or in rows >= n is read.  Deterministic: two calls give the same bits. */
 int HMiSymResidualProbe(int n, const double *Mlower, long ld, const double *x, const double *b, double *r, double *norm2);
+/* the tile form's residual kernel on a host matrix (lower-triangular CSC, diagonal entry first in every column; the pattern must
+   take the tile form: m > 128): r = b - M x and |r|_2^2 in twice the working precision, vectors in the caller's order.  The
+   padding rows and columns of the tile store and its spare tile are filled with NaN first: nothing of them may be read. */
+int HMiTileResidualProbe(int m, const int *colBeg, const int *rowIdx, const double *val, const double *x, const double *b, double *r,
+                         double *norm2);
+/* HMiBspSolve's factorisation followed by the production refined solve of the tile form (at most maxSteps corrections, tolerances
+   as HFpLinsysSetParam takes them).  *info = 0 or first zero pivot + 1 (then nothing is solved); status, steps, resid0, resid, tol
+   as HMiLinsysGetRefine; stats[0..3] = block rows, tiles stored, levels, negative pivots.  Every output but x may be NULL. */
+int HMiBspRefinedSolve(int m, const int *colBeg, const int *rowIdx, const double *val, const double *b, double *x, int maxSteps, double relTol,
+                       double absTol, int *info, int *status, int *steps, double *resid0, double *resid, double *tol, int *stats);
+/* what that refined solve costs beside the unrefined one: ONE factorisation, then nVariants variants alternate solve by solve for
+   warmup + reps rounds, host clock around each solve (each ends in a stream synchronisation).  caps[v] < 0: the unrefined solve
+   (HMiBspSolve's); otherwise the refined solve with that step cap under relTols[v] / absTols[v].  ms[v * reps + r] milliseconds;
+   corrections[v] = correction solves over the timed rounds; status[v], resid[2 v] = |r_0| and resid[2 v + 1] = |r| of the last
+   solve; stats as HMiBspSolve; *workBytes = device memory the refined solve allocated.  Outputs after ms may be NULL. */
+int HMiBspRefineTimingProbe(int m, const int *colBeg, const int *rowIdx, const double *val, const double *b, int nVariants, const int *caps,
+                            const double *relTols, const double *absTols, int warmup, int reps, double *ms, int *corrections, int *status,
+                            double *resid, int *stats, int64_t *workBytes);
 int HMiCholEnvelopeProbe(int n, int band, int reps, double *ms_dense, double *ms_env);   /* factorisation time of a block-banded matrix, dense vs on its envelope */
 double HMiDiagBlockProbe(int variant, int reps);   /* us per 128 x 128 diagonal-block kernel of the Cholesky (0: LDS panels, 1: register sweep) */
 double HMiMfmaPeakProbe(int iters);    /* measured fp64 MFMA TFLOP/s of a register-only loop */
