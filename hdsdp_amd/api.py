@@ -41,6 +41,7 @@ EXPORTS = [
     "HMiMfmaPeakProbe", "HMiDiagBlockProbe", "HMiCholEnvelopeSolve", "HMiCholEnvelopeProbe", "HMiKKTEnvelopeInfo", "HMiKKTTileInfo", "HMiKKTNegativePivots", "HMiBspSolve", "HMiBspSymbolic", "HMiRcmOrder", "HMiSetKernelTiming", "HMiGetKernelTiming", "HMiGetKernelTimingEx", "HMiPresolveCSC", "HMiMfmaIssueProbe", "HMiSetDebugBuffer",
     "HMiGemmRoleLayout", "HMiGemmRoleSpan", "HMiCongStep1", "HMiCongStep2", "HMiCongIRow", "HMiGramSplits", "HMiGramGathered", "HMiGramLp",
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
+    "HMiKKTSetGroupedCheck", "HMiKKTGetGroupedCheck", "HMiKKTCheckIsInterior",
     "HMiLinsysSetRefine", "HMiLinsysGetRefine", "HMiLinsysRefineBytes", "HMiKKTSetRefine", "HMiSymResidualProbe",
     "HMiLinsysSetRefineTiles", "HMiLinsysGetRefineTiles", "HMiKKTSetRefineTiles", "HMiTileResidualProbe", "HMiBspRefinedSolve", "HMiBspRefineTimingProbe",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
@@ -299,6 +300,9 @@ def load_library():
         "HMiConeGetWorkPlan": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "HMiKKTSetGroupedBuild": (C.c_int, [kp, C.c_int]),
         "HMiKKTGetGroupedBuild": (C.c_int, [kp, ip, ip, ip]),
+        "HMiKKTSetGroupedCheck": (C.c_int, [kp, C.c_int]),
+        "HMiKKTGetGroupedCheck": (C.c_int, [kp, C.POINTER(C.c_long)]),
+        "HMiKKTCheckIsInterior": (C.c_int, [kp, C.c_double, dp, ip, dp, ip]),
         "HMiLinsysSetRefine": (C.c_int, [vp, C.c_int]),
         "HMiLinsysGetRefine": (C.c_int, [vp, ip, ip, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "HMiLinsysRefineBytes": (C.c_int64, [vp]),
@@ -1057,6 +1061,31 @@ class KKT:
         c, j, l = C.c_int(0), C.c_int(0), C.c_int(0)
         load_library().HMiKKTGetGroupedBuild(self._k, C.byref(c), C.byref(j), C.byref(l))
         return {"cones": c.value, "jobs": j.value, "launches": l.value}
+
+    def set_grouped_check(self, on):
+        """HMiKKTSetGroupedCheck: a point question (check_is_interior, log_barrier with y) put to one member of the operator's
+        check set puts every member at that point in one launch (csrc/small_check_rule.h has the rule); returns the number of
+        members (0: off, or fewer than two members)"""
+        return int(load_library().HMiKKTSetGroupedCheck(self._k, 1 if on else 0))
+
+    def grouped_check_info(self):
+        """HMiKKTGetGroupedCheck: dict(on, members, launches, last_cones, total_cones, from_state, left_out)"""
+        out = (C.c_long * 6)()
+        on = load_library().HMiKKTGetGroupedCheck(self._k, out)
+        return {"on": bool(on), "members": out[0], "launches": out[1], "last_cones": out[2], "total_cones": out[3],
+                "from_state": out[4], "left_out": out[5]}
+
+    def check_is_interior(self, tau, y):
+        """HMiKKTCheckIsInterior: every cone of the operator at (tau, y), in order and without early exit; returns
+        (flags, logdets, all): logdets[k] is NaN where flags[k] is False"""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        n = len(self.cones)
+        flags = np.zeros(n, dtype=np.int32)
+        logdets = np.full(n, np.nan)
+        every = C.c_int(0)
+        _check(load_library().HMiKKTCheckIsInterior(self._k, float(tau), _dptr(y), _iptr(flags), _dptr(logdets), C.byref(every)),
+               "HMiKKTCheckIsInterior")
+        return flags.astype(bool), logdets, bool(every.value)
 
     def diag_target(self):
         """HMiKKTGetDiagTarget: 0 = kktDiag[] points into kktMatElem, 1 = into the diagonal channel"""

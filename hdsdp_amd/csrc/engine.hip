@@ -138,6 +138,7 @@ int ensure_ctx() {
 namespace {
 #include "engine_build_small.h"
 #include "engine_grouped.h"
+#include "engine_check_set.h"
 }  // namespace
 
 // =============================================================================================

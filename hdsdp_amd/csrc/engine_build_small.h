@@ -123,6 +123,7 @@ hdsdp_retcode build_sparse_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int ty
 void cone_destroy_data(void **pcd) {
     if (!pcd || !*pcd) return;
     MiCone *c = (MiCone *) *pcd;
+    check_set_forget(c);
     HFpLinsysDestroy(&c->dualFactor);
     for (hipEvent_t e : c->piece_ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->pe_s2) if (e) (void) hipEventDestroy(e);

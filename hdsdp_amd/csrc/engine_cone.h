@@ -7,6 +7,7 @@
 enum { PATH_GEMM = 0, PATH_R1 = 1, PATH_SPARSE = 2 };
 
 struct MiKKTPriv;
+struct MiCheckSet;
 
 struct MiCone {
     int n = 0, m = 0;          // block dimension, global number of constraints
@@ -134,6 +135,10 @@ struct MiCone {
     // from which cone_assemble answers a request on the line through them without a sweep.  Every writer of S, dS or the
     // dual factor object names what it did through one of this object's transitions.
     HdmDualState dual;
+    // the check set this cone is a member of (engine_check_set.h), and its place there; not owned.  Set by the operator's
+    // HKKTInit, cleared by the set (HKKTInit again, HKKTClear) and by this cone's destruction, whichever comes first.
+    MiCheckSet *chk_set = nullptr;
+    int chk_slot = -1;
     // fused single-launch Phase-A pass of a small rank-one block (small.hip): factors as a CSR, built on first use
     struct SmallPlan {
         int state = 0;         // 0 = not looked at, 1 = ready, -1 = not eligible
@@ -166,8 +171,31 @@ struct MiGrouped {
     bool used() const { return on && plan.used(); }
 };
 
+// The check set of an operator (engine_check_set.h performs it): the small SDP cones whose point questions
+// on the dual buffer -- "interior at (tau, y)?", "log det S at (tau, y)" -- are answered for ALL of them by one launch of
+// hdm_grouped_check_kernel the first time one of them is asked at a new point.  HKKTInit decides membership (small_check_rule.h:
+// the cones whose own one-launch check would run); the switch allocates the table, and turning it off frees it.
+struct MiCheckSet {
+    bool on = false;                       // HMiKKTSetGroupedCheck / HDSDP_MI355X_GROUPED_CHECK
+    std::vector<MiCone *> members;         // in cones[] order; nullptr: destroyed since HKKTInit (not owned)
+    HdmPinned<HdmSmallCheckArgs> table;    // mapped pinned, one entry per member: the launch's arguments, launched members first
+    std::vector<int> launched;             // slots of the members in the launch being made
+    // HMiKKTGetGroupedCheck: launches, cones in the last one, cones launched in all, per-cone calls answered from state since
+    // the switch went on, members left out of the last launch because they already stood at the point
+    long launches = 0, last_cones = 0, total_cones = 0, from_state = 0, last_left_out = 0;
+    int count() const { int k = 0; for (const MiCone *c : members) k += c ? 1 : 0; return k; }
+    void release() {                       // the members are free again (for another operator's set)
+        for (MiCone *c : members) if (c) { c->chk_set = nullptr; c->chk_slot = -1; }
+        members.clear();
+        table.reset();
+        on = false;
+    }
+    ~MiCheckSet() { release(); }
+};
+
 struct MiKKTPriv {
     MiGrouped grp;
+    MiCheckSet chk;
     // how M is stored, what state it is in and where the last factorised matrix came from (kkt_store.h); the operator's linear
     // system (MiLin::st) points here
     HdmKktState st;
@@ -472,34 +500,50 @@ hdsdp_retcode cone_checker(MiCone *c, HdmChol **out);
 // same point asked for again -- the reference's line search asks "interior?" and then for the barrier at the point it has just
 // checked -- is answered from what the factor object holds, with no device work at all.
 // Returns 0 when it has answered (*isPsd set), 1 when the block is not eligible (the caller takes the call-by-call route).
-int cone_small_check(MiCone *c, double tau, const double *y_host, const double *eye_override, int whichBuffer, int *isPsd, hdsdp_retcode *rc) {
+// The pieces are shared with the grouped form (engine_check_set.h), which puts every member of an operator's check set at the
+// asked point in one launch: the rule, the point (gathered into the cone's own mapped block), the launch's arguments, and
+// what a report word means for the factor object and the dual state.
+bool small_check_switch() {
     static const bool on = [] { const char *e = getenv("HDSDP_MI355X_SMALL_CHECK"); return !(e && atoi(e) == 0); }();
-    *rc = HDSDP_RETCODE_OK;
-    // (a single workgroup walks the resident constraint data: up to 1 MB of it in general, 4 MB for blocks of dimension <= 64,
-    // where the call-by-call assembly's few workgroups are latency-bound themselves -- theta1: 0.45 ms per check)
-    const long resident = (long) c->mloc * c->n16 * c->n16;
-    if (!on || c->world != 1 || !c->Afull.get() || c->n16 > SMALL_P || resident > ((c->n16 <= 64) ? (1L << 19) : (1L << 17))) return 1;
-    HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
-    if (whichBuffer != 0) { if (cone_checker(c, &ch) != HDSDP_RETCODE_OK) return 1; }
-    if (ch->npad != SMALL_P || ch->nblk != 1) return 1;
-    if (!c->chk) {
-        if (c->chk.alloc((size_t) (c->mloc + 4), hipHostMallocMapped) != hipSuccess) { (void) hipGetLastError(); return 1; }
-    }
+    return on;
+}
+// the cone as small_check_rule.h sees it; `ch`: the factor object the launch would write (nullptr: the block's own part only)
+HdmSmallCheckCone small_check_desc(const MiCone *c, const HdmChol *ch) {
+    HdmSmallCheckCone d;
+    d.on = small_check_switch(); d.world = c->world; d.resident = c->Afull.get() != nullptr; d.n16 = c->n16; d.mloc = c->mloc;
+    if (ch) { d.fac_npad = ch->npad; d.fac_nblk = ch->nblk; }
+    return d;
+}
+// the cone's mapped block (y[mloc], then info and log det), made on first use
+int small_check_block(MiCone *c) {
+    if (c->chk) return 0;
+    if (c->chk.alloc((size_t) (c->mloc + 4), hipHostMallocMapped) != hipSuccess) { (void) hipGetLastError(); return 1; }
+    return 0;
+}
+// the point (tau, eye, y gathered through own[] into the cone's block)
+HdmDualPoint small_check_point(MiCone *c, double tau, const double *y_host, double eye) {
     double *yo = c->chk.get();
     for (int q = 0; q < c->mloc; ++q) yo[q] = y_host ? y_host[c->own[q]] : 0.0;
     HdmDualPoint p;
-    p.tau = tau; p.eye = eye_override ? *eye_override : cone_eye(c); p.y = yo; p.ny = c->mloc;
-    if (whichBuffer == 0 && c->dual.S_factored_at(p, isPsd)) return 0;       // S = T(p) and its factor are in place
+    p.tau = tau; p.eye = eye; p.y = yo; p.ny = c->mloc;
+    return p;
+}
+// the launch's arguments for the point in the cone's block; the report word is set to -1 ("nothing reported")
+HdmSmallCheckArgs small_check_args(MiCone *c, HdmChol *ch, const HdmDualPoint &p, int whichBuffer) {
     HdmSmallCheckArgs a = {};
     a.n = c->n; a.n16 = c->n16; a.m = c->mloc; a.A = c->Afull.get(); a.astride = c->astride; a.C = c->Cfull.get();
-    a.y = c->chk.dev(); a.tau = tau; a.eye = p.eye;
+    a.y = c->chk.dev(); a.tau = p.tau; a.eye = p.eye;
     a.Sout = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     a.L = ch->L.get(); a.W = ch->Dinv.get(); a.out = c->chk.dev() + c->mloc;
-    yo[c->mloc] = -1.0;
-    if (whichBuffer == 0) c->dual.S_overwritten();   // the launch writes S: what it holds is known again when the launch has reported
-    if (hdm_small_check(a, g.stream) || hipStreamSynchronize(g.stream) != hipSuccess) { *rc = HDSDP_RETCODE_FAILED; return 0; }
+    c->chk.get()[c->mloc] = -1.0;
+    return a;
+}
+// after the synchronisation: the report word into the factor object and the dual state.  Returns info, or -1 when the
+// launch has not reported for this cone (nothing is committed then: a dual buffer stays S_overwritten).
+int small_check_commit(MiCone *c, HdmChol *ch, const HdmDualPoint &p, int whichBuffer) {
+    const double *yo = c->chk.get();
     const int info = (int) yo[c->mloc];
-    if (info < 0) { *rc = HDSDP_RETCODE_FAILED; return 0; }
+    if (info < 0) return -1;
     ch->factored = (info == 0); ch->have_inv = false;
     ch->logdet_ok = (info == 0); ch->logdet_val = yo[c->mloc + 1];
     if (whichBuffer == 0) {
@@ -507,6 +551,37 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
         c->dual.S_assembled_at(p);
         c->dual.S_factored(info == 0);
     }
+    return info;
+}
+// engine_check_set.h: c is a member of an active set and does not stand at (tau, y_host): one launch for every member that
+// does not.  Returns nonzero when the launch could not be made or did not finish.
+int check_set_launch(MiCheckSet *set, double tau, const double *y_host);
+void check_set_forget(MiCone *c);   // c is being destroyed: its set no longer names it
+
+int cone_small_check(MiCone *c, double tau, const double *y_host, const double *eye_override, int whichBuffer, int *isPsd, hdsdp_retcode *rc) {
+    *rc = HDSDP_RETCODE_OK;
+    if (!hdm_small_check_block_ok(small_check_desc(c, nullptr))) return 1;
+    HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
+    if (whichBuffer != 0) { if (cone_checker(c, &ch) != HDSDP_RETCODE_OK) return 1; }
+    if (!hdm_small_check_factor_ok(ch->npad, ch->nblk)) return 1;
+    if (small_check_block(c)) return 1;
+    const bool grouped = whichBuffer == 0 && !eye_override && c->chk_set && c->chk_set->on;
+    HdmDualPoint p = small_check_point(c, tau, y_host, eye_override ? *eye_override : cone_eye(c));
+    if (whichBuffer == 0 && c->dual.S_factored_at(p, isPsd)) {               // S = T(p) and its factor are in place
+        if (grouped) c->chk_set->from_state += 1;
+        return 0;
+    }
+    if (grouped) {
+        // every member of the set is put at this point in one launch; this cone then answers from its state.  A member the
+        // launch has not reported for stays S_overwritten, and the call for that member fails.
+        if (check_set_launch(c->chk_set, tau, y_host) || !c->dual.S_factored_at(p, isPsd)) *rc = HDSDP_RETCODE_FAILED;
+        return 0;
+    }
+    const HdmSmallCheckArgs a = small_check_args(c, ch, p, whichBuffer);
+    if (whichBuffer == 0) c->dual.S_overwritten();   // the launch writes S: what it holds is known again when the launch has reported
+    if (hdm_small_check(a, g.stream) || hipStreamSynchronize(g.stream) != hipSuccess) { *rc = HDSDP_RETCODE_FAILED; return 0; }
+    const int info = small_check_commit(c, ch, p, whichBuffer);
+    if (info < 0) { *rc = HDSDP_RETCODE_FAILED; return 0; }
     if (isPsd) *isPsd = (info == 0);
     return 0;
 }

@@ -418,6 +418,13 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
         const int k = grouped_set(HKKT, pv, 1);
         fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_BUILD=1: %d of %d cone(s) are built in one grouped pass\n", k, nCones);
     }
+    // the check set (engine_check_set.h): membership is decided for every operator, the grouped launch is used when the switch is on
+    check_set_init(HKKT, pv);
+    static const bool grouped_check_env = [] { const char *e = getenv("HDSDP_MI355X_GROUPED_CHECK"); return e && atoi(e) != 0; }();
+    if (grouped_check_env) {
+        const int k = check_set_switch(pv, 1);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_CHECK=1: %d of %d cone(s) answer a point question in one grouped launch\n", k, nCones);
+    }
     // HDSDP_MI355X_REFINE=k: an unchanged driver's Schur solves are refined with at most k steps (HMiKKTSetRefine)
     if (const char *e = getenv("HDSDP_MI355X_REFINE")) {
         if (atoi(e) > 0) {
@@ -754,6 +761,19 @@ int HMiKKTGetGroupedBuild(hdsdp_kkt *HKKT, int *cones, int *jobs, int *launches)
     if (jobs) *jobs = gr.last_jobs;
     if (launches) *launches = gr.last_launches;
     return gr.last_cones > 0 ? 1 : 0;
+}
+int HMiKKTSetGroupedCheck(hdsdp_kkt *HKKT, int on) { return check_set_switch(priv_of(HKKT), on); }
+int HMiKKTGetGroupedCheck(hdsdp_kkt *HKKT, long out[6]) {
+    const MiCheckSet &cs = priv_of(HKKT)->chk;
+    if (out) {
+        out[0] = cs.count(); out[1] = cs.launches; out[2] = cs.last_cones; out[3] = cs.total_cones;
+        out[4] = cs.from_state; out[5] = cs.last_left_out;
+    }
+    return cs.on ? 1 : 0;
+}
+hdsdp_retcode HMiKKTCheckIsInterior(hdsdp_kkt *HKKT, double tau, const double *y, int *flags, double *logdets, int *all) {
+    if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
+    return check_all_cones(HKKT, tau, y, flags, logdets, all);
 }
 int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
     MiKKTPriv *pv = priv_of(HKKT);

@@ -3,8 +3,10 @@
 #include "hdm_common.h"
 #include "bsparse.h"
 #include "grouped_plan.h"
+#include "small_check_rule.h"
 
 #define SMALL_P 128       // padded dimension: n, m <= 128
+static_assert(SMALL_P == HDM_SMALL_CHECK_P, "small_check_rule.h states the sweep's padded dimension");
 #define SMALL_SPMAX 8      // a rank-one factor with more entries than this is treated as dense
 #define SMALL_NDENSE 4     // at most this many dense factors per block
 
@@ -44,6 +46,10 @@ struct HdmSmallCheckArgs {
     double *out;                        // [0] info (0, or first non-positive pivot + 1), [1] log det S
 };
 int hdm_small_check(const HdmSmallCheckArgs &args, hipStream_t s);
+// The grouped form (hdm_grouped_check_kernel): ONE launch of `count` independent workgroups, workgroup b running the same body
+// on table[b]; the dynamic LDS is sized for max_m, the largest m of the table.  The table is a mapped pinned block: the checks
+// hdm_small_check makes on its argument are made on every entry through the host's address, the kernel reads the device's.
+int hdm_grouped_check(const HdmSmallCheckArgs *table_host, const HdmSmallCheckArgs *table_dev, int count, int max_m, hipStream_t s);
 
 size_t hdm_small_lds_bytes();
 int hdm_small_phase_a(const HdmSmallArgs &args, hipStream_t s);

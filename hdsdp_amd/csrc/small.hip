@@ -329,8 +329,9 @@ __global__ __launch_bounds__(SM_T) void hdm_small_phase_a_kernel(HdmSmallArgs p)
 }
 
 // ---- interior check of a small block in one launch (see small.h) ------------------------------------------------------
-__global__ __launch_bounds__(SM_T) void hdm_small_check_kernel(HdmSmallCheckArgs p) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
+// The body: one workgroup, one block.  It reads its arguments and the block's data, writes the block's S, L, W and report words
+// and nothing else; `sm` is the workgroup's dynamic LDS (128 x 129 + 128 + m doubles).
+__device__ __forceinline__ void sm_check_body(const HdmSmallCheckArgs &p, double *sm) {
     constexpr int ld = SMALL_P + 1;
     double *Xl = sm;                                   // S, full symmetric: 128 x 129 (its head: the sweep's block images)
     double *rsv = sm + (long) SMALL_P * ld;            // 128 deferred scale factors
@@ -377,18 +378,53 @@ __global__ __launch_bounds__(SM_T) void hdm_small_check_kernel(HdmSmallCheckArgs
     sm_store_factor(n, a, rr, Xl, p.L, p.W, ty, tx, tid);
 }
 
+__global__ __launch_bounds__(SM_T) void hdm_small_check_kernel(HdmSmallCheckArgs p) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    sm_check_body(p, sm);
+}
+
+// The grouped form: workgroup b runs the same body on table[b].  The workgroups are independent: none waits for another, none
+// reads a word another writes, and any number of them may be resident at a time.
+__global__ __launch_bounds__(SM_T) void hdm_grouped_check_kernel(const HdmSmallCheckArgs *__restrict__ table, int count) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int) blockIdx.x >= count) return;
+    const HdmSmallCheckArgs p = table[blockIdx.x];
+    sm_check_body(p, sm);
+}
+
+static bool sm_check_args_ok(const HdmSmallCheckArgs &a) {
+    return !(a.n < 1 || a.n > SMALL_P || a.n16 > SMALL_P || a.m < 0 || a.m > 4096) && hdm_small_check_lds_bytes(a.m) <= HDM_SMALL_CHECK_LDS_MAX;
+}
+
 int hdm_small_check(const HdmSmallCheckArgs &args, hipStream_t s) {
-    if (args.n < 1 || args.n > SMALL_P || args.n16 > SMALL_P || args.m < 0 || args.m > 4096) return 1;
-    const size_t lds = sizeof(double) * ((size_t) SMALL_P * (SMALL_P + 1) + SMALL_P + (size_t) std::max(1, args.m));
-    if (lds > 160 * 1024) return 1;
+    if (!sm_check_args_ok(args)) return 1;
+    const size_t lds = (size_t) hdm_small_check_lds_bytes(args.m);
     static thread_local int configured_dev = -1;
     int dev = 0;
     HDM_HIP_CHECK(hipGetDevice(&dev));
     if (configured_dev != dev) {
-        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_small_check_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_small_check_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) HDM_SMALL_CHECK_LDS_MAX));
         configured_dev = dev;
     }
     hipLaunchKernelGGL(hdm_small_check_kernel, dim3(1), dim3(SM_T), lds, s, args);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int hdm_grouped_check(const HdmSmallCheckArgs *table_host, const HdmSmallCheckArgs *table_dev, int count, int max_m, hipStream_t s) {
+    if (!table_host || !table_dev || count < 1) return 1;
+    for (int k = 0; k < count; ++k)
+        if (!sm_check_args_ok(table_host[k]) || table_host[k].m > max_m) return 1;
+    if (max_m < 0 || max_m > 4096 || hdm_small_check_lds_bytes(max_m) > HDM_SMALL_CHECK_LDS_MAX) return 1;
+    const size_t lds = (size_t) hdm_small_check_lds_bytes(max_m);
+    static thread_local int configured_dev = -1;
+    int dev = 0;
+    HDM_HIP_CHECK(hipGetDevice(&dev));
+    if (configured_dev != dev) {
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_grouped_check_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) HDM_SMALL_CHECK_LDS_MAX));
+        configured_dev = dev;
+    }
+    hipLaunchKernelGGL(hdm_grouped_check_kernel, dim3((unsigned) count), dim3(SM_T), lds, s, table_dev, count);
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

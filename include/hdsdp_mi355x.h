@@ -408,6 +408,27 @@ int HMiKKTGetGroupedBuild(hdsdp_kkt *HKKT, int *cones, int *jobs, int *launches)
 int HMiGroupedPlanQuery(int nRow, int nCones, const int *dims, const int *kindOk, const int *rowBeg, const int *rows, int64_t *counts,
                         int *eligible, int *slotOf, int *jobs, int *mRow, int *mCol, int64_t *mPtr, int *mSlot, int *mIdx, int *vRow,
                         int64_t *vPtr, int *vSlot, int *vIdx);
+/* The grouped interior check (csrc/small_check_rule.h, csrc/small.hip, csrc/engine_check_set.h).  The
+ * reference's line search puts every point question -- "interior at (tau, y)?", "log det S at (tau, y)" -- to all cones in a loop
+ * with the same arguments; a small SDP cone answers each in one launch and one synchronisation of its own.  With the switch on,
+ * the first such question put to a member of the operator's check set at a new point puts EVERY member there in one launch
+ * (one workgroup per member, the one-launch check's own body: the same bits), and the loop's later calls are answered from the
+ * members' state with no device work.  Members: the engine SDP cones of cones[] on one device whose own one-launch check would run
+ * (n <= 128, constraint data resident, mloc * n16 * n16 <= 2^19 for n16 <= 64 and <= 2^17 above), not held by another operator's
+ * active set.  Only the dual buffer's point questions group: the expert form, the checker buffer, step-and-check and the ratio test
+ * stay on their own paths.  One difference from the loop: a question put to one member moves every member's dual buffer and dual
+ * factor to that point, also those behind a cone at which the loop breaks.  Off by default.
+ * HMiKKTSetGroupedCheck: after HKKTInit; returns the number of members (0: off, or fewer than two members).
+ * HMiKKTGetGroupedCheck: out[0] members [1] grouped launches since HKKTInit [2] cones in the last launch [3] cones launched in all
+ * [4] per-cone calls answered from state since the switch went on [5] members left out of the last launch because they already
+ * stood at the point; returns 1 if the switch is on, else 0.
+ * HMiKKTCheckIsInterior: the whole-operator question.  Every cone of cones[] in order, without early exit, through its own
+ * coneInteriorCheck and (where interior) coneGetBarrier slots: flags[k], logdets[k] (NaN where flags[k] == 0) and *all (1 if every
+ * cone is interior); any of the three may be NULL.  With the switch off it is the plain loop; with it on the members are
+ * answered by one launch.  Returns the first retcode of a slot that was not OK. */
+int HMiKKTSetGroupedCheck(hdsdp_kkt *HKKT, int on);
+int HMiKKTGetGroupedCheck(hdsdp_kkt *HKKT, long out[6]);
+hdsdp_retcode HMiKKTCheckIsInterior(hdsdp_kkt *HKKT, double tau, const double *y, int *flags, double *logdets, int *all);
 /* multi-GPU (world > 1): constraint rows are sharded (row i on rank i % world).  Each rank congruence-
  * transforms its own rows, a transpose (all-to-all) re-shards the transformed data from "by constraint"
  * to "by packed-index range", each rank forms the Gram partial sum over its range, and an all-reduce
@@ -588,6 +609,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           cones[] is a host cone (diagonal channel); else one stderr line
  *  HDSDP_MI355X_GROUPED_BUILD     0         1: HKKTInit turns the grouped Schur build on (all eligible    test_gpu_grouped_build.py
  *                                           small SDP cones of an operator in three launches)
+ *  HDSDP_MI355X_GROUPED_CHECK     0         1: HKKTInit turns the grouped interior check on (a point      test_gpu_grouped_check.py
+ *                                           question to one small SDP cone answers all in one launch)
  *  HDSDP_MI355X_REFINE           0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on
  *                                           steps (HMiKKTSetRefine)
  *  HDSDP_MI355X_REFINE_TILES     0         1: HKKTInit turns the tile form's refined solve on as well    test_gpu_refine_tiles.py::test_the_environment_switches_refine_a_tile_operator
