@@ -2,7 +2,7 @@
 #include "hdm_common.h"
 
 hipError_t hdm_malloc(void **p, size_t bytes) {
-    static const bool poison = [] { const char *e = getenv("HDM_POISON"); return e && atoi(e) != 0; }();
+    const bool poison = hdm_env_on<ENV_POISON>();
     const hipError_t e = hipMalloc(p, bytes);
     if (e == hipSuccess && poison && bytes) {
         // (hipMemset of device memory may return before the fill has run, and the engine's streams are non-blocking: without

@@ -15,14 +15,6 @@ struct HdmChol {
     bool factored = false, have_inv = false;
     bool logdet_ok = false;  // log det of the factored matrix is known (single-launch small-block check): 2 sum log L_kk
     double logdet_val = 0.0;
-    // The factorisation (3 launches per 128-block) and the block substitutions (2 launches per block) are chains of
-    // short dependent launches with fixed arguments: after one eager run they can be captured into a hipGraph and
-    // replayed (policy and measurements: hdm_graph_level in chol.hip).  A failed capture falls back to eager launches.
-    struct Replay { const void *b = nullptr, *x = nullptr; int nrhs = 0, which = 0; long ldv = 0; hipGraphExec_t exec = nullptr; };
-    hipGraphExec_t factor_graph = nullptr;
-    Replay solves[4];
-    int nsolves = 0, factor_runs = 0, solve_runs = 0;
-    bool graphs_ok = true;
     // single-launch block substitution (hdm_trsv_flow_kernel): per (rhs, direction, block) publication flags + error word
     HdmBuf<int> flow_flags;
     HdmPinned<int> flow_err;     // mapped host word: a workgroup gave up waiting
@@ -42,8 +34,6 @@ struct HdmChol {
 
     int init(int n);
     int set_envelope(const int *first_blockcol_of_blockrow);   // nblk entries; nullptr = dense.  Before the first factor().
-    void destroy();
-    ~HdmChol() { destroy(); }
     int load_host(const double *A, long lda, hipStream_t s);
     int load_device(const double *A, long lda, hipStream_t s);
     int finish_load(hipStream_t s);
@@ -57,8 +47,6 @@ struct HdmChol {
     int reverse_signs(double *sig_dev, hipStream_t s);  // sig[i] = sgn[n - 1 - i] for i < n, +1 in the padding (npad entries)
     int get_diag(double *diag_host, hipStream_t s);
     int solve_device(double *b_dev, double *x_dev, int nrhs, long ldv, int which, hipStream_t s);
-    int enqueue_factor(hipStream_t s);
-    int enqueue_solve(double *b_dev, double *x_dev, int nrhs, long ldv, int which, hipStream_t s);
     int solve_host(const double *rhs, double *sol, int nrhs, int which, hipStream_t s);
     // after the synchronisation that follows solve_device: did a workgroup of the single-launch substitution give up waiting?
     // Then its result is to be thrown away; later solves use per-block launches.  (Reads and clears the give-up word.)

@@ -606,7 +606,6 @@ int HdmChol::init(int n_) {
 int HdmChol::set_envelope(const int *first) {
     env_first.clear(); env_colh.clear();
     env_dev.reset();
-    if (factor_graph) { (void) hipGraphExecDestroy(factor_graph); factor_graph = nullptr; factor_runs = 0; }
     if (!first || nblk <= 1) return 0;
     env_first.assign(first, first + nblk);
     env_colh.assign(nblk, 0);
@@ -624,12 +623,6 @@ int HdmChol::set_envelope(const int *first) {
     HDM_HIP_CHECK(env_dev.alloc(both.size()));
     HDM_HIP_CHECK(hdm_memcpy_h2d_sync(env_dev.get(), both.data(), sizeof(int) * both.size()));
     return 0;
-}
-
-void HdmChol::destroy() {   // the graph-exec handles; the buffers go with their members
-    if (factor_graph) (void) hipGraphExecDestroy(factor_graph);
-    for (int i = 0; i < nsolves; ++i) if (solves[i].exec) (void) hipGraphExecDestroy(solves[i].exec);
-    factor_graph = nullptr; nsolves = 0;
 }
 
 int HdmChol::load_host(const double *A, long lda, hipStream_t s) {
@@ -667,51 +660,6 @@ int HdmChol::set_reverse_inverse(hipStream_t s) {
                        (long) npad, n, npad);
     HDM_HIP_CHECK(hipGetLastError());
     have_inv = true;
-    return 0;
-}
-
-// capture `body` (launches on stream s with fixed arguments) into an executable graph; nullptr if that is not possible
-template <class F> static hipGraphExec_t hdm_capture(hipStream_t s, F body) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void) hipGetLastError(); return nullptr; }
-    hdm_gemm_capture_mode(1);
-    const int rc = body();
-    hdm_gemm_capture_mode(0);
-    const hipError_t e = hipStreamEndCapture(s, &graph);
-    if (rc || e != hipSuccess || !graph) { (void) hipGetLastError(); if (graph) (void) hipGraphDestroy(graph); return nullptr; }
-    if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) { (void) hipGetLastError(); exec = nullptr; }
-    (void) hipGraphDestroy(graph);
-    return exec;
-}
-// HDM_GRAPHS: 0 (default since round 4) = never; 1 = the factorisation chain when it is long enough (>= 4 diagonal blocks);
-// 2 = also the block substitutions.  When replay was introduced (round 1) the chain at n = 2000 went 2.86 -> 2.71 ms; since the
-// diagonal-block kernel halved (round 2) the chain is sixteen dependent 56 us sweeps plus launch-to-launch latency and replay
-// buys nothing (1.859 ms replayed, 1.855 ms eager, n = 4000: 4.006 / 3.975 -- profiles/r04_e_cholesky.txt), the substitutions
-// never gained (no gain at 16 blocks, +8 us per solve at one block), and replay has cost twice: a replayed MEMSET node that wrote
-// stale bytes (profiles/r04_c_poison.txt) and rocprofiler-sdk 7.2 dying in its queue interceptor on multi-packet submissions
-// (profiles/r04_a_headline_segv.txt).  The paths stay (tests run levels 1 and 2).
-static int hdm_graph_level() {
-    static int lvl = -1;
-    if (lvl < 0) { const char *e = getenv("HDM_GRAPHS"); lvl = e ? atoi(e) : 0; }
-    return lvl;
-}
-
-int HdmChol::factor(hipStream_t s, int *info_host) {
-    if (hdm_graph_level() >= 1 && nblk >= 4 && graphs_ok && !factor_graph && factor_runs >= 1) {
-        factor_graph = hdm_capture(s, [&]() { return enqueue_factor(s); });
-        if (!factor_graph) graphs_ok = false;
-    }
-    if (factor_graph) HDM_HIP_CHECK(hipGraphLaunch(factor_graph, s));
-    else if (enqueue_factor(s)) return 1;
-    ++factor_runs;
-    int info = 0;
-    HDM_HIP_CHECK(hipMemcpyAsync(&info, info_dev.get(), sizeof(int), hipMemcpyDeviceToHost, s));
-    HDM_HIP_CHECK(hipStreamSynchronize(s));
-    if (info > n) info = 0;  // failures inside the identity padding cannot happen; be safe
-    if (info_host) *info_host = info;
-    factored = (info == 0);
-    have_inv = false;
     return 0;
 }
 
@@ -806,8 +754,7 @@ static int hdm_k128_launch(bool update, const double *A, long lda, const double 
 // The two GEMMs of a block column of the blocked factorisations: through the K = 128 kernel above where it applies (rows a
 // multiple of 64, a leading dimension its offsets cover, HDM_CHOL_K128 not 0), as the plain product of the GEMM family otherwise.
 static bool hdm_chol_k128(int rows, long ld) {
-    static const bool k128 = [] { const char *e = getenv("HDM_CHOL_K128"); return !(e && atoi(e) == 0); }();
-    return k128 && rows % 64 == 0 && ld < (1L << 20);
+    return hdm_env_on<ENV_CHOL_K128>() && rows % 64 == 0 && ld < (1L << 20);
 }
 // panel product, in place: P <- P * Dinv_k
 static int hdm_chol_panel(double *P, long ld, const double *Dk, int rows, hipStream_t s) {
@@ -822,14 +769,13 @@ static int hdm_chol_update(double *A22, long ld, const double *P, const double *
 
 __global__ void hdm_zero_word_kernel(int *p) { *p = 0; }
 
-int HdmChol::enqueue_factor(hipStream_t s) {
-    // (a kernel, not hipMemsetAsync: this chain is captured into a hipGraph, and under HDM_POISON a replay of the captured
-    // MEMSET node was seen to leave 0xFFFFFFFF in the word -- profiles/r04_c_poison.txt; a kernel node behaves like its neighbours)
+int HdmChol::factor(hipStream_t s, int *info_host) {
+    // (the info word is cleared by a kernel, in stream order like the chain that writes it)
     hipLaunchKernelGGL(hdm_zero_word_kernel, dim3(1), dim3(1), 0, s, info_dev.get());
     HDM_HIP_CHECK(hipGetLastError());   // a launch that did not happen would leave the previous chain's info word in place
     const long ld = npad;
     const size_t shm = (NB * NB + LDW * PB) * sizeof(double);
-    static const bool diag_sweep = [] { const char *e = getenv("HDM_DIAG_SWEEP"); return !(e && atoi(e) == 0); }();
+    const bool diag_sweep = hdm_env_on<ENV_DIAG_SWEEP>();
     for (int k = 0; k < nblk; ++k) {
         double *Akk = L.get() + (long) k * NB * (ld + 1);
         if (diag_sweep)
@@ -847,6 +793,13 @@ int HdmChol::enqueue_factor(hipStream_t s) {
         if (hdm_chol_panel(P, ld, Dinv.get() + (long) k * NB * NB, rows, s)) return 1;
         if (hdm_chol_update(Akk + (long) NB * (ld + 1), ld, P, P, ld, rows, s)) return 1;
     }
+    int info = 0;
+    HDM_HIP_CHECK(hipMemcpyAsync(&info, info_dev.get(), sizeof(int), hipMemcpyDeviceToHost, s));
+    HDM_HIP_CHECK(hipStreamSynchronize(s));
+    if (info > n) info = 0;  // failures inside the identity padding cannot happen; be safe
+    if (info_host) *info_host = info;
+    factored = (info == 0);
+    have_inv = false;
     return 0;
 }
 
@@ -855,7 +808,7 @@ int HdmChol::enqueue_factor(hipStream_t s) {
 // F_kk S_k F_kk^T and inverts F_kk (sweep128.h; S_k = the pivots' signs, F_kk with a positive diagonal); the panel is
 // Q = A_ik inv(F_kk)^T (the same product as the Cholesky panel), F_ik = Q S_k; the trailing update is
 // A22 -= F_ik S_k F_jk^T = F_ik Q^T -- the Cholesky update's product with Q kept aside in Z as its second operand.  Same
-// kernels as enqueue_factor apart from the sweep's flavour and one scaling pass per panel; dense only (no envelope), eager only.
+// kernels as factor apart from the sweep's flavour and one scaling pass per panel; dense only (no envelope).
 int HdmChol::factor_signed(hipStream_t s, int *info_host, int *nneg_host) {
     if (!sgn.get()) {
         HDM_HIP_CHECK(sgn.alloc((size_t) npad));
@@ -964,35 +917,9 @@ int HdmChol::get_diag(double *diag_host, hipStream_t s) {
 static std::atomic<int> g_flow_shared_device{0};
 void hdm_flow_set_shared_device(int on) { g_flow_shared_device.store(on); }
 bool hdm_flow_shared_device() { return g_flow_shared_device.load() != 0; }
-static bool hdm_flow_enabled() {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("HDM_TRSV_FLOW"); on = (e && atoi(e) == 0) ? 0 : 1; }
-    return on == 1 && g_flow_shared_device.load() == 0;
-}
+static bool hdm_flow_enabled() { return hdm_env_on<ENV_TRSV_FLOW>() && g_flow_shared_device.load() == 0; }
 
 int HdmChol::solve_device(double *b_dev, double *x_dev, int nrhs, long ldv, int which, hipStream_t s) {
-    // replay the launch chain of an earlier call with the same buffers when there is one (the C-ABI solves always
-    // come through the object's own scratch vectors, so this is the common case)
-    if (hdm_graph_level() >= 2 && graphs_ok && !(hdm_flow_enabled() && flow_ok)) {   // (a replayed launch would reuse its epoch)
-        Replay *r = nullptr;
-        for (int i = 0; i < nsolves; ++i)
-            if (solves[i].b == b_dev && solves[i].x == x_dev && solves[i].nrhs == nrhs && solves[i].which == which &&
-                solves[i].ldv == ldv) r = &solves[i];
-        if (!r && solve_runs >= 1 && nsolves < 4) {
-            hipGraphExec_t ex = hdm_capture(s, [&]() { return enqueue_solve(b_dev, x_dev, nrhs, ldv, which, s); });
-            if (!ex) graphs_ok = false;
-            else { r = &solves[nsolves++]; r->b = b_dev; r->x = x_dev; r->nrhs = nrhs; r->which = which; r->ldv = ldv; r->exec = ex; }
-        }
-        if (r) {
-            HDM_HIP_CHECK(hipGraphLaunch(r->exec, s));
-            return 0;
-        }
-    }
-    ++solve_runs;
-    return enqueue_solve(b_dev, x_dev, nrhs, ldv, which, s);
-}
-
-int HdmChol::enqueue_solve(double *b_dev, double *x_dev, int nrhs, long ldv, int which, hipStream_t s) {
     // which: 0 = full solve (L L^T x = b), 1 = forward only (L x = b), 2 = backward only (L^T x = b)
     // b_dev is overwritten (workspace); vectors have npad entries (zero padded)
     const long ld = npad;
@@ -1045,9 +972,8 @@ int HdmChol::enqueue_solve(double *b_dev, double *x_dev, int nrhs, long ldv, int
 // HDM_TRSV_FLOW_FAIL_ONCE=1 (tests): the first single-launch substitution of the process is treated as timed out and its
 // result is thrown away, so that the retry below is exercised
 static bool hdm_flow_fail_once() {
-    static int left = -1;
-    if (left < 0) { const char *e = getenv("HDM_TRSV_FLOW_FAIL_ONCE"); left = (e && atoi(e) != 0) ? 1 : 0; }
-    if (left == 1) { left = 0; return true; }
+    static bool left = hdm_env_on<ENV_TRSV_FLOW_FAIL_ONCE>();
+    if (left) { left = false; return true; }
     return false;
 }
 

@@ -3,6 +3,7 @@
 // storage positions the dense rank-one probe reads, where its quicksort leaves ties, which comparisons are strict) the
 // corner is stated where it is implemented.
 #include "coeff.h"
+#include "env_switches.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -15,7 +16,7 @@
 // HDSDP_MI355X_HOST_THREADS, default min(16, hardware threads)
 int mi_host_threads() {
     static const int n = [] {
-        if (const char *e = getenv("HDSDP_MI355X_HOST_THREADS")) return std::max(1, atoi(e));
+        if (const HdmEnvInt e = hdm_env_int<ENV_HOST_THREADS>(); e.set) return std::max(1, (int) e.value);
         const unsigned hw = std::thread::hardware_concurrency();
         return (int) std::max(1u, std::min(16u, hw ? hw : 1u));
     }();

@@ -9,6 +9,7 @@
 // commits it (engine_cone.h: cone_assemble); every other writer of S, dS or the factor names what it did through one of
 // HdmDualState's transitions.  tests/test_dual_state_cpu.py compiles this header alone.
 #pragma once
+#include "env_switches.h"
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -34,15 +35,12 @@ static inline bool hdm_sweep_costs(long mloc, long n) { return mloc * n * (n + 1
 // differ from a sweep's in the last bits (as a sweep's differ from the reference's own summation order).
 // Default: 2 where a sweep costs something, and 1 on small blocks, where the sweep is free and the end game of a badly
 // conditioned instance can turn on the last bits (gpp100 through the reference's driver in mode 2: same dual objective, a primal
-// estimate 3e-4 further away).  HDSDP_MI355X_AFFINE_S=0/1/2 overrides (read once per process).
+// estimate 3e-4 further away).  HDSDP_MI355X_AFFINE_S=0/1/2 overrides (read time: env_switches.h).
 static inline int hdm_dual_mode(long mloc, long n) {
-    static const int env = [] { const char *e = getenv("HDSDP_MI355X_AFFINE_S"); return e ? atoi(e) : -1; }();
+    const int env = hdm_env_int<ENV_AFFINE_S>().value_or(-1);
     return env >= 0 ? env : (hdm_sweep_costs(mloc, n) ? 2 : 1);
 }
-static inline bool hdm_dual_debug() {
-    static const bool on = [] { const char *e = getenv("HDSDP_MI355X_AFFINE_DEBUG"); return e && atoi(e); }();
-    return on;
-}
+static inline bool hdm_dual_debug() { return hdm_env_on<ENV_AFFINE_DEBUG>(); }
 
 // ---- counters -------------------------------------------------------------------------------
 // how a request was answered (HMiGetAssembleCounts and the exit table of engine_stats.h index them in this order)

@@ -85,7 +85,7 @@ std::thread g_preload_thread;
 std::once_flag g_preload_once;
 void preload_join() { if (g_preload_thread.joinable()) g_preload_thread.join(); }
 void preload_modules(int dev) {
-    if (const char *e = getenv("HDSDP_MI355X_PRELOAD")) if (!atoi(e)) return;
+    if (!hdm_env_on<ENV_PRELOAD>()) return;
     std::call_once(g_preload_once, [dev] {
         g_preload_thread = std::thread([dev] {
             if (hipSetDevice(dev) != hipSuccess) return;
@@ -112,15 +112,15 @@ int ctx_open(Ctx &c, int dev) {
 int ensure_ctx() {
     if (g.init) return 0;
     int dev = 0;
-    const char *lr = getenv("LOCAL_RANK");
+    const HdmEnvInt lr = hdm_env_int<ENV_LOCAL_RANK>();
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         fprintf(stderr, "[hdsdp_mi355x] no HIP device visible: this library has no CPU fallback\n");
         return 1;
     }
-    if (lr) dev = atoi(lr) % ndev;
+    if (lr.set) dev = (int) lr.value % ndev;
     if (g_main_device_request >= 0) dev = g_main_device_request % ndev;
-    if (const char *e = getenv("HDSDP_MI355X_CALL_STATS")) if (atoi(e)) atexit(stats_print_at_exit);
+    if (hdm_env_on<ENV_CALL_STATS>()) atexit(stats_print_at_exit);
     return ctx_open(g, dev);
 }
 

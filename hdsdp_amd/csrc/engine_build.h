@@ -57,7 +57,7 @@ int gram_all(MiCone *c) {
 // number of pieces of the piecewise exchange (whole groups of Gram K splits)
 int exchange_pieces(const MiCone *c) {
     int P = (c->a2a_start && c->a2a_wait) ? c->a2a_pieces : 1;
-    if (const char *e = getenv("HDSDP_MI355X_A2A_PIECES")) P = std::max(1, atoi(e));
+    if (const HdmEnvInt e = hdm_env_int<ENV_A2A_PIECES>(); e.set) P = std::max(1, (int) e.value);
     if (!(c->a2a_start && c->a2a_wait)) P = 1;
     while (P > 1 && (c->nsplit % P)) --P;
     return P;
@@ -352,10 +352,7 @@ int primal_signed_factor(MiCone *c, HdmChol &ch, const double *Xr, const double 
     return 0;
 }
 
-static bool primal_signed_enabled() {
-    const char *e = getenv("HDSDP_MI355X_PRIMAL_SIGNED");
-    return !(e && atoi(e) == 0);
-}
+static bool primal_signed_enabled() { return hdm_env_on<ENV_PRIMAL_SIGNED>(); }
 
 // Every shard of a sharded block factors the same replicated X with the same kernels, so all of them must come to the same
 // decision (a shard that went on alone would wait for the others in the exchange).  Checked, not assumed: the sums of
@@ -537,8 +534,7 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
     // owned rows in one launch group and at most 64 tile columns.  HDSDP_MI355X_STAGED_A2A=0: drain, then exchange.
     const int NT = hdm_ntiles(c->n16);
     int P = (c->world > 1) ? exchange_pieces(c) : 1;
-    bool staged = c->world > 1 && P > 1 && P <= 64 && c->mloc <= c->Bc && hdm_colmask_honoured(NT);
-    if (const char *e = getenv("HDSDP_MI355X_STAGED_A2A")) staged = staged && atoi(e) != 0;
+    bool staged = c->world > 1 && P > 1 && P <= 64 && c->mloc <= c->Bc && hdm_colmask_honoured(NT) && hdm_env_on<ENV_STAGED_A2A>();
     c->last_pieces = P; c->last_staged = 0;
     if (c->streamed) {
         // constraint data not resident: a batch is regenerated, transformed, and its buffer reused (stream order keeps the

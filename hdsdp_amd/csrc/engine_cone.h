@@ -402,7 +402,7 @@ bool cone_has_rows(const MiCone *c) { return c->streamed ? c->Abatch.get() != nu
 // of the stored positions are non-zero or the memory is not there (then the sweeps read the dense storage).
 // HDSDP_MI355X_ZS=0: never; 2: any size, any fill.
 int cone_build_zs(MiCone *c) {
-    static const int zs_env = [] { const char *e = getenv("HDSDP_MI355X_ZS"); return e ? atoi(e) : 1; }();
+    const int zs_env = hdm_env_int<ENV_ZS>().value_or(1);
     if (c->zs_state != 0) return 0;
     c->zs_state = -1;
     if (!cone_has_rows(c) || c->mloc <= 0 || !zs_env || !(zs_env >= 2 || hdm_sweep_costs(c->mloc, c->n))) return 0;
@@ -503,10 +503,7 @@ hdsdp_retcode cone_checker(MiCone *c, HdmChol **out);
 // The pieces are shared with the grouped form (engine_check_set.h), which puts every member of an operator's check set at the
 // asked point in one launch: the rule, the point (gathered into the cone's own mapped block), the launch's arguments, and
 // what a report word means for the factor object and the dual state.
-bool small_check_switch() {
-    static const bool on = [] { const char *e = getenv("HDSDP_MI355X_SMALL_CHECK"); return !(e && atoi(e) == 0); }();
-    return on;
-}
+bool small_check_switch() { return hdm_env_on<ENV_SMALL_CHECK>(); }
 // the cone as small_check_rule.h sees it; `ch`: the factor object the launch would write (nullptr: the block's own part only)
 HdmSmallCheckCone small_check_desc(const MiCone *c, const HdmChol *ch) {
     HdmSmallCheckCone d;
@@ -741,7 +738,7 @@ hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *
         if (ok) break;
         step *= 0.9;
     }
-    static const bool dbg = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e); }();
+    const bool dbg = hdm_env_int<ENV_RATIO_DEBUG>().value_or(0) != 0;
     if (dbg) fprintf(stderr, "[hdsdp_mi355x ratio] n %d: step %.6e left the cone, safeguarded to %.6e (fresh start %.6e)\n", c->n,
                      *maxStep, step, fresh);
     *maxStep = ok ? step : 0.0;
@@ -781,7 +778,7 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
         if (c->lanczos->init(c->n)) return HDSDP_RETCODE_MEMORY;
     }
     int steps = 0;
-    static const bool dbg = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e); }();
+    const bool dbg = hdm_env_int<ENV_RATIO_DEBUG>().value_or(0) != 0;
     const auto t0 = std::chrono::steady_clock::now();
     if (c->lanczos->solve(fac->Linv.get(), fac->npad, c->dS.get(), c->n16, g.stream, maxStep, &steps)) return HDSDP_RETCODE_FAILED;
     if (dbg) fprintf(stderr, "[hdsdp_mi355x ratio] n %d: %d Lanczos steps, step %.6e, solve %.1f us\n", c->n, steps, *maxStep,
@@ -1055,7 +1052,7 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
     int info = 0;
     if (ch.load_device(c->Scheck.get(), c->n16, g.stream) || ch.factor(g.stream, &info)) return fail("factorisation failed");
     if (info != 0) {
-        if (stat_trace()) fprintf(stderr, "[hdsdp_mi355x trace]     primal recovery: factorisation stopped at pivot %d (runs %d, graph %d)\n", info, ch.factor_runs, ch.factor_graph ? 1 : 0);
+        if (stat_trace()) fprintf(stderr, "[hdsdp_mi355x trace]     primal recovery: factorisation stopped at pivot %d\n", info);
         printf("Recovery step is infeasible\n");
         return;
     }

@@ -132,7 +132,7 @@ static bool cone_wants_streaming(const MiCone *c) {
     if (hipMemGetInfo(&fr, &tot) == hipSuccess)
         stream = (afull + ahat + work + schur > (c->world > 1 ? 0.97 * (double) tot : (double) fr));
     (void) hipGetLastError();
-    if (const char *e = getenv("HDSDP_MI355X_STREAM_A")) stream = (atoi(e) != 0);
+    if (const HdmEnvInt e = hdm_env_int<ENV_STREAM_A>(); e.set) stream = (int) e.value != 0;
     return stream && c->mloc > 0;
 }
 static int cone_alloc_batch(MiCone *c) {
@@ -210,8 +210,8 @@ static_assert(HDM_DR_ZERO == MI_COEFF_ZERO && HDM_DR_SPARSE == MI_COEFF_SPARSE &
               HDM_DR_SPR1 == MI_COEFF_SPR1 && HDM_DR_DSR1 == MI_COEFF_DSR1 && HDM_DR_PATH_GEMM == PATH_GEMM,
               "direct_rows.h restates the classes of coeff.h and the path numbers");
 static int cone_plan_direct_rows(MiCone *c, int natural, bool force_gemm, bool force_path, bool streamed) {
-    int sw = -1;
-    if (const char *e = getenv("HDSDP_MI355X_DIRECT_ROWS")) sw = std::max(0, atoi(e));
+    const HdmEnvInt e = hdm_env_int<ENV_DIRECT_ROWS>();
+    const int sw = e.set ? std::max(0, (int) e.value) : -1;
     const HdmDirectRule rule = hdm_direct_rule(c->world, c->synthetic, streamed, natural, force_gemm, force_path, c->n, c->n16, sw);
     if (!rule.on || c->mloc == 0 || (int) c->blk.rows.size() != c->m) return 0;
     std::vector<int> type((size_t) c->m);
@@ -287,16 +287,16 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
     for (int i = 0; i < nRow; ++i) c->trA[i] = c->blk.rows[i].trace;
     const int natural = natural_path(c->blk, nRow, nCol, world);
     c->path = natural;
-    const char *force = getenv("HDSDP_MI355X_FORCE_GEMM");
-    if (force && atoi(force)) c->path = PATH_GEMM;
-    const char *forcesp = getenv("HDSDP_MI355X_FORCE_PATH");
-    if (forcesp && world == 1) c->path = atoi(forcesp);
+    const bool force = hdm_env_on<ENV_FORCE_GEMM>();
+    if (force) c->path = PATH_GEMM;
+    const HdmEnvInt forcesp = hdm_env_int<ENV_FORCE_PATH>();
+    if (forcesp.set && world == 1) c->path = (int) forcesp.value;
     if (c->mloc == 0) c->path = PATH_GEMM;   // no constraint touches this block: only the objective's scalars remain
     {
         CreateTimer t_(1);
         // (rows too many to stay resident beside the work buffers -- congruence + Gram path only -- live in the compressed copy)
         const bool stream = (c->path == PATH_GEMM) && cone_wants_streaming(c);
-        if (cone_plan_direct_rows(c, natural, force && atoi(force), forcesp != nullptr, stream)) return HDSDP_RETCODE_MEMORY;
+        if (cone_plan_direct_rows(c, natural, force, forcesp.set, stream)) return HDSDP_RETCODE_MEMORY;
         if (stream ? upload_streamed_rows(c) : upload_dense_rows(c)) return HDSDP_RETCODE_MEMORY;   // the dense forms also feed the S assembly
     }
     if (c->path == PATH_R1) {

@@ -398,6 +398,29 @@ static void kkt_apply_device_m(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
     else fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_DEVICE_M=1: the host copy of M is kept: the operator has no engine cone\n");
 }
 
+// What else an unchanged driver can opt into through the environment, each by the setter a caller would use
+static void kkt_apply_opt_ins(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
+    const int nCones = HKKT->nCones;
+    if (hdm_env_on<ENV_GROUPED_BUILD>()) {
+        const int k = grouped_set(HKKT, pv, 1);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_BUILD=1: %d of %d cone(s) are built in one grouped pass\n", k, nCones);
+    }
+    if (hdm_env_on<ENV_GROUPED_CHECK>()) {
+        const int k = check_set_switch(pv, 1);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_CHECK=1: %d of %d cone(s) answer a point question in one grouped launch\n", k, nCones);
+    }
+    // HDSDP_MI355X_REFINE=k: Schur solves are refined with at most k steps (HMiKKTSetRefine)
+    if (const int k = hdm_env_int<ENV_REFINE>().value_or(0); k > 0) {
+        (void) HMiKKTSetRefine(HKKT, k);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_REFINE=%d: Schur solves are refined, at most %d step(s)\n", k, pv->st.refine());
+    }
+    // HDSDP_MI355X_REFINE_TILES=1: ... and a tile-form operator's too (HMiKKTSetRefineTiles; it needs the step cap above as well)
+    if (const int t = hdm_env_int<ENV_REFINE_TILES>().value_or(0); t > 0) {
+        (void) HMiKKTSetRefineTiles(HKKT, 1);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_REFINE_TILES=%d: the tile form of a sparse operator is refined too (step cap %d)\n", t, pv->st.refine());
+    }
+}
+
 hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones) {
     if (ensure_ctx() || !kkt_cones_combine(nCones, cones)) return HDSDP_RETCODE_FAILED;
     const HdmKktSwitches sw = hdm_kkt_switches();
@@ -411,34 +434,11 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     rc = kkt_init_device_common(HKKT, pv);
     if (rc != HDSDP_RETCODE_OK) return rc;
     if (sw.device_m) kkt_apply_device_m(HKKT, pv);
-    // the grouped Schur build (engine_grouped.h): eligibility is decided for every operator, the pass is used when the switch is on
+    // eligibility for the grouped Schur build (engine_grouped.h) and membership of the check set (engine_check_set.h) are decided
+    // for every operator; the grouped pass and the grouped launch are used when their switches are on
     grouped_init_plan(HKKT, pv);
-    static const bool grouped_env = [] { const char *e = getenv("HDSDP_MI355X_GROUPED_BUILD"); return e && atoi(e) != 0; }();
-    if (grouped_env) {
-        const int k = grouped_set(HKKT, pv, 1);
-        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_BUILD=1: %d of %d cone(s) are built in one grouped pass\n", k, nCones);
-    }
-    // the check set (engine_check_set.h): membership is decided for every operator, the grouped launch is used when the switch is on
     check_set_init(HKKT, pv);
-    static const bool grouped_check_env = [] { const char *e = getenv("HDSDP_MI355X_GROUPED_CHECK"); return e && atoi(e) != 0; }();
-    if (grouped_check_env) {
-        const int k = check_set_switch(pv, 1);
-        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_CHECK=1: %d of %d cone(s) answer a point question in one grouped launch\n", k, nCones);
-    }
-    // HDSDP_MI355X_REFINE=k: an unchanged driver's Schur solves are refined with at most k steps (HMiKKTSetRefine)
-    if (const char *e = getenv("HDSDP_MI355X_REFINE")) {
-        if (atoi(e) > 0) {
-            (void) HMiKKTSetRefine(HKKT, atoi(e));
-            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_REFINE=%d: Schur solves are refined, at most %d step(s)\n", atoi(e), pv->st.refine());
-        }
-    }
-    // HDSDP_MI355X_REFINE_TILES=1: ... and a tile-form operator's too (HMiKKTSetRefineTiles; it needs the step cap above as well)
-    if (const char *e = getenv("HDSDP_MI355X_REFINE_TILES")) {
-        if (atoi(e) > 0) {
-            (void) HMiKKTSetRefineTiles(HKKT, 1);
-            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_REFINE_TILES=%d: the tile form of a sparse operator is refined too (step cap %d)\n", atoi(e), pv->st.refine());
-        }
-    }
+    kkt_apply_opt_ins(HKKT, pv);
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
 }

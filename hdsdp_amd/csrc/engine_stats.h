@@ -15,7 +15,7 @@ struct StatFn { const char *name; int k; double sec; long calls; double mx; };
 StatFn g_stat_fn[64];
 int g_stat_nfn = 0;
 thread_local int t_stat_depth = 0;
-static bool stat_trace() { static int t = -1; if (t < 0) { const char *e = getenv("HDSDP_MI355X_TRACE"); t = (e && atoi(e)) ? 1 : 0; } return t == 1; }
+static bool stat_trace() { return hdm_env_on<ENV_TRACE>(); }
 struct StatScope {
     int k;
     bool on = false;

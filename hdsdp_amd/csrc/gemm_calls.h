@@ -6,7 +6,7 @@
 // destination, the row segments of a sharded Gram operand, the spans that vouch for the unmasked tile loads (work_plan.h, beside
 // the byte counts that size the same buffers), the algorithmic flops of the roofline -- so what the launcher would refuse at run
 // time cannot be written, and tests/test_gemm_calls_cpu.py checks every field without a device.
-// Pure host arithmetic: no HIP header, no allocation, no getenv, no I/O, no state.
+// Pure host arithmetic: no HIP header, no allocation, no environment, no I/O, no state.
 #pragma once
 #include "gemm_geom.h"
 #include "work_plan.h"

@@ -27,7 +27,6 @@
 namespace {
 struct TimedLaunch { hipEvent_t e0, e1; int role; double flops, issued; };
 bool g_timing = false;
-thread_local bool g_capturing = false;   // per host thread: each shard of a device group captures its own chains
 std::vector<TimedLaunch> g_timed;
 unsigned long long *g_dbg = nullptr;
 int g_dbg_role = -1;
@@ -60,7 +59,7 @@ int persist_counters(int **cnt, int *slots) {
         HDM_HIP_CHECK(hdm_malloc((void **) &pd.ring, sizeof(int) * 8 * PERSIST_RING));
         pd.slots = 2 * std::max(1, cus);
     }
-    static const int env_reserve = [] { const char *e = getenv("HDM_PERSIST_RESERVE_CUS"); return e ? atoi(e) : -1; }();
+    const int env_reserve = hdm_env_int<ENV_PERSIST_RESERVE_CUS>().value_or(-1);
     const int reserve = env_reserve >= 0 ? env_reserve : g_reserved_cus;
     *cnt = pd.ring + 8 * (pd.seq++ % PERSIST_RING);
     *slots = std::max(2, pd.slots - 2 * reserve);
@@ -191,7 +190,7 @@ static int launch_tiles(const HdmGemmArgs &args, int subset, hipStream_t stream)
     d.ntiles = tl.n;
     d.dbg = (g_dbg && args.role == g_dbg_role) ? g_dbg : nullptr;
 #ifdef HDM_DIAGNOSTICS
-    if (d.dbg && !g_capturing && getenv("HDM_DBG_SYNC")) HDM_HIP_CHECK(hipDeviceSynchronize());   // diagnostic: isolate the stamped launch from its neighbours
+    if (d.dbg && hdm_env_int<ENV_DBG_SYNC>().set) HDM_HIP_CHECK(hipDeviceSynchronize());   // diagnostic: isolate the stamped launch from its neighbours
 #endif
     // Kernel variants.  The shipped library carries ONE loop for the three Schur roles (variant 64: rotated, explicitly
     // interleaved K loop, persistent and one-workgroup-per-tile forms) and the masked loop of generic launches (variant 0).
@@ -203,12 +202,11 @@ static int launch_tiles(const HdmGemmArgs &args, int subset, hipStream_t stream)
     // same time with one workgroup per tile, 1.4 % slower than the LDS loop with persistent workgroups).
     int var = 64;
 #ifdef HDM_DIAGNOSTICS
-    static const int g_env_var = [] { const char *e = getenv("HDM_VAR"); return e ? atoi(e) : -1; }();
+    const int g_env_var = hdm_env_int<ENV_VAR>().value_or(-1);
     if (g_env_var >= 0) var = g_env_var;
     if (var == 576 && args.role != HDM_ROLE_CONG2) var = 64;
     if (args.role == HDM_ROLE_CONG2) {
-        static const int g_direct = [] { const char *e = getenv("HDM_CONG2_DIRECT"); return e ? atoi(e) : 0; }();
-        const bool direct = g_direct && var == 64 && args.A2 && !args.a_kmajor && !args.b_kmajor &&
+        const bool direct = hdm_env_on<ENV_CONG2_DIRECT>() && var == 64 && args.A2 && !args.a_kmajor && !args.b_kmajor &&
                             args.epilogue == HDM_EPI_BLOCKED && args.lower_only && args.klimit == HDM_KLIM_BY_N &&
                             args.A2 == args.B && args.B2 == args.A;
         if (direct) var = 320;
@@ -217,9 +215,8 @@ static int launch_tiles(const HdmGemmArgs &args, int subset, hipStream_t stream)
     long nwg = (long) tl.n * (args.batch >= 8 ? ((args.batch + 7) & ~7) : args.batch);
     // roles 1-3 with a batch: persistent workgroups drawing tiles from per-XCD counters (hdm_gemm_persist_kernel), where
     // the variant has a persistent form (gemm_persist.hip); the grid is then what the chip holds
-    static const int g_persist = [] { const char *e = getenv("HDM_PERSIST"); return e ? atoi(e) : 1; }();
     int *cnt = nullptr;
-    const bool persist = g_persist && args.role != HDM_ROLE_GENERIC && args.batch >= 8 && !g_capturing &&
+    const bool persist = hdm_env_on<ENV_PERSIST>() && args.role != HDM_ROLE_GENERIC && args.batch >= 8 &&
                          hdm_persist_supported(args.a_kmajor != 0, args.b_kmajor != 0, args.role, var);
     if (!persist && (var == 320 || var == 576)) var = 64;       // persistent-only variants
     if (persist) {
@@ -230,7 +227,7 @@ static int launch_tiles(const HdmGemmArgs &args, int subset, hipStream_t stream)
     }
     dim3 grid((unsigned) nwg), block(256);
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = g_timing && !g_capturing;
+    const bool timed = g_timing;
     if (timed) {
         if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 1;
         HDM_HIP_CHECK(hipEventRecord(e0, stream));
@@ -279,7 +276,6 @@ static int launch_tiles(const HdmGemmArgs &args, int subset, hipStream_t stream)
 }
 
 void hdm_timing_enable(int on) { g_timing = (on != 0); }
-void hdm_gemm_capture_mode(int on) { g_capturing = (on != 0); }
 void hdm_gemm_reserve_cus(int cus) { g_reserved_cus = std::max(0, cus); }
 
 int hdm_timing_collect(double *ms, double *flops, long *launches, double *issued) {

@@ -201,7 +201,7 @@ int group_setup(int n, const int *ids, int transport_request) {
         return 1;
     };
     // transport: device copies unless RCCL is asked for (transport_request, or HDSDP_MI355X_TRANSPORT=rccl) -- see the header
-    if (transport_request < 0) if (const char *t = getenv("HDSDP_MI355X_TRANSPORT")) transport_request = (strcmp(t, "rccl") == 0) ? GRP_RCCL : GRP_COPIES;
+    if (transport_request < 0) if (const char *t = hdm_env_string<ENV_TRANSPORT>()) transport_request = (strcmp(t, "rccl") == 0) ? GRP_RCCL : GRP_COPIES;
     G->transport = (transport_request == GRP_RCCL && !G->shared_device) ? GRP_RCCL : GRP_COPIES;
     if (transport_request == GRP_RCCL && G->shared_device)
         fprintf(stderr, "[hdsdp_mi355x] RCCL needs one device per shard; shards share a device here: using device copies\n");
@@ -245,7 +245,7 @@ int group_setup(int n, const int *ids, int transport_request) {
     }
     (void) hipSetDevice(ids[0]);
     hdm_flow_set_shared_device(G->shared_device ? 1 : 0);
-    if (const char *e = getenv("HDSDP_MI355X_SHARD_MIN_N")) G->min_n = atoi(e);
+    G->min_n = hdm_env_int<ENV_SHARD_MIN_N>().value_or(G->min_n);
     for (int r = 0; r < n; ++r) G->th.emplace_back([G, r] { G->worker(r); });
     g_group = G;
     fprintf(stderr, "[hdsdp_mi355x] device group: %d shards on device(s)", n);
@@ -259,13 +259,11 @@ int group_setup(int n, const int *ids, int transport_request) {
 int group_configure_from_env() {
     if (g_group_env_done || g_group) return 0;
     g_group_env_done = true;
-    const char *e = getenv("HDSDP_MI355X_GPUS");
-    if (!e || atoi(e) <= 1) return 0;
-    const int n = atoi(e);
+    const int n = hdm_env_int<ENV_GPUS>().value_or(1);
+    if (n <= 1) return 0;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return 1;
-    const char *lb = getenv("HDSDP_MI355X_LOOPBACK");
-    const bool loop = lb && atoi(lb) != 0;
+    const bool loop = hdm_env_on<ENV_LOOPBACK>();
     if (n > ndev && !loop) {
         fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GPUS=%d but %d device(s) visible (HDSDP_MI355X_LOOPBACK=1 rehearses the "
                         "sharding on the devices there are)\n", n, ndev);
@@ -283,7 +281,7 @@ bool group_wants_synthetic(int nRow, int nCol) {
 }
 bool group_wants_block(const MiBlockData &blk) {
     if (!group_wants_synthetic(blk.m, blk.n)) return false;
-    if (const char *f = getenv("HDSDP_MI355X_FORCE_GEMM")) if (atoi(f)) return true;
+    if (hdm_env_on<ENV_FORCE_GEMM>()) return true;
     return natural_path(blk, blk.m, blk.n, 1) == PATH_GEMM;
 }
 
@@ -552,7 +550,7 @@ hdsdp_retcode group_create_cone(hdsdp_cone **pCone, int iCone, int nRow, int nCo
             return bad;
         }
     int pieces = 8;
-    if (const char *e = getenv("HDSDP_MI355X_A2A_PIECES")) pieces = std::max(1, std::min(GRP_MAX_PIECES, atoi(e)));
+    if (const HdmEnvInt e = hdm_env_int<ENV_A2A_PIECES>(); e.set) pieces = std::max(1, std::min(GRP_MAX_PIECES, (int) e.value));
     for (int r = 0; r < G->W; ++r) {
         MiCone *c = cg->shard[r];
         cg->x[r].cg = cg; cg->x[r].r = r;

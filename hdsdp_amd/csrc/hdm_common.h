@@ -14,6 +14,7 @@
 // ends (gemm_f64.hip, schur.hip: never freed, raw pointers on purpose) call it by name.
 hipError_t hdm_malloc(void **p, size_t bytes);   // alloc.cpp
 #include "devbuf.h"
+#include "env_switches.h"
 
 #include "gemm_geom.h"   // HDM_TILE / HDM_BK / HDM_SUB, HdmKLimit / HdmEpilogue / HdmRole, skyline storage, and the family's geometry
 #include "gemm_calls.h"  // HdmGemmArgs and its call forms; with work_plan.h: the layout, the operand slack and the spans
@@ -46,8 +47,6 @@ static inline hipError_t hdm_memcpy_h2d_sync(void *dst, const void *src, size_t 
 
 // the GEMM family (gemm_f64.hip): its argument block and the call forms that fill it are gemm_calls.h's
 int hdm_launch_gemm(const HdmGemmArgs &args, hipStream_t stream);
-// while a stream capture is recording the launches (chol.hip), the launcher must not record timing events
-void hdm_gemm_capture_mode(int on);
 void hdm_gemm_reserve_cus(int cus);   // CUs the persistent GEMM launches leave to concurrent kernels (collectives of a sharded build)
 // per-role live timing with HIP events on the launch stream (off by default)
 void hdm_timing_enable(int on);

@@ -6,6 +6,7 @@
 // Pure host arithmetic: no HIP call, no engine state.  The engine performs these rules (engine_kkt.h, engine_linsys.h, and
 // HMiKKTPhaseA in engine_api.h); tests/test_kkt_store_cpu.py compiles this header alone.
 #pragma once
+#include "env_switches.h"
 #include "refine_rule.h"
 #include <algorithm>
 #include <cstdint>
@@ -19,15 +20,11 @@
 // HDSDP_MI355X_KKT_ENVELOPE=0  the dense device matrix of a sparse operator is factored in full, in the driver's order
 // HDSDP_MI355X_KKT_RCM=0     no reverse Cuthill-McKee order is looked for
 // HDSDP_MI355X_DEVICE_M=1    HKKTInit turns the host mirror off where it can
-// SPARSE_KKT and DEVICE_M are read at every HKKTInit (tests/test_gpu_device_m.py sets DEVICE_M in-process); the other three
-// are read once per process, by the first HKKTInit.
+// (when each is read: env_switches.h)
 struct HdmKktSwitches { bool sparse, tiles, envelope, rcm, device_m; };
-static inline bool hdm_kkt_not_zero(const char *e) { return !(e && atoi(e) == 0); }
 static inline HdmKktSwitches hdm_kkt_switches() {
-    static const bool tiles = hdm_kkt_not_zero(getenv("HDSDP_MI355X_KKT_TILES")),
-                      envelope = hdm_kkt_not_zero(getenv("HDSDP_MI355X_KKT_ENVELOPE")), rcm = hdm_kkt_not_zero(getenv("HDSDP_MI355X_KKT_RCM"));
-    const char *dm = getenv("HDSDP_MI355X_DEVICE_M");
-    return {hdm_kkt_not_zero(getenv("HDSDP_MI355X_SPARSE_KKT")), tiles, envelope, rcm, dm && atoi(dm) == 1};
+    return {hdm_env_on<ENV_SPARSE_KKT>(), hdm_env_on<ENV_KKT_TILES>(), hdm_env_on<ENV_KKT_ENVELOPE>(), hdm_env_on<ENV_KKT_RCM>(),
+            hdm_env_int<ENV_DEVICE_M>().value_or(0) == 1};
 }
 
 // ---- sparse or dense ------------------------------------------------------------------------

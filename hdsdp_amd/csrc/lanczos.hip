@@ -1020,7 +1020,7 @@ struct LzDeviceBackend {
 }  // namespace
 
 int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, hipStream_t s, double *maxStep, int *steps) {
-    static const bool dbg2 = [] { const char *e = getenv("HDSDP_MI355X_RATIO_DEBUG"); return e && atoi(e) >= 2; }();
+    const bool dbg2 = hdm_env_int<ENV_RATIO_DEBUG>().value_or(0) >= 2;
     for (;;) {
         const HdmLzForm form = hdm_lz_form(n16, hdm_lz_switches(), big_ok, hdm_flow_shared_device(), cus);
         if (form == LZ_FORM_WHOLE_RESIDENT || form == LZ_FORM_WHOLE_GLOBAL) return lz_solve_whole(*this, form, Linv, ldl, dS, ldd, s, maxStep, steps);

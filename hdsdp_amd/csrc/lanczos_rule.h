@@ -4,6 +4,7 @@
 // Pure arithmetic: no HIP header, no allocation.  Under hipcc the predicates and the acceptance rule are __host__ __device__;
 // the switches are host only.  tests/test_lanczos_rule_cpu.py compiles this header alone with the host compiler.
 #pragma once
+#include "env_switches.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -73,12 +74,11 @@ static_assert(LZ_MB_GROUP + LZ_MB_GROUP_LEN <= LZ_MB_WHOLE, "a group of steps (t
 static_assert(LZ_MB_WHOLE + LZ_MB_WHOLE_LEN <= LZ_MB_Y2 && LZ_MB_Y2 + LZ_MD <= LZ_MB_SIZE, "mailbox ranges overlap");
 
 // ---- which form runs ------------------------------------------------------------------------
-// HDM_LANCZOS_WHOLE / _FUSED / _GROUP / _BIG = 0 switch a form off (A/B, tests/test_gpu_switches.py); read once per process.
+// HDM_LANCZOS_WHOLE / _FUSED / _GROUP / _BIG = 0 switch a form off (A/B, tests/test_gpu_switches.py; read time: env_switches.h).
 struct HdmLzSwitches { bool whole, fused, group, big; };
-static inline bool hdm_lz_not_zero(const char *e) { return !(e && atoi(e) == 0); }
 static inline const HdmLzSwitches &hdm_lz_switches() {
-    static const HdmLzSwitches sw = {hdm_lz_not_zero(getenv("HDM_LANCZOS_WHOLE")), hdm_lz_not_zero(getenv("HDM_LANCZOS_FUSED")),
-                                     hdm_lz_not_zero(getenv("HDM_LANCZOS_GROUP")), hdm_lz_not_zero(getenv("HDM_LANCZOS_BIG"))};
+    static const HdmLzSwitches sw = {hdm_env_on<ENV_LANCZOS_WHOLE>(), hdm_env_on<ENV_LANCZOS_FUSED>(), hdm_env_on<ENV_LANCZOS_GROUP>(),
+                                     hdm_env_on<ENV_LANCZOS_BIG>()};
     return sw;
 }
 

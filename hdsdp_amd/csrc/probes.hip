@@ -246,7 +246,7 @@ int HMiSymResidualProbe(int n, const double *Mlower, long ld, const double *x, c
     return 0;
 }
 
-// diagnostic: factorisation time (ms, HIP events, graph replay included) of an n x n matrix whose pattern is a band of
+// diagnostic: factorisation time (ms, HIP events) of an n x n matrix whose pattern is a band of
 // `band` 128-blocks below the diagonal block, once as a dense matrix and once on its block envelope
 __global__ void mi_band_spd_kernel(double *A, long ld, int n, int band) {
     const long e = (long) blockIdx.x * blockDim.x + threadIdx.x;

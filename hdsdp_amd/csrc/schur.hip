@@ -926,7 +926,7 @@ int hdm_extract(const double *G, long ldg, long R, long pI, const int *rows_seg,
 
 int hdm_sym_combine(const double *A, long astride, int m, const double *y, const double *C, double tau, double eye,
                     double *S, int n, long lda, long lds_, hipStream_t s) {
-    static const bool sky_order = [] { const char *e = getenv("HDM_SYM_COMBINE_SKY"); return !(e && atoi(e) == 0); }();
+    const bool sky_order = hdm_env_on<ENV_SYM_COMBINE_SKY>();
     const long sky = hdm_sky_size((int) lda);
     if (sky_order && m > 0) {
         hipLaunchKernelGGL(hdm_sym_combine_sky_kernel, dim3((unsigned) ((sky + 1023) / 1024)), dim3(256), 0, s, A, astride, m, y, C,

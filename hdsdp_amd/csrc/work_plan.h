@@ -4,6 +4,7 @@
 // what this header says (engine_cone.h: cone_alloc_common, cone_alloc_gemm_work; engine_create.h: cone_alloc_batch), and
 // HMiWorkPlanQuery hands the same numbers to callers without a device (hdsdp_amd/dist.py: ShardPlan.hbm_bytes).
 #pragma once
+#include "env_switches.h"
 #include "gemm_geom.h"
 #include <algorithm>
 #include <climits>
@@ -58,8 +59,8 @@ static inline long hdm_exchange_span(const HdmLayout &L) { return (long) hdm_exc
 static inline long hdm_lp_span(int kc, int mpad) { return (long) (kc / 16) * mpad * 16 + HDM_OPERAND_PAD_DOUBLES; }
 
 // ---- knobs ----------------------------------------------------------------------------------
-// The A/B and test switches of the plan (include/hdsdp_mi355x.h lists them), as the environment states them NOW: the engine
-// reads them per allocation, not once per process (tests set them between cones).
+// The A/B and test switches of the plan (include/hdsdp_mi355x.h lists them), as the environment states them at the call
+// (env_switches.h: NOW).
 struct HdmKnobs {
     long tcap_gib = 32;             // HDM_TCAP_GIB: GiB of congruence intermediates
     // HDM_BC, as written (not clamped here).  The plan takes min(memory bound, bc_max) and clamps THAT to at least 1
@@ -74,12 +75,12 @@ struct HdmKnobs {
 };
 static inline HdmKnobs hdm_knobs_from_env() {
     HdmKnobs k;
-    if (const char *e = getenv("HDM_TCAP_GIB")) k.tcap_gib = atol(e);
-    if (const char *e = getenv("HDM_BC")) k.bc_max = atol(e);
-    if (const char *e = getenv("HDM_GRAM_KSTAGES")) k.gram_kstages = std::max(1L, atol(e));
-    if (const char *e = getenv("HDM_NSPLIT")) { k.nsplit_set = true; k.nsplit = atol(e); }
-    if (const char *e = getenv("HDM_SHARE_T_SLABS")) k.share_t_slabs = atoi(e) != 0;
-    if (const char *e = getenv("HDM_GRAM_QUEUE")) k.gram_queue_global = atoi(e) != 0;
+    if (const HdmEnvInt e = hdm_env_int<ENV_TCAP_GIB>(); e.set) k.tcap_gib = e.value;
+    if (const HdmEnvInt e = hdm_env_int<ENV_BC>(); e.set) k.bc_max = e.value;
+    if (const HdmEnvInt e = hdm_env_int<ENV_GRAM_KSTAGES>(); e.set) k.gram_kstages = std::max(1L, e.value);
+    if (const HdmEnvInt e = hdm_env_int<ENV_NSPLIT>(); e.set) { k.nsplit_set = true; k.nsplit = e.value; }
+    k.share_t_slabs = hdm_env_on<ENV_SHARE_T_SLABS>();
+    k.gram_queue_global = hdm_env_on<ENV_GRAM_QUEUE>();
     return k;
 }
 

@@ -574,7 +574,9 @@ void HMiSDPAFree(HMiSDPA **pp);
 
 
 /* =====================================  environment switches  =====================================
- * Every environment variable the shipped library reads (tests/test_abi_cpu.py holds this table to the sources, both ways).
+ * Every environment variable the shipped library reads.  The table is held to the one list the library reads them through,
+ * csrc/env_switches.h -- which also states how each text is parsed and when it is read -- by tests/test_abi_cpu.py and
+ * tests/test_env_switches_cpu.py, both ways, on name and default.
  * "other position" tests: tests/test_gpu_switches.py runs every device path under the non-default setting in a child
  * process and compares with the default run.  A -DHDM_DIAGNOSTICS build (python -m hdsdp_amd.build --diagnostics) reads
  * three more -- HDM_VAR, HDM_CONG2_DIRECT, HDM_DBG_SYNC -- for stamped kernels and timing ablations; the product never does.
@@ -600,7 +602,7 @@ void HMiSDPAFree(HMiSDPA **pp);
  *  HDSDP_MI355X_ZS                by cost   0 / 1 / 2: zero-suppressed copy for the S / dS sweeps (schur.h) test_gpu_switches.py
  *  HDSDP_MI355X_PRIMAL_SIGNED     1         KKT_TYPE_PRIMAL with an indefinite X: signed factor + signed  test_gpu_primal_signed.py
  *                                           Gram correction (route 1); 0: row-by-row fallback / refusal
- *  HDSDP_MI355X_DIRECT_ROWS      by size   rank-one and short triplet rows of a congruence + Gram block   test_gpu_direct_rows.py
+ *  HDSDP_MI355X_DIRECT_ROWS       by size   rank-one and short triplet rows of a congruence + Gram block   test_gpu_direct_rows.py
  *                                           built without the congruence (direct_rows.h); 0: off; k > 0: on
  *                                           whatever the size, up to k entries per row.  Read at cone creation
  *  HDSDP_MI355X_STREAM_A          by memory 0 / 1: synthetic constraint data resident / regenerated per     test_gpu_streamed.py
@@ -611,9 +613,9 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           small SDP cones of an operator in three launches)
  *  HDSDP_MI355X_GROUPED_CHECK     0         1: HKKTInit turns the grouped interior check on (a point      test_gpu_grouped_check.py
  *                                           question to one small SDP cone answers all in one launch)
- *  HDSDP_MI355X_REFINE           0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on
+ *  HDSDP_MI355X_REFINE            0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on
  *                                           steps (HMiKKTSetRefine)
- *  HDSDP_MI355X_REFINE_TILES     0         1: HKKTInit turns the tile form's refined solve on as well    test_gpu_refine_tiles.py::test_the_environment_switches_refine_a_tile_operator
+ *  HDSDP_MI355X_REFINE_TILES      0         1: HKKTInit turns the tile form's refined solve on as well    test_gpu_refine_tiles.py::test_the_environment_switches_refine_a_tile_operator
  *                                           (HMiKKTSetRefineTiles; needs HDSDP_MI355X_REFINE=k too)
  *  -- the next six are the work plan's knobs: all read in csrc/work_plan.h (hdm_knobs_from_env), per allocation; HMiWorkPlanQuery sees them too --
  *  HDM_TCAP_GIB                   32        GiB of congruence intermediates per launch group              test_gpu_switches.py, test_gpu_group.py
@@ -633,14 +635,6 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           memory; 0: the general GEMM kernel
  *  HDM_TRSV_FLOW                  1         single-launch substitution; 0: per-block launches             test_gpu_switches.py, test_gpu_kernels.py
  *  HDM_TRSV_FLOW_FAIL_ONCE        0         test hook: throw the first single-launch result away          test_gpu_kernels.py::test_fallback_chains_of_the_factor_and_solve_kernels
- *  HDM_GRAPHS                     0         DIAGNOSTIC ONLY, not a supported position: 1 / 2 replay the    (diagnostic; still run by test_gpu_switches.py and
- *                                           factorisation / substitution chains from a hipGraph.  No gain     test_gpu_kernels.py so that it keeps working)
- *                                            and two runtime hazards on record: a replayed
- *                                           MEMSET node once wrote bytes that were not its captured value
- *                                           (profiles/r04_c_poison.txt; not reproducible stand-alone:
- *                                           tools/probes/memset_node_probe.hip, profiles/r05_e_memset_node_
- *                                           probe.txt -- the captured chains hold kernel nodes only since),
- *                                           and rocprofv3 dies beneath hipGraphLaunch (profiles/r04_a_*)
  *  HDM_SYM_COMBINE_SKY            1         S assembly in storage order; 0: element-indexed kernel        test_gpu_switches.py
  *  HDM_LANCZOS_WHOLE              1         small blocks: whole ratio test in one launch                  test_gpu_switches.py
  *  HDM_LANCZOS_FUSED              1         small blocks: three Lanczos steps per launch                  test_gpu_switches.py

@@ -414,31 +414,46 @@ def test_library_exports_nothing_but_the_declared_surface():
     assert exported == _declared_functions(), sorted(set(exported) ^ set(_declared_functions()))
 
 
-def test_every_environment_switch_is_listed_in_the_header_and_covered():
-    """the header's table of environment switches against the sources (both ways), and every switch that selects a code path
-    against the settings tests/test_gpu_switches.py runs or the test the table names"""
+def test_every_environment_switch_is_listed_in_the_header_and_covered(tmp_path):
+    """the header's table of environment switches against the one list the sources read the environment through
+    (csrc/env_switches.h, printed by tests/env_switches_driver.cpp): the same names and defaults both ways, no read of the
+    environment beside the list, every entry of the list read somewhere, the diagnostic entries in diagnostic regions only -- and
+    every switch that selects a code path against the settings tests/test_gpu_switches.py runs or the test the table names"""
+    import importlib.util
+
+    def load(name):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+
+    env = load("test_env_switches_cpu")
+    if env.CXX is None:
+        pytest.skip("no host C++ compiler")
+    table, rows = env.header_table()
+    listed = env.driver_list(env.build_driver(tmp_path))
+    assert sorted((e[0], e[3]) for e in listed) == sorted(rows)
     csrc = os.path.join(ROOT, "hdsdp_amd", "csrc")
-    read = set()
-    diag_only = set()
-    for f in os.listdir(csrc):
-        if not f.endswith((".hip", ".h", ".cpp")):
+    head = open(os.path.join(csrc, "env_switches.h")).read()
+    ids = re.findall(r"^    X\((\w+),", head, flags=re.M)
+    diag_ids = re.findall(r"^    X\((\w+),", head.split("#ifdef HDM_DIAGNOSTICS")[1].split("#else")[0], flags=re.M)
+    assert len(ids) == len(listed) + 3 and diag_ids == ["VAR", "CONG2_DIRECT", "DBG_SYNC"]
+    used, used_in_product = set(), set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".cpp")) or f == "env_switches.h":
             continue
         txt = open(os.path.join(csrc, f)).read()
-        # variables read only inside #ifdef HDM_DIAGNOSTICS blocks do not exist in the product
+        assert "getenv" not in txt, f + " reads the environment beside csrc/env_switches.h"
+        # what stands inside #ifdef HDM_DIAGNOSTICS blocks does not exist in the product
         parts = re.split(r"#ifdef HDM_DIAGNOSTICS(.*?)#e(?:ndif|lse)", txt, flags=re.S)
         for k, part in enumerate(parts):
-            for v in re.findall(r'getenv\("([A-Za-z_0-9]+)"\)', part):
-                (diag_only if k % 2 == 1 else read).add(v)
-    diag_only -= read
-    table = open(HEADER).read().split("environment switches")[1].split("utilities")[0]
-    listed = set(re.findall(r"^ \*  ([A-Z][A-Z_0-9]+)\s", table, flags=re.M))
-    assert read == listed, (sorted(read - listed), sorted(listed - read))
-    assert diag_only <= {"HDM_VAR", "HDM_CONG2_DIRECT", "HDM_DBG_SYNC"}
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("switch_tests", os.path.join(ROOT, "tests", "test_gpu_switches.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    run = set(k for s in mod.SETTINGS for k in s)
+            found = set(re.findall(r"\bENV_([A-Z][A-Z_0-9]*)\b", part))
+            used |= found
+            if k % 2 == 0:
+                used_in_product |= found
+    assert used == set(ids), (sorted(set(ids) - used), sorted(used - set(ids)))
+    assert used_in_product == set(ids) - set(diag_ids), sorted(used_in_product & set(diag_ids))
+    run = set(k for s in load("test_gpu_switches").SETTINGS for k in s)
     for line in table.splitlines():
         m = re.match(r"^ \*  ([A-Z][A-Z_0-9]+)\s", line)
         if m and "test_gpu_switches.py" in line:

@@ -345,8 +345,7 @@ dhash = []
 for n in (130, 300, 1000):
     ls = api.LinSys(n, api.HDSDP_LINSYS_DENSE_DIRECT)
     for trial in range(3):
-        # a new matrix every time through ONE factor object: the first factorisation runs eagerly, the second is captured into a
-        # hipGraph, the third replays it (chol.hip)
+        # a new matrix every time through ONE factor object
         G = rng.uniform(-1, 1, (n, n))
         S = G @ G.T / n + (1.0 + trial) * np.eye(n)
         ls.numeric(np.triu(S))
@@ -385,15 +384,14 @@ print("FALLBACK_OK")
 '''
 
 
-@pytest.mark.parametrize("env", [{"HDM_TRSV_FLOW": "0"}, {"HDM_GRAPHS": "1"}, {"HDM_GRAPHS": "2", "HDM_TRSV_FLOW": "0"},
-                                 {"HDM_TRSV_FLOW_FAIL_ONCE": "1"}, {"HDM_DIAG_SWEEP": "0"}, {"HDM_PERSIST": "0"}, {"HDM_CHOL_K128": "0"}],
-                         ids=["per-block-substitution", "graph-replayed-factorisation", "graph-replayed-substitution", "flow-gives-up-once",
-                              "lds-panel-diagonal-block", "one-tile-per-workgroup", "general-gemm-panel-and-update"])
+@pytest.mark.parametrize("env", [{"HDM_TRSV_FLOW": "0"}, {"HDM_TRSV_FLOW_FAIL_ONCE": "1"}, {"HDM_DIAG_SWEEP": "0"}, {"HDM_PERSIST": "0"},
+                                 {"HDM_CHOL_K128": "0"}],
+                         ids=["per-block-substitution", "flow-gives-up-once", "lds-panel-diagonal-block", "one-tile-per-workgroup",
+                              "general-gemm-panel-and-update"])
 def test_fallback_chains_of_the_factor_and_solve_kernels(env):
     """the paths behind the defaults stay covered: the per-block substitution launches (HDM_TRSV_FLOW=0, also what a
     timed-out single-launch substitution falls back to), the LDS-panel diagonal-block kernel (HDM_DIAG_SWEEP=0), the
-    one-tile-per-workgroup GEMM launches (HDM_PERSIST=0), graph-replayed instead of eager factorisation chains
-    (HDM_GRAPHS=1), graph-replayed substitutions (HDM_GRAPHS=2), and the give-up path itself (HDM_TRSV_FLOW_FAIL_ONCE=1
+    one-tile-per-workgroup GEMM launches (HDM_PERSIST=0), and the give-up path itself (HDM_TRSV_FLOW_FAIL_ONCE=1
     throws the first single-launch result away): in-place solves included -- a retry must start from the caller's
     untouched right-hand side -- all against LAPACK.  Child process: the switches are read once per process."""
     import os, subprocess, sys
@@ -420,20 +418,6 @@ def test_persistent_and_one_tile_per_workgroup_launches_give_the_same_bits():
         assert r.returncode == 0 and "FALLBACK_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
         h.append(re.search(r"MHASH (\w+)", r.stdout).group(1))
     assert h[0] == h[1] == h[2], h
-
-
-def test_graph_replayed_factorisations_give_the_eager_bits():
-    """one factor object, a new matrix every time (first factorisation eager, second captured into a hipGraph, third replayed):
-    the factors' diagonals of the nine factorisations of the script above are the same bits with and without graph replay"""
-    import os, subprocess, sys, re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    h = []
-    for extra in ({}, {"HDM_GRAPHS": "1"}):
-        r = subprocess.run([sys.executable, "-c", FALLBACK_SCRIPT % root], capture_output=True, text=True, timeout=600,
-                           env=dict(os.environ, **extra))
-        assert r.returncode == 0 and "FALLBACK_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
-        h.append(re.search(r"DHASH (\w+)", r.stdout).group(1))
-    assert h[0] == h[1], h
 
 
 def test_cholesky_small_tile_products_give_the_same_bits():

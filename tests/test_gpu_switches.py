@@ -28,7 +28,7 @@ SETTINGS = [
     {"HDM_GRAM_KSTAGES": "16", "HDM_NSPLIT": "8"},                       # more K splits than slabs: groups of 8 accumulate into the slabs
     {"HDSDP_MI355X_HOST_THREADS": "1"},                                  # ingest on one host thread
     {"HDM_PERSIST": "0"}, {"HDM_PERSIST_RESERVE_CUS": "200"}, {"HDSDP_MI355X_PRELOAD": "0"},
-    {"HDM_DIAG_SWEEP": "0"}, {"HDM_CHOL_K128": "0"}, {"HDM_TRSV_FLOW": "0"}, {"HDM_GRAPHS": "1"}, {"HDM_GRAPHS": "2"},
+    {"HDM_DIAG_SWEEP": "0"}, {"HDM_CHOL_K128": "0"}, {"HDM_TRSV_FLOW": "0"},
     {"SWITCH_WORKER_SHARDS": "2"},                                       # in-process device group, defaults
     {"SWITCH_WORKER_SHARDS": "3", "HDSDP_MI355X_A2A_PIECES": "1"},       # one blocking exchange
     {"SWITCH_WORKER_SHARDS": "2", "HDSDP_MI355X_STAGED_A2A": "0"},       # congruence complete, then exchange

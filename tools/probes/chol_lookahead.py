@@ -1,5 +1,5 @@
 """device-resident interior check (assemble S at y = 0: one pass over C, then the blocked Cholesky) at a few dimensions: time per
-check.  Run under HDM_CHOL_LOOKAHEAD=0 / 1 (and HDM_GRAPHS=0 / 1) for the A/B."""
+check.  Run under HDM_CHOL_LOOKAHEAD=0 / 1 for the A/B."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,4 +20,4 @@ for n in (512, 1000, 2000, 4000):
         cone.check_is_interior(taus[k & 1], y)
     out.append("n=%d %.3f ms" % (n, (time.perf_counter() - t0) / reps * 1e3))
     cone.destroy()
-print({k: os.environ.get(k) for k in ("HDM_CHOL_LOOKAHEAD", "HDM_GRAPHS")}, "  ".join(out), flush=True)
+print({k: os.environ.get(k) for k in ("HDM_CHOL_LOOKAHEAD",)}, "  ".join(out), flush=True)

@@ -14,11 +14,11 @@ if len(sys.argv) > 1:
     if sys.argv[1] == "ratio":
         par = g["rt_par1"]; cone.ratio_test(float(par[0]), g["rt_dy1"], float(par[1]))
     X = cone.get_primal(float(g["pr_mu"][0]), g["pr_y"], g["pr_dy"])
-    print(sys.argv[1], dict((k, os.environ.get(k)) for k in ("HDSDP_MI355X_ZS", "HDSDP_MI355X_AFFINE_S", "HDM_GRAPHS")), "interior", ok,
+    print(sys.argv[1], dict((k, os.environ.get(k)) for k in ("HDSDP_MI355X_ZS", "HDSDP_MI355X_AFFINE_S")), "interior", ok,
           "X", None if X is None else bool(np.isfinite(X).all()), "sweep copy", cone.sweep_info()[0], flush=True)
 else:
     for mode in ("plain", "ratio"):
-        for extra in ({}, {"HDSDP_MI355X_ZS": "0"}, {"HDSDP_MI355X_AFFINE_S": "0"}, {"HDM_GRAPHS": "0"}):
+        for extra in ({}, {"HDSDP_MI355X_ZS": "0"}, {"HDSDP_MI355X_AFFINE_S": "0"}):
             env = dict(os.environ, HDM_POISON="1", **extra)
             r = subprocess.run([sys.executable, os.path.abspath(__file__), mode], env=env, capture_output=True, text=True)
             print((r.stdout + r.stderr).strip().splitlines()[-2:], flush=True)
