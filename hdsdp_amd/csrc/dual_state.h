@@ -25,7 +25,7 @@ constexpr double HDM_DUAL_LINE_TOL = 8e-15;
 // updates of S in place before a request for S is swept afresh, so that the rounding of a chain of S + alpha dS stays bounded
 constexpr int HDM_DUAL_CHAIN_MAX = 16;
 // "a sweep costs something": 16 MiB of owned constraint data or more, i.e. from about n = m = 160 on.  From here on a block
-// tracks lines by default (hdm_dual_mode) and gets a zero-suppressed sweep copy (engine_cone.h: cone_build_zs).
+// tracks lines by default (hdm_dual_mode) and gets a zero-suppressed sweep copy (row_store_rule.h: hdm_sweep_copy_rule).
 constexpr long HDM_SWEEP_COSTS_BYTES = 16L << 20;
 static inline bool hdm_sweep_costs(long mloc, long n) { return mloc * n * (n + 1) * 4 >= HDM_SWEEP_COSTS_BYTES; }
 

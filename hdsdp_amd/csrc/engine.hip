@@ -19,6 +19,7 @@
 #include "hdm_common.h"
 #include "work_plan.h"
 #include "dual_state.h"
+#include "row_store_rule.h"
 #include "kkt_store.h"
 #include "schur.h"
 #include "direct_rows.h"
@@ -127,6 +128,7 @@ int ensure_ctx() {
 
 #include "engine_stats.h"
 #include "engine_linsys.h"
+#include "engine_rows.h"
 #include "engine_cone.h"
 #include "engine_build.h"
 #include "engine_lp.h"

@@ -190,23 +190,21 @@ int HMiConeUseSweepCopy(hdsdp_cone *cone, int on) {
     MiCone *c = cone_data(cone);
     if (!c || ensure_ctx()) return 1;
     c->dual.data_changed();          // the next request is assembled, not short-cut
-    if (!on) { c->zs_state = -1; return 0; }
-    if (!c->zs.val && cone_has_rows(c) && c->mloc > 0 &&
-        hdm_zs_build_from([&](int q0, int nb) { return cone_rows(c, q0, nb); }, cone_batch(c), c->astride, c->mloc, c->astride, 1.0,
-                          &c->zs, g.stream)) return 1;
-    c->zs_state = c->zs.val ? 1 : -1;
-    return c->zs.val ? 0 : 1;
+    if (!on) { c->rows.use_sweep_copy(false); return 0; }   // (the copy stays: switching it on again costs nothing)
+    if (c->rows.make_sweep_copy(1.0)) return 1;
+    return c->rows.sweep_copy_in_use() ? 0 : 1;
 }
 int HMiConeGetStreaming(hdsdp_cone *cone, int *batchRows) {
     const MiCone *c = cone_data(cone);
-    if (batchRows) *batchRows = (c && c->streamed) ? c->Bs : 0;
-    return (c && c->streamed) ? 1 : 0;
+    const bool on = c && c->rows.streamed();
+    if (batchRows) *batchRows = on ? c->rows.batch() : 0;
+    return on ? 1 : 0;
 }
 int HMiConeSweepInfo(hdsdp_cone *cone, int64_t *values, int64_t *positions) {
     const MiCone *c = cone_data(cone);
-    const bool on = c && (c->zs_state == 1);
-    if (values) *values = on ? (int64_t) c->zs.nnz : 0;
-    if (positions) *positions = on ? (int64_t) c->zs.sky * c->zs.m : 0;
+    const bool on = c && c->rows.sweep_copy_in_use();
+    if (values) *values = on ? (int64_t) c->rows.sweep_copy().nnz : 0;
+    if (positions) *positions = on ? (int64_t) c->rows.sweep_copy().sky * c->rows.sweep_copy().m : 0;
     return on ? 1 : 0;
 }
 // the work plan (work_plan.h): what the engine would plan here and now -- host only, no context, no device -- and what a cone holds

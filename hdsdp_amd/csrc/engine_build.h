@@ -276,7 +276,7 @@ hdsdp_retcode build_primal_general(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, con
     for (int qi = 0; qi < c->mloc && rc == HDSDP_RETCODE_OK; ++qi) {
         // this fallback multiplies with A_L as a generic operand in both orientations: unpack the row's skyline storage
         // into a square scratch matrix first
-        const double *Arow = cone_rows(c, qi, 1);
+        const double *Arow = c->rows.rows(qi, 1);
         if (!Arow || hdm_sky_to_square(Arow, ALsq.get(), c->n16, g.stream)) { rc = HDSDP_RETCODE_FAILED; break; }
         const double *AL = ALsq.get();
         // Pr1 = X A_L            (B operand element (j, k) = A_L(k, j): K-major)
@@ -527,7 +527,7 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
     HIP_RC(hipEventRecord(g.ev[0], g.stream));
     RC(ch.invert_factor(g.stream));
     HIP_RC(hipEventRecord(g.ev[1], g.stream));
-    const long afull_rows = std::max(1, c->mloc);   // matrices behind Afull (allocation sites)
+    const long afull_rows = std::max(1, c->mloc);   // matrices behind the resident storage (engine_rows.h: its allocation)
     // Multi-GPU: run step 2 of the owned rows by packed-index range, in the order of the exchange pieces, so that a piece
     // crosses the links while the later ranges are still being computed (at two ranks the all-to-all moves 8 GB per
     // rank over a single link, more than the Gram product alone can hide).  Needs the piecewise exchange hooks, all
@@ -536,17 +536,18 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
     int P = (c->world > 1) ? exchange_pieces(c) : 1;
     bool staged = c->world > 1 && P > 1 && P <= 64 && c->mloc <= c->Bc && hdm_colmask_honoured(NT) && hdm_env_on<ENV_STAGED_A2A>();
     c->last_pieces = P; c->last_staged = 0;
-    if (c->streamed) {
+    const double *Ares = c->rows.resident();
+    if (c->rows.streamed()) {
         // constraint data not resident: a batch is regenerated, transformed, and its buffer reused (stream order keeps the
         // generator of batch k + 1 behind step 1 of batch k, the only reader)
         staged = false;
-        for (int q0 = 0; q0 < c->mloc; q0 += c->Bs) {
-            const int nb = std::min(c->Bs, c->mloc - q0);
-            const double *A = cone_rows(c, q0, nb);
+        for (int q0 = 0, B = c->rows.batch(); q0 < c->mloc; q0 += B) {
+            const int nb = std::min(B, c->mloc - q0);
+            const double *A = c->rows.rows(q0, nb);
             if (!A) return HDSDP_RETCODE_FAILED;
-            RC(congruence_rows(c, ch, A, c->Bs, nb, q0));
+            RC(congruence_rows(c, ch, A, B, nb, q0));
         }
-    } else if (!staged) RC(congruence_rows(c, ch, c->Afull.get(), afull_rows, c->mloc - c->dr_n, 0));
+    } else if (!staged) RC(congruence_rows(c, ch, Ares, afull_rows, c->mloc - c->dr_n, 0));
     if (c->dr_n > 0) RC(direct_rows_build(c, ch));   // (one device, resident rows: never staged, never streamed)
     if (c->rank == 0) {
         // "I row": A = I => T = Linv, At = Linv Linv^T.  Reuse step 2 with T := Linv.
@@ -561,13 +562,13 @@ hdsdp_retcode build_gemm_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int type
         }
     }
     if (staged) {
-        RC(congruence_rows(c, ch, c->Afull.get(), afull_rows, c->mloc, 0, 1));
+        RC(congruence_rows(c, ch, Ares, afull_rows, c->mloc, 0, 1));
         if (prof_record(c->pe_s1, g.stream)) return HDSDP_RETCODE_FAILED;
         const unsigned long long all = (NT >= 64) ? ~0ULL : ((1ULL << NT) - 1);
         unsigned long long done = 0;
         for (int k = 0; k < P; ++k) {
             unsigned long long mk = (k == P - 1 ? all : piece_tile_cols(c, k, P)) & all & ~done;
-            if (mk) { RC(congruence_rows(c, ch, c->Afull.get(), afull_rows, c->mloc, 0, 2, mk)); c->last_staged += 1; }
+            if (mk) { RC(congruence_rows(c, ch, Ares, afull_rows, c->mloc, 0, 2, mk)); c->last_staged += 1; }
             done |= mk;
             if (!c->piece_ev[k]) HIP_RC(hipEventCreateWithFlags(&c->piece_ev[k], hipEventDisableTiming));
             HIP_RC(hipEventRecord(c->piece_ev[k], g.stream));

@@ -32,23 +32,13 @@ struct MiCone {
     HdmBuf<double> dr_fac, dr_U;      // n16 x dr_r1_16: the rank-one direct rows' factors (K-major, zero-padded), and L^-1 times them
     int dr_r1_16 = 0;
     // device data
-    HdmBuf<double> Afull;      // mloc x (n16 x n16) constraint matrices in A_L form: strict lower + half diagonal
-    HdmZs zs; int zs_state = 0; // zero-suppressed copy of Afull for the S / dS sweeps (schur.h); 0 = not looked at, 1 = in use, -1 = not built
-    // STREAMED constraint data (synthetic family only): the A_L forms are not resident -- BASELINE configs[4] on one
-    // device is 136 GB of them beside 130 GB of transformed rows -- and every consumer walks them batch by batch through
-    // cone_rows(), which regenerates a batch into Abatch (counter-based generator: any range of matrices, any number of times,
-    // bit-identical).  The sweeps read the zero-suppressed copy when it fits (built the same way, in two passes).
-    bool streamed = false;
-    bool rows_from_zs = false; // streamed INGESTED rows (round 5): the zero-suppressed copy is the only image of the constraint data, a
-                               // batch of A_L forms is expanded from it (hdm_zs_expand) where the synthetic family runs its generator
-    HdmBuf<double> Abatch;     // regeneration buffer, Bs matrices
-    int Bs = 0;
+    MiRows rows;               // the constraint rows: resident, generated per batch or expanded per batch, and the sweep copy (engine_rows.h)
     HdmBuf<double> Cfull;      // n16 x n16 objective, full symmetric
     HdmBuf<double> CL;         // objective in A_L form (GEMM path, HSD builds)
     HdmBuf<double> Avec;       // n16 x mloc16 rank-one factors (R1 path)
     HdmBuf<double> sgn;        // mloc signs (R1 path)
     int mloc16 = 0;
-    long astride = 0;          // elements per constraint matrix in Afull (skyline storage of the A_L form, gemm_geom.h)
+    long astride = 0;          // elements per stored constraint matrix (skyline storage of the A_L form, gemm_geom.h)
     HdmBuf<int> sp_rp, sp_ti, sp_tj;   // sparse path: triplets of the owned rows
     HdmBuf<double> sp_tv;
     HdmBuf<int> rows_seg;      // world*Lr: segment-ordered Gram row -> global constraint (-1 pad, -2.. aug)
@@ -245,6 +235,15 @@ bool group_wants_synthetic(int nRow, int nCol);
 hdsdp_retcode group_create_cone(hdsdp_cone **pCone, int iCone, int nRow, int nCol, MiBlockData *blk, bool synthetic);
 
 HdmLayout cone_layout(const MiCone *c) { return {c->world, c->n16, c->nblk, c->npb, c->npb_loc, c->Lr, c->R, c->astride}; }
+// the block and the device as row_store_rule.h sees them
+HdmRowFacts cone_row_facts(const MiCone *c) { return hdm_row_facts(cone_layout(c), c->n, c->m, c->mloc, c->synthetic, c->path == PATH_GEMM); }
+MiRowShape cone_row_shape(const MiCone *c) { return {c->n, c->n16, c->mloc, c->world, c->astride, &c->own}; }
+HdmDeviceFacts device_facts() {
+    HdmDeviceFacts d;
+    d.known = hipMemGetInfo(&d.free_bytes, &d.total_bytes) == hipSuccess;
+    (void) hipGetLastError();
+    return d;
+}
 
 int cone_alloc_common(MiCone *c) {
     c->own.clear();
@@ -285,25 +284,15 @@ int cone_alloc_common(MiCone *c) {
 // is short, through the plan's own helpers, so that what the cone holds is always a plan the rule could have made.
 int cone_alloc_gemm_work(MiCone *c) {
     const HdmLayout L = cone_layout(c);
-    const size_t n2 = (size_t) c->n16 * c->n16, nn = sizeof(double) * n2, tpad = hdm_operand_pad(c->n16);
-    {   // The zero-suppressed sweep copy (cone_build_zs) was made at creation, before these work buffers: it must never be the
-        // reason they come out smaller.  If what is free does not cover a generous bound of what the builders take, the copy
-        // goes (the sweeps then read the dense storage).
-        size_t fr = 0, tot = 0;
-        if (c->zs_state == 1 && !c->rows_from_zs && hipMemGetInfo(&fr, &tot) == hipSuccess) {
-            const double rows = (double) std::max(1, c->mloc);
-            const double want = std::min(32.0 * (1L << 30), (double) nn * rows) + (double) hdm_exchange_bytes(L) + 41.0 * (1L << 30);
-            if ((double) fr < want) { hdm_zs_free(&c->zs); c->zs_state = -1; }
-        }
-        (void) hipGetLastError();
-    }
+    const size_t n2 = (size_t) c->n16 * c->n16, tpad = hdm_operand_pad(c->n16);
+    if (hdm_sweep_copy_yields(c->rows.form(), c->rows.sweep_copy_in_use(), cone_row_facts(c), device_facts())) c->rows.yield_sweep_copy();
     const HdmKnobs knobs = hdm_knobs_from_env();
-    HdmWorkPlan p = hdm_work_plan(L, c->mloc, c->streamed, c->Bs, knobs);
+    HdmWorkPlan p = hdm_work_plan(L, c->mloc, c->rows.streamed(), c->rows.batch(), knobs);
     // the intermediates: if the allocation fails the batch is halved (and the slab count planned again for that batch)
     while (c->T.alloc(n2 * (size_t) p.Bc, tpad) != hipSuccess) {
         (void) hipGetLastError();
         if (p.Bc <= 8) { fprintf(stderr, "[hdsdp_mi355x] out of device memory for the congruence intermediates\n"); return 1; }
-        p = hdm_work_plan(L, c->mloc, c->streamed, c->Bs, knobs, p.Bc / 2);
+        p = hdm_work_plan(L, c->mloc, c->rows.streamed(), c->rows.batch(), knobs, p.Bc / 2);
     }
     c->Bc = (int) p.Bc;
     HDM_HIP_CHECK(hdm_memset_sync(c->T.get(), 0, p.t_bytes));  // step 1 writes lower tiles only; the rest must read as 0
@@ -377,39 +366,13 @@ void cone_get_kkt_map(void *cd, int iCol, int *schurMatCol) {
     if (c->kkt_counted < c->mloc && c->own_asc[c->kkt_counted] == iCol) c->kkt_counted += 1;
 }
 
-// The A_L forms of the owned rows q0 .. q0 + count - 1 on the device (stride c->astride): the resident storage, or -- streamed
-// cone -- the batch buffer after regenerating them into it (count <= c->Bs; valid until the next call; ordered on the engine
-// stream behind whatever still reads the previous batch).
-const double *cone_rows(MiCone *c, int q0, int count) {
-    if (!c->streamed) return c->Afull.get() ? c->Afull.get() + (long) q0 * c->astride : nullptr;
-    if (!c->Abatch.get() || count > c->Bs || q0 < 0 || q0 + count > c->mloc) return nullptr;
-    if (c->rows_from_zs) return hdm_zs_expand(c->zs, q0, count, c->Abatch.get(), c->astride, g.stream) ? nullptr : c->Abatch.get();
-    if (c->world == 1) {                       // owned rows are consecutive in the global numbering
-        if (hdm_synth_fill_low(c->Abatch.get(), c->astride, c->n, c->n16, c->own[q0], count, g.stream)) return nullptr;
-    } else {
-        for (int q = 0; q < count; ++q)
-            if (hdm_synth_fill_low(c->Abatch.get() + (long) q * c->astride, c->astride, c->n, c->n16, c->own[q0 + q], 1, g.stream)) return nullptr;
-    }
-    return c->Abatch.get();
-}
-int cone_batch(const MiCone *c) { return c->streamed ? std::max(1, c->Bs) : std::max(1, c->mloc); }
-bool cone_has_rows(const MiCone *c) { return c->streamed ? c->Abatch.get() != nullptr : c->Afull.get() != nullptr; }
-
-// The zero-suppressed copy of the constraint data (schur.h: HdmZs) that the S / dS sweeps and the corrector's dot products
-// read: made once, when the block's data has arrived (cone creation -- format preparation like the unpacking into A_L form; the
-// two passes and the 14 GB allocation take 0.3-0.8 s at n = m = 2000, which does not belong into the first line search),
-// for blocks whose sweep costs something (dual_state.h: hdm_sweep_costs, 16 MiB of constraint data or more) unless over 60 %
-// of the stored positions are non-zero or the memory is not there (then the sweeps read the dense storage).
-// HDSDP_MI355X_ZS=0: never; 2: any size, any fill.
-int cone_build_zs(MiCone *c) {
-    const int zs_env = hdm_env_int<ENV_ZS>().value_or(1);
-    if (c->zs_state != 0) return 0;
-    c->zs_state = -1;
-    if (!cone_has_rows(c) || c->mloc <= 0 || !zs_env || !(zs_env >= 2 || hdm_sweep_costs(c->mloc, c->n))) return 0;
-    if (hdm_zs_build_from([&](int q0, int nb) { return cone_rows(c, q0, nb); }, cone_batch(c), c->astride, c->mloc, c->astride,
-                          zs_env >= 2 ? 1.0 : 0.6, &c->zs, g.stream)) return 1;
-    if (c->zs.val) c->zs_state = 1;
-    return 0;
+// The sweep copy at creation, when the block's rows have arrived: by the rule (row_store_rule.h: hdm_sweep_copy_rule).  A block
+// whose rows live in the copy has it already.
+int cone_make_sweep_copy(MiCone *c) {
+    const HdmEnvInt zs_env = hdm_env_int<ENV_ZS>();
+    if (c->rows.form() == HDM_ROWS_EXPANDED) return 0;
+    const HdmSweepCopyRule r = hdm_sweep_copy_rule(cone_row_facts(c), c->rows.has_rows(), zs_env);
+    return r.build ? c->rows.make_sweep_copy(r.max_fill) : 0;
 }
 
 // the identity coefficient of the dual matrix: the residual and the perturbation   hdsdp_conic_sdp.c:383-385
@@ -423,19 +386,19 @@ double *cone_dual_buffer(MiCone *c, HdmDualTarget which) {
 int cone_sweep(MiCone *c, const HdmDualPoint &p, bool any, double *target) {
     HDM_HIP_CHECK(hipMemcpyAsync(c->ydev.get(), p.y, sizeof(double) * c->mloc, hipMemcpyHostToDevice, g.stream));
     const double lead = (c->rank == 0) ? 1.0 : 0.0, ctau = lead * p.tau, ceye = lead * p.eye;
-    // The sweep reads the zero-suppressed copy of the constraint data where one exists (cone_build_zs: made at creation).
-    if (any && c->zs_state == 0 && cone_build_zs(c)) return 1;
-    if (any && c->zs_state == 1) {
-        if (hdm_sym_combine_zs(c->zs, c->ydev.get(), c->Cfull.get(), ctau, ceye, target, c->n, c->n16, c->n16, g.stream)) return 1;
-    } else if (!c->streamed || !any) {
-        if (hdm_sym_combine(c->Afull.get(), c->astride, any ? c->mloc : 0, c->ydev.get(), c->Cfull.get(), ctau, ceye, target, c->n,
+    // The sweep reads the zero-suppressed copy of the constraint data where one is in use (cone_make_sweep_copy: made at creation).
+    MiRows &rows = c->rows;
+    if (any && rows.sweep_copy_in_use()) {
+        if (hdm_sym_combine_zs(rows.sweep_copy(), c->ydev.get(), c->Cfull.get(), ctau, ceye, target, c->n, c->n16, c->n16, g.stream)) return 1;
+    } else if (!rows.streamed() || !any) {
+        if (hdm_sym_combine(rows.resident(), c->astride, any ? c->mloc : 0, c->ydev.get(), c->Cfull.get(), ctau, ceye, target, c->n,
                             c->n16, c->n16, g.stream)) return 1;
     } else {
         // streamed data without a sweep copy: batch after batch, the later ones on top of what the earlier ones left in the
         // target (tau' = 1, no identity term; each element is read and rewritten by the one thread that owns it)
-        for (int q0 = 0; q0 < c->mloc; q0 += c->Bs) {
-            const int nb = std::min(c->Bs, c->mloc - q0);
-            const double *A = cone_rows(c, q0, nb);
+        for (int q0 = 0, B = rows.batch(); q0 < c->mloc; q0 += B) {
+            const int nb = std::min(B, c->mloc - q0);
+            const double *A = rows.rows(q0, nb);
             if (!A) return 1;
             if (hdm_sym_combine(A, c->astride, nb, c->ydev.get() + q0, q0 == 0 ? c->Cfull.get() : target, q0 == 0 ? ctau : 1.0,
                                 q0 == 0 ? ceye : 0.0, target, c->n, c->n16, c->n16, g.stream)) return 1;
@@ -481,11 +444,11 @@ int cone_assemble(MiCone *c, double tau, const double *y_host, HdmDualTarget whi
 
 // <A_i, X> (and <A_i, Y>) over the owned constraints: from the zero-suppressed copy when the cone has one, else from the dense storage
 int cone_sym_dot2(MiCone *c, const double *X, const double *Y, long ldx, double *outx, double *outy, double sx, double sy) {
-    if (c->zs_state == 1)
-        return hdm_sym_dot2_zs(c->zs, c->n16, c->n16, X, Y, ldx, outx, outy, c->rows_own.get(), sx, sy, g.stream);
-    for (int q0 = 0, B = cone_batch(c); q0 < c->mloc; q0 += B) {     // (one batch = everything when the data is resident)
+    if (c->rows.sweep_copy_in_use())
+        return hdm_sym_dot2_zs(c->rows.sweep_copy(), c->n16, c->n16, X, Y, ldx, outx, outy, c->rows_own.get(), sx, sy, g.stream);
+    for (int q0 = 0, B = c->rows.batch(); q0 < c->mloc; q0 += B) {     // (one batch = everything when the data is resident)
         const int nb = std::min(B, c->mloc - q0);
-        const double *A = cone_rows(c, q0, nb);
+        const double *A = c->rows.rows(q0, nb);
         if (!A || hdm_sym_dot2(A, c->astride, c->n16, c->n16, nb, X, Y, ldx, outx, outy, c->rows_own.get() + q0, sx, sy, g.stream)) return 1;
     }
     return 0;
@@ -507,7 +470,7 @@ bool small_check_switch() { return hdm_env_on<ENV_SMALL_CHECK>(); }
 // the cone as small_check_rule.h sees it; `ch`: the factor object the launch would write (nullptr: the block's own part only)
 HdmSmallCheckCone small_check_desc(const MiCone *c, const HdmChol *ch) {
     HdmSmallCheckCone d;
-    d.on = small_check_switch(); d.world = c->world; d.resident = c->Afull.get() != nullptr; d.n16 = c->n16; d.mloc = c->mloc;
+    d.on = small_check_switch(); d.world = c->world; d.resident = c->rows.resident() != nullptr; d.n16 = c->n16; d.mloc = c->mloc;
     if (ch) { d.fac_npad = ch->npad; d.fac_nblk = ch->nblk; }
     return d;
 }
@@ -528,7 +491,7 @@ HdmDualPoint small_check_point(MiCone *c, double tau, const double *y_host, doub
 // the launch's arguments for the point in the cone's block; the report word is set to -1 ("nothing reported")
 HdmSmallCheckArgs small_check_args(MiCone *c, HdmChol *ch, const HdmDualPoint &p, int whichBuffer) {
     HdmSmallCheckArgs a = {};
-    a.n = c->n; a.n16 = c->n16; a.m = c->mloc; a.A = c->Afull.get(); a.astride = c->astride; a.C = c->Cfull.get();
+    a.n = c->n; a.n16 = c->n16; a.m = c->mloc; a.A = c->rows.resident(); a.astride = c->astride; a.C = c->Cfull.get();
     a.y = c->chk.dev(); a.tau = p.tau; a.eye = p.eye;
     a.Sout = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     a.L = ch->L.get(); a.W = ch->Dinv.get(); a.out = c->chk.dev() + c->mloc;
@@ -871,7 +834,7 @@ int cone_data_norms(MiCone *c, double *rows_abs, double *rows_fro, double *obj_a
     double ra = 0.0, rf2 = 0.0, oa = 0.0, of2 = 0.0;
     // (a block on the congruence + Gram path has its data resident in A_L form: one HBM-bound pass over it instead of a host
     // loop over the CSC entries, which took 1.0 s of the driver's presolve at n = m = 2000)
-    const bool on_device = c->synthetic || (c->path == PATH_GEMM && cone_has_rows(c));   // (resident rows, or batches regenerated / expanded)
+    const bool on_device = c->synthetic || (c->path == PATH_GEMM && c->rows.has_rows());   // (resident rows, or batches regenerated / expanded)
     if (!on_device) {
         for (int i = 0; i < c->m; ++i) { double a_, f_; coeff_norms(c->blk.rows[i], c->n, &a_, &f_); ra += a_; rf2 += f_; }
         coeff_norms(c->blk.obj, c->n, &oa, &of2);
@@ -880,9 +843,9 @@ int cone_data_norms(MiCone *c, double *rows_abs, double *rows_fro, double *obj_a
         HdmBuf<double> tmp;
         HDM_HIP_CHECK(tmp.alloc(4));
         HDM_HIP_CHECK(hipMemsetAsync(tmp.get(), 0, sizeof(double) * 4, g.stream));
-        for (int q0 = 0, B = cone_batch(c); q0 < c->mloc; q0 += B) {
+        for (int q0 = 0, B = c->rows.batch(); q0 < c->mloc; q0 += B) {
             const int nb = std::min(B, c->mloc - q0);
-            const double *A = cone_rows(c, q0, nb);
+            const double *A = c->rows.rows(q0, nb);
             if (!A) return 1;
             hipLaunchKernelGGL(mi_low_norms_kernel, dim3(nb), dim3(256), 0, g.stream, A, c->astride, c->n, (long) c->n16, nb, 1, tmp.get());
         }

@@ -1,4 +1,4 @@
-// engine_create.h -- cone construction: upload of the constraint data, choice of the device path, the synthetic family
+// engine_create.h -- cone construction: choice of the device path and of the rows' form (the rows themselves: engine_rows.h), the objective, the synthetic family
 // Implementation header of engine.hip: included exactly once, there, in this order (the pieces share the anonymous namespace
 // and the engine's thread-local context `g`); split out of a 3 300-line file in round 3, nothing else changed.
 int grp_sum_launch(const double *const *ptrs, int W, long lo, long cnt, double *out, hipStream_t s) {
@@ -8,81 +8,10 @@ int grp_sum_launch(const double *const *ptrs, int W, long lo, long cnt, double *
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 // ---------------------------------------------------------------- cone construction
-// Rows of a presolved block -> A_L forms in skyline storage on the device.  The entries travel as they are -- (packed index,
-// value), 12 bytes each -- and are scattered on the device into a zeroed target (hdm_scatter_low): host threads copy a group
-// of rows into one of two pinned staging buffers while the other one crosses PCIe.  (Up to round 4 the host densified every row
-// into a packed image first -- a 16 MB memset and an 800 K-entry scatter per row on one core, one synchronisation per 16 rows:
-// most of the 14 s the reference's driver spent in its pre-solver at n = m = 2000.)
-struct RowUploader {
-    struct Stage { HdmPinned<int> hi; HdmBuf<int> di; HdmPinned<double> hv; HdmBuf<double> dv; HdmPinned<long> hb; HdmBuf<long> db; hipEvent_t ev = nullptr; bool used = false; } st[2];
-    long cap = 0;
-    static constexpr int rowcap = 1024;
-    int which = 0;
-    int init(const MiCone *c) {
-        long maxrow = 1, total = 0;
-        for (int q = 0; q < c->mloc; ++q) {
-            const long k = (long) c->blk.rows[c->own[q]].idx.size();
-            maxrow = std::max(maxrow, k);
-            total += k;
-        }
-        // entries per staging buffer: 192 MiB worth, or one row if that is more -- and never more than the block holds (a problem
-        // of many small blocks creates many cones: each would otherwise pin 384 MiB of host memory for a few KB of entries)
-        cap = std::max(maxrow, std::min((long) ((192L << 20) / 12), std::max(1L, total)));
-        for (auto &b : st) {
-            if (b.hi.alloc((size_t) cap) != hipSuccess ||
-                b.hv.alloc((size_t) cap) != hipSuccess ||
-                b.hb.alloc(rowcap + 1) != hipSuccess ||
-                b.di.alloc((size_t) cap) != hipSuccess || b.dv.alloc((size_t) cap) != hipSuccess ||
-                b.db.alloc(rowcap + 1) != hipSuccess || hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess)
-                return 1;
-        }
-        return 0;
-    }
-    // owned rows q0 .. q0 + count - 1 into the ZEROED storage at dst (stride c->astride), queued on the engine stream
-    int rows(const MiCone *c, int q0, int count, double *dst) {
-        for (int r0 = q0; r0 < q0 + count;) {
-            Stage &b = st[which];
-            which ^= 1;
-            if (b.used && hipEventSynchronize(b.ev) != hipSuccess) return 1;   // its previous group has left the buffer
-            int nc = 0;
-            long tot = 0, mx = 0;
-            long *hb = b.hb.get();
-            hb[0] = 0;
-            while (r0 + nc < q0 + count && nc < rowcap) {
-                const long k = (long) c->blk.rows[c->own[r0 + nc]].idx.size();
-                if (nc > 0 && tot + k > cap) break;
-                tot += k; mx = std::max(mx, k); nc += 1;
-                hb[nc] = tot;
-            }
-            std::atomic<int> next{0};
-            mi_parallel(tot >= (1L << 20) ? 0 : 1, [&](int) {
-                for (int q = next.fetch_add(1); q < nc; q = next.fetch_add(1)) {
-                    const MiCoeff &co = c->blk.rows[c->own[r0 + q]];
-                    if (co.idx.empty()) continue;
-                    memcpy(b.hi.get() + hb[q], co.idx.data(), sizeof(int) * co.idx.size());
-                    memcpy(b.hv.get() + hb[q], co.val.data(), sizeof(double) * co.val.size());
-                }
-            });
-            if (tot > 0) {
-                if (hipMemcpyAsync(b.di.get(), b.hi.get(), sizeof(int) * (size_t) tot, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
-                    hipMemcpyAsync(b.dv.get(), b.hv.get(), sizeof(double) * (size_t) tot, hipMemcpyHostToDevice, g.stream) != hipSuccess ||
-                    hipMemcpyAsync(b.db.get(), hb, sizeof(long) * (size_t) (nc + 1), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
-                    hdm_scatter_low(b.di.get(), b.dv.get(), b.db.get(), mx, dst + (long) (r0 - q0) * c->astride, c->astride, c->n, c->n16, nc, g.stream))
-                    return 1;
-            }
-            if (hipEventRecord(b.ev, g.stream) != hipSuccess) return 1;
-            b.used = true;
-            r0 += nc;
-        }
-        return 0;
-    }
-    ~RowUploader() {   // (the stages' buffers go after this body: once their last copies have left them)
-        for (auto &b : st) {
-            if (b.ev) (void) hipEventSynchronize(b.ev);
-            if (b.ev) (void) hipEventDestroy(b.ev);
-        }
-    }
-};
+// A cone under construction is owned: whichever way a make_* function leaves before it has handed the cone over, everything the
+// cone holds goes back through the teardown of a finished cone (engine_build_small.h: cone_destroy_data).
+struct ConeDeleter { void operator()(MiCone *c) const { void *p = c; cone_destroy_data(&p); } };
+using ConeOwner = std::unique_ptr<MiCone, ConeDeleter>;
 
 static int upload_objective(MiCone *c) {   // full symmetric (it feeds the S assembly), through a packed image
     const long P = (long) c->n * (c->n + 1) / 2;
@@ -99,82 +28,11 @@ static int upload_objective(MiCone *c) {   // full symmetric (it feeds the S ass
     return 0;
 }
 
-// every owned constraint resident as an A_L form in skyline storage
-static int upload_dense_rows(MiCone *c) {
-    HDM_HIP_CHECK(c->Afull.alloc((size_t) c->astride * std::max(1, c->mloc), hdm_operand_pad(c->n16)));
-    HDM_HIP_CHECK(hdm_memset_sync(c->Afull.get(), 0, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc)));
-    {
-        RowUploader up;
-        if (up.init(c) || up.rows(c, 0, c->mloc, c->Afull.get()) || hipStreamSynchronize(g.stream) != hipSuccess) return 1;
-    }
-    return upload_objective(c);
-}
-
-// Resident or streamed constraint data (MiCone::streamed)?  Resident needs the skyline storage of all owned rows NEXT TO what a
-// build takes -- the transformed rows, intermediates / Gram slabs, the Schur matrix with its factor and some slack; if the device
-// does not have that, the rows are regenerated per batch instead.  HDSDP_MI355X_STREAM_A=1 forces streaming (tests run small
-// blocks both ways), 0 forbids it.
+// Resident or streamed constraint rows?  The rule is row_store_rule.h's (hdm_rows_stream); the device's figures are read here.
+// (Only the congruence + Gram path asks: the other paths' rows are always resident.)
 static bool cone_wants_streaming(const MiCone *c) {
-    const double rows = (double) std::max(1, c->mloc);
-    const double afull = 8.0 * (double) c->astride * rows;
-    const double ahat = (double) hdm_exchange_bytes(cone_layout(c));
-    const double work = std::min(41.0 * (1L << 30), std::max(8.0 * (double) c->n16 * c->n16 * std::min(rows, 1024.0),
-                                                             8.0 * (double) c->R * c->R * 8.0));
-    // (the Schur matrix, its factor and its inverse blocks, plus 16 GiB of slack: at n = 2000, m = 8000 the resident form comes
-    // to 285 of the 287 GiB a fresh MI355X shows -- it has run, but nothing else may be on the device then)
-    const double schur = 3.0 * 8.0 * (double) c->m * c->m + (16.0 * (1L << 30));
-    size_t fr = 0, tot = 0;
-    bool stream = false;
-    // one device: against what is FREE now (whatever else lives on the device counts).  A shard of a sharded block
-    // (process per GPU or device group): against the device's CAPACITY, so that every rank of a job on identical devices
-    // takes the same decision -- streaming changes the launch staging, and ranks that disagreed would run differently
-    // labelled, differently timed steps (equal results); a resident allocation that then fails is an error with a message.
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess)
-        stream = (afull + ahat + work + schur > (c->world > 1 ? 0.97 * (double) tot : (double) fr));
-    (void) hipGetLastError();
-    if (const HdmEnvInt e = hdm_env_int<ENV_STREAM_A>(); e.set) stream = (int) e.value != 0;
-    return stream && c->mloc > 0;
-}
-static int cone_alloc_batch(MiCone *c) {
-    // batch = what one congruence launch takes: HDM_BC clamped to at least 1 here, launches evened out as the plan's are
-    // (work_plan.h: HdmKnobs::bc_max says which clamp the plan applies)
-    c->Bs = (int) hdm_even_out(c->mloc, std::max(1L, hdm_knobs_from_env().bc_max));
-    if (c->Abatch.alloc((size_t) c->astride * c->Bs, hdm_operand_pad(c->n16)) != hipSuccess) {
-        fprintf(stderr, "[hdsdp_mi355x] cannot allocate %.1f GiB for a batch of constraint matrices\n", (double) c->astride * c->Bs * 8 / (1 << 30));
-        return 1;
-    }
-    return hdm_memset_sync(c->Abatch.get(), 0, sizeof(double) * (size_t) c->astride * c->Bs) != hipSuccess;
-}
-
-// INGESTED rows that are too many to stay resident (round 5): batch after batch they are scattered into the batch buffer and
-// compressed into the zero-suppressed copy (two passes: counts, then values -- every batch crosses PCIe twice), which from then
-// on is the ONLY image of the constraint data: the sweeps read it as they always do, and whoever needs the dense A_L forms
-// (the congruence, norms, A X) has a batch expanded from it (cone_rows -> hdm_zs_expand) -- what the counter-based generator
-// does for the synthetic family.  n = 2000, m = 8000 at 40 % fill: 57 GB instead of 136.
-static int upload_streamed_rows(MiCone *c) {
-    if (cone_alloc_batch(c)) return 1;
-    {
-        RowUploader up;
-        if (up.init(c)) return 1;
-        bool bad = false;
-        auto source = [&](int q0, int nb) -> const double * {
-            if (hipMemsetAsync(c->Abatch.get(), 0, sizeof(double) * (size_t) c->astride * nb, g.stream) != hipSuccess || up.rows(c, q0, nb, c->Abatch.get())) { bad = true; return nullptr; }
-            return c->Abatch.get();
-        };
-        if (hdm_zs_build_from(source, c->Bs, c->astride, c->mloc, c->astride, 1.0, &c->zs, g.stream) || bad) return 1;
-        if (hipStreamSynchronize(g.stream) != hipSuccess) return 1;
-    }
-    if (!c->zs.val) {
-        fprintf(stderr, "[hdsdp_mi355x] block n = %d, m = %d: no room for the compressed copy its streamed rows live in\n", c->n, c->mloc);
-        return 1;
-    }
-    c->zs_state = 1;
-    c->rows_from_zs = true;
-    c->streamed = true;
-    fprintf(stderr, "[hdsdp_mi355x] block n = %d, m = %d: %.1f GiB of constraint data are kept as a %.1f GiB zero-suppressed copy and expanded %d matrices at a time, not resident\n",
-            c->n, c->mloc, (double) c->astride * c->mloc * 8 / (1 << 30),
-            (8.0 * (double) c->zs.nnz + 192.0 * (double) c->zs.nchunk * c->mloc) / (1 << 30), c->Bs);
-    return upload_objective(c);
+    const HdmRowFacts f = cone_row_facts(c);
+    return hdm_rows_stream(f, f.gemm_path ? device_facts() : HdmDeviceFacts(), hdm_env_int<ENV_STREAM_A>());
 }
 
 // device path a block takes by itself: the rank-one fast path iff every non-zero constraint is rank one (the reference's
@@ -264,7 +122,8 @@ static int cone_plan_direct_rows(MiCone *c, int natural, bool force_gemm, bool f
 static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bool take, int rank, int world) {
     if (ensure_ctx()) return HDSDP_RETCODE_FAILED;
     const int nRow = src.m, nCol = src.n;
-    MiCone *c = new MiCone();
+    ConeOwner owner(new MiCone());
+    MiCone *c = owner.get();
     c->n = nCol; c->m = nRow; c->rank = rank; c->world = world;
     if (world > 1) hdm_gemm_reserve_cus(8);   // the exchange's collectives run beside the persistent GEMM launches
     if (take) c->blk = std::move(src);
@@ -295,9 +154,10 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
     {
         CreateTimer t_(1);
         // (rows too many to stay resident beside the work buffers -- congruence + Gram path only -- live in the compressed copy)
-        const bool stream = (c->path == PATH_GEMM) && cone_wants_streaming(c);
+        const bool stream = cone_wants_streaming(c);
         if (cone_plan_direct_rows(c, natural, force, forcesp.set, stream)) return HDSDP_RETCODE_MEMORY;
-        if (stream ? upload_streamed_rows(c) : upload_dense_rows(c)) return HDSDP_RETCODE_MEMORY;   // the dense forms also feed the S assembly
+        if (stream ? c->rows.ingest_expanded(cone_row_shape(c), c->blk) : c->rows.upload_resident(cone_row_shape(c), c->blk)) return HDSDP_RETCODE_MEMORY;   // the dense forms also feed the S assembly
+        if (upload_objective(c)) return HDSDP_RETCODE_MEMORY;
     }
     if (c->path == PATH_R1) {
         c->mloc16 = (int) hdm_roundup(std::max(1, c->mloc), 16);
@@ -355,33 +215,20 @@ static hdsdp_retcode make_sdp_cone_from_block(MiCone **out, MiBlockData &src, bo
     if (c->path == PATH_GEMM) { for (MiCoeff &co : c->blk.rows) co.release(); c->blk.obj.release(); }
     {
         CreateTimer t_(2);
-        if (cone_build_zs(c)) return HDSDP_RETCODE_FAILED;
+        if (cone_make_sweep_copy(c)) return HDSDP_RETCODE_FAILED;
     }
-    *out = c;
+    *out = owner.release();
     return HDSDP_RETCODE_OK;
 }
 
 static hdsdp_retcode make_synth_cone(MiCone **out, int nCol, int nRow, int rank, int world) {
     if (ensure_ctx()) return HDSDP_RETCODE_FAILED;
-    MiCone *c = new MiCone();
+    ConeOwner owner(new MiCone());
+    MiCone *c = owner.get();
     c->n = nCol; c->m = nRow; c->rank = rank; c->world = world; c->synthetic = true; c->path = PATH_GEMM;
     if (world > 1) hdm_gemm_reserve_cus(8);
     if (cone_alloc_common(c)) return HDSDP_RETCODE_MEMORY;
-    c->streamed = cone_wants_streaming(c);
-    if (c->streamed) {
-        if (cone_alloc_batch(c)) return HDSDP_RETCODE_MEMORY;
-        fprintf(stderr, "[hdsdp_mi355x] block n = %d, m = %d: %.1f GiB of constraint data are streamed (regenerated %d matrices at a time), not resident\n",
-                c->n, c->mloc, (double) c->astride * c->mloc * 8 / (1 << 30), c->Bs);
-    } else {
-        if (c->Afull.alloc((size_t) c->astride * std::max(1, c->mloc), hdm_operand_pad(c->n16)) != hipSuccess) {
-            fprintf(stderr, "[hdsdp_mi355x] cannot allocate %.1f GiB for the constraint matrices\n",
-                    (double) c->astride * c->mloc * 8 / (1 << 30));
-            return HDSDP_RETCODE_MEMORY;
-        }
-        if (hdm_memset_sync(c->Afull.get(), 0, sizeof(double) * (size_t) c->astride * std::max(1, c->mloc)) != hipSuccess) return HDSDP_RETCODE_FAILED;
-        for (int q = 0; q < c->mloc; ++q)  // owned rows are strided in the global numbering
-            if (hdm_synth_fill_low(c->Afull.get() + (long) q * c->astride, c->astride, c->n, c->n16, c->own[q], 1, g.stream)) return HDSDP_RETCODE_FAILED;
-    }
+    if (const hdsdp_retcode rc = c->rows.generate(cone_row_shape(c), cone_wants_streaming(c)); rc != HDSDP_RETCODE_OK) return rc;
     if (hdm_synth_obj(c->Cfull.get(), c->n, c->n16, c->m, g.stream)) return HDSDP_RETCODE_FAILED;
     // b_i = tr(A_i): diagonal draws only (host, m*n splitmix evaluations)
     c->trA.assign((size_t) nRow, 0.0);
@@ -400,7 +247,7 @@ static hdsdp_retcode make_synth_cone(MiCone **out, int nCol, int nRow, int rank,
         c->trA[i] = tr;
     }
     if (hipStreamSynchronize(g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
-    if (cone_build_zs(c)) return HDSDP_RETCODE_FAILED;
-    *out = c;
+    if (cone_make_sweep_copy(c)) return HDSDP_RETCODE_FAILED;
+    *out = owner.release();
     return HDSDP_RETCODE_OK;
 }

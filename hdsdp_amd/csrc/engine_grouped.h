@@ -10,7 +10,7 @@
 bool grouped_kind_ok(const hdsdp_cone *hc) {
     if (hc->coneBuildSchur != cone_build_schur) return false;
     const MiCone *c = (const MiCone *) hc->coneData;
-    if (c->world != 1 || c->synthetic || c->streamed || !c->Afull.get() || !c->dualFactor) return false;
+    if (c->world != 1 || c->synthetic || c->rows.streamed() || !c->rows.resident() || !c->dualFactor) return false;
     const HdmChol &ch = ((const MiLin *) c->dualFactor->chol)->ch;
     return ch.nblk == 1 && ch.npad == SMALL_P;
 }
@@ -95,7 +95,7 @@ hdsdp_retcode grouped_build(hdsdp_kkt *HKKT, MiKKTPriv *pv, int typeKKT) {
         }
         HdmGroupedConeDev &d = gr.cones_host.get()[s];
         d.n = c->n; d.n16 = c->n16; d.mloc = c->mloc; d.pad = 0;
-        d.W = ch.Dinv.get(); d.A = c->Afull.get(); d.C = c->Cfull.get(); d.Rd = c->Rd;
+        d.W = ch.Dinv.get(); d.A = c->rows.resident(); d.C = c->Cfull.get(); d.Rd = c->Rd;
         d.xoff = p.xoff[(size_t) s]; d.goff = p.goff[(size_t) s]; d.voff = p.voff[(size_t) s];
     }
     // (the pinned block is free to be rewritten: every build ends in kkt_pull's synchronisation)

@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256) void hdm_zs_fill_kernel(const double *__restri
 // The copy back into A_L-form skyline storage: matrices c0 .. c0 + count - 1 of the copy, chunk by chunk (zeros where the mask has
 // none).  A cone whose ingested rows are too many to stay resident keeps ONLY the copy and expands a batch of rows whenever the
 // congruence (or any other reader of the dense form) asks for one -- what the counter-based generator does for the synthetic
-// family (engine_cone.h: cone_rows).  blockIdx.y splits the matrices of a chunk over several workgroups.
+// family (engine_rows.h: MiRows::rows).  blockIdx.y splits the matrices of a chunk over several workgroups.
 __global__ __launch_bounds__(256) void hdm_zs_expand_kernel(const unsigned long long *__restrict__ meta, const double *__restrict__ val,
                                                              const unsigned long long *__restrict__ base, int mtot, int c0, int count,
                                                              double *__restrict__ A, long astride, long sky) {

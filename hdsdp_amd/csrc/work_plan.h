@@ -1,7 +1,7 @@
 // work_plan.h -- how much work space a dense block's Schur build on the congruence + Gram path takes: the block's layout, the
 // environment knobs, and the plan (constraints per congruence launch, K splits and slabs of the Gram product, buffer sizes).
 // Pure host arithmetic on integers and doubles: no HIP call, no allocation, no engine state, no I/O -- the engine allocates
-// what this header says (engine_cone.h: cone_alloc_common, cone_alloc_gemm_work; engine_create.h: cone_alloc_batch), and
+// what this header says (engine_cone.h: cone_alloc_common, cone_alloc_gemm_work; row_store_rule.h: hdm_rows_batch for a streamed block's batch buffer), and
 // HMiWorkPlanQuery hands the same numbers to callers without a device (hdsdp_amd/dist.py: ShardPlan.hbm_bytes).
 #pragma once
 #include "env_switches.h"
@@ -50,7 +50,7 @@ static inline size_t hdm_operand_pad(long ld) { return (size_t) 128 * (size_t) (
 #define HDM_OPERAND_PAD_DOUBLES 8192   /* the same slack for the [p-block][row][16] congruence output, in doubles */
 // Elements readable from the start of each operand buffer of the Schur build, slack included -- what a role launch vouches for
 // (gemm_calls.h), never more than the allocation: the intermediates T of `Bc` matrices, the factor inverse (npad x npad), a
-// buffer of `rows` skyline matrices (Afull, a regenerated batch, CL), an exchange buffer, the LP cone's dense buffer.
+// buffer of `rows` skyline matrices (the resident rows, a regenerated batch, CL), an exchange buffer, the LP cone's dense buffer.
 static inline long hdm_t_span(const HdmLayout &L, long Bc) { return (long) L.n16 * L.n16 * Bc + (long) (hdm_operand_pad(L.n16) / sizeof(double)); }
 static inline long hdm_linv_span(long npad) { return npad * npad; }
 static inline long hdm_afull_span(const HdmLayout &L, long rows) { return L.astride * rows + (long) (hdm_operand_pad(L.n16) / sizeof(double)); }
@@ -65,7 +65,7 @@ struct HdmKnobs {
     long tcap_gib = 32;             // HDM_TCAP_GIB: GiB of congruence intermediates
     // HDM_BC, as written (not clamped here).  The plan takes min(memory bound, bc_max) and clamps THAT to at least 1
     // (hdm_work_plan); the batch of regenerated rows clamps bc_max itself to at least 1 before it evens the launches out
-    // (engine_create.h: cone_alloc_batch).  Both come to 1 row per launch for HDM_BC <= 0.
+    // (row_store_rule.h: hdm_rows_batch).  Both come to 1 row per launch for HDM_BC <= 0.
     long bc_max = 1024;
     long gram_kstages = 0;          // HDM_GRAM_KSTAGES: stages per Gram job at any size (>= 1); 0 = by size.  One device only.
     bool nsplit_set = false;        // HDM_NSPLIT: the slab count, within [1, kblocks / 16]

@@ -358,7 +358,7 @@ void HMiConeGetDirectRows(hdsdp_cone *cone, int *nDirect, int *nRankOne, int *nC
 /* the zero-suppressed copy of the constraint data the S / dS sweeps read (csrc/schur.h: HdmZs): returns 1 and the number of
  * stored values / of skyline positions it stands for when the cone has built one, 0 when its sweeps read the dense storage */
 int HMiConeSweepInfo(hdsdp_cone *cone, int64_t *values, int64_t *positions);
-/* Streamed constraint data (synthetic family, csrc/engine_cone.h: MiCone::streamed): when the A_L forms of all owned rows do
+/* Streamed constraint data (synthetic family; csrc/row_store_rule.h): when the A_L forms of all owned rows do
  * not fit next to what a build needs -- BASELINE configs[4], n = 2000, m = 8000, on ONE device: 136 GB of them beside 130 GB of
  * transformed rows -- HMiConeCreateSynthetic keeps none of them: every consumer (congruence batches, S / dS sweeps without a
  * sweep copy, corrector dots, norms, A X) regenerates the rows it needs into a batch buffer from the counter-based generator,
@@ -606,7 +606,7 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           built without the congruence (direct_rows.h); 0: off; k > 0: on
  *                                           whatever the size, up to k entries per row.  Read at cone creation
  *  HDSDP_MI355X_STREAM_A          by memory 0 / 1: synthetic constraint data resident / regenerated per     test_gpu_streamed.py
- *                                           batch (MiCone::streamed)
+ *                                           batch
  *  HDSDP_MI355X_DEVICE_M          0         1: HKKTInit turns the host mirror of M off when no cone of    test_gpu_device_m.py
  *                                           cones[] is a host cone (diagonal channel); else one stderr line
  *  HDSDP_MI355X_GROUPED_BUILD     0         1: HKKTInit turns the grouped Schur build on (all eligible    test_gpu_grouped_build.py

@@ -460,6 +460,25 @@ def test_every_environment_switch_is_listed_in_the_header_and_covered(tmp_path):
             assert m.group(1) in run, m.group(1) + " is said to be covered by test_gpu_switches.py but no setting names it"
 
 
+def test_a_cones_constraint_rows_are_named_only_inside_their_store():
+    """the constraint rows of an SDP cone have one owner (csrc/engine_rows.h: MiRows).  The loose fields and the
+    three-valued state they used to be are gone from the sources, and the storage is named in the owner's file alone --
+    elsewhere only a comment may speak of it"""
+    csrc = os.path.join(ROOT, "hdsdp_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp"))}
+    owner = [f for f, txt in sources.items() if re.search(r"^(?:struct|class) MiRows\b", txt, flags=re.M)]
+    assert owner == ["engine_rows.h"]
+    for f, txt in sources.items():
+        for gone in ("zs_state", "rows_from_zs", "->streamed"):
+            assert gone not in txt, (f, gone)
+        if f in owner:
+            continue
+        code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+        code = "\n".join(line.split("//")[0] for line in code.splitlines())
+        for name in ("Afull", "Abatch"):
+            assert not re.search(r"\b%s\b" % name, code), (f, name)
+
+
 def test_full_stages_of_the_gemm_roles_carry_no_vector_alu_instruction(tmp_path):
     """every vector ALU instruction between the MFMAs of the fp64 GEMM K loop costs the matrix pipe about 11 cycles
     (profiles/r04_h_issue_mix.txt), so the stage body's addressing is arranged to need none.  That is a property of the machine

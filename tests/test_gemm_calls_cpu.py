@@ -126,7 +126,7 @@ def test_congruence_forms(driver):
     for L, plan_bc, _ in grid(driver):
         n, n16, nn, ldl = L["n"], L["n16"], L["n16"] ** 2, L["npad"]
         n3 = (float(n) * n) * n
-        rows_held = max(1, L["mloc"])                                     # matrices behind Afull
+        rows_held = max(1, L["mloc"])                                     # matrices behind the resident rows
         afull = L["astride"] * rows_held + operand_pad(n16)               # what the engine allocates for it
         for Bc in sorted({1, 8, plan_bc}):
             t_buf = nn * Bc + operand_pad(n16)

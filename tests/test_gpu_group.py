@@ -111,7 +111,7 @@ def test_in_process_shards_match_one_device(n, m, world, group):
 
 
 def test_streamed_shards_match_one_resident_device(group, monkeypatch):
-    """streamed constraint data (MiCone::streamed) under sharding: every shard regenerates ITS rows (cyclic deal: one launch of the
+    """streamed constraint data (csrc/engine_rows.h: MiRows) under sharding: every shard regenerates ITS rows (cyclic deal: one launch of the
     generator per row) batch by batch; three shards with batches of 8 rows against one device with resident data"""
     from hdsdp_amd import api
     n, m, world = 200, 70, 3

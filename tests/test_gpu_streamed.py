@@ -1,4 +1,4 @@
-"""Streamed constraint data (include/hdsdp_mi355x.h: HMiConeGetStreaming; csrc/engine_cone.h: MiCone::streamed): the synthetic
+"""Streamed constraint data (include/hdsdp_mi355x.h: HMiConeGetStreaming; csrc/engine_rows.h: MiRows): the synthetic
 family's A_L forms regenerated per batch instead of kept resident -- what lets BASELINE configs[4] (n = 2000, m = 8000: 136 GB
 of constraint data beside 130 GB of transformed rows) run on ONE MI355X.  Small blocks are run both ways and must agree; the
 workload itself is held to the independent host-fp64 fixture tests/golden/full8000_rows.npz."""
@@ -108,8 +108,8 @@ def test_config5_at_size_on_one_device(mode, monkeypatch):
 
 @pytest.mark.parametrize("name,bc", [("syn96x40_B", 16), ("syn200", 64), ("mix40_B", 8)])
 def test_ingested_rows_kept_only_as_the_compressed_copy(name, bc, monkeypatch):
-    """round 5: INGESTED rows that do not stay resident live in the zero-suppressed copy alone (csrc/engine_create.h:
-    upload_streamed_rows) and a batch of A_L forms is expanded from it wherever the dense form is read (congruence, data norms,
+    """round 5: INGESTED rows that do not stay resident live in the zero-suppressed copy alone (csrc/engine_rows.h:
+    MiRows::ingest_expanded) and a batch of A_L forms is expanded from it wherever the dense form is read (congruence, data norms,
     A X, indefinite-X builds) -- what the counter-based generator does for the synthetic family.  A CSC block taken in both ways
     (HDSDP_MI355X_STREAM_A = 0 / 1, several batches with a ragged last one) gives the same operator in every quantity, with the
     sweeps reading the copy and with the sweeps expanding batches; and the reference's numbers (the golden's M)."""
@@ -153,6 +153,57 @@ def test_ingested_rows_kept_only_as_the_compressed_copy(name, bc, monkeypatch):
             cone.destroy()
     _compare(out[0], out[1], m, tol=1e-12)
     _compare(out[0], out[2], m, tol=1e-12)
+
+
+def test_expanded_rows_under_the_sweep_copy_switch(monkeypatch):
+    """the EXPANDED form (csrc/row_store_rule.h: ingested rows that live in the zero-suppressed copy alone) with the sweep copy
+    switched on, off and on again: the copy stays -- it is the only image of the data -- and only the sweeps' route changes.  A
+    dense ingested block, n = 40, m = 11 in batches of 4, 4 and 3: the dual matrix at one point from the copy, batch by batch
+    (another summation order: 1e-12), and from the copy again (the same bits); then a Phase-A pass against the same block
+    kept resident."""
+    from hdsdp_amd import api
+    from test_gpu_group import _phase_a, _compare
+    from util import lower_mask
+    n, m = 40, 11
+    P = n * (n + 1) // 2
+    rng = np.random.default_rng(20261020)
+    from test_gpu_parity import _splitmix_u
+    from test_gpu_ingest import _packed_positions
+    A = rng.uniform(-1.0, 1.0, size=(m, P))                          # every packed position of every constraint stored
+    ii, jj = _packed_positions(n)
+    y0 = _splitmix_u(np.uint64(2 * m * P) + np.arange(m, dtype=np.uint64))
+    Cp = (ii == jj).astype(np.float64) + y0 @ A                      # C = I + sum y0_i A_i: strictly feasible at the y0 _phase_a recovers X near
+    val = np.concatenate([Cp, A.ravel()])                            # column 0 = C
+    beg = (np.arange(m + 2) * P).astype(np.int32)
+    idx = np.tile(np.arange(P, dtype=np.int32), m + 1)
+    Rd, tau = -2.5 * n, 0.8
+    y = 0.03 * np.sin(1.1 * np.arange(m) + 0.2)
+    monkeypatch.setenv("HDM_BC", "4")
+    out = {}
+    for stream in ("1", "0"):
+        monkeypatch.setenv("HDSDP_MI355X_STREAM_A", stream)
+        cone = api.SDPCone.from_csc(n, m, beg, idx, val)
+        try:
+            assert cone.streaming() == ((True, 4) if stream == "1" else (False, 0))
+            if stream == "1":
+                cone.set_start(Rd)
+                S = []
+                for on in (True, False, True):
+                    cone.use_sweep_copy(on)
+                    assert cone.sweep_info()[0] == on
+                    assert cone.check_is_interior(tau, y)
+                    S.append(cone.dual_matrix().copy())
+                low = lower_mask(n)
+                assert np.array_equal(S[0][low], S[2][low])
+                print("expanded rows, S batch by batch against S from the copy: max abs difference %.3e of %.3e"
+                      % (np.max(np.abs(S[1][low] - S[0][low])), np.max(np.abs(S[0][low]))))
+                _compare({"S": S[0]}, {"S": S[1]}, m, tol=1e-12)
+            kkt = api.KKT(m, [cone])
+            out[stream] = _phase_a(api, cone, kkt, Rd, y)
+            kkt.destroy()
+        finally:
+            cone.destroy()
+    _compare(out["0"], out["1"], m, tol=1e-12)
 
 
 def test_an_ingested_config5_block_fits_one_device():
