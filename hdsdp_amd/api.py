@@ -42,6 +42,7 @@ EXPORTS = [
     "HMiGemmRoleLayout", "HMiGemmRoleSpan", "HMiCongStep1", "HMiCongStep2", "HMiCongIRow", "HMiGramSplits", "HMiGramGathered", "HMiGramLp",
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
     "HMiKKTSetGroupedCheck", "HMiKKTGetGroupedCheck", "HMiKKTCheckIsInterior",
+    "HMiKKTSetGroupedRatio", "HMiKKTGetGroupedRatio", "HMiKKTRatioTest",
     "HMiLinsysSetRefine", "HMiLinsysGetRefine", "HMiLinsysRefineBytes", "HMiKKTSetRefine", "HMiSymResidualProbe",
     "HMiLinsysSetRefineTiles", "HMiLinsysGetRefineTiles", "HMiKKTSetRefineTiles", "HMiTileResidualProbe", "HMiBspRefinedSolve", "HMiBspRefineTimingProbe",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
@@ -303,6 +304,9 @@ def load_library():
         "HMiKKTSetGroupedCheck": (C.c_int, [kp, C.c_int]),
         "HMiKKTGetGroupedCheck": (C.c_int, [kp, C.POINTER(C.c_long)]),
         "HMiKKTCheckIsInterior": (C.c_int, [kp, C.c_double, dp, ip, dp, ip]),
+        "HMiKKTSetGroupedRatio": (C.c_int, [kp, C.c_int]),
+        "HMiKKTGetGroupedRatio": (C.c_int, [kp, C.POINTER(C.c_long)]),
+        "HMiKKTRatioTest": (C.c_int, [kp, C.c_double, dp, C.c_double, C.c_int, dp, dp]),
         "HMiLinsysSetRefine": (C.c_int, [vp, C.c_int]),
         "HMiLinsysGetRefine": (C.c_int, [vp, ip, ip, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "HMiLinsysRefineBytes": (C.c_int64, [vp]),
@@ -1086,6 +1090,29 @@ class KKT:
         _check(load_library().HMiKKTCheckIsInterior(self._k, float(tau), _dptr(y), _iptr(flags), _dptr(logdets), C.byref(every)),
                "HMiKKTCheckIsInterior")
         return flags.astype(bool), logdets, bool(every.value)
+
+    def set_grouped_ratio(self, on):
+        """HMiKKTSetGroupedRatio: a ratio test on the dual buffer asked of one member of the operator's ratio set runs every
+        member's test in one pair of launches (csrc/small_ratio_rule.h has the rule); the later calls fetch their answers.
+        Returns the number of members (0: off, or fewer than two members)"""
+        return int(load_library().HMiKKTSetGroupedRatio(self._k, 1 if on else 0))
+
+    def grouped_ratio_info(self):
+        """HMiKKTGetGroupedRatio: dict(on, members, launches, last_cones, total_cones, from_slots, left_out, fallbacks)"""
+        out = (C.c_long * 7)()
+        on = load_library().HMiKKTGetGroupedRatio(self._k, out)
+        return {"on": bool(on), "members": out[0], "launches": out[1], "last_cones": out[2], "total_cones": out[3],
+                "from_slots": out[4], "left_out": out[5], "fallbacks": out[6]}
+
+    def ratio_test(self, dtau_step, dy, ada_ratio=0.0, buffer=BUFFER_DUALVAR):
+        """HMiKKTRatioTest: every cone of the operator along (dtau_step, dy), in order and without early exit; returns
+        (steps, min_step): steps[k] is NaN where cone k's slot failed"""
+        dy = np.ascontiguousarray(dy, dtype=np.float64)
+        steps = np.full(len(self.cones), np.nan)
+        mn = C.c_double(0.0)
+        _check(load_library().HMiKKTRatioTest(self._k, float(dtau_step), _dptr(dy), float(ada_ratio), buffer, _dptr(steps),
+                                              C.byref(mn)), "HMiKKTRatioTest")
+        return steps, mn.value
 
     def diag_target(self):
         """HMiKKTGetDiagTarget: 0 = kktDiag[] points into kktMatElem, 1 = into the diagonal channel"""

@@ -96,6 +96,7 @@ class HdmDualState {
     bool pS_ok = false, pD_ok = false;
     int aff_chain = 0;                   // updates of S in place since its last full assembly
     bool fac_ok = false; int fac_psd = 0;   // the dual factor object holds the factorisation of S = T(pS) (result: fac_psd)
+    unsigned long n_moves = 0;           // transitions so far: whoever keeps something derived from S, dS or the factor compares it
     friend HdmDualPlan hdm_dual_plan(const HdmDualState &, const HdmDualPoint &, HdmDualTarget, int, int);
     friend void hdm_dual_print_miss(FILE *, const HdmDualState &, const HdmDualPoint &, HdmDualTarget, const HdmDualPlan &);
 
@@ -109,27 +110,31 @@ public:
         return true;
     }
 
+    // every transition below counts here; a value read after one and found again later says that none has happened in between
+    // (small_ratio_rule.h: a stored ratio-test answer is served only then)
+    unsigned long moves() const { return n_moves; }
+
     // Transitions, named for what happened.  Whatever moves S leaves its factor behind.
     // S assembled at p: a sweep of a tracking block, or the one-launch small check (which assembles S itself)
-    void S_assembled_at(const HdmDualPoint &p) { p.store(pS); pS_ok = true; aff_chain = 0; fac_ok = false; }
+    void S_assembled_at(const HdmDualPoint &p) { n_moves += 1; p.store(pS); pS_ok = true; aff_chain = 0; fac_ok = false; }
     // dS assembled at p (every ratio test, the primal recovery: a request on the OLD line is then off the new one)
-    void dS_assembled_at(const HdmDualPoint &p) { p.store(pD); pD_ok = true; }
+    void dS_assembled_at(const HdmDualPoint &p) { n_moves += 1; p.store(pD); pD_ok = true; }
     // S advanced along the line to p: S <- S + alpha dS (+ delta I) in place
-    void S_advanced_to(const HdmDualPoint &p) { p.store(pS); aff_chain += 1; fac_ok = false; }
+    void S_advanced_to(const HdmDualPoint &p) { n_moves += 1; p.store(pS); aff_chain += 1; fac_ok = false; }
     // S written by someone else, at a point this state is not told: the next request assembles it.
     //  * S += step dS without a point being named (cone_axpy_check on the dual buffer);
     //  * the fused Phase-A pass writes S itself (HMiKKTPhaseA);
     //  * a sweep of a block that does not track points.
-    void S_overwritten() { pS_ok = false; fac_ok = false; }
+    void S_overwritten() { n_moves += 1; pS_ok = false; fac_ok = false; }
     // the data under S and dS changed: both are T of nothing known, no short-cut from them.
     //  * the objective was rescaled (cone_scal): S and dS were assembled with the old one;
     //  * the sweep copy was switched (HMiConeUseSweepCopy): the next request is assembled, not short-cut.
-    void data_changed() { pS_ok = pD_ok = false; fac_ok = false; }
+    void data_changed() { n_moves += 1; pS_ok = pD_ok = false; fac_ok = false; }
     // S factored with result r, in the dual factor object, by a path that keeps the result (the one-launch small check)
-    void S_factored(int psd) { fac_ok = true; fac_psd = psd; }
+    void S_factored(int psd) { n_moves += 1; fac_ok = true; fac_psd = psd; }
     // the factor no longer follows S: S moves and its factor does not (cone_update), or the factor object is being rewritten by
     // a path that does not record its result (cone_factor_S)
-    void factor_stale() { fac_ok = false; }
+    void factor_stale() { n_moves += 1; fac_ok = false; }
 
     // what performing `plan` for a request of T(p) into `target` did to the buffers
     void commit(const HdmDualPlan &plan, const HdmDualPoint &p, HdmDualTarget target) {

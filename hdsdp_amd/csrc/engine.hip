@@ -141,6 +141,7 @@ namespace {
 #include "engine_build_small.h"
 #include "engine_grouped.h"
 #include "engine_check_set.h"
+#include "engine_ratio_set.h"
 }  // namespace
 
 // =============================================================================================

@@ -124,6 +124,7 @@ void cone_destroy_data(void **pcd) {
     if (!pcd || !*pcd) return;
     MiCone *c = (MiCone *) *pcd;
     check_set_forget(c);
+    ratio_set_forget(c);
     HFpLinsysDestroy(&c->dualFactor);
     for (hipEvent_t e : c->piece_ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->pe_s2) if (e) (void) hipEventDestroy(e);

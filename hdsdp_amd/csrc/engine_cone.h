@@ -8,6 +8,7 @@ enum { PATH_GEMM = 0, PATH_R1 = 1, PATH_SPARSE = 2 };
 
 struct MiKKTPriv;
 struct MiCheckSet;
+struct MiRatioSet;
 
 struct MiCone {
     int n = 0, m = 0;          // block dimension, global number of constraints
@@ -129,6 +130,9 @@ struct MiCone {
     // HKKTInit, cleared by the set (HKKTInit again, HKKTClear) and by this cone's destruction, whichever comes first.
     MiCheckSet *chk_set = nullptr;
     int chk_slot = -1;
+    // the same for the ratio set (engine_ratio_set.h), with the same lifetime rules
+    MiRatioSet *rat_set = nullptr;
+    int rat_slot = -1;
     // fused single-launch Phase-A pass of a small rank-one block (small.hip): factors as a CSR, built on first use
     struct SmallPlan {
         int state = 0;         // 0 = not looked at, 1 = ready, -1 = not eligible
@@ -183,9 +187,35 @@ struct MiCheckSet {
     ~MiCheckSet() { release(); }
 };
 
+// The ratio set of an operator (engine_ratio_set.h performs it): the small SDP cones whose ratio test on the
+// dual buffer -- "how far along (dTauStep, dy)?" -- is run for ALL of them by one pair of launches the first time one of them is
+// asked a question its slot does not hold.  HKKTInit decides membership (small_ratio_rule.h); the switch allocates the table, the
+// multipliers' staging block and every member's Lanczos object and step buffer, so that a launch allocates nothing.
+struct MiRatioSet {
+    bool on = false;                       // HMiKKTSetGroupedRatio / HDSDP_MI355X_GROUPED_RATIO
+    std::vector<MiCone *> members;         // in cones[] order; nullptr: destroyed since HKKTInit (not owned)
+    std::vector<HdmRatioSlot> slots;       // one per member: the answer of the last launch it was in (small_ratio_rule.h)
+    std::vector<long> yoff;                // one per member: where its multipliers start in `ybuf`
+    HdmPinned<HdmGroupedRatioArgs> table;  // mapped pinned, one entry per member: the launch's arguments, launched members first
+    HdmPinned<double> ybuf;                // mapped pinned: the members' gathered multipliers
+    std::vector<int> launched;             // slots of the members in the launch being made
+    // HMiKKTGetGroupedRatio: launches, cones in the last one, cones launched in all, answers served from slots, members left out
+    // of the last launch, safeguard fallbacks (members whose step left the cone and took the host's fresh-start test and cuts)
+    long launches = 0, last_cones = 0, total_cones = 0, from_slots = 0, last_left_out = 0, fallbacks = 0;
+    int count() const { int k = 0; for (const MiCone *c : members) k += c ? 1 : 0; return k; }
+    void release() {                       // the members are free again (for another operator's set)
+        for (MiCone *c : members) if (c) { c->rat_set = nullptr; c->rat_slot = -1; }
+        members.clear(); slots.clear(); yoff.clear();
+        table.reset(); ybuf.reset();
+        on = false;
+    }
+    ~MiRatioSet() { release(); }
+};
+
 struct MiKKTPriv {
     MiGrouped grp;
     MiCheckSet chk;
+    MiRatioSet rat;
     // how M is stored, what state it is in and where the last factorised matrix came from (kkt_store.h); the operator's linear
     // system (MiLin::st) points here
     HdmKktState st;
@@ -614,8 +644,16 @@ hdsdp_retcode cone_axpy_check(void *cd, double dStep, int whichBuffer, int *isIn
     return (whichBuffer == 0) ? cone_factor_S(c, isInterior) : cone_factor_check(c, isInterior);
 }
 
-void cone_reduce_resi(void *cd, double resiReduction) { ((MiCone *) cd)->Rd = resiReduction; }   // :2224-2228
-void cone_set_perturb(void *cd, double dDualPerturb) { ((MiCone *) cd)->perturb = dDualPerturb; }  // :2236-2241
+// engine_ratio_set.h: a member's stored ratio-test answer is dropped (the identity coefficients are part of no dual-state
+// transition, and an answer is served only while nothing at all has changed under it); nothing else happens
+void ratio_set_drop_answer(MiCone *c);
+void ratio_set_forget(MiCone *c);   // c is being destroyed: its set no longer names it
+// c is a member of an active set and is asked (dTauStep, dy, dAdaRatio) on the dual buffer.  Returns true when the set has
+// answered (*rc, *maxStep), false when c's own path must run
+bool ratio_set_answer(MiCone *c, double dTauStep, const double *dy, double dAdaRatio, double *maxStep, hdsdp_retcode *rc);
+
+void cone_reduce_resi(void *cd, double resiReduction) { ((MiCone *) cd)->Rd = resiReduction; ratio_set_drop_answer((MiCone *) cd); }   // :2224-2228
+void cone_set_perturb(void *cd, double dDualPerturb) { ((MiCone *) cd)->perturb = dDualPerturb; ratio_set_drop_answer((MiCone *) cd); }  // :2236-2241
 
 // hdsdp_conic_sdp.c:2172-2180
 hdsdp_retcode cone_interior(void *cd, double tau, double *y, int *isInterior) {
@@ -665,29 +703,26 @@ hdsdp_retcode cone_barrier(void *cd, double tau, double *y, int whichBuffer, dou
 // checked: S + (1 - 1e-3) step dS is factored in a scratch object.  If that succeeds the reference's number stands unchanged; if not, a
 // Lanczos test from the fresh start vector is run (its own object: the warm-start state stays the reference's), the smaller
 // step taken, and it is cut by 10 % until the factorisation succeeds.
-hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *maxStep) {
-    // (a step of 1e6 or more stands for "unbounded": S + step dS is then rounding noise times the step, and no caller takes it)
-    if (!(*maxStep > 0.0) || !(*maxStep < 1e6)) return HDSDP_RETCODE_OK;
-    const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
+// The check: is S + (1 - 1e-3) step dS inside the cone?  Factored in the scratch object (made on first use).
+// (checked at (1 - 1e-3) step: the reference's own acceptance tolerance (gamma < 1e-3).  A step that is alpha* to
+// rounding -- a rank-one dS, dS = -S -- or within that tolerance of it stands as the reference computed it, and
+// the driver's trajectory with it; what is caught is a test that stopped at the wrong eigenvalue)
+hdsdp_retcode ratio_inside(MiCone *c, int whichBuffer, double step, bool *ok) {
     if (!c->safe) {
         c->safe.reset(new HdmChol());
         if (c->safe->init(c->n)) return HDSDP_RETCODE_MEMORY;
     }
-    HIP_RC(c->Ssafe.reserve(nn / sizeof(double)));
+    HIP_RC(c->Ssafe.reserve((size_t) c->n16 * c->n16));
     const double *Sb = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
-    auto inside = [&](double step, bool *ok) -> int {
-        int info = 0;
-        // (checked at (1 - 1e-3) step: the reference's own acceptance tolerance (gamma < 1e-3).  A step that is alpha* to
-        // rounding -- a rank-one dS, dS = -S -- or within that tolerance of it stands as the reference computed it, and
-        // the driver's trajectory with it; what is caught is a test that stopped at the wrong eigenvalue)
-        if (hdm_axpy_mat(c->Ssafe.get(), Sb, c->dS.get(), (1.0 - 1e-3) * step, (long) c->n16 * c->n16, g.stream) ||
-            c->safe->load_device(c->Ssafe.get(), c->n16, g.stream) || c->safe->factor(g.stream, &info)) return 1;
-        *ok = (info == 0);
-        return 0;
-    };
-    bool ok = false;
-    if (inside(*maxStep, &ok)) return HDSDP_RETCODE_FAILED;
-    if (ok) return HDSDP_RETCODE_OK;
+    int info = 0;
+    if (hdm_axpy_mat(c->Ssafe.get(), Sb, c->dS.get(), (1.0 - 1e-3) * step, (long) c->n16 * c->n16, g.stream) ||
+        c->safe->load_device(c->Ssafe.get(), c->n16, g.stream) || c->safe->factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
+    *ok = (info == 0);
+    return HDSDP_RETCODE_OK;
+}
+// The rest, once a step has failed the check: the fresh-start test and the 10 % cuts.  The grouped form (engine_ratio_set.h) makes
+// the check itself, in its second launch, and comes here for the members whose step failed it.
+hdsdp_retcode ratio_safeguard_rest(MiCone *c, HdmChol *fac, int whichBuffer, double *maxStep) {
     if (!c->lanczos_fresh) {
         c->lanczos_fresh.reset(new HdmLanczos());
         if (c->lanczos_fresh->init(c->n)) return HDSDP_RETCODE_MEMORY;
@@ -695,9 +730,10 @@ hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *
     c->lanczos_fresh->nComputed = 0;
     double step = *maxStep, fresh = INFINITY;
     int steps = 0;
+    bool ok = false;
     if (c->lanczos_fresh->solve(fac->Linv.get(), fac->npad, c->dS.get(), c->n16, g.stream, &fresh, &steps) == 0 && fresh < step) step = fresh;
     for (int it = 0; it < 64; ++it) {
-        if (inside(step, &ok)) return HDSDP_RETCODE_FAILED;
+        RC(ratio_inside(c, whichBuffer, step, &ok));
         if (ok) break;
         step *= 0.9;
     }
@@ -706,6 +742,14 @@ hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *
                      *maxStep, step, fresh);
     *maxStep = ok ? step : 0.0;
     return HDSDP_RETCODE_OK;
+}
+hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *maxStep) {
+    // (a step of 1e6 or more stands for "unbounded": S + step dS is then rounding noise times the step, and no caller takes it)
+    if (!(*maxStep > 0.0) || !(*maxStep < 1e6)) return HDSDP_RETCODE_OK;
+    bool ok = false;
+    if (const hdsdp_retcode rc = ratio_inside(c, whichBuffer, *maxStep, &ok); rc != HDSDP_RETCODE_OK) return rc;
+    if (ok) return HDSDP_RETCODE_OK;
+    return ratio_safeguard_rest(c, fac, whichBuffer, maxStep);
 }
 
 // sdpDenseConeRatioTestImpl (hdsdp_conic_sdp.c:1640-1686): dS = dTauStep*C - sum dy_i A_i + dAdaRatio*Rd*I, then the
@@ -717,6 +761,10 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
     MiLin *l = (MiLin *) c->dualFactor->chol;
     HdmChol *fac = (whichBuffer == 0) ? &l->ch : c->checker.get();   // LTarget, :1661-1665
     if (!fac || !fac->factored) return HDSDP_RETCODE_FAILED;
+    if (whichBuffer == 0 && c->rat_set && c->rat_set->on) {      // (the checker buffer stays per cone, as it does for the check set)
+        hdsdp_retcode rcs;
+        if (ratio_set_answer(c, dTauStep, dy, dAdaRatio, maxStep, &rcs)) return rcs;
+    }
     const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
     if (!c->dS.get()) {
         HIP_RC(c->dS.alloc(nn / sizeof(double)));

@@ -409,6 +409,10 @@ static void kkt_apply_opt_ins(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
         const int k = check_set_switch(pv, 1);
         fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_CHECK=1: %d of %d cone(s) answer a point question in one grouped launch\n", k, nCones);
     }
+    if (hdm_env_on<ENV_GROUPED_RATIO>()) {
+        const int k = ratio_set_switch(pv, 1);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_RATIO=1: %d of %d cone(s) answer a ratio test in one grouped launch pair\n", k, nCones);
+    }
     // HDSDP_MI355X_REFINE=k: Schur solves are refined with at most k steps (HMiKKTSetRefine)
     if (const int k = hdm_env_int<ENV_REFINE>().value_or(0); k > 0) {
         (void) HMiKKTSetRefine(HKKT, k);
@@ -434,10 +438,12 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     rc = kkt_init_device_common(HKKT, pv);
     if (rc != HDSDP_RETCODE_OK) return rc;
     if (sw.device_m) kkt_apply_device_m(HKKT, pv);
-    // eligibility for the grouped Schur build (engine_grouped.h) and membership of the check set (engine_check_set.h) are decided
-    // for every operator; the grouped pass and the grouped launch are used when their switches are on
+    // eligibility for the grouped Schur build (engine_grouped.h) and membership of the check set (engine_check_set.h) and of the
+    // ratio set (engine_ratio_set.h) are decided for every operator; the grouped pass and the grouped launches are used when
+    // their switches are on
     grouped_init_plan(HKKT, pv);
     check_set_init(HKKT, pv);
+    ratio_set_init(HKKT, pv);
     kkt_apply_opt_ins(HKKT, pv);
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
@@ -774,6 +780,20 @@ int HMiKKTGetGroupedCheck(hdsdp_kkt *HKKT, long out[6]) {
 hdsdp_retcode HMiKKTCheckIsInterior(hdsdp_kkt *HKKT, double tau, const double *y, int *flags, double *logdets, int *all) {
     if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
     return check_all_cones(HKKT, tau, y, flags, logdets, all);
+}
+int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on) { return ratio_set_switch(priv_of(HKKT), on); }
+int HMiKKTGetGroupedRatio(hdsdp_kkt *HKKT, long out[7]) {
+    const MiRatioSet &rs = priv_of(HKKT)->rat;
+    if (out) {
+        out[0] = rs.count(); out[1] = rs.launches; out[2] = rs.last_cones; out[3] = rs.total_cones;
+        out[4] = rs.from_slots; out[5] = rs.last_left_out; out[6] = rs.fallbacks;
+    }
+    return rs.on ? 1 : 0;
+}
+hdsdp_retcode HMiKKTRatioTest(hdsdp_kkt *HKKT, double dTauStep, const double *dy, double dAdaRatio, int whichBuffer, double *steps,
+                              double *minStep) {
+    if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
+    return ratio_all_cones(HKKT, dTauStep, dy, dAdaRatio, whichBuffer, steps, minStep);
 }
 int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
     MiKKTPriv *pv = priv_of(HKKT);

@@ -3,6 +3,7 @@
 #include <vector>
 #include "hdm_common.h"
 #include "lanczos_host.h"   // the rules (lanczos_rule.h), the host driver, the start vector
+#include "small_ratio_rule.h"
 
 struct HdmLanczos {
     int n = 0, n16 = 0;
@@ -29,3 +30,28 @@ int hdm_mirror_lower(double *A, long ld, int n, hipStream_t s);
 int hdm_sym_scale(double *A, long ld, int n, double diag_add, double scale, hipStream_t s);   // A <- scale*(sym(A) + diag_add*I)
 int hdm_axpy_mat(double *out, const double *S, const double *dS, double step, long count, hipStream_t s);   // out = S + step*dS
 int hdm_axpy_mat_eye(double *out, const double *S, const double *dS, double step, double eye, long ld, int n, hipStream_t s);   // out = S + step*dS + eye*I
+#if defined(__HIPCC__)
+// one element of out = S + step * dS: hdm_axpy_mat's kernel and the grouped safeguard (small.hip) share the expression
+__device__ __forceinline__ double hdm_axpy_elem(double s, double d, double step) { return s + step * d; }
+#endif
+
+// ---- the grouped ratio test (small_ratio_rule.h has the rule, engine_ratio_set.h the set) -----------------
+// One table entry per launched member, in mapped pinned memory.  Two launches work on the table, queued back to back:
+// hdm_grouped_ratio_kernel (lanczos.hip) forms the member's step matrix and runs the one-launch Lanczos test's body on it,
+// hdm_grouped_safeguard_kernel (small.hip) factors S + (1 - 1e-3) step dS and reports whether that succeeded.
+struct HdmGroupedRatioArgs {
+    int n, n16, m;                      // block dimension, its leading dimension, rows that enter the sum (0: every owned multiplier is zero)
+    int fresh;                          // the member's Lanczos object has computed nothing yet: no warm start
+    const double *A; long astride;      // m matrices in A_L form (strict lower + half diagonal), column-major n16 x n16
+    const double *C;                    // objective, full symmetric, ld n16
+    const double *y;                    // m multipliers (mapped host or device)
+    double tau, eye;
+    double *dS;                         // the member's step matrix, ld n16: both triangles of the leading n x n are written
+    const double *S;                    // the member's dual matrix (lower triangle read), ld n16
+    const double *Linv;                 // 128 x 128 triangular inverse of the dual factor (HdmChol::Dinv of a one-block factor)
+    double *V, *warm;                   // HdmLanczos::V, ::warm
+    const double *start;                // HdmLanczos::startd
+    double *out;                        // mailbox + LZ_MB_WHOLE: [0] step [1] Lanczos steps [2] status [3] safeguard: 0, or first bad pivot + 1
+};
+int hdm_grouped_ratio(const HdmGroupedRatioArgs *table_host, const HdmGroupedRatioArgs *table_dev, int count, hipStream_t s);
+int hdm_grouped_safeguard(const HdmGroupedRatioArgs *table_dev, int count, hipStream_t s);   // small.hip

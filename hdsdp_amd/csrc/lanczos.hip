@@ -438,11 +438,13 @@ __global__ __launch_bounds__(256) void hdm_transpose_kernel(const double *__rest
 // RESIDENT = true (n16 <= 128): the two matrices are first packed into LDS (lower triangles, column by column: 2 x 66 KB at
 // n16 = 128) and the 30-50 operator applications of a test read them there; from global memory every application is three
 // dependent passes of L2 round trips -- 12 us each at n = 100, 0.42 ms per ratio test on mcp100.
+// The body: one workgroup of 1024 threads, one test.  hdm_lanczos_whole_kernel runs it on its arguments, the grouped form
+// (hdm_grouped_ratio_kernel) on a table entry behind its own prologue; the static LDS below is the body's, once per kernel.
 template <bool RESIDENT>
-__global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *__restrict__ Linv, long ldl, const double *__restrict__ dS,
-                                                                 long ldd, int n, double *__restrict__ V, long ldv,
-                                                                 const double *__restrict__ start, double *__restrict__ warm, int fresh,
-                                                                 double *__restrict__ out) {
+__device__ __forceinline__ void lz_whole_body(const double *__restrict__ Linv, long ldl, const double *__restrict__ dS,
+                                              long ldd, int n, double *__restrict__ V, long ldv,
+                                              const double *__restrict__ start, double *__restrict__ warm, int fresh,
+                                              double *__restrict__ out) {
     __shared__ double sv[LZ_FUSED_MAX], st1[LZ_FUSED_MAX], st2[LZ_FUSED_MAX], part[4][LZ_FUSED_MAX], red[16];
     __shared__ double hd[LZ_MD + 2], he[LZ_MD + 2], td[LZ_MD + 2], te[LZ_MD + 2], Z[32 * 32], y1[32], y2[32];
     __shared__ double bc, sh_eig1, sh_eig2;
@@ -670,6 +672,69 @@ __global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *_
     if (tid == 0) { out[0] = step; out[1] = (double) k; out[2] = (double) status; }
 }
 
+template <bool RESIDENT>
+__global__ __launch_bounds__(1024) void hdm_lanczos_whole_kernel(const double *__restrict__ Linv, long ldl, const double *__restrict__ dS,
+                                                                 long ldd, int n, double *__restrict__ V, long ldv,
+                                                                 const double *__restrict__ start, double *__restrict__ warm, int fresh,
+                                                                 double *__restrict__ out) {
+    lz_whole_body<RESIDENT>(Linv, ldl, dS, ldd, n, V, ldv, start, warm, fresh, out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The grouped form (lanczos.h: HdmGroupedRatioArgs): workgroup b runs the ratio test of table[b].  The
+// workgroups are independent: none waits for another, none reads a word another writes, any number may be resident at a time.
+//
+// Prologue: the member's step matrix dS = tau C - sum_c y_c A_c + eye I into the member's own buffer, BOTH triangles (the
+// per-cone path sweeps the lower one and mirrors it).  Every element has ONE accumulator over the rows in ascending order and
+// the operations of hdm_sym_combine_kernel / hdm_sym_combine_sky_kernel (schur.hip), written as they are there so that the
+// multiply-adds contract alike: acc -= y[c] * a, then * 2 on the diagonal (A_L form: half of it is stored), then + tau C, then
+// + eye on the diagonal -- the per-cone sweep's bits (tests/test_gpu_grouped_ratio.py compares without a tolerance).  A thread
+// walks four elements at a time, each with its own chain: the elements are a thread's parallelism, a chain is never split.  The
+// multipliers are staged in the dynamic LDS the body packs its triangles into afterwards (small_ratio_rule.h states the bound).
+// Then the body, as the one-launch test runs it, on the member's own Lanczos buffers.
+__global__ __launch_bounds__(1024) void hdm_grouped_ratio_kernel(const HdmGroupedRatioArgs *__restrict__ table, int count) {
+    if ((int) blockIdx.x >= count) return;
+    const HdmGroupedRatioArgs p = table[blockIdx.x];
+    extern __shared__ __attribute__((aligned(16))) double lz_dyn[];
+    const int tid = threadIdx.x, n = p.n, n16 = p.n16, m = p.m;
+    double *yl = lz_dyn;
+    for (int q = tid; q < m; q += 1024) yl[q] = p.y[q];
+    __syncthreads();
+    const int tot = n * n;
+    for (int e0 = tid; e0 < tot; e0 += 4096) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        int ii[4], jj[4];
+        bool use[4];
+        const double *a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e = e0 + 1024 * u;
+            ii[u] = e % n; jj[u] = e / n;
+            use[u] = e < tot && ii[u] >= jj[u];
+            a[u] = p.A + (use[u] ? ii[u] + (long) jj[u] * n16 : 0);      // (n16 <= 128: the skyline storage of an A_L form is the plain square)
+        }
+        for (int c = 0; c < m; ++c) {
+            const double yc = yl[c];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (use[u]) acc[u] -= yc * a[u][(long) c * p.astride];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (!use[u]) continue;
+            const int i = ii[u], j = jj[u];
+            double v = acc[u];
+            if (i == j) v *= 2.0;
+            v += p.tau * p.C[i + (long) j * n16];
+            if (i == j) v += p.eye;
+            p.dS[i + (long) j * n16] = v;
+            p.dS[j + (long) i * n16] = v;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    lz_whole_body<true>(p.Linv, (long) HDM_SMALL_CHECK_P, p.dS, (long) n16, n16, p.V, (long) n16, p.start, p.warm, p.fresh, p.out);
+}
+
 // z = V[:, 0..kc) * coef   (single workgroup; V column stride ldv)
 __global__ __launch_bounds__(1024) void hdm_lincomb_kernel(const double *__restrict__ V, long ldv, int kc,
                                                            const double *__restrict__ coef, double *__restrict__ z, int n) {
@@ -794,7 +859,7 @@ int hdm_sym_scale(double *A, long ld, int n, double diag_add, double scale, hipS
 // out = S + step * dS over `count` doubles (out may alias S)
 __global__ void hdm_axpy_mat_kernel(double *out, const double *S, const double *dS, double step, long count) {
     long e = (long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) out[e] = S[e] + step * dS[e];
+    if (e < count) out[e] = hdm_axpy_elem(S[e], dS[e], step);
 }
 
 // out = S + step * dS + eye * I for an n x n matrix of leading dimension ld (out may alias S)
@@ -1042,6 +1107,32 @@ int HdmLanczos::solve(const double *Linv, long ldl, const double *dS, long ldd, 
         if (steps) *steps = k;
         return 0;
     }
+}
+
+// The grouped ratio test's first launch: `count` independent workgroups, workgroup b on table[b].  The table is a mapped pinned
+// block: the checks are made through the host's address, the kernel reads the device's.  The dynamic LDS is sized for max_n16.
+int hdm_grouped_ratio(const HdmGroupedRatioArgs *table_host, const HdmGroupedRatioArgs *table_dev, int count, hipStream_t s) {
+    if (!table_host || !table_dev || count < 1) return 1;
+    int max_n16 = 0;
+    for (int k = 0; k < count; ++k) {
+        const HdmGroupedRatioArgs &a = table_host[k];
+        if (a.n < 2 || a.n > a.n16 || a.n16 > LZ_RESIDENT_MAX || (a.n16 & 15) || a.m < 0 || a.m > hdm_small_ratio_lds_doubles(a.n16)) return 1;
+        if (!a.A && a.m > 0) return 1;
+        if (!a.C || !a.y || !a.dS || !a.S || !a.Linv || !a.V || !a.start || !a.warm || !a.out) return 1;
+        max_n16 = std::max(max_n16, a.n16);
+    }
+    const size_t dyn = sizeof(double) * (size_t) hdm_small_ratio_lds_doubles(max_n16);
+    static thread_local int configured_dev = -1;
+    int dev = 0;
+    HDM_HIP_CHECK(hipGetDevice(&dev));
+    if (configured_dev != dev) {
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_grouped_ratio_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int) (sizeof(double) * LZ_RESIDENT_MAX * (LZ_RESIDENT_MAX + 1))));
+        configured_dev = dev;
+    }
+    hipLaunchKernelGGL(hdm_grouped_ratio_kernel, dim3((unsigned) count), dim3(1024), dyn, s, table_dev, count);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 // one kernel of this translation unit (= one code object): what the preload thread asks the runtime about (engine.hip: preload_modules)

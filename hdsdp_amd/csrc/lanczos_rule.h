@@ -64,6 +64,7 @@ enum HdmLzMailbox {
     LZ_MB_CARRY = 43,             // launch-per-product form: the norm carried into a group's first step
     LZ_MB_GROUP = 44,             // a group of g steps: g (alpha, norm) pairs, the number of steps done, the give-up word
     LZ_MB_WHOLE = 60,             // one-launch form: step, Lanczos steps done, status
+    LZ_MB_SAFE = 63,              // grouped form: the safeguard's word (0, or the first non-positive pivot + 1), behind the three
     LZ_MB_Y2 = 64,                // coefficients of the second Ritz vector
     LZ_MB_SIZE = 128
 };
@@ -71,6 +72,7 @@ constexpr int LZ_MB_GROUP_LEN = 2 * LZ_CHECK_FREQ + 2, LZ_MB_WHOLE_LEN = 3;
 static_assert(LZ_MB_R1 + 1 <= LZ_MB_R2 && LZ_MB_R2 + 1 <= LZ_MB_Y1 && LZ_MB_Y1 + LZ_MD <= LZ_MB_CARRY && LZ_MB_CARRY + 1 <= LZ_MB_GROUP,
               "mailbox ranges overlap");
 static_assert(LZ_MB_GROUP + LZ_MB_GROUP_LEN <= LZ_MB_WHOLE, "a group of steps (the check frequency at most) must fit the mailbox's group block");
+static_assert(LZ_MB_WHOLE + LZ_MB_WHOLE_LEN == LZ_MB_SAFE && LZ_MB_SAFE + 1 <= LZ_MB_Y2, "the safeguard's word follows the one-launch form's three");
 static_assert(LZ_MB_WHOLE + LZ_MB_WHOLE_LEN <= LZ_MB_Y2 && LZ_MB_Y2 + LZ_MD <= LZ_MB_SIZE, "mailbox ranges overlap");
 
 // ---- which form runs ------------------------------------------------------------------------

@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "sweep128.h"
+#include "lanczos.h"
 
 // x = W'W for the lower-triangular W in registers (x_ij = sum_k W_ki W_kj).  Every thread owns exactly one row of each
 // block of sixteen rows (row 16 KR + ty, its local row KR), so a block is published by ALL threads at once -- no owner
@@ -425,6 +426,65 @@ int hdm_grouped_check(const HdmSmallCheckArgs *table_host, const HdmSmallCheckAr
         configured_dev = dev;
     }
     hipLaunchKernelGGL(hdm_grouped_check_kernel, dim3((unsigned) count), dim3(SM_T), lds, s, table_dev, count);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- the grouped ratio test's safeguard (lanczos.h: HdmGroupedRatioArgs) ---------------------------------
+// Queued behind hdm_grouped_ratio_kernel on the same stream.  Workgroup b reads the step its member's test has just reported and,
+// where that is a finite step inside (0, 1e6), factors S + (1 - 1e-3) step dS with the sweep HdmChol::factor runs on a one-block
+// object (the lower triangle and the identity padding are what the sweep reads); the word it writes is that factorisation's info,
+// 0 otherwise.  No factor is stored: only yes / no is used (engine_cone.h: ratio_safeguard).  Independent workgroups.
+__global__ __launch_bounds__(SM_T) void hdm_grouped_safeguard_kernel(const HdmGroupedRatioArgs *__restrict__ table, int count) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int) blockIdx.x >= count) return;
+    const HdmGroupedRatioArgs p = table[blockIdx.x];
+    constexpr int ld = SMALL_P + 1;
+    double *Xl = sm;                                   // 128 x 129 (its head: the sweep's block images)
+    double *rsv = sm + (long) SMALL_P * ld;            // 128 deferred scale factors
+    const int n = p.n, n16 = p.n16;
+    const int tid = threadIdx.x, ty = tid >> 5, tx = tid & 31;
+    const double step = p.out[0], status = p.out[2];
+    if (status != 0.0 || !(step > 0.0) || !(step < 1e6)) {      // (uniform: every thread read the same two words)
+        if (tid == 0) p.out[3] = 0.0;
+        return;
+    }
+    const double st = (1.0 - 1e-3) * step;
+    const int ei = tid & (SMALL_P - 1), ej0 = tid >> 7;
+    if (ei < n) {
+        for (int j = ej0; j <= ei; j += SM_T / SMALL_P) {
+            const long e = ei + (long) j * n16;
+            const double v = hdm_axpy_elem(p.S[e], p.dS[e], st);
+            Xl[ei + j * ld] = v;
+            Xl[j + ei * ld] = v;
+        }
+    }
+    __syncthreads();
+    double a[SM_NR][SM_NC], rr[SM_NR][SM_NC];
+#pragma unroll
+    for (int r = 0; r < SM_NR; ++r)
+#pragma unroll
+        for (int c = 0; c < SM_NC; ++c) {
+            const int i = ty + 16 * r, j = tx + 32 * c;
+            a[r][c] = (i < n && j < n) ? Xl[i + j * ld] : ((i == j) ? 1.0 : 0.0);
+        }
+    __syncthreads();
+    double unused;
+    const int info = sm_sweep<false>(n, a, rr, Xl, rsv, ty, tx, &unused);
+    if (tid == 0) p.out[3] = (double) info;
+}
+
+int hdm_grouped_safeguard(const HdmGroupedRatioArgs *table_dev, int count, hipStream_t s) {
+    if (!table_dev || count < 1) return 1;
+    const size_t lds = (size_t) hdm_small_check_lds_bytes(0);
+    static thread_local int configured_dev = -1;
+    int dev = 0;
+    HDM_HIP_CHECK(hipGetDevice(&dev));
+    if (configured_dev != dev) {
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_grouped_safeguard_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) HDM_SMALL_CHECK_LDS_MAX));
+        configured_dev = dev;
+    }
+    hipLaunchKernelGGL(hdm_grouped_safeguard_kernel, dim3((unsigned) count), dim3(SM_T), lds, s, table_dev, count);
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

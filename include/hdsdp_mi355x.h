@@ -429,6 +429,29 @@ int HMiGroupedPlanQuery(int nRow, int nCones, const int *dims, const int *kindOk
 int HMiKKTSetGroupedCheck(hdsdp_kkt *HKKT, int on);
 int HMiKKTGetGroupedCheck(hdsdp_kkt *HKKT, long out[6]);
 hdsdp_retcode HMiKKTCheckIsInterior(hdsdp_kkt *HKKT, double tau, const double *y, int *flags, double *logdets, int *all);
+/* The grouped ratio test (csrc/small_ratio_rule.h, csrc/lanczos.hip, csrc/small.hip,
+ * csrc/engine_ratio_set.h).  The reference's line search puts "how far along (dTauStep, dy)?" to all cones in a loop with the same
+ * arguments; a small SDP cone answers in five launches and two or three synchronisations of its own.  With the switch on, a
+ * question on BUFFER_DUALVAR that a member's slot does not hold runs EVERY member's test in one pair of launches and one
+ * synchronisation (one workgroup per member: the per-cone sweep's sums, the one-launch Lanczos test's own body, the safeguard's
+ * factorisation: the same bits), and the loop's later calls fetch their answers from the members' slots, each exactly once and only
+ * while the member's dual matrix, step matrix and factor have not moved.  Members: the check set's population (above) with n >= 2
+ * whose Lanczos form is the LDS-resident one-launch test (HDM_LANCZOS_WHOLE not 0) and with mloc <= n16 (n16 + 1).  The checker
+ * buffer, n = 1 and larger blocks keep their own paths.  One difference from the loop: a question put to one member runs every
+ * member's test -- a member that is never asked that question has its warm-start state one test further and its step matrix
+ * overwritten.  Off by default.
+ * HMiKKTSetGroupedRatio: after HKKTInit; returns the number of members (0: off, or fewer than two members).
+ * HMiKKTGetGroupedRatio: out[0] members [1] grouped launch pairs since HKKTInit [2] cones in the last one [3] cones launched in all
+ * [4] answers served from slots since the switch went on [5] members left out of the last launch (dual factor not in place, or an
+ * unfetched answer to the same question) [6] safeguard fallbacks (steps that left the cone and took the host's fresh-start test);
+ * returns 1 if the switch is on, else 0.
+ * HMiKKTRatioTest: the whole-operator question.  Every cone of cones[] in order, without early exit, through its own coneRatioTest
+ * slot: steps[k] (NaN where the slot failed; may be NULL) and *minStep, the smallest step of the cones that answered (infinite if
+ * none bounds it; may be NULL).  With the switch off it is the plain loop.  Returns the first retcode of a slot that was not OK. */
+int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on);
+int HMiKKTGetGroupedRatio(hdsdp_kkt *HKKT, long out[7]);
+hdsdp_retcode HMiKKTRatioTest(hdsdp_kkt *HKKT, double dTauStep, const double *dy, double dAdaRatio, int whichBuffer, double *steps,
+                              double *minStep);
 /* multi-GPU (world > 1): constraint rows are sharded (row i on rank i % world).  Each rank congruence-
  * transforms its own rows, a transpose (all-to-all) re-shards the transformed data from "by constraint"
  * to "by packed-index range", each rank forms the Gram partial sum over its range, and an all-reduce
@@ -613,6 +636,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           small SDP cones of an operator in three launches)
  *  HDSDP_MI355X_GROUPED_CHECK     0         1: HKKTInit turns the grouped interior check on (a point      test_gpu_grouped_check.py
  *                                           question to one small SDP cone answers all in one launch)
+ *  HDSDP_MI355X_GROUPED_RATIO     0         1: HKKTInit turns the grouped ratio test on (a ratio test     test_gpu_grouped_ratio.py
+ *                                           asked of one small SDP cone runs all in one launch pair)
  *  HDSDP_MI355X_REFINE            0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on
  *                                           steps (HMiKKTSetRefine)
  *  HDSDP_MI355X_REFINE_TILES      0         1: HKKTInit turns the tile form's refined solve on as well    test_gpu_refine_tiles.py::test_the_environment_switches_refine_a_tile_operator
