@@ -21,6 +21,7 @@
 #include "dual_state.h"
 #include "row_store_rule.h"
 #include "kkt_store.h"
+#include "cone_set.h"
 #include "schur.h"
 #include "direct_rows.h"
 #include "lanczos.h"

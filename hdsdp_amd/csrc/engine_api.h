@@ -179,7 +179,7 @@ hdsdp_retcode HMiConeGetTraces(hdsdp_cone *cone, double *trA) {
 }
 int HMiConeGetPath(hdsdp_cone *cone) { const MiCone *c = cone_data(cone); return c ? c->path : -1; }
 void HMiConeGetDirectRows(hdsdp_cone *cone, int *nDirect, int *nRankOne, int *nCongruence, int *kmax) {
-    const MiCone *c = (cone && cone->coneBuildSchur == cone_build_schur) ? (const MiCone *) cone->coneData : nullptr;
+    const MiCone *c = own_cone_data(cone);
     const bool on = c && c->dr_n > 0;
     if (nDirect) *nDirect = on ? c->dr_n : 0;
     if (nRankOne) *nRankOne = on ? c->dr_r1 : 0;

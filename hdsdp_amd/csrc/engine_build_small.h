@@ -1,6 +1,7 @@
-// engine_build_small.h -- the rank-one and the sparse-gather Schur builders, cone destruction and the cone shell (vtable)
+// engine_build_small.h -- the rank-one and the sparse-gather Schur builders, cone destruction, the cone shell (vtable) and the way
+// back from a shell to the engine's own cone (own_cone_data, own_cone_with_factor)
 // Implementation header of engine.hip: included exactly once, there, in this order (the pieces share the anonymous namespace
-// and the engine's thread-local context `g`); split out of a 3 300-line file in round 3, nothing else changed.
+// and the engine's thread-local context `g`).
 
 #define TRACE_STEP(msg)                                                                                          \
     do {                                                                                                         \
@@ -12,8 +13,7 @@
     } while (0)
 hdsdp_retcode build_r1_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKKT) {
     // all (non-zero) constraints are rank one: A_i = s_i a_i a_i'  (reference strategy M2)
-    MiLin *l = (MiLin *) c->dualFactor->chol;
-    HdmChol &ch = l->ch;
+    HdmChol &ch = *dual_chol(c);
     const int m = kkt->nRow;
     const int n16 = c->n16, m16 = c->mloc16;
     RC(ch.invert_factor(g.stream));
@@ -83,8 +83,7 @@ hdsdp_retcode build_r1_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKK
 hdsdp_retcode build_sparse_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int typeKKT) {
     // every constraint is a short triplet list: gather from X = S^-1 (reference strategy M5, and the corrector /
     // HSD components that the reference evaluates with the same gathers, hdsdp_conic_sdp.c:923-1056)
-    MiLin *l = (MiLin *) c->dualFactor->chol;
-    HdmChol &ch = l->ch;
+    HdmChol &ch = *dual_chol(c);
     const int m = kkt->nRow;
     const long ldx = ch.npad;
     const int n16 = c->n16;
@@ -123,15 +122,13 @@ hdsdp_retcode build_sparse_path(MiCone *c, hdsdp_kkt *kkt, MiKKTPriv *pv, int ty
 void cone_destroy_data(void **pcd) {
     if (!pcd || !*pcd) return;
     MiCone *c = (MiCone *) *pcd;
-    check_set_forget(c);
-    ratio_set_forget(c);
     HFpLinsysDestroy(&c->dualFactor);
     for (hipEvent_t e : c->piece_ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->pe_s2) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->pe_ga) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->pe_gb) if (e) (void) hipEventDestroy(e);
     if (c->pe_s1) (void) hipEventDestroy(c->pe_s1);
-    delete c;
+    delete c;                 // (its links leave their sets: cone_set.h)
     *pcd = nullptr;
 }
 
@@ -169,3 +166,8 @@ hdsdp_cone *new_cone_shell(MiCone *c, int iCone) {
     h->coneGetBarrier = cone_barrier;
     return h;
 }
+// ... and back: the cone behind a shell this function made, nullptr behind any other (a device-group cone -- cone_data answers
+// for those too --, an LP cone, a host cone); and the same with a dual factor object: what the grouped build, the check set and
+// the ratio set may look at
+MiCone *own_cone_data(const hdsdp_cone *cone) { return (cone && cone->coneBuildSchur == cone_build_schur) ? (MiCone *) cone->coneData : nullptr; }
+MiCone *own_cone_with_factor(const hdsdp_cone *cone) { MiCone *c = own_cone_data(cone); return (c && c->dualFactor) ? c : nullptr; }

@@ -3,42 +3,23 @@
 // anonymous namespace and the engine's thread-local context `g`).
 // The rule is small_check_rule.h's, the kernel small.hip's (hdm_grouped_check_kernel: the one-launch check's body, one
 // workgroup per table entry), the book-keeping dual_state.h's; the struct (MiCheckSet) is engine_cone.h's, next to the cones it
-// names.  This file says which cones of an operator are members, keeps the table, and makes the launch.  DESIGN.md section 19.
+// names; who is a member for how long is cone_set.h's.  This file says which cones of an operator are
+// eligible, keeps the table, and makes the launch.  DESIGN.md section 19.
 
 // a member: an SDP cone of this engine (not a device-group cone, not an LP cone, not a host cone) whose own one-launch check on
 // the dual buffer would run -- a sharded cone fails the rule by world != 1
-bool check_set_kind_ok(const hdsdp_cone *hc) {
-    if (hc->coneBuildSchur != cone_build_schur) return false;
-    const MiCone *c = (const MiCone *) hc->coneData;
-    if (!c || !c->dualFactor) return false;
-    return hdm_small_check_eligible(small_check_desc(c, &((const MiLin *) c->dualFactor->chol)->ch));
+MiCone *check_set_eligible(const hdsdp_cone *hc) {
+    MiCone *c = own_cone_with_factor(hc);
+    return (c && hdm_small_check_eligible(small_check_desc(c, dual_chol(c)))) ? c : nullptr;
 }
 
-// HKKTInit: membership only.  A cone that another operator's ACTIVE set holds is not taken; one that an inactive set holds
-// moves here (the operator initialised last has it).
+// HKKTInit: membership only, by cone_set.h's rules (the operator initialised last has a cone no ACTIVE set holds)
 void check_set_init(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
     MiCheckSet &cs = pv->chk;
     cs.release();
-    cs.launches = cs.last_cones = cs.total_cones = cs.from_state = cs.last_left_out = 0;
-    for (int i = 0; i < HKKT->nCones; ++i) {
-        if (!check_set_kind_ok(HKKT->cones[i])) continue;
-        MiCone *c = (MiCone *) HKKT->cones[i]->coneData;
-        if (c->chk_set == &cs) continue;                       // (the same cone named twice)
-        if (c->chk_set) {
-            if (c->chk_set->on) continue;
-            check_set_forget(c);
-        }
-        c->chk_set = &cs; c->chk_slot = (int) cs.members.size();
-        cs.members.push_back(c);
-    }
-}
-
-void check_set_forget(MiCone *c) {
-    MiCheckSet *cs = c->chk_set;
-    if (!cs) return;
-    if (c->chk_slot >= 0 && c->chk_slot < (int) cs->members.size() && cs->members[(size_t) c->chk_slot] == c)
-        cs->members[(size_t) c->chk_slot] = nullptr;
-    c->chk_set = nullptr; c->chk_slot = -1;
+    cs.reset_counters(); cs.from_state = 0;
+    for (int i = 0; i < HKKT->nCones; ++i)
+        if (MiCone *c = check_set_eligible(HKKT->cones[i])) cs.adopt(c);
 }
 
 // the switch: returns the number of members (0: off, or fewer than two members)
@@ -61,7 +42,7 @@ int check_set_switch(MiKKTPriv *pv, int on) {
 // One launch for every member that does not stand at (tau, y_host) with its own identity coefficient.
 int check_set_launch(MiCheckSet *cs, double tau, const double *y_host) {
     HdmSmallCheckArgs *tab = cs->table.get();
-    cs->launched.clear();
+    cs->launch_begin();
     int left_out = 0, max_m = 0;
     std::vector<HdmDualPoint> pts;
     for (size_t k = 0; k < cs->members.size(); ++k) {
@@ -69,24 +50,23 @@ int check_set_launch(MiCheckSet *cs, double tau, const double *y_host) {
         if (!c) continue;
         // (the rule is asked again: whether the check is switched on and the factor object's shape do not change under a
         // set, so this holds for every member -- a cone for which it did not would be left to its own path)
-        HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
+        HdmChol *ch = dual_chol(c);
         if (!hdm_small_check_eligible(small_check_desc(c, ch)) || small_check_block(c)) continue;
         const HdmDualPoint p = small_check_point(c, tau, y_host, cone_eye(c));
         if (c->dual.S_factored_at(p, nullptr)) { left_out += 1; continue; }
-        tab[cs->launched.size()] = small_check_args(c, ch, p, 0);
+        tab[cs->launch_take(k)] = small_check_args(c, ch, p, 0);
         c->dual.S_overwritten();          // the launch writes S: what it holds is known again when the launch has reported
         max_m = std::max(max_m, c->mloc);
-        cs->launched.push_back((int) k);
         pts.push_back(p);
     }
     cs->last_left_out = left_out;
     const int nl = (int) cs->launched.size();
     if (nl == 0) return 0;
     if (hdm_grouped_check(tab, cs->table.dev(), nl, max_m, g.stream) || hipStreamSynchronize(g.stream) != hipSuccess) return 1;
-    cs->launches += 1; cs->last_cones = nl; cs->total_cones += nl;
+    cs->launch_made();
     for (int s = 0; s < nl; ++s) {
         MiCone *c = cs->members[(size_t) cs->launched[(size_t) s]];
-        (void) small_check_commit(c, &((MiLin *) c->dualFactor->chol)->ch, pts[(size_t) s], 0);
+        (void) small_check_commit(c, dual_chol(c), pts[(size_t) s], 0);
     }
     return 0;
 }

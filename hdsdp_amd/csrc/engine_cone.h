@@ -7,8 +7,6 @@
 enum { PATH_GEMM = 0, PATH_R1 = 1, PATH_SPARSE = 2 };
 
 struct MiKKTPriv;
-struct MiCheckSet;
-struct MiRatioSet;
 
 struct MiCone {
     int n = 0, m = 0;          // block dimension, global number of constraints
@@ -126,13 +124,9 @@ struct MiCone {
     // from which cone_assemble answers a request on the line through them without a sweep.  Every writer of S, dS or the
     // dual factor object names what it did through one of this object's transitions.
     HdmDualState dual;
-    // the check set this cone is a member of (engine_check_set.h), and its place there; not owned.  Set by the operator's
-    // HKKTInit, cleared by the set (HKKTInit again, HKKTClear) and by this cone's destruction, whichever comes first.
-    MiCheckSet *chk_set = nullptr;
-    int chk_slot = -1;
-    // the same for the ratio set (engine_ratio_set.h), with the same lifetime rules
-    MiRatioSet *rat_set = nullptr;
-    int rat_slot = -1;
+    // the check set (engine_check_set.h) and the ratio set (engine_ratio_set.h) this cone is a member of, and its place there:
+    // cone_set.h's links, assigned and cleared by its rules alone
+    HdmConeLink<MiCone> in_check, in_ratio;
     // fused single-launch Phase-A pass of a small rank-one block (small.hip): factors as a CSR, built on first use
     struct SmallPlan {
         int state = 0;         // 0 = not looked at, 1 = ready, -1 = not eligible
@@ -168,49 +162,33 @@ struct MiGrouped {
 // The check set of an operator (engine_check_set.h performs it): the small SDP cones whose point questions
 // on the dual buffer -- "interior at (tau, y)?", "log det S at (tau, y)" -- are answered for ALL of them by one launch of
 // hdm_grouped_check_kernel the first time one of them is asked at a new point.  HKKTInit decides membership (small_check_rule.h:
-// the cones whose own one-launch check would run); the switch allocates the table, and turning it off frees it.
-struct MiCheckSet {
-    bool on = false;                       // HMiKKTSetGroupedCheck / HDSDP_MI355X_GROUPED_CHECK
-    std::vector<MiCone *> members;         // in cones[] order; nullptr: destroyed since HKKTInit (not owned)
+// the cones whose own one-launch check would run); the switch (HMiKKTSetGroupedCheck / HDSDP_MI355X_GROUPED_CHECK) allocates the
+// table.  Members, lifetimes and the launch counters are cone_set.h's; left out of a launch: who already stood at the point.
+struct MiCheckSet : HdmConeSet<MiCone> {
     HdmPinned<HdmSmallCheckArgs> table;    // mapped pinned, one entry per member: the launch's arguments, launched members first
-    std::vector<int> launched;             // slots of the members in the launch being made
-    // HMiKKTGetGroupedCheck: launches, cones in the last one, cones launched in all, per-cone calls answered from state since
-    // the switch went on, members left out of the last launch because they already stood at the point
-    long launches = 0, last_cones = 0, total_cones = 0, from_state = 0, last_left_out = 0;
-    int count() const { int k = 0; for (const MiCone *c : members) k += c ? 1 : 0; return k; }
-    void release() {                       // the members are free again (for another operator's set)
-        for (MiCone *c : members) if (c) { c->chk_set = nullptr; c->chk_slot = -1; }
-        members.clear();
-        table.reset();
-        on = false;
-    }
-    ~MiCheckSet() { release(); }
+    long from_state = 0;                   // per-cone calls answered from state since the switch went on
+    MiCheckSet() : HdmConeSet<MiCone>(&MiCone::in_check) {}
+    void release() { HdmConeSet<MiCone>::release(); table.reset(); }
 };
 
 // The ratio set of an operator (engine_ratio_set.h performs it): the small SDP cones whose ratio test on the
 // dual buffer -- "how far along (dTauStep, dy)?" -- is run for ALL of them by one pair of launches the first time one of them is
 // asked a question its slot does not hold.  HKKTInit decides membership (small_ratio_rule.h); the switch allocates the table, the
-// multipliers' staging block and every member's Lanczos object and step buffer, so that a launch allocates nothing.
-struct MiRatioSet {
-    bool on = false;                       // HMiKKTSetGroupedRatio / HDSDP_MI355X_GROUPED_RATIO
-    std::vector<MiCone *> members;         // in cones[] order; nullptr: destroyed since HKKTInit (not owned)
+// multipliers' staging block and every member's Lanczos object and step buffer, so that a launch allocates nothing
+// (HMiKKTSetGroupedRatio / HDSDP_MI355X_GROUPED_RATIO).  Members, lifetimes and the launch counters are cone_set.h's.
+struct MiRatioSet : HdmConeSet<MiCone> {
     std::vector<HdmRatioSlot> slots;       // one per member: the answer of the last launch it was in (small_ratio_rule.h)
     std::vector<long> yoff;                // one per member: where its multipliers start in `ybuf`
     HdmPinned<HdmGroupedRatioArgs> table;  // mapped pinned, one entry per member: the launch's arguments, launched members first
     HdmPinned<double> ybuf;                // mapped pinned: the members' gathered multipliers
-    std::vector<int> launched;             // slots of the members in the launch being made
-    // HMiKKTGetGroupedRatio: launches, cones in the last one, cones launched in all, answers served from slots, members left out
-    // of the last launch, safeguard fallbacks (members whose step left the cone and took the host's fresh-start test and cuts)
-    long launches = 0, last_cones = 0, total_cones = 0, from_slots = 0, last_left_out = 0, fallbacks = 0;
-    int count() const { int k = 0; for (const MiCone *c : members) k += c ? 1 : 0; return k; }
-    void release() {                       // the members are free again (for another operator's set)
-        for (MiCone *c : members) if (c) { c->rat_set = nullptr; c->rat_slot = -1; }
-        members.clear(); slots.clear(); yoff.clear();
-        table.reset(); ybuf.reset();
-        on = false;
-    }
-    ~MiRatioSet() { release(); }
+    // answers served from slots; safeguard fallbacks (members whose step left the cone and took the host's fresh-start test and cuts)
+    long from_slots = 0, fallbacks = 0;
+    MiRatioSet() : HdmConeSet<MiCone>(&MiCone::in_ratio) {}
+    void release() { HdmConeSet<MiCone>::release(); slots.clear(); yoff.clear(); table.reset(); ybuf.reset(); }
 };
+// the set a cone is a member of, as its own kind (the links are assigned by sets of these two types only)
+MiCheckSet *check_set_of(const MiCone *c) { return static_cast<MiCheckSet *>(c->in_check.set); }
+MiRatioSet *ratio_set_of(const MiCone *c) { return static_cast<MiRatioSet *>(c->in_ratio.set); }
 
 struct MiKKTPriv {
     MiGrouped grp;
@@ -263,6 +241,31 @@ int group_configure_from_env();
 bool group_wants_block(const MiBlockData &blk);
 bool group_wants_synthetic(int nRow, int nCol);
 hdsdp_retcode group_create_cone(hdsdp_cone **pCone, int iCone, int nRow, int nCol, MiBlockData *blk, bool synthetic);
+
+// the factor object of the cone's dual matrix
+HdmChol *dual_chol(const MiCone *c) { return &((MiLin *) c->dualFactor->chol)->ch; }
+// the point (tau, eye, y): the owned multipliers gathered through own[] into a buffer of the caller's (mloc doubles; no y_host:
+// zeros), which the point then names; *any: one of them is non-zero
+HdmDualPoint cone_point(const MiCone *c, double tau, double eye, const double *y_host, double *yo, bool *any = nullptr) {
+    bool a = false;
+    for (int q = 0; q < c->mloc; ++q) { yo[q] = y_host ? y_host[c->own[q]] : 0.0; a |= (yo[q] != 0.0); }
+    if (any) *any = a;
+    return HdmDualPoint{tau, eye, yo, c->mloc};
+}
+
+// The cone's lazy state, each piece made if absent where a path first needs it (the ratio set's switch makes a member's step matrix
+// and Lanczos object, so that a launch allocates nothing): a factor or Lanczos object of the block's dimension, which is not kept
+// if its buffers could not be made; and the step matrix, zeros, so that the padding reads as 0.
+template <class T> hdsdp_retcode cone_make(std::unique_ptr<T> &p, int n) {
+    if (!p) { p.reset(new T()); if (p->init(n)) { p.reset(); return HDSDP_RETCODE_MEMORY; } }
+    return HDSDP_RETCODE_OK;
+}
+hipError_t cone_make_dS(MiCone *c) {
+    if (c->dS.get()) return hipSuccess;
+    const size_t n2 = (size_t) c->n16 * c->n16;
+    if (const hipError_t e = c->dS.alloc(n2); e != hipSuccess) return e;
+    return hdm_memset_sync(c->dS.get(), 0, sizeof(double) * n2);
+}
 
 HdmLayout cone_layout(const MiCone *c) { return {c->world, c->n16, c->nblk, c->npb, c->npb_loc, c->Lr, c->R, c->astride}; }
 // the block and the device as row_store_rule.h sees them
@@ -449,11 +452,8 @@ int cone_assemble(MiCone *c, double tau, const double *y_host, HdmDualTarget whi
     // been consumed by the time it is rewritten (every caller synchronises on the factorisation that follows)
     if (!c->yhost) HDM_HIP_CHECK(c->yhost.alloc((size_t) std::max(1, c->mloc)));
     HDM_HIP_CHECK(hipStreamSynchronize(g.stream));
-    double *yo = c->yhost.get();
     bool any = false;
-    for (int q = 0; q < c->mloc; ++q) { yo[q] = y_host ? y_host[c->own[q]] : 0.0; any |= (yo[q] != 0.0); }
-    HdmDualPoint p;
-    p.tau = tau; p.eye = eye_override ? *eye_override : cone_eye(c); p.y = yo; p.ny = c->mloc;
+    const HdmDualPoint p = cone_point(c, tau, eye_override ? *eye_override : cone_eye(c), y_host, c->yhost.get(), &any);
     const HdmDualPlan plan = hdm_dual_plan(c->dual, p, which, hdm_dual_mode(c->mloc, c->n), c->world);
     g_asm_counts[plan.counter].fetch_add(1, std::memory_order_relaxed);
     if (plan.line_missed && hdm_dual_debug()) hdm_dual_print_miss(stderr, c->dual, p, which, plan);
@@ -511,13 +511,7 @@ int small_check_block(MiCone *c) {
     return 0;
 }
 // the point (tau, eye, y gathered through own[] into the cone's block)
-HdmDualPoint small_check_point(MiCone *c, double tau, const double *y_host, double eye) {
-    double *yo = c->chk.get();
-    for (int q = 0; q < c->mloc; ++q) yo[q] = y_host ? y_host[c->own[q]] : 0.0;
-    HdmDualPoint p;
-    p.tau = tau; p.eye = eye; p.y = yo; p.ny = c->mloc;
-    return p;
-}
+HdmDualPoint small_check_point(MiCone *c, double tau, const double *y_host, double eye) { return cone_point(c, tau, eye, y_host, c->chk.get()); }
 // the launch's arguments for the point in the cone's block; the report word is set to -1 ("nothing reported")
 HdmSmallCheckArgs small_check_args(MiCone *c, HdmChol *ch, const HdmDualPoint &p, int whichBuffer) {
     HdmSmallCheckArgs a = {};
@@ -546,25 +540,24 @@ int small_check_commit(MiCone *c, HdmChol *ch, const HdmDualPoint &p, int whichB
 // engine_check_set.h: c is a member of an active set and does not stand at (tau, y_host): one launch for every member that
 // does not.  Returns nonzero when the launch could not be made or did not finish.
 int check_set_launch(MiCheckSet *set, double tau, const double *y_host);
-void check_set_forget(MiCone *c);   // c is being destroyed: its set no longer names it
 
 int cone_small_check(MiCone *c, double tau, const double *y_host, const double *eye_override, int whichBuffer, int *isPsd, hdsdp_retcode *rc) {
     *rc = HDSDP_RETCODE_OK;
     if (!hdm_small_check_block_ok(small_check_desc(c, nullptr))) return 1;
-    HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
+    HdmChol *ch = dual_chol(c);
     if (whichBuffer != 0) { if (cone_checker(c, &ch) != HDSDP_RETCODE_OK) return 1; }
     if (!hdm_small_check_factor_ok(ch->npad, ch->nblk)) return 1;
     if (small_check_block(c)) return 1;
-    const bool grouped = whichBuffer == 0 && !eye_override && c->chk_set && c->chk_set->on;
+    const bool grouped = whichBuffer == 0 && !eye_override && c->in_check.active();
     HdmDualPoint p = small_check_point(c, tau, y_host, eye_override ? *eye_override : cone_eye(c));
     if (whichBuffer == 0 && c->dual.S_factored_at(p, isPsd)) {               // S = T(p) and its factor are in place
-        if (grouped) c->chk_set->from_state += 1;
+        if (grouped) check_set_of(c)->from_state += 1;
         return 0;
     }
     if (grouped) {
         // every member of the set is put at this point in one launch; this cone then answers from its state.  A member the
         // launch has not reported for stays S_overwritten, and the call for that member fails.
-        if (check_set_launch(c->chk_set, tau, y_host) || !c->dual.S_factored_at(p, isPsd)) *rc = HDSDP_RETCODE_FAILED;
+        if (check_set_launch(check_set_of(c), tau, y_host) || !c->dual.S_factored_at(p, isPsd)) *rc = HDSDP_RETCODE_FAILED;
         return 0;
     }
     const HdmSmallCheckArgs a = small_check_args(c, ch, p, whichBuffer);
@@ -583,11 +576,11 @@ void cone_update(void *cd, double tau, double *y) {
 }
 
 hdsdp_retcode cone_factor_S(MiCone *c, int *isPsd) {
-    MiLin *l = (MiLin *) c->dualFactor->chol;
+    HdmChol *ch = dual_chol(c);
     c->dual.factor_stale();
-    RC(l->ch.load_device(c->S.get(), c->n16, g.stream));
+    RC(ch->load_device(c->S.get(), c->n16, g.stream));
     int info = 0;
-    RC(l->ch.factor(g.stream, &info));
+    RC(ch->factor(g.stream, &info));
     c->dualFactor->nFactorizes += 1;
     if (isPsd) *isPsd = (info == 0);
     return HDSDP_RETCODE_OK;
@@ -596,10 +589,7 @@ hdsdp_retcode cone_factor_S(MiCone *c, int *isPsd) {
 // the second factor object ("dualChecker" of the reference, def_hdsdp_conic.h): trial points of the line search and the
 // primal recovery are factored here so that the factor of the current S stays valid
 hdsdp_retcode cone_checker(MiCone *c, HdmChol **out) {
-    if (!c->checker) {
-        c->checker.reset(new HdmChol());
-        if (c->checker->init(c->n)) return HDSDP_RETCODE_MEMORY;
-    }
+    if (const hdsdp_retcode rc = cone_make(c->checker, c->n); rc != HDSDP_RETCODE_OK) return rc;
     *out = c->checker.get();
     return HDSDP_RETCODE_OK;
 }
@@ -647,7 +637,6 @@ hdsdp_retcode cone_axpy_check(void *cd, double dStep, int whichBuffer, int *isIn
 // engine_ratio_set.h: a member's stored ratio-test answer is dropped (the identity coefficients are part of no dual-state
 // transition, and an answer is served only while nothing at all has changed under it); nothing else happens
 void ratio_set_drop_answer(MiCone *c);
-void ratio_set_forget(MiCone *c);   // c is being destroyed: its set no longer names it
 // c is a member of an active set and is asked (dTauStep, dy, dAdaRatio) on the dual buffer.  Returns true when the set has
 // answered (*rc, *maxStep), false when c's own path must run
 bool ratio_set_answer(MiCone *c, double dTauStep, const double *dy, double dAdaRatio, double *maxStep, hdsdp_retcode *rc);
@@ -681,7 +670,7 @@ hdsdp_retcode cone_barrier(void *cd, double tau, double *y, int whichBuffer, dou
         }
     }
     {   // a factor that came from the single-launch check brought its log det along
-        const HdmChol *fq = (whichBuffer == 0) ? &((MiLin *) c->dualFactor->chol)->ch : c->checker.get();
+        const HdmChol *fq = (whichBuffer == 0) ? dual_chol(c) : c->checker.get();
         if (fq && fq->factored && fq->logdet_ok) { *logdet = fq->logdet_val; return HDSDP_RETCODE_OK; }
     }
     std::vector<double> d(c->n);
@@ -708,10 +697,7 @@ hdsdp_retcode cone_barrier(void *cd, double tau, double *y, int whichBuffer, dou
 // rounding -- a rank-one dS, dS = -S -- or within that tolerance of it stands as the reference computed it, and
 // the driver's trajectory with it; what is caught is a test that stopped at the wrong eigenvalue)
 hdsdp_retcode ratio_inside(MiCone *c, int whichBuffer, double step, bool *ok) {
-    if (!c->safe) {
-        c->safe.reset(new HdmChol());
-        if (c->safe->init(c->n)) return HDSDP_RETCODE_MEMORY;
-    }
+    if (const hdsdp_retcode rc = cone_make(c->safe, c->n); rc != HDSDP_RETCODE_OK) return rc;
     HIP_RC(c->Ssafe.reserve((size_t) c->n16 * c->n16));
     const double *Sb = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     int info = 0;
@@ -723,10 +709,7 @@ hdsdp_retcode ratio_inside(MiCone *c, int whichBuffer, double step, bool *ok) {
 // The rest, once a step has failed the check: the fresh-start test and the 10 % cuts.  The grouped form (engine_ratio_set.h) makes
 // the check itself, in its second launch, and comes here for the members whose step failed it.
 hdsdp_retcode ratio_safeguard_rest(MiCone *c, HdmChol *fac, int whichBuffer, double *maxStep) {
-    if (!c->lanczos_fresh) {
-        c->lanczos_fresh.reset(new HdmLanczos());
-        if (c->lanczos_fresh->init(c->n)) return HDSDP_RETCODE_MEMORY;
-    }
+    if (const hdsdp_retcode rc = cone_make(c->lanczos_fresh, c->n); rc != HDSDP_RETCODE_OK) return rc;
     c->lanczos_fresh->nComputed = 0;
     double step = *maxStep, fresh = INFINITY;
     int steps = 0;
@@ -758,18 +741,13 @@ hdsdp_retcode ratio_safeguard(MiCone *c, HdmChol *fac, int whichBuffer, double *
 hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAdaRatio, int whichBuffer, double *maxStep) {
     StatScope stat_(ST_RATIO, __func__);
     MiCone *c = (MiCone *) cd;
-    MiLin *l = (MiLin *) c->dualFactor->chol;
-    HdmChol *fac = (whichBuffer == 0) ? &l->ch : c->checker.get();   // LTarget, :1661-1665
+    HdmChol *fac = (whichBuffer == 0) ? dual_chol(c) : c->checker.get();   // LTarget, :1661-1665
     if (!fac || !fac->factored) return HDSDP_RETCODE_FAILED;
-    if (whichBuffer == 0 && c->rat_set && c->rat_set->on) {      // (the checker buffer stays per cone, as it does for the check set)
+    if (whichBuffer == 0 && c->in_ratio.active()) {              // (the checker buffer stays per cone, as it does for the check set)
         hdsdp_retcode rcs;
         if (ratio_set_answer(c, dTauStep, dy, dAdaRatio, maxStep, &rcs)) return rcs;
     }
-    const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
-    if (!c->dS.get()) {
-        HIP_RC(c->dS.alloc(nn / sizeof(double)));
-        HIP_RC(hdm_memset_sync(c->dS.get(), 0, nn));
-    }
+    HIP_RC(cone_make_dS(c));
     const double eye = dAdaRatio * c->Rd;
     if (cone_assemble(c, dTauStep, dy, HDM_DUAL_DS, &eye)) return HDSDP_RETCODE_FAILED;
     if (c->n == 1) {   // :1668-1675
@@ -784,10 +762,7 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
     }
     RC(hdm_mirror_lower(c->dS.get(), c->n16, c->n, g.stream));
     if (fac->invert_factor(g.stream)) return HDSDP_RETCODE_FAILED;
-    if (!c->lanczos) {
-        c->lanczos.reset(new HdmLanczos());
-        if (c->lanczos->init(c->n)) return HDSDP_RETCODE_MEMORY;
-    }
+    if (const hdsdp_retcode rc = cone_make(c->lanczos, c->n); rc != HDSDP_RETCODE_OK) return rc;
     int steps = 0;
     const bool dbg = hdm_env_int<ENV_RATIO_DEBUG>().value_or(0) != 0;
     const auto t0 = std::chrono::steady_clock::now();
@@ -944,8 +919,7 @@ void cone_scal(void *cd, double dScal) {
 
 // X (host, n x n column-major, symmetric) -> the device scratch matrix Xup (ld = npad of the dual factor)
 static int cone_upload_X(MiCone *c, const double *X, long *ldx) {
-    MiLin *l = (MiLin *) c->dualFactor->chol;
-    const long ld = l->ch.npad;
+    const long ld = dual_chol(c)->npad;
     const size_t np2 = sizeof(double) * (size_t) ld * ld;
     HDM_HIP_CHECK(c->Xup.reserve(np2 / sizeof(double)));   // (Xinv / Yinv belong to the builders, sized per path)
     HDM_HIP_CHECK(hipMemsetAsync(c->Xup.get(), 0, np2, g.stream));
@@ -1054,7 +1028,6 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
     MiCone *c = (MiCone *) cd;
     const double zero = 0.0;
     const int n = c->n;
-    const size_t nn = sizeof(double) * (size_t) c->n16 * c->n16;
     auto fail = [](const char *what) { fprintf(stderr, "[hdsdp_mi355x] primal recovery: %s\n", what); };
     if (cone_assemble(c, 1.0, y, HDM_DUAL_SCHECK, &zero)) return fail("S assembly failed");
     HdmChol *chp = nullptr;
@@ -1067,9 +1040,7 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
         printf("Recovery step is infeasible\n");
         return;
     }
-    if (!c->dS.get()) {
-        if (c->dS.alloc(nn / sizeof(double)) != hipSuccess || hdm_memset_sync(c->dS.get(), 0, nn) != hipSuccess) return fail("out of memory");
-    }
+    if (cone_make_dS(c) != hipSuccess) return fail("out of memory");
     std::vector<double> ndy(c->m);
     for (int i = 0; i < c->m; ++i) ndy[i] = -dy[i];           // cone_assemble subtracts: dS = + sum dy_i A_i
     if (cone_assemble(c, 0.0, ndy.data(), HDM_DUAL_DS, &zero)) return fail("dS assembly failed");

@@ -8,10 +8,9 @@
 // what only the engine can say about a cone (grouped_plan.h: HdmGroupedCone::kind_ok): an SDP cone of this engine on one device,
 // not synthetic, not streamed, its A_L forms resident -- and a one-block dual factor, whose Dinv is the triangular inverse
 bool grouped_kind_ok(const hdsdp_cone *hc) {
-    if (hc->coneBuildSchur != cone_build_schur) return false;
-    const MiCone *c = (const MiCone *) hc->coneData;
-    if (c->world != 1 || c->synthetic || c->rows.streamed() || !c->rows.resident() || !c->dualFactor) return false;
-    const HdmChol &ch = ((const MiLin *) c->dualFactor->chol)->ch;
+    const MiCone *c = own_cone_with_factor(hc);
+    if (!c || c->world != 1 || c->synthetic || c->rows.streamed() || !c->rows.resident()) return false;
+    const HdmChol &ch = *dual_chol(c);
     return ch.nblk == 1 && ch.npad == SMALL_P;
 }
 
@@ -88,7 +87,7 @@ hdsdp_retcode grouped_build(hdsdp_kkt *HKKT, MiKKTPriv *pv, int typeKKT) {
     const int nc = (int) p.cones.size();
     for (int s = 0; s < nc; ++s) {
         const MiCone *c = (const MiCone *) HKKT->cones[p.cones[(size_t) s]]->coneData;
-        const HdmChol &ch = ((const MiLin *) c->dualFactor->chol)->ch;
+        const HdmChol &ch = *dual_chol(c);
         if (!ch.factored) {
             fprintf(stderr, "[hdsdp_mi355x] BuildSchur: the dual matrix has no valid Cholesky factor\n");
             return HDSDP_RETCODE_FAILED;

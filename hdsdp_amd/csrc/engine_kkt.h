@@ -772,7 +772,7 @@ int HMiKKTSetGroupedCheck(hdsdp_kkt *HKKT, int on) { return check_set_switch(pri
 int HMiKKTGetGroupedCheck(hdsdp_kkt *HKKT, long out[6]) {
     const MiCheckSet &cs = priv_of(HKKT)->chk;
     if (out) {
-        out[0] = cs.count(); out[1] = cs.launches; out[2] = cs.last_cones; out[3] = cs.total_cones;
+        cs.report(out);
         out[4] = cs.from_state; out[5] = cs.last_left_out;
     }
     return cs.on ? 1 : 0;
@@ -785,7 +785,7 @@ int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on) { return ratio_set_switch(pri
 int HMiKKTGetGroupedRatio(hdsdp_kkt *HKKT, long out[7]) {
     const MiRatioSet &rs = priv_of(HKKT)->rat;
     if (out) {
-        out[0] = rs.count(); out[1] = rs.launches; out[2] = rs.last_cones; out[3] = rs.total_cones;
+        rs.report(out);
         out[4] = rs.from_slots; out[5] = rs.last_left_out; out[6] = rs.fallbacks;
     }
     return rs.on ? 1 : 0;

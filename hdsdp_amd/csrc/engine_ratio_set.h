@@ -4,55 +4,36 @@
 // The rules are small_ratio_rule.h's (membership, and when a stored answer may be served), the kernels lanczos.hip's
 // (hdm_grouped_ratio_kernel: step matrix + the one-launch Lanczos test's body, one workgroup per table entry) and small.hip's
 // (hdm_grouped_safeguard_kernel), the book-keeping dual_state.h's; the struct (MiRatioSet) is engine_cone.h's, next to the cones it
-// names.  This file says which cones of an operator are members, keeps the table and the slots, and makes the launch.
-// DESIGN.md section 22.
+// names; who is a member for how long is cone_set.h's.  This file says which cones of an operator are
+// eligible, keeps the table and the slots, and makes the launch.  DESIGN.md section 22.
 
 // the cone as small_ratio_rule.h sees it, with its dual factor object
 HdmSmallRatioCone ratio_set_desc(const MiCone *c) {
     HdmSmallRatioCone d;
-    d.chk = small_check_desc(c, &((const MiLin *) c->dualFactor->chol)->ch);
+    d.chk = small_check_desc(c, dual_chol(c));
     d.n = c->n;
     return d;
 }
 // a member: an SDP cone of this engine (not a device-group cone, not an LP cone, not a host cone) the rule admits
-bool ratio_set_kind_ok(const hdsdp_cone *hc) {
-    if (hc->coneBuildSchur != cone_build_schur) return false;
-    const MiCone *c = (const MiCone *) hc->coneData;
-    if (!c || !c->dualFactor) return false;
-    return hdm_small_ratio_member(ratio_set_desc(c), hdm_lz_switches());
+MiCone *ratio_set_eligible(const hdsdp_cone *hc) {
+    MiCone *c = own_cone_with_factor(hc);
+    return (c && hdm_small_ratio_member(ratio_set_desc(c), hdm_lz_switches())) ? c : nullptr;
 }
 
-// HKKTInit: membership only, by the check set's lifetime rules.  A cone that another operator's ACTIVE set holds is not taken;
-// one that an inactive set holds moves here (the operator initialised last has it).
+// HKKTInit: membership only, by cone_set.h's rules (the operator initialised last has a cone no ACTIVE set holds)
 void ratio_set_init(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
     MiRatioSet &rs = pv->rat;
     rs.release();
-    rs.launches = rs.last_cones = rs.total_cones = rs.from_slots = rs.last_left_out = rs.fallbacks = 0;
-    for (int i = 0; i < HKKT->nCones; ++i) {
-        if (!ratio_set_kind_ok(HKKT->cones[i])) continue;
-        MiCone *c = (MiCone *) HKKT->cones[i]->coneData;
-        if (c->rat_set == &rs) continue;                       // (the same cone named twice)
-        if (c->rat_set) {
-            if (c->rat_set->on) continue;
-            ratio_set_forget(c);
-        }
-        c->rat_set = &rs; c->rat_slot = (int) rs.members.size();
-        rs.members.push_back(c);
-    }
+    rs.reset_counters(); rs.from_slots = rs.fallbacks = 0;
+    for (int i = 0; i < HKKT->nCones; ++i)
+        if (MiCone *c = ratio_set_eligible(HKKT->cones[i])) rs.adopt(c);
     rs.slots.assign(rs.members.size(), HdmRatioSlot());
 }
 
-void ratio_set_forget(MiCone *c) {
-    MiRatioSet *rs = c->rat_set;
-    if (!rs) return;
-    if (c->rat_slot >= 0 && c->rat_slot < (int) rs->members.size() && rs->members[(size_t) c->rat_slot] == c)
-        rs->members[(size_t) c->rat_slot] = nullptr;
-    c->rat_set = nullptr; c->rat_slot = -1;
-}
-
 void ratio_set_drop_answer(MiCone *c) {
-    MiRatioSet *rs = c->rat_set;
-    if (rs && c->rat_slot >= 0 && c->rat_slot < (int) rs->slots.size()) rs->slots[(size_t) c->rat_slot].valid = false;
+    MiRatioSet *rs = ratio_set_of(c);
+    const int slot = c->in_ratio.slot;
+    if (rs && slot >= 0 && slot < (int) rs->slots.size()) rs->slots[(size_t) slot].valid = false;
 }
 
 // the switch: returns the number of members (0: off, or fewer than two members).  Turning it on makes everything a launch needs.
@@ -77,14 +58,8 @@ int ratio_set_switch(MiKKTPriv *pv, int on) {
         if (!c) continue;
         rs.yoff[q] = ytot;
         ytot += std::max(1, c->mloc);
-        if (!c->dS.get()) {                                     // (as cone_ratio_test makes it: zero, so the padding reads as 0)
-            const size_t n2 = (size_t) c->n16 * c->n16;
-            if (c->dS.alloc(n2) != hipSuccess || hdm_memset_sync(c->dS.get(), 0, sizeof(double) * n2) != hipSuccess) return stays("a step matrix");
-        }
-        if (!c->lanczos) {
-            c->lanczos.reset(new HdmLanczos());
-            if (c->lanczos->init(c->n)) { c->lanczos.reset(); return stays("a member's Lanczos buffers"); }
-        }
+        if (cone_make_dS(c) != hipSuccess) return stays("a step matrix");
+        if (cone_make(c->lanczos, c->n) != HDSDP_RETCODE_OK) return stays("a member's Lanczos buffers");
     }
     if (rs.table.alloc(rs.members.size(), hipHostMallocMapped) != hipSuccess) return stays("the table");
     if (rs.ybuf.alloc((size_t) ytot, hipHostMallocMapped) != hipSuccess) return stays("the multipliers");
@@ -94,25 +69,20 @@ int ratio_set_switch(MiKKTPriv *pv, int on) {
 
 // the member's question: dTauStep, eye = dAdaRatio * its own Rd, dy gathered through its own own[] into `yo`; *any: one of them is non-zero
 HdmDualPoint ratio_set_question(const MiCone *c, double dTauStep, const double *dy, double dAdaRatio, double *yo, bool *any) {
-    bool a = false;
-    for (int q = 0; q < c->mloc; ++q) { yo[q] = dy ? dy[c->own[q]] : 0.0; a |= (yo[q] != 0.0); }
-    if (any) *any = a;
-    HdmDualPoint p;
-    p.tau = dTauStep; p.eye = dAdaRatio * c->Rd; p.y = yo; p.ny = c->mloc;
-    return p;
+    return cone_point(c, dTauStep, dAdaRatio * c->Rd, dy, yo, any);
 }
 
 // One pair of launches and one synchronisation for every member whose dual factor stands and whose slot does not already hold an
 // unconsumed answer to this question.  Returns nonzero when the launches could not be made or did not finish.
 int ratio_set_launch(MiRatioSet *rs, double dTauStep, const double *dy, double dAdaRatio) {
     HdmGroupedRatioArgs *tab = rs->table.get();
-    rs->launched.clear();
+    rs->launch_begin();
     int left_out = 0;
     std::vector<HdmDualPoint> pts;
     for (size_t k = 0; k < rs->members.size(); ++k) {
         MiCone *c = rs->members[k];
         if (!c) continue;
-        HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
+        HdmChol *ch = dual_chol(c);
         // (the rule is asked again: neither the switches nor the factor object's shape change under a set)
         if (!hdm_small_ratio_member(ratio_set_desc(c), hdm_lz_switches()) || !c->lanczos || !c->dS.get()) continue;
         if (!ch->factored) { left_out += 1; continue; }         // its own call fails as it does today
@@ -132,8 +102,7 @@ int ratio_set_launch(MiRatioSet *rs, double dTauStep, const double *dy, double d
         double *r = c->lanczos->scal_h.get() + LZ_MB_WHOLE;
         r[0] = 0.0; r[1] = 0.0; r[2] = -1.0; r[3] = -1.0;       // "nothing reported"
         slot.valid = false;
-        tab[rs->launched.size()] = a;
-        rs->launched.push_back((int) k);
+        tab[rs->launch_take(k)] = a;
         pts.push_back(p);
     }
     rs->last_left_out = left_out;
@@ -141,7 +110,7 @@ int ratio_set_launch(MiRatioSet *rs, double dTauStep, const double *dy, double d
     if (nl == 0) return 0;
     if (hdm_grouped_ratio(tab, rs->table.dev(), nl, g.stream) || hdm_grouped_safeguard(rs->table.dev(), nl, g.stream) ||
         hipStreamSynchronize(g.stream) != hipSuccess) return 1;
-    rs->launches += 1; rs->last_cones = nl; rs->total_cones += nl;
+    rs->launch_made();
     const bool dbg = hdm_env_int<ENV_RATIO_DEBUG>().value_or(0) != 0;
     for (int s = 0; s < nl; ++s) {
         const size_t k = (size_t) rs->launched[(size_t) s];
@@ -161,7 +130,7 @@ int ratio_set_launch(MiRatioSet *rs, double dTauStep, const double *dy, double d
             if (r[3] != 0.0) {
                 // the step left the cone: the rest of the safeguard on the host, for this cone alone (its fresh-start test reads
                 // the factor's Linv, which the per-cone path would have made before its own test)
-                HdmChol *ch = &((MiLin *) c->dualFactor->chol)->ch;
+                HdmChol *ch = dual_chol(c);
                 rs->fallbacks += 1;
                 slot.rc = ch->invert_factor(g.stream) ? HDSDP_RETCODE_FAILED : ratio_safeguard_rest(c, ch, 0, &slot.step);
             }
@@ -174,9 +143,10 @@ int ratio_set_launch(MiRatioSet *rs, double dTauStep, const double *dy, double d
 }
 
 bool ratio_set_answer(MiCone *c, double dTauStep, const double *dy, double dAdaRatio, double *maxStep, hdsdp_retcode *rc) {
-    MiRatioSet *rs = c->rat_set;
-    if (c->rat_slot < 0 || c->rat_slot >= (int) rs->slots.size() || !rs->table || !c->lanczos || !c->dS.get()) return false;
-    HdmRatioSlot &slot = rs->slots[(size_t) c->rat_slot];
+    MiRatioSet *rs = ratio_set_of(c);
+    const int at = c->in_ratio.slot;
+    if (at < 0 || at >= (int) rs->slots.size() || !rs->table || !c->lanczos || !c->dS.get()) return false;
+    HdmRatioSlot &slot = rs->slots[(size_t) at];
     std::vector<double> yq((size_t) std::max(1, c->mloc));
     const HdmDualPoint q = ratio_set_question(c, dTauStep, dy, dAdaRatio, yq.data(), nullptr);
     const bool held = hdm_ratio_slot_serves(slot, q, c->dual.moves());

@@ -522,8 +522,7 @@ void gc_destroy_data(void **pcd) {
 MiCone *cone_data(hdsdp_cone *cone) {
     if (!cone) return nullptr;
     if (cone->coneBuildSchur == gc_build_schur) return ((MiConeGroup *) cone->coneData)->shard[0];
-    if (cone->coneBuildSchur != cone_build_schur) return nullptr;     // an LP cone (engine_lp.h) or a foreign one: no SDP data
-    return (MiCone *) cone->coneData;
+    return own_cone_data(cone);       // (nullptr for an LP cone (engine_lp.h) or a foreign one: no SDP data)
 }
 
 hdsdp_retcode group_create_cone(hdsdp_cone **pCone, int iCone, int nRow, int nCol, MiBlockData *blk, bool synthetic) {
