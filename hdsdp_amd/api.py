@@ -43,6 +43,7 @@ EXPORTS = [
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
     "HMiKKTSetGroupedCheck", "HMiKKTGetGroupedCheck", "HMiKKTCheckIsInterior",
     "HMiKKTSetGroupedRatio", "HMiKKTGetGroupedRatio", "HMiKKTRatioTest",
+    "HMiKKTSetGroupedStep", "HMiKKTGetGroupedStep", "HMiKKTAddStepToBufferAndCheck", "HMiConeGetChecker",
     "HMiLinsysSetRefine", "HMiLinsysGetRefine", "HMiLinsysRefineBytes", "HMiKKTSetRefine", "HMiSymResidualProbe",
     "HMiLinsysSetRefineTiles", "HMiLinsysGetRefineTiles", "HMiKKTSetRefineTiles", "HMiTileResidualProbe", "HMiBspRefinedSolve", "HMiBspRefineTimingProbe",
     "HMiReadSDPA", "HMiSDPAGetDims", "HMiSDPAGetBlock", "HMiSDPAGetBlock64", "HMiSDPAGetLPBlock", "HMiSDPAGetRHS", "HMiSDPAFree",
@@ -307,6 +308,10 @@ def load_library():
         "HMiKKTSetGroupedRatio": (C.c_int, [kp, C.c_int]),
         "HMiKKTGetGroupedRatio": (C.c_int, [kp, C.POINTER(C.c_long)]),
         "HMiKKTRatioTest": (C.c_int, [kp, C.c_double, dp, C.c_double, C.c_int, dp, dp]),
+        "HMiKKTSetGroupedStep": (C.c_int, [kp, C.c_int]),
+        "HMiKKTGetGroupedStep": (C.c_int, [kp, C.POINTER(C.c_long)]),
+        "HMiKKTAddStepToBufferAndCheck": (C.c_int, [kp, C.c_double, C.c_int, ip, ip]),
+        "HMiConeGetChecker": (C.c_int, [vp, dp, dp, dp]),
         "HMiLinsysSetRefine": (C.c_int, [vp, C.c_int]),
         "HMiLinsysGetRefine": (C.c_int, [vp, ip, ip, dp, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "HMiLinsysRefineBytes": (C.c_int64, [vp]),
@@ -785,6 +790,14 @@ class SDPCone:
         _check(load_library().HMiConeGetDualMatrix(self._h, _dptr(S)), "HMiConeGetDualMatrix")
         return S
 
+    def checker_state(self):
+        """HMiConeGetChecker: (Scheck, L, Dinv) as the last write of the checker left them -- the checker buffer, n16 x n16,
+        and the checker factor object's two 128 x 128 matrices; element (i, j) of each is [j, i] (column-major storage)"""
+        n16 = (self.n + 15) // 16 * 16
+        Sc, L, D = np.zeros((n16, n16)), np.zeros((128, 128)), np.zeros((128, 128))
+        _check(load_library().HMiConeGetChecker(self._h, _dptr(Sc), _dptr(L), _dptr(D)), "HMiConeGetChecker")
+        return Sc, L, D
+
     def traces(self):
         t = np.zeros(self.m, dtype=np.float64)
         _check(load_library().HMiConeGetTraces(self._h, _dptr(t)), "HMiConeGetTraces")
@@ -1113,6 +1126,27 @@ class KKT:
         _check(load_library().HMiKKTRatioTest(self._k, float(dtau_step), _dptr(dy), float(ada_ratio), buffer, _dptr(steps),
                                               C.byref(mn)), "HMiKKTRatioTest")
         return steps, mn.value
+
+    def set_grouped_step(self, on):
+        """HMiKKTSetGroupedStep: a step-and-check on the checker buffer asked of one member of the operator's step set puts
+        every member's checker at S + step dS in one launch (csrc/small_step_rule.h has the rule); the later calls answer from
+        their slots.  Returns the number of members (0: off, or fewer than two members)"""
+        return int(load_library().HMiKKTSetGroupedStep(self._k, 1 if on else 0))
+
+    def grouped_step_info(self):
+        """HMiKKTGetGroupedStep: dict(on, members, launches, last_cones, total_cones, from_slots, left_out)"""
+        out = (C.c_long * 6)()
+        on = load_library().HMiKKTGetGroupedStep(self._k, out)
+        return {"on": bool(on), "members": out[0], "launches": out[1], "last_cones": out[2], "total_cones": out[3],
+                "from_slots": out[4], "left_out": out[5]}
+
+    def axpy_buffer_and_check(self, step, buffer=BUFFER_DUALCHECK):
+        """HMiKKTAddStepToBufferAndCheck: every cone of the operator at S + step dS, in order and without early exit; returns
+        (flags, all, rc): flags[k] is False where cone k is outside or its slot failed, rc the first retcode that was not OK"""
+        flags = np.zeros(len(self.cones), dtype=np.int32)
+        every = C.c_int(0)
+        rc = int(load_library().HMiKKTAddStepToBufferAndCheck(self._k, float(step), buffer, _iptr(flags), C.byref(every)))
+        return flags.astype(bool), bool(every.value), rc
 
     def diag_target(self):
         """HMiKKTGetDiagTarget: 0 = kktDiag[] points into kktMatElem, 1 = into the diagonal channel"""

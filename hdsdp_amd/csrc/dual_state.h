@@ -97,6 +97,10 @@ class HdmDualState {
     int aff_chain = 0;                   // updates of S in place since its last full assembly
     bool fac_ok = false; int fac_psd = 0;   // the dual factor object holds the factorisation of S = T(pS) (result: fac_psd)
     unsigned long n_moves = 0;           // transitions so far: whoever keeps something derived from S, dS or the factor compares it
+    // Two counters the transitions above do not give (small_step_rule.h: a stored step-and-check answer is served only while
+    // neither has moved): every rewrite of dS, whether or not the block tracks points (dS_assembled_at is a tracking block's alone),
+    // and every write of the checker buffer or the checker factor object, which no transition names.  Neither enters moves().
+    unsigned long n_dS_writes = 0, n_checker = 0;
     friend HdmDualPlan hdm_dual_plan(const HdmDualState &, const HdmDualPoint &, HdmDualTarget, int, int);
     friend void hdm_dual_print_miss(FILE *, const HdmDualState &, const HdmDualPoint &, HdmDualTarget, const HdmDualPlan &);
 
@@ -113,6 +117,12 @@ public:
     // every transition below counts here; a value read after one and found again later says that none has happened in between
     // (small_ratio_rule.h: a stored ratio-test answer is served only then)
     unsigned long moves() const { return n_moves; }
+    unsigned long dS_writes() const { return n_dS_writes; }
+    unsigned long checker_epoch() const { return n_checker; }
+    // dS rewritten by a path that does not go through commit (the grouped ratio launch); Scheck or the checker factor object
+    // written (cone_small_check on the checker, cone_factor_check, cone_axpy_check, the primal recovery, the grouped step launch)
+    void dS_written() { n_dS_writes += 1; }
+    void checker_written() { n_checker += 1; }
 
     // Transitions, named for what happened.  Whatever moves S leaves its factor behind.
     // S assembled at p: a sweep of a tracking block, or the one-launch small check (which assembles S itself)
@@ -138,6 +148,8 @@ public:
 
     // what performing `plan` for a request of T(p) into `target` did to the buffers
     void commit(const HdmDualPlan &plan, const HdmDualPoint &p, HdmDualTarget target) {
+        if (target == HDM_DUAL_DS) dS_written();                              // in every mode: tracking decides what is REMEMBERED of it
+        if (target == HDM_DUAL_SCHECK) checker_written();
         switch (plan.action) {
         case HDM_DUAL_NONE: case HDM_DUAL_COPY_FROM_S: break;                 // S stays; the checker buffer is not tracked
         case HDM_DUAL_AXPY: case HDM_DUAL_AXPY_EYE: if (target == HDM_DUAL_S) S_advanced_to(p); break;

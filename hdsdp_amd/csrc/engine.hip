@@ -28,6 +28,7 @@
 #include "lu.h"
 #include "refine.h"
 #include "small.h"
+#include "small_step_rule.h"
 #include "bsparse.h"
 #include <algorithm>
 #include <atomic>
@@ -143,6 +144,7 @@ namespace {
 #include "engine_grouped.h"
 #include "engine_check_set.h"
 #include "engine_ratio_set.h"
+#include "engine_step_set.h"
 }  // namespace
 
 // =============================================================================================

@@ -171,6 +171,16 @@ hdsdp_retcode HMiConeGetDualMatrix(hdsdp_cone *cone, double *S) {
                          hipMemcpyDeviceToHost, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
     return hipStreamSynchronize(g.stream) == hipSuccess ? HDSDP_RETCODE_OK : HDSDP_RETCODE_FAILED;
 }
+hdsdp_retcode HMiConeGetChecker(hdsdp_cone *cone, double *Scheck, double *L, double *Dinv) {
+    MiCone *c = own_cone_data(cone);
+    if (!c || !c->checker || !hdm_small_check_factor_ok(c->checker->npad, c->checker->nblk)) return HDSDP_RETCODE_FAILED;
+    const HdmChol &ch = *c->checker;
+    const size_t np2 = sizeof(double) * (size_t) ch.npad * ch.npad;
+    if (Scheck && hipMemcpyAsync(Scheck, c->Scheck.get(), sizeof(double) * (size_t) c->n16 * c->n16, hipMemcpyDeviceToHost, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+    if (L && hipMemcpyAsync(L, ch.L.get(), np2, hipMemcpyDeviceToHost, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+    if (Dinv && hipMemcpyAsync(Dinv, ch.Dinv.get(), np2, hipMemcpyDeviceToHost, g.stream) != hipSuccess) return HDSDP_RETCODE_FAILED;
+    return hipStreamSynchronize(g.stream) == hipSuccess ? HDSDP_RETCODE_OK : HDSDP_RETCODE_FAILED;
+}
 hdsdp_retcode HMiConeGetTraces(hdsdp_cone *cone, double *trA) {
     MiCone *c = cone_data(cone);
     if (!c || c->trA.empty()) return HDSDP_RETCODE_FAILED;

@@ -124,9 +124,9 @@ struct MiCone {
     // from which cone_assemble answers a request on the line through them without a sweep.  Every writer of S, dS or the
     // dual factor object names what it did through one of this object's transitions.
     HdmDualState dual;
-    // the check set (engine_check_set.h) and the ratio set (engine_ratio_set.h) this cone is a member of, and its place there:
-    // cone_set.h's links, assigned and cleared by its rules alone
-    HdmConeLink<MiCone> in_check, in_ratio;
+    // the check set (engine_check_set.h), the ratio set (engine_ratio_set.h) and the step set (engine_step_set.h) this cone is a
+    // member of, and its place there: cone_set.h's links, assigned and cleared by its rules alone
+    HdmConeLink<MiCone> in_check, in_ratio, in_step;
     // fused single-launch Phase-A pass of a small rank-one block (small.hip): factors as a CSR, built on first use
     struct SmallPlan {
         int state = 0;         // 0 = not looked at, 1 = ready, -1 = not eligible
@@ -186,14 +186,32 @@ struct MiRatioSet : HdmConeSet<MiCone> {
     MiRatioSet() : HdmConeSet<MiCone>(&MiCone::in_ratio) {}
     void release() { HdmConeSet<MiCone>::release(); slots.clear(); yoff.clear(); table.reset(); ybuf.reset(); }
 };
-// the set a cone is a member of, as its own kind (the links are assigned by sets of these two types only)
+// The step set of an operator (engine_step_set.h performs it): the small SDP cones whose step-and-check on
+// the checker buffer -- "is S + dStep dS still inside?" -- is run for ALL of them by one launch of hdm_grouped_step_check_kernel the
+// first time one of them is asked a step its slot does not hold.  HKKTInit decides membership (small_step_rule.h); the switch
+// allocates the table and the report words and makes every member's checker object and step buffer, so that a launch allocates
+// nothing (HMiKKTSetGroupedStep / HDSDP_MI355X_GROUPED_STEP).  Members, lifetimes and the launch counters are cone_set.h's.
+struct MiStepSet : HdmConeSet<MiCone> {
+    std::vector<HdmStepSlot> slots;        // one per member: the answer of the last launch it was in (small_step_rule.h)
+    // one per member: the switch made its step buffer (zeros: no step matrix yet), when its dS counter stood at ds_at_on
+    std::vector<char> made_dS;
+    std::vector<unsigned long> ds_at_on;
+    HdmPinned<HdmGroupedStepArgs> table;   // mapped pinned, one entry per member: the launch's arguments, launched members first
+    HdmPinned<int> words;                  // mapped pinned, one word per member: the sweep's info, -1 until the launch has reported
+    long from_slots = 0;                   // answers served from slots since the switch went on
+    MiStepSet() : HdmConeSet<MiCone>(&MiCone::in_step) {}
+    void release() { HdmConeSet<MiCone>::release(); slots.clear(); made_dS.clear(); ds_at_on.clear(); table.reset(); words.reset(); }
+};
+// the set a cone is a member of, as its own kind (the links are assigned by sets of these three types only)
 MiCheckSet *check_set_of(const MiCone *c) { return static_cast<MiCheckSet *>(c->in_check.set); }
 MiRatioSet *ratio_set_of(const MiCone *c) { return static_cast<MiRatioSet *>(c->in_ratio.set); }
+MiStepSet *step_set_of(const MiCone *c) { return static_cast<MiStepSet *>(c->in_step.set); }
 
 struct MiKKTPriv {
     MiGrouped grp;
     MiCheckSet chk;
     MiRatioSet rat;
+    MiStepSet stp;
     // how M is stored, what state it is in and where the last factorised matrix came from (kkt_store.h); the operator's linear
     // system (MiLin::st) points here
     HdmKktState st;
@@ -562,6 +580,7 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
     }
     const HdmSmallCheckArgs a = small_check_args(c, ch, p, whichBuffer);
     if (whichBuffer == 0) c->dual.S_overwritten();   // the launch writes S: what it holds is known again when the launch has reported
+    else c->dual.checker_written();                  // ... or the checker buffer and the checker factor object
     if (hdm_small_check(a, g.stream) || hipStreamSynchronize(g.stream) != hipSuccess) { *rc = HDSDP_RETCODE_FAILED; return 0; }
     const int info = small_check_commit(c, ch, p, whichBuffer);
     if (info < 0) { *rc = HDSDP_RETCODE_FAILED; return 0; }
@@ -598,6 +617,7 @@ hdsdp_retcode cone_factor_check(MiCone *c, int *isPsd) {
     HdmChol *ch = nullptr;
     RC(cone_checker(c, &ch));
     int info = 0;
+    c->dual.checker_written();
     if (ch->load_device(c->Scheck.get(), c->n16, g.stream) || ch->factor(g.stream, &info)) return HDSDP_RETCODE_FAILED;
     if (isPsd) *isPsd = (info == 0);
     return HDSDP_RETCODE_OK;
@@ -621,15 +641,24 @@ hdsdp_retcode cone_interior_expert(void *cd, double dCCoef, double dACoefScal, d
     return (whichBuffer == 0) ? cone_factor_S(c, isInterior) : cone_factor_check(c, isInterior);
 }
 
+// engine_step_set.h: c is a member of an active set and is asked dStep on the checker buffer.  Returns true when the set has
+// answered (*rc, *isInterior), false when c's own path must run
+bool step_set_answer(MiCone *c, double dStep, int *isInterior, hdsdp_retcode *rc);
+
 // sdpDenseConeAddStepToBufferAndCheck (hdsdp_conic_sdp.c:2333-2361): S + dStep*dS with the dS of the last ratio test;
 // BUFFER_DUALVAR updates S in place, BUFFER_DUALCHECK leaves S alone and factors the trial point in the checker
 hdsdp_retcode cone_axpy_check(void *cd, double dStep, int whichBuffer, int *isInterior) {
     StatScope stat_(ST_ASSEMBLE_FACTOR, __func__);
     MiCone *c = (MiCone *) cd;
+    if (whichBuffer != 0 && c->in_step.active()) {               // (the dual buffer stays per cone: S itself moves there)
+        hdsdp_retcode rcs;
+        if (step_set_answer(c, dStep, isInterior, &rcs)) return rcs;
+    }
     if (!c->dS.get()) return HDSDP_RETCODE_FAILED;
     const long cnt = (long) c->n16 * c->n16;
     double *target = (whichBuffer == 0) ? c->S.get() : c->Scheck.get();
     if (whichBuffer == 0) c->dual.S_overwritten();   // S moves without a point being named: the next request assembles it
+    else c->dual.checker_written();                  // the checker buffer is written here, its factor object in cone_factor_check
     RC(hdm_axpy_mat(target, c->S.get(), c->dS.get(), dStep, cnt, g.stream));
     return (whichBuffer == 0) ? cone_factor_S(c, isInterior) : cone_factor_check(c, isInterior);
 }
@@ -1034,6 +1063,7 @@ void cone_precover(void *cd, double dBarrierMu, double *y, double *dy, double *X
     if (cone_checker(c, &chp) != HDSDP_RETCODE_OK) return fail("out of memory");
     HdmChol &ch = *chp;
     int info = 0;
+    c->dual.checker_written();
     if (ch.load_device(c->Scheck.get(), c->n16, g.stream) || ch.factor(g.stream, &info)) return fail("factorisation failed");
     if (info != 0) {
         if (stat_trace()) fprintf(stderr, "[hdsdp_mi355x trace]     primal recovery: factorisation stopped at pivot %d\n", info);

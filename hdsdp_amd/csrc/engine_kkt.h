@@ -413,6 +413,10 @@ static void kkt_apply_opt_ins(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
         const int k = ratio_set_switch(pv, 1);
         fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_RATIO=1: %d of %d cone(s) answer a ratio test in one grouped launch pair\n", k, nCones);
     }
+    if (hdm_env_on<ENV_GROUPED_STEP>()) {
+        const int k = step_set_switch(pv, 1);
+        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_STEP=1: %d of %d cone(s) answer a step-and-check in one grouped launch\n", k, nCones);
+    }
     // HDSDP_MI355X_REFINE=k: Schur solves are refined with at most k steps (HMiKKTSetRefine)
     if (const int k = hdm_env_int<ENV_REFINE>().value_or(0); k > 0) {
         (void) HMiKKTSetRefine(HKKT, k);
@@ -438,12 +442,13 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     rc = kkt_init_device_common(HKKT, pv);
     if (rc != HDSDP_RETCODE_OK) return rc;
     if (sw.device_m) kkt_apply_device_m(HKKT, pv);
-    // eligibility for the grouped Schur build (engine_grouped.h) and membership of the check set (engine_check_set.h) and of the
-    // ratio set (engine_ratio_set.h) are decided for every operator; the grouped pass and the grouped launches are used when
+    // eligibility for the grouped Schur build (engine_grouped.h) and membership of the check set (engine_check_set.h), of the
+    // ratio set (engine_ratio_set.h) and of the step set (engine_step_set.h) are decided for every operator; the grouped pass and the grouped launches are used when
     // their switches are on
     grouped_init_plan(HKKT, pv);
     check_set_init(HKKT, pv);
     ratio_set_init(HKKT, pv);
+    step_set_init(HKKT, pv);
     kkt_apply_opt_ins(HKKT, pv);
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
@@ -794,6 +799,19 @@ hdsdp_retcode HMiKKTRatioTest(hdsdp_kkt *HKKT, double dTauStep, const double *dy
                               double *minStep) {
     if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
     return ratio_all_cones(HKKT, dTauStep, dy, dAdaRatio, whichBuffer, steps, minStep);
+}
+int HMiKKTSetGroupedStep(hdsdp_kkt *HKKT, int on) { return step_set_switch(priv_of(HKKT), on); }
+int HMiKKTGetGroupedStep(hdsdp_kkt *HKKT, long out[6]) {
+    const MiStepSet &ss = priv_of(HKKT)->stp;
+    if (out) {
+        ss.report(out);
+        out[4] = ss.from_slots; out[5] = ss.last_left_out;
+    }
+    return ss.on ? 1 : 0;
+}
+hdsdp_retcode HMiKKTAddStepToBufferAndCheck(hdsdp_kkt *HKKT, double dStep, int whichBuffer, int *flags, int *allInterior) {
+    if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
+    return step_all_cones(HKKT, dStep, whichBuffer, flags, allInterior);
 }
 int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
     MiKKTPriv *pv = priv_of(HKKT);

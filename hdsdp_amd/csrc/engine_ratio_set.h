@@ -119,6 +119,7 @@ int ratio_set_launch(MiRatioSet *rs, double dTauStep, const double *dy, double d
         const HdmDualPoint &p = pts[(size_t) s];
         const double *r = c->lanczos->scal_h.get() + LZ_MB_WHOLE;
         g_asm_counts[HDM_ASM_SWEEP_STEP].fetch_add(1, std::memory_order_relaxed);
+        c->dual.dS_written();                                   // in every tracking mode (small_step_rule.h)
         if (hdm_dual_mode(c->mloc, c->n) > 0) c->dual.dS_assembled_at(p);       // (a member is on one device: it tracks points unless mode 0)
         if (r[2] < 0.0 || r[3] < 0.0) continue;                 // the launch has not reported for this member: its slot stays empty
         slot.rc = HDSDP_RETCODE_OK;

@@ -51,6 +51,20 @@ int hdm_small_check(const HdmSmallCheckArgs &args, hipStream_t s);
 // hdm_small_check makes on its argument are made on every entry through the host's address, the kernel reads the device's.
 int hdm_grouped_check(const HdmSmallCheckArgs *table_host, const HdmSmallCheckArgs *table_dev, int count, int max_m, hipStream_t s);
 
+// The grouped step-and-check (small_step_rule.h has the rule, engine_step_set.h the set): ONE launch of `count`
+// independent workgroups.  Workgroup b writes table[b]'s checker buffer, Scheck = S + dStep dS over all n16 x n16 elements (what
+// hdm_axpy_mat writes), factors it with the sweep HdmChol::factor runs on a one-block object, leaves L and Dinv as that path
+// leaves them (L's strict upper triangle too: what the rectangle copy and the padding put there), and reports the sweep's info.
+struct HdmGroupedStepArgs {
+    int n, n16;                         // block dimension, leading dimension of S, dS, Scheck
+    const double *S, *dS;               // the dual matrix and the step matrix, n16 x n16
+    double dStep;
+    double *Scheck;                     // n16 x n16, all of it written
+    double *L, *Dinv;                   // 128 x 128 each: the checker factor object's HdmChol::L and ::Dinv
+    int *info;                          // the report word (mapped host): preset to -1, "nothing reported"
+};
+int hdm_grouped_step_check(const HdmGroupedStepArgs *table_host, const HdmGroupedStepArgs *table_dev, int count, hipStream_t s);
+
 size_t hdm_small_lds_bytes();
 int hdm_small_phase_a(const HdmSmallArgs &args, hipStream_t s);
 

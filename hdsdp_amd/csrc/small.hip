@@ -489,6 +489,75 @@ int hdm_grouped_safeguard(const HdmGroupedRatioArgs *table_dev, int count, hipSt
     return 0;
 }
 
+// ---- the grouped step-and-check (small.h: HdmGroupedStepArgs) --------------------------------------------
+// Workgroup b puts table[b]'s checker at S + dStep dS: what cone_axpy_check does for one cone in five launches -- hdm_axpy_mat into
+// Scheck, the rectangle copy into the checker object's L, the identity padding, the cleared info word, the diagonal-block sweep --
+// and leaves the same bits everywhere those launches write.  One pass over the 128 x 128 index square forms every element of the
+// n16 x n16 sum once: it goes to Scheck; inside n x n its lower part goes into the LDS image the sweep starts from (zeros above the
+// diagonal, the identity in the padding: what hdm_potrf_diag_sweep_body reads back from L), its strict upper part into L, where the
+// rectangle copy would have put it and the sweep's store leaves it.  Then that body's own steps: sm_sweep<false> over the n pivots,
+// L's lower triangle and all of Dinv stored whether or not a pivot failed, the first bad pivot reported.  Independent workgroups:
+// none waits for another, none reads a word another writes.
+__global__ __launch_bounds__(SM_T) void hdm_grouped_step_check_kernel(const HdmGroupedStepArgs *__restrict__ table, int count) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int) blockIdx.x >= count) return;
+    const HdmGroupedStepArgs p = table[blockIdx.x];
+    constexpr int ldi = SMALL_P + 1;
+    double *img = sm;                                  // 128 x 129 staging image; its head doubles as the sweep's block images
+    double *rsv = sm + SMALL_P * (SMALL_P + 1);        // 128 deferred scale factors
+    const int n = p.n, n16 = p.n16;
+    const int tid = threadIdx.x, ty = tid >> 5, tx = tid & 31;
+    const int ei = tid & (SMALL_P - 1), ej0 = tid >> 7;
+#pragma unroll 8
+    for (int j = ej0; j < SMALL_P; j += SM_T / SMALL_P) {
+        double v = 0.0;
+        if (ei < n16 && j < n16) {
+            const long e = ei + (long) j * n16;
+            v = hdm_axpy_elem(p.S[e], p.dS[e], p.dStep);
+            p.Scheck[e] = v;
+        }
+        const bool in = (ei < n && j < n);
+        if (ei >= j) img[ei + j * ldi] = in ? v : ((ei == j) ? 1.0 : 0.0);
+        else {
+            img[ei + j * ldi] = 0.0;
+            p.L[ei + (long) j * SMALL_P] = in ? v : 0.0;
+        }
+    }
+    __syncthreads();
+    double a[SM_NR][SM_NC], rr[SM_NR][SM_NC];
+#pragma unroll
+    for (int r = 0; r < SM_NR; ++r)
+#pragma unroll
+        for (int c = 0; c < SM_NC; ++c) a[r][c] = img[(ty + 16 * r) + (tx + 32 * c) * ldi];
+    __syncthreads();
+    double unused;
+    const int bad = sm_sweep<false>(n, a, rr, img, rsv, ty, tx, &unused);
+    __syncthreads();
+    sm_store_one<true>(SMALL_P, a, img, p.L, SMALL_P, ty, tx, tid);
+    sm_store_one<false>(SMALL_P, rr, img, p.Dinv, SMALL_P, ty, tx, tid);
+    if (tid == 0) *p.info = bad;
+}
+
+int hdm_grouped_step_check(const HdmGroupedStepArgs *table_host, const HdmGroupedStepArgs *table_dev, int count, hipStream_t s) {
+    if (!table_host || !table_dev || count < 1) return 1;
+    for (int k = 0; k < count; ++k) {
+        const HdmGroupedStepArgs &a = table_host[k];
+        if (a.n < 1 || a.n > SMALL_P || a.n16 < a.n || a.n16 > SMALL_P || (a.n16 & 15)) return 1;
+        if (!a.S || !a.dS || !a.Scheck || !a.L || !a.Dinv || !a.info) return 1;
+    }
+    const size_t lds = (size_t) hdm_small_check_lds_bytes(0);
+    static thread_local int configured_dev = -1;
+    int dev = 0;
+    HDM_HIP_CHECK(hipGetDevice(&dev));
+    if (configured_dev != dev) {
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_grouped_step_check_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) HDM_SMALL_CHECK_LDS_MAX));
+        configured_dev = dev;
+    }
+    hipLaunchKernelGGL(hdm_grouped_step_check_kernel, dim3((unsigned) count), dim3(SM_T), lds, s, table_dev, count);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 size_t hdm_small_lds_bytes() {
     return sizeof(double) * ((size_t) SMALL_P * (SMALL_P + 1) + SMALL_NDENSE * SMALL_P + 5 * SMALL_P + SMALL_P * SMALL_SPMAX + SMALL_P) +
            sizeof(int) * ((size_t) SMALL_P * SMALL_SPMAX + (SMALL_P + 4) + 2 * SMALL_P);

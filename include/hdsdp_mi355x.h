@@ -345,6 +345,10 @@ hdsdp_retcode HMiPresolveCSC(int nRow, int nCol, const int *coneMatBeg, const in
                              int *kktStrategy, int *objType);
 /* host copies of device state for parity checks: S (n x n, lower valid), b_i = tr(A_i) */
 hdsdp_retcode HMiConeGetDualMatrix(hdsdp_cone *cone, double *S);
+/* read-only observer for tests: the checker buffer (n16 x n16 doubles, n16 = n rounded up to 16, column-major) and the checker factor
+ * object's L and Dinv (128 x 128 each) as the last step-and-check, expert check or primal recovery left them; any of the three may be
+ * NULL.  Fails for a cone without a checker object yet, for n > 128, and for a cone that is not an SDP cone of the engine. */
+hdsdp_retcode HMiConeGetChecker(hdsdp_cone *cone, double *Scheck, double *L, double *Dinv);
 hdsdp_retcode HMiConeGetTraces(hdsdp_cone *cone, double *trA);
 /* which device path the cone's builder uses: 0 = dense congruence + Gram (MFMA), 1 = rank-one */
 int HMiConeGetPath(hdsdp_cone *cone);
@@ -452,6 +456,28 @@ int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on);
 int HMiKKTGetGroupedRatio(hdsdp_kkt *HKKT, long out[7]);
 hdsdp_retcode HMiKKTRatioTest(hdsdp_kkt *HKKT, double dTauStep, const double *dy, double dAdaRatio, int whichBuffer, double *steps,
                               double *minStep);
+/* The grouped step-and-check (csrc/small_step_rule.h, csrc/small.hip, csrc/engine_step_set.h).  Between the
+ * ratio test and the barrier the reference's line search asks every cone "is S + dStep dS still inside?" on BUFFER_DUALCHECK, and
+ * again with a smaller step until all are; a small SDP cone answers in five launches and one synchronisation of its own.  With the
+ * switch on, a step on BUFFER_DUALCHECK that a member's slot does not hold puts EVERY member's checker buffer and checker factor at
+ * that step in one launch and one synchronisation (one workgroup per member, the per-cone path's sums and its diagonal-block sweep:
+ * the same bits), and the loop's later calls answer from the members' slots -- any number of times, while dStep is exactly the
+ * same and nothing has been written to the member's S, dS, checker buffer or checker factor.  Members: the check set's population
+ * (above) whose checker object is one 128-block too, with HDM_DIAG_SWEEP not 0; n = 1 is a member.  BUFFER_DUALVAR, the ratio test
+ * on the checker and larger blocks keep their own paths.  One difference from the loop: a step put to one member moves every
+ * member's checker there, also those behind a cone at which the loop breaks.  Turning the switch on makes each member's checker
+ * object and step buffer; a member that has had no ratio test yet has no step matrix: it is left out and its own call fails, as it
+ * does per cone.  Off by default.
+ * HMiKKTSetGroupedStep: after HKKTInit; returns the number of members (0: off, or fewer than two members).
+ * HMiKKTGetGroupedStep: out[0] members [1] grouped launches since HKKTInit [2] cones in the last launch [3] cones launched in all
+ * [4] answers served from slots since the switch went on [5] members left out of the last launch (no step matrix, or a slot that
+ * serves this step already); returns 1 if the switch is on, else 0.
+ * HMiKKTAddStepToBufferAndCheck: the whole-operator question.  Every cone of cones[] in order, without early exit, through its own
+ * coneAxpyBufferAndCheck slot: flags[k] (0 where the slot failed; may be NULL) and *allInterior (1 if every cone is inside; may be
+ * NULL).  With the switch off it is the plain loop.  Returns the first retcode of a slot that was not OK. */
+int HMiKKTSetGroupedStep(hdsdp_kkt *HKKT, int on);
+int HMiKKTGetGroupedStep(hdsdp_kkt *HKKT, long out[6]);
+hdsdp_retcode HMiKKTAddStepToBufferAndCheck(hdsdp_kkt *HKKT, double dStep, int whichBuffer, int *flags, int *allInterior);
 /* multi-GPU (world > 1): constraint rows are sharded (row i on rank i % world).  Each rank congruence-
  * transforms its own rows, a transpose (all-to-all) re-shards the transformed data from "by constraint"
  * to "by packed-index range", each rank forms the Gram partial sum over its range, and an all-reduce
@@ -638,6 +664,8 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           question to one small SDP cone answers all in one launch)
  *  HDSDP_MI355X_GROUPED_RATIO     0         1: HKKTInit turns the grouped ratio test on (a ratio test     test_gpu_grouped_ratio.py
  *                                           asked of one small SDP cone runs all in one launch pair)
+ *  HDSDP_MI355X_GROUPED_STEP      0         1: HKKTInit turns the grouped step-and-check on (a step asked test_gpu_grouped_step.py
+ *                                           of one small SDP cone's checker puts all there in one launch)
  *  HDSDP_MI355X_REFINE            0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on
  *                                           steps (HMiKKTSetRefine)
  *  HDSDP_MI355X_REFINE_TILES      0         1: HKKTInit turns the tile form's refined solve on as well    test_gpu_refine_tiles.py::test_the_environment_switches_refine_a_tile_operator
