@@ -1079,18 +1079,23 @@ class KKT:
         load_library().HMiKKTGetGroupedBuild(self._k, C.byref(c), C.byref(j), C.byref(l))
         return {"cones": c.value, "jobs": j.value, "launches": l.value}
 
+    def _set_grouped(self, kind, on):       # a question set's switch (kind: Check, Ratio, Step) ...
+        return int(getattr(load_library(), f"HMiKKTSetGrouped{kind}")(self._k, 1 if on else 0))
+
+    def _grouped_info(self, kind, *own):    # ... and its Get call: on, the counters every kind has, the kind's `own`
+        out = (C.c_long * (4 + len(own)))()
+        on = getattr(load_library(), f"HMiKKTGetGrouped{kind}")(self._k, out)
+        return {"on": bool(on), **dict(zip(("members", "launches", "last_cones", "total_cones") + own, out))}
+
     def set_grouped_check(self, on):
         """HMiKKTSetGroupedCheck: a point question (check_is_interior, log_barrier with y) put to one member of the operator's
         check set puts every member at that point in one launch (csrc/small_check_rule.h has the rule); returns the number of
         members (0: off, or fewer than two members)"""
-        return int(load_library().HMiKKTSetGroupedCheck(self._k, 1 if on else 0))
+        return self._set_grouped("Check", on)
 
     def grouped_check_info(self):
         """HMiKKTGetGroupedCheck: dict(on, members, launches, last_cones, total_cones, from_state, left_out)"""
-        out = (C.c_long * 6)()
-        on = load_library().HMiKKTGetGroupedCheck(self._k, out)
-        return {"on": bool(on), "members": out[0], "launches": out[1], "last_cones": out[2], "total_cones": out[3],
-                "from_state": out[4], "left_out": out[5]}
+        return self._grouped_info("Check", "from_state", "left_out")
 
     def check_is_interior(self, tau, y):
         """HMiKKTCheckIsInterior: every cone of the operator at (tau, y), in order and without early exit; returns
@@ -1108,14 +1113,11 @@ class KKT:
         """HMiKKTSetGroupedRatio: a ratio test on the dual buffer asked of one member of the operator's ratio set runs every
         member's test in one pair of launches (csrc/small_ratio_rule.h has the rule); the later calls fetch their answers.
         Returns the number of members (0: off, or fewer than two members)"""
-        return int(load_library().HMiKKTSetGroupedRatio(self._k, 1 if on else 0))
+        return self._set_grouped("Ratio", on)
 
     def grouped_ratio_info(self):
         """HMiKKTGetGroupedRatio: dict(on, members, launches, last_cones, total_cones, from_slots, left_out, fallbacks)"""
-        out = (C.c_long * 7)()
-        on = load_library().HMiKKTGetGroupedRatio(self._k, out)
-        return {"on": bool(on), "members": out[0], "launches": out[1], "last_cones": out[2], "total_cones": out[3],
-                "from_slots": out[4], "left_out": out[5], "fallbacks": out[6]}
+        return self._grouped_info("Ratio", "from_slots", "left_out", "fallbacks")
 
     def ratio_test(self, dtau_step, dy, ada_ratio=0.0, buffer=BUFFER_DUALVAR):
         """HMiKKTRatioTest: every cone of the operator along (dtau_step, dy), in order and without early exit; returns
@@ -1131,14 +1133,11 @@ class KKT:
         """HMiKKTSetGroupedStep: a step-and-check on the checker buffer asked of one member of the operator's step set puts
         every member's checker at S + step dS in one launch (csrc/small_step_rule.h has the rule); the later calls answer from
         their slots.  Returns the number of members (0: off, or fewer than two members)"""
-        return int(load_library().HMiKKTSetGroupedStep(self._k, 1 if on else 0))
+        return self._set_grouped("Step", on)
 
     def grouped_step_info(self):
         """HMiKKTGetGroupedStep: dict(on, members, launches, last_cones, total_cones, from_slots, left_out)"""
-        out = (C.c_long * 6)()
-        on = load_library().HMiKKTGetGroupedStep(self._k, out)
-        return {"on": bool(on), "members": out[0], "launches": out[1], "last_cones": out[2], "total_cones": out[3],
-                "from_slots": out[4], "left_out": out[5]}
+        return self._grouped_info("Step", "from_slots", "left_out")
 
     def axpy_buffer_and_check(self, step, buffer=BUFFER_DUALCHECK):
         """HMiKKTAddStepToBufferAndCheck: every cone of the operator at S + step dS, in order and without early exit; returns

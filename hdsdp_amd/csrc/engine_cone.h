@@ -159,53 +159,77 @@ struct MiGrouped {
     bool used() const { return on && plan.used(); }
 };
 
-// The check set of an operator (engine_check_set.h performs it): the small SDP cones whose point questions
-// on the dual buffer -- "interior at (tau, y)?", "log det S at (tau, y)" -- are answered for ALL of them by one launch of
-// hdm_grouped_check_kernel the first time one of them is asked at a new point.  HKKTInit decides membership (small_check_rule.h:
-// the cones whose own one-launch check would run); the switch (HMiKKTSetGroupedCheck / HDSDP_MI355X_GROUPED_CHECK) allocates the
-// table.  Members, lifetimes and the launch counters are cone_set.h's; left out of a launch: who already stood at the point.
-struct MiCheckSet : HdmConeSet<MiCone> {
-    HdmPinned<HdmSmallCheckArgs> table;    // mapped pinned, one entry per member: the launch's arguments, launched members first
-    long from_state = 0;                   // per-cone calls answered from state since the switch went on
-    MiCheckSet() : HdmConeSet<MiCone>(&MiCone::in_check) {}
-    void release() { HdmConeSet<MiCone>::release(); table.reset(); }
-};
+// The three question sets of an operator: a question put to one small SDP cone is answered for ALL members in one launch, the
+// first time one of them is asked something its stored answer does not serve.  Members, lifetimes and counters are cone_set.h's,
+// and so is what a set does with its members (HdmQuestionSet: populate at HKKTInit, the switch, the launch, the answer); each
+// struct here is a kind's own state and declares the hooks (cone_set.h lists them) its engine_*_set.h defines.  The switch makes
+// everything a launch needs, so that a launch allocates nothing.  DESIGN.md section 25.
+// a hook's "could not be made": the HIP error that says so is cleared
+const char *set_lacks(const char *what) { (void) hipGetLastError(); return what; }
 
-// The ratio set of an operator (engine_ratio_set.h performs it): the small SDP cones whose ratio test on the
-// dual buffer -- "how far along (dTauStep, dy)?" -- is run for ALL of them by one pair of launches the first time one of them is
-// asked a question its slot does not hold.  HKKTInit decides membership (small_ratio_rule.h); the switch allocates the table, the
-// multipliers' staging block and every member's Lanczos object and step buffer, so that a launch allocates nothing
-// (HMiKKTSetGroupedRatio / HDSDP_MI355X_GROUPED_RATIO).  Members, lifetimes and the launch counters are cone_set.h's.
-struct MiRatioSet : HdmConeSet<MiCone> {
+// The check set (engine_check_set.h): "interior at (tau, y)?" and "log det S at (tau, y)" on the dual buffer,
+// by one launch of hdm_grouped_check_kernel.  Members: small_check_rule.h (the cones whose own one-launch check would run).  The
+// stored answer is the dual state itself; left out of a launch: who already stood at the point.
+// HMiKKTSetGroupedCheck / HDSDP_MI355X_GROUPED_CHECK.
+struct MiCheckQ { double tau; const double *y; };
+struct MiCheckSet : HdmQuestionSet<MiCone, MiCheckSet> {
+    static constexpr const char *NO_MEMORY = "[hdsdp_mi355x] grouped interior check: no pinned memory for %s; the per-cone checks stay\n";
+    HdmPinned<HdmSmallCheckArgs> table;    // mapped pinned, one entry per member: the launch's arguments, launched members first
+    MiCheckSet() : HdmQuestionSet<MiCone, MiCheckSet>(&MiCone::in_check) {}
+    void free_launch() { table.reset(); }
+    bool eligible(const MiCone *c) const;
+    void empty();
+    const char *prepare(size_t k, MiCone *c), *alloc_tables();
+    HdmSetSort sort(size_t k, MiCone *c, const MiCheckQ &q);
+    bool serves(size_t k, MiCone *c, const MiCheckQ &q);
+    void fill(int place, size_t k, MiCone *c, const MiCheckQ &q), commit(int place, size_t k, MiCone *c, const MiCheckQ &q);
+    int fire(int nl, const MiCheckQ &q);
+};
+// The ratio set (engine_ratio_set.h): "how far along (dTauStep, dy)?" on the dual buffer, by one pair of
+// launches.  Members: small_ratio_rule.h.  HMiKKTSetGroupedRatio / HDSDP_MI355X_GROUPED_RATIO.
+struct MiRatioQ { double dTauStep; const double *dy; double dAdaRatio; };
+struct MiRatioSet : HdmQuestionSet<MiCone, MiRatioSet> {
+    static constexpr const char *NO_MEMORY = "[hdsdp_mi355x] grouped ratio test: no memory for %s; the per-cone tests stay\n";
     std::vector<HdmRatioSlot> slots;       // one per member: the answer of the last launch it was in (small_ratio_rule.h)
-    std::vector<long> yoff;                // one per member: where its multipliers start in `ybuf`
+    std::vector<long> yoff;                // one per member: where its multipliers start in `ybuf`; ytot: where the next would
+    long ytot = 0;
     HdmPinned<HdmGroupedRatioArgs> table;  // mapped pinned, one entry per member: the launch's arguments, launched members first
     HdmPinned<double> ybuf;                // mapped pinned: the members' gathered multipliers
-    // answers served from slots; safeguard fallbacks (members whose step left the cone and took the host's fresh-start test and cuts)
-    long from_slots = 0, fallbacks = 0;
-    MiRatioSet() : HdmConeSet<MiCone>(&MiCone::in_ratio) {}
-    void release() { HdmConeSet<MiCone>::release(); slots.clear(); yoff.clear(); table.reset(); ybuf.reset(); }
+    // safeguard fallbacks since HKKTInit (members whose step left the cone and took the host's fresh-start test and cuts)
+    long fallbacks = 0;
+    MiRatioSet() : HdmQuestionSet<MiCone, MiRatioSet>(&MiCone::in_ratio) {}
+    void free_launch() { table.reset(); ybuf.reset(); }
+    void reset_counters() { HdmConeSet<MiCone>::reset_counters(); fallbacks = 0; }
+    bool eligible(const MiCone *c) const;
+    void empty();
+    const char *prepare(size_t k, MiCone *c), *alloc_tables();
+    HdmSetSort sort(size_t k, MiCone *c, const MiRatioQ &q);
+    bool serves(size_t k, MiCone *c, const MiRatioQ &q);
+    void fill(int place, size_t k, MiCone *c, const MiRatioQ &q), commit(int place, size_t k, MiCone *c, const MiRatioQ &q);
+    int fire(int nl, const MiRatioQ &q);
 };
-// The step set of an operator (engine_step_set.h performs it): the small SDP cones whose step-and-check on
-// the checker buffer -- "is S + dStep dS still inside?" -- is run for ALL of them by one launch of hdm_grouped_step_check_kernel the
-// first time one of them is asked a step its slot does not hold.  HKKTInit decides membership (small_step_rule.h); the switch
-// allocates the table and the report words and makes every member's checker object and step buffer, so that a launch allocates
-// nothing (HMiKKTSetGroupedStep / HDSDP_MI355X_GROUPED_STEP).  Members, lifetimes and the launch counters are cone_set.h's.
-struct MiStepSet : HdmConeSet<MiCone> {
+// The step set (engine_step_set.h): "is S + dStep dS still inside?" on the checker buffer, by one launch of
+// hdm_grouped_step_check_kernel.  Members: small_step_rule.h.  HMiKKTSetGroupedStep / HDSDP_MI355X_GROUPED_STEP.
+struct MiStepSet : HdmQuestionSet<MiCone, MiStepSet> {
+    static constexpr const char *NO_MEMORY = "[hdsdp_mi355x] grouped step-and-check: no memory for %s; the per-cone checks stay\n";
     std::vector<HdmStepSlot> slots;        // one per member: the answer of the last launch it was in (small_step_rule.h)
     // one per member: the switch made its step buffer (zeros: no step matrix yet), when its dS counter stood at ds_at_on
     std::vector<char> made_dS;
     std::vector<unsigned long> ds_at_on;
     HdmPinned<HdmGroupedStepArgs> table;   // mapped pinned, one entry per member: the launch's arguments, launched members first
     HdmPinned<int> words;                  // mapped pinned, one word per member: the sweep's info, -1 until the launch has reported
-    long from_slots = 0;                   // answers served from slots since the switch went on
-    MiStepSet() : HdmConeSet<MiCone>(&MiCone::in_step) {}
-    void release() { HdmConeSet<MiCone>::release(); slots.clear(); made_dS.clear(); ds_at_on.clear(); table.reset(); words.reset(); }
+    MiStepSet() : HdmQuestionSet<MiCone, MiStepSet>(&MiCone::in_step) {}
+    void free_launch() { table.reset(); words.reset(); }
+    bool eligible(const MiCone *c) const;
+    void empty();
+    const char *prepare(size_t k, MiCone *c), *alloc_tables();
+    HdmSetSort sort(size_t k, MiCone *c, const double &q);
+    bool serves(size_t k, MiCone *c, const double &q);
+    void fill(int place, size_t k, MiCone *c, const double &q), commit(int place, size_t k, MiCone *c, const double &q);
+    int fire(int nl, const double &q);
 };
-// the set a cone is a member of, as its own kind (the links are assigned by sets of these three types only)
-MiCheckSet *check_set_of(const MiCone *c) { return static_cast<MiCheckSet *>(c->in_check.set); }
-MiRatioSet *ratio_set_of(const MiCone *c) { return static_cast<MiRatioSet *>(c->in_ratio.set); }
-MiStepSet *step_set_of(const MiCone *c) { return static_cast<MiStepSet *>(c->in_step.set); }
+// the set a cone is a member of through `link`, as its own kind (a link is assigned by sets of its kind's type only)
+template <class Set> Set *set_of(const HdmConeLink<MiCone> &link) { return static_cast<Set *>(link.set); }
 
 struct MiKKTPriv {
     MiGrouped grp;
@@ -555,10 +579,6 @@ int small_check_commit(MiCone *c, HdmChol *ch, const HdmDualPoint &p, int whichB
     }
     return info;
 }
-// engine_check_set.h: c is a member of an active set and does not stand at (tau, y_host): one launch for every member that
-// does not.  Returns nonzero when the launch could not be made or did not finish.
-int check_set_launch(MiCheckSet *set, double tau, const double *y_host);
-
 int cone_small_check(MiCone *c, double tau, const double *y_host, const double *eye_override, int whichBuffer, int *isPsd, hdsdp_retcode *rc) {
     *rc = HDSDP_RETCODE_OK;
     if (!hdm_small_check_block_ok(small_check_desc(c, nullptr))) return 1;
@@ -568,14 +588,16 @@ int cone_small_check(MiCone *c, double tau, const double *y_host, const double *
     if (small_check_block(c)) return 1;
     const bool grouped = whichBuffer == 0 && !eye_override && c->in_check.active();
     HdmDualPoint p = small_check_point(c, tau, y_host, eye_override ? *eye_override : cone_eye(c));
+    // (the grouped case is HdmQuestionSet::answer written out: the first test below also serves a cone outside any set, sets *isPsd,
+    // and must keep its place before the launch's arguments are made)
     if (whichBuffer == 0 && c->dual.S_factored_at(p, isPsd)) {               // S = T(p) and its factor are in place
-        if (grouped) check_set_of(c)->from_state += 1;
+        if (grouped) set_of<MiCheckSet>(c->in_check)->from_store += 1;
         return 0;
     }
     if (grouped) {
         // every member of the set is put at this point in one launch; this cone then answers from its state.  A member the
         // launch has not reported for stays S_overwritten, and the call for that member fails.
-        if (check_set_launch(check_set_of(c), tau, y_host) || !c->dual.S_factored_at(p, isPsd)) *rc = HDSDP_RETCODE_FAILED;
+        if (set_of<MiCheckSet>(c->in_check)->launch(MiCheckQ{tau, y_host}) || !c->dual.S_factored_at(p, isPsd)) *rc = HDSDP_RETCODE_FAILED;
         return 0;
     }
     const HdmSmallCheckArgs a = small_check_args(c, ch, p, whichBuffer);

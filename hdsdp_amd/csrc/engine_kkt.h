@@ -405,18 +405,16 @@ static void kkt_apply_opt_ins(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
         const int k = grouped_set(HKKT, pv, 1);
         fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_BUILD=1: %d of %d cone(s) are built in one grouped pass\n", k, nCones);
     }
-    if (hdm_env_on<ENV_GROUPED_CHECK>()) {
-        const int k = check_set_switch(pv, 1);
-        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_CHECK=1: %d of %d cone(s) answer a point question in one grouped launch\n", k, nCones);
-    }
-    if (hdm_env_on<ENV_GROUPED_RATIO>()) {
-        const int k = ratio_set_switch(pv, 1);
-        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_RATIO=1: %d of %d cone(s) answer a ratio test in one grouped launch pair\n", k, nCones);
-    }
-    if (hdm_env_on<ENV_GROUPED_STEP>()) {
-        const int k = step_set_switch(pv, 1);
-        fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_STEP=1: %d of %d cone(s) answer a step-and-check in one grouped launch\n", k, nCones);
-    }
+    // the three question sets (cone_set.h): environment switch, setter, what the members then do
+    const struct { bool asked; const char *name; int (*set)(hdsdp_kkt *, int); const char *does; } sets[3] = {
+        {hdm_env_on<ENV_GROUPED_CHECK>(), "CHECK", HMiKKTSetGroupedCheck, "a point question in one grouped launch"},
+        {hdm_env_on<ENV_GROUPED_RATIO>(), "RATIO", HMiKKTSetGroupedRatio, "a ratio test in one grouped launch pair"},
+        {hdm_env_on<ENV_GROUPED_STEP>(), "STEP", HMiKKTSetGroupedStep, "a step-and-check in one grouped launch"}};
+    for (const auto &t : sets)
+        if (t.asked) {
+            const int k = t.set(HKKT, 1);
+            fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_%s=1: %d of %d cone(s) answer %s\n", t.name, k, nCones, t.does);
+        }
     // HDSDP_MI355X_REFINE=k: Schur solves are refined with at most k steps (HMiKKTSetRefine)
     if (const int k = hdm_env_int<ENV_REFINE>().value_or(0); k > 0) {
         (void) HMiKKTSetRefine(HKKT, k);
@@ -442,13 +440,14 @@ hdsdp_retcode HKKTInit(hdsdp_kkt *HKKT, int nRow, int nCones, hdsdp_cone **cones
     rc = kkt_init_device_common(HKKT, pv);
     if (rc != HDSDP_RETCODE_OK) return rc;
     if (sw.device_m) kkt_apply_device_m(HKKT, pv);
-    // eligibility for the grouped Schur build (engine_grouped.h) and membership of the check set (engine_check_set.h), of the
-    // ratio set (engine_ratio_set.h) and of the step set (engine_step_set.h) are decided for every operator; the grouped pass and the grouped launches are used when
-    // their switches are on
+    // eligibility for the grouped Schur build (engine_grouped.h) and membership of the three question sets (cone_set.h's rules:
+    // the operator initialised last has a cone no ACTIVE set holds) are decided for every operator; the grouped pass and the
+    // grouped launches are used when their switches are on
     grouped_init_plan(HKKT, pv);
-    check_set_init(HKKT, pv);
-    ratio_set_init(HKKT, pv);
-    step_set_init(HKKT, pv);
+    const auto engine_cone = [&](int i) { return own_cone_with_factor(HKKT->cones[i]); };
+    pv->chk.populate(nCones, engine_cone);
+    pv->rat.populate(nCones, engine_cone);
+    pv->stp.populate(nCones, engine_cone);
     kkt_apply_opt_ins(HKKT, pv);
     HKKT->dPrimalX = nullptr;
     return HDSDP_RETCODE_OK;
@@ -773,45 +772,78 @@ int HMiKKTGetGroupedBuild(hdsdp_kkt *HKKT, int *cones, int *jobs, int *launches)
     if (launches) *launches = gr.last_launches;
     return gr.last_cones > 0 ? 1 : 0;
 }
-int HMiKKTSetGroupedCheck(hdsdp_kkt *HKKT, int on) { return check_set_switch(priv_of(HKKT), on); }
-int HMiKKTGetGroupedCheck(hdsdp_kkt *HKKT, long out[6]) {
-    const MiCheckSet &cs = priv_of(HKKT)->chk;
-    if (out) {
-        cs.report(out);
-        out[4] = cs.from_state; out[5] = cs.last_left_out;
-    }
-    return cs.on ? 1 : 0;
+// The question sets (cone_set.h).  An all-cones call: every cone of cones[] in order, no early exit, each through its own slot
+// (`ask`, which also keeps the call's per-cone array and its reduction) -- the members of an active set reach the grouped launch
+// through the first of them that is asked.  The first failing retcode is returned.
+extern "C++" {
+template <class Ask> hdsdp_retcode kkt_all_cones(hdsdp_kkt *HKKT, Ask ask) {
+    hdsdp_retcode first = HDSDP_RETCODE_OK;
+    for (int i = 0; i < HKKT->nCones; ++i)
+        if (const hdsdp_retcode rc = ask(i, HKKT->cones[i]); rc != HDSDP_RETCODE_OK && first == HDSDP_RETCODE_OK) first = rc;
+    return first;
 }
+// A Get call: living members, the three launch counters, answers from the store, members left out of the last launch
+template <class Set> int kkt_set_get(const Set &s, long *out) {
+    if (out) s.report(out);
+    return s.on ? 1 : 0;
+}
+}  // extern "C++"
+int HMiKKTSetGroupedCheck(hdsdp_kkt *HKKT, int on) { return priv_of(HKKT)->chk.turn(on); }
+int HMiKKTGetGroupedCheck(hdsdp_kkt *HKKT, long out[6]) { return kkt_set_get(priv_of(HKKT)->chk, out); }
 hdsdp_retcode HMiKKTCheckIsInterior(hdsdp_kkt *HKKT, double tau, const double *y, int *flags, double *logdets, int *all) {
     if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
-    return check_all_cones(HKKT, tau, y, flags, logdets, all);
+    int every = 1;
+    const hdsdp_retcode first = kkt_all_cones(HKKT, [&](int i, hdsdp_cone *hc) {
+        int in = 0;
+        double ld = NAN;
+        hdsdp_retcode rc = hc->coneInteriorCheck(hc->coneData, tau, (double *) y, &in);
+        if (rc == HDSDP_RETCODE_OK && in) {
+            rc = hc->coneGetBarrier(hc->coneData, tau, (double *) y, 0, &ld);
+            if (rc != HDSDP_RETCODE_OK) ld = NAN;
+        } else in = 0;
+        if (flags) flags[i] = in;
+        if (logdets) logdets[i] = in ? ld : NAN;
+        every &= in;
+        return rc;
+    });
+    if (all) *all = every;
+    return first;
 }
-int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on) { return ratio_set_switch(priv_of(HKKT), on); }
+int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on) { return priv_of(HKKT)->rat.turn(on); }
 int HMiKKTGetGroupedRatio(hdsdp_kkt *HKKT, long out[7]) {
-    const MiRatioSet &rs = priv_of(HKKT)->rat;
-    if (out) {
-        rs.report(out);
-        out[4] = rs.from_slots; out[5] = rs.last_left_out; out[6] = rs.fallbacks;
-    }
-    return rs.on ? 1 : 0;
+    if (out) out[6] = priv_of(HKKT)->rat.fallbacks;
+    return kkt_set_get(priv_of(HKKT)->rat, out);
 }
 hdsdp_retcode HMiKKTRatioTest(hdsdp_kkt *HKKT, double dTauStep, const double *dy, double dAdaRatio, int whichBuffer, double *steps,
                               double *minStep) {
     if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
-    return ratio_all_cones(HKKT, dTauStep, dy, dAdaRatio, whichBuffer, steps, minStep);
+    double mn = INFINITY;
+    const hdsdp_retcode first = kkt_all_cones(HKKT, [&](int i, hdsdp_cone *hc) {
+        double step = NAN;
+        const hdsdp_retcode rc = hc->coneRatioTest(hc->coneData, dTauStep, (double *) dy, dAdaRatio, whichBuffer, &step);
+        if (rc != HDSDP_RETCODE_OK) step = NAN;
+        else if (step < mn) mn = step;
+        if (steps) steps[i] = step;
+        return rc;
+    });
+    if (minStep) *minStep = mn;
+    return first;
 }
-int HMiKKTSetGroupedStep(hdsdp_kkt *HKKT, int on) { return step_set_switch(priv_of(HKKT), on); }
-int HMiKKTGetGroupedStep(hdsdp_kkt *HKKT, long out[6]) {
-    const MiStepSet &ss = priv_of(HKKT)->stp;
-    if (out) {
-        ss.report(out);
-        out[4] = ss.from_slots; out[5] = ss.last_left_out;
-    }
-    return ss.on ? 1 : 0;
-}
+int HMiKKTSetGroupedStep(hdsdp_kkt *HKKT, int on) { return priv_of(HKKT)->stp.turn(on); }
+int HMiKKTGetGroupedStep(hdsdp_kkt *HKKT, long out[6]) { return kkt_set_get(priv_of(HKKT)->stp, out); }
 hdsdp_retcode HMiKKTAddStepToBufferAndCheck(hdsdp_kkt *HKKT, double dStep, int whichBuffer, int *flags, int *allInterior) {
     if (!HKKT || ensure_ctx()) return HDSDP_RETCODE_FAILED;
-    return step_all_cones(HKKT, dStep, whichBuffer, flags, allInterior);
+    int every = 1;
+    const hdsdp_retcode first = kkt_all_cones(HKKT, [&](int i, hdsdp_cone *hc) {
+        int in = 0;
+        const hdsdp_retcode rc = hc->coneAxpyBufferAndCheck(hc->coneData, dStep, whichBuffer, &in);
+        if (rc != HDSDP_RETCODE_OK) in = 0;
+        if (flags) flags[i] = in;
+        every &= in ? 1 : 0;
+        return rc;
+    });
+    if (allInterior) *allInterior = every;
+    return first;
 }
 int HMiKKTGetDiagTarget(hdsdp_kkt *HKKT) {
     MiKKTPriv *pv = priv_of(HKKT);

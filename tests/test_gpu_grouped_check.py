@@ -2,52 +2,30 @@
 DESIGN.md section 19): a point question put to one small SDP cone of an operator answers all of them in one launch.  The
 yardstick is the per-cone path of the same library on a second set of cones made from the same data: the grouped kernel runs
 the one-launch check's own body, so dual matrix, log det, flag and a following ratio test agree bit for bit -- no tolerance."""
+import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from util import check_close, golden_schur_dense, load_golden, lower_mask, y_of
+import grouped_cases
+from grouped_cases import EXE, INSTANCES, _destroy, _lp_cone
+from util import load_golden, y_of
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-EXE = os.path.join(ROOT, "oracle", "_ref", "sdpasolve_mi355x")
-INSTANCES = {"truss1_A": ("truss1.dat-s", 7), "blocks3_A": ("blocks3.dat-s", 3), "chain16_A": ("chain16.dat-s", 16),
-             "arrow128_A": ("arrow128.dat-s", 128)}
+_rule = functools.partial(grouped_cases._rule, "check")
+_golden_cones = functools.partial(grouped_cases._golden_cones, _rule)
+instance = grouped_cases.instance_of(_golden_cones)
+_block = functools.partial(grouped_cases._block, "check")
+_set = functools.partial(grouped_cases._set, "check")
+_two_sets = functools.partial(grouped_cases._two_sets, "check")
+_check_goldens = functools.partial(grouped_cases._check_goldens, full=True)
 
 
-def _rule(n, mloc):
-    """csrc/small_check_rule.h for an engine SDP cone on one device with resident data and a one-block factor (n <= 128)"""
-    n16 = (n + 15) // 16 * 16
-    return n16 <= 128 and mloc * n16 * n16 <= ((1 << 19) if n16 <= 64 else (1 << 17))
-
-
-def _golden_cones(name, m):
-    from hdsdp_amd import api
-    prob = api.read_sdpa(os.path.join(GOLDEN, INSTANCES[name][0]))
-    cones = [api.SDPCone.from_csc(blk["n"], m, blk["beg"], blk["idx"], blk["val"], iCone=k) for k, blk in enumerate(prob["blocks"])]
-    members = sum(_rule(blk["n"], int(np.count_nonzero(np.diff(np.asarray(blk["beg"])[1:])))) for blk in prob["blocks"])
-    return cones, members
-
-
-@pytest.fixture(scope="module", params=sorted(INSTANCES))
-def instance(request):
-    """two sets of cones of a multi-block golden, made from the same file: `loop` is asked cone by cone with the switch off,
-    `grp` cone by cone under an operator with the switch on"""
-    name = request.param
-    g = load_golden(name)
-    m = int(g["mb_dims"][1])
-    loop, members = _golden_cones(name, m)
-    grp, _ = _golden_cones(name, m)
-    for c in loop + grp:
-        c.set_start(float(g["Rd"][0]))
-    yield name, g, m, loop, grp, members
-    for c in loop + grp:
-        c.destroy()
+def _drive(inst, grouped):
+    return grouped_cases._drive(inst, ("HDSDP_MI355X_GROUPED_CHECK",) if grouped else ())
 
 
 def _ask(cones, tau, y, dtau, dy, stop_at_first_failure=False):
@@ -124,46 +102,6 @@ def test_bit_identity_against_the_per_cone_path(instance):
             _same(got, _ask(loop, tau, y, dtau, dy), f"{name} point {k}")
     finally:
         kkt.destroy()
-
-
-# ---- operators from seeded numpy data ----------------------------------------------------------------------------------
-def _sym(rng, n, density):
-    A = rng.uniform(-1.0, 1.0, (n, n)) * (rng.uniform(0.0, 1.0, (n, n)) < density)
-    A = np.tril(A) + np.tril(A, -1).T
-    if not A.any():
-        A[n - 1, n - 1] = 1.0
-    return A
-
-
-def _block(rng, n, m, rows):
-    """(cone, C, A): a block of dimension n with seeded data on `rows` of the m constraints; A is m x n x n"""
-    from hdsdp_amd import api
-    C = 0.1 * _sym(rng, n, 1.0) + 4.0 * np.eye(n)
-    A = np.zeros((m, n, n))
-    for k, r in enumerate(rows):
-        A[r] = _sym(rng, n, 1.0 if k % 3 == 0 else 0.3)
-    iu = np.triu_indices(n)                      # (j, i) with i >= j, column by column: the packed lower triangle
-    beg, idx, val = [0], [], []
-    for mat in [C] + list(A):
-        v = mat[iu]
-        nz = np.flatnonzero(v)
-        idx.extend(nz.tolist()); val.extend(v[nz].tolist()); beg.append(len(idx))
-    return api.SDPCone.from_csc(n, m, beg, np.asarray(idx, dtype=np.int32), np.asarray(val)), C, A
-
-
-def _set(seed, m, plan):
-    return [_block(np.random.default_rng([seed, k]), n, m, rows) for k, (n, rows) in enumerate(plan)]
-
-
-def _two_sets(seed, m, plan):
-    """the same seeded blocks twice: (loop blocks, grouped blocks)"""
-    return _set(seed, m, plan), _set(seed, m, plan)
-
-
-def _destroy(*sets):
-    for s in sets:
-        for b in s:
-            b[0].destroy()
 
 
 M_SHAPES = 40
@@ -290,16 +228,6 @@ def test_a_non_interior_member():
         _destroy(first, loop, grp)
 
 
-def _lp_cone(m, ncol, seed):
-    from hdsdp_amd import api
-    rng = np.random.default_rng(seed)
-    A = rng.uniform(-1.0, 1.0, (m, ncol))
-    c = 4.0 + rng.uniform(0.0, 1.0, ncol)
-    beg = (np.arange(m + 2, dtype=np.int64) * ncol).astype(np.int32)
-    idx = np.tile(np.arange(ncol, dtype=np.int32), m + 1)
-    return api.LPCone.from_csc(m, ncol, beg, idx, np.concatenate([c, A.ravel()]))
-
-
 def test_mixed_operator():
     """two members, a cone the rule refuses (n = 130) and an LP cone: two members; HMiKKTCheckIsInterior agrees with the per-cone
     loop on every cone, the non-members through their own slots; and a second operator over the same cones takes none of the
@@ -387,38 +315,6 @@ def test_lifetime():
         _destroy(loop, grp)
 
 
-def _check_goldens(name, g, kkt, ncones):
-    from hdsdp_amd import api
-    msk = lower_mask(kkt.m)
-    assert kkt.is_sparse == bool(int(g["kkt_sparse"][0]))
-    kkt.build_up(api.KKT_TYPE_HOMOGENEOUS)
-    info = kkt.grouped_build_info()
-    assert info["cones"] == ncones and 1 <= info["launches"] <= 3 and info["jobs"] >= ncones, info
-    ex = kkt.export()
-    if kkt.is_sparse and kkt.diag_target() == 0:
-        check_close(kkt.csc()[2], g["M_hsd"], name + " M_hsd (CSC values)")
-    if kkt.diag_target() == 0:
-        check_close(kkt.M[msk], golden_schur_dense(g, "M_hsd")[msk], name + " M_hsd")
-    check_close(ex["ASinv"], g["ASinv_hsd"], name + " ASinv")
-    check_close(ex["ASinvRdSinv"], g["ASinvRdSinv_hsd"], name + " ASinvRdSinv")
-    check_close(ex["ASinvCSinv"], g["ASinvCSinv_hsd"], name + " ASinvCSinv")
-    check_close([ex["CSinv"], ex["CSinvCSinv"], ex["CSinvRdSinv"], ex["TraceSinv"]], g["hsd_scalars"], name + " scalars")
-    kkt.build_up(api.KKT_TYPE_CORRECTOR)
-    info = kkt.grouped_build_info()
-    assert info["cones"] == ncones and 1 <= info["launches"] <= 3, info
-    exc = kkt.export()
-    check_close(exc["ASinv"], g["ASinv_cor"], name + " ASinv_cor")
-    check_close(exc["ASinvRdSinv"], g["ASinvRdSinv_cor"], name + " ASinvRdSinv_cor")
-    kkt.build_up(api.KKT_TYPE_INFEASIBLE)
-    info = kkt.grouped_build_info()
-    assert info["cones"] == ncones and 1 <= info["launches"] <= 3, info
-    if kkt.diag_target() == 0:
-        check_close(kkt.M[msk], golden_schur_dense(g, "M_inf")[msk], name + " M_inf")
-    kkt.factorize()
-    x = kkt.solve(g["b"])
-    assert np.linalg.norm(x - g["sol_b"]) <= 1e-8 * np.linalg.norm(g["sol_b"])
-
-
 @pytest.mark.parametrize("name", ["arrow128_A", "chain16_A"])
 def test_with_the_grouped_build(name):
     """both switches on: the grouped inverse kernel reads the Dinv the grouped check's launch wrote; test_gpu_grouped_build.py's
@@ -482,19 +378,6 @@ def test_state_transitions():
 
 # the optimum the driver prints, as tests/test_gpu_reference_driver.py expects it for the same files
 DRIVER_CASES = {"truss1": (8.999996, "7"), "chain16": (74.932288321, "16")}
-
-
-def _drive(inst, grouped):
-    env = dict(os.environ, HDSDP_DROP_ATTACH="1")
-    env.pop("HDSDP_MI355X_GROUPED_CHECK", None)
-    if grouped:
-        env["HDSDP_MI355X_GROUPED_CHECK"] = "1"
-    r = subprocess.run([EXE, os.path.join(GOLDEN, inst + ".dat-s")], capture_output=True, text=True, timeout=600, env=env)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    assert "SDP Status: Primal dual optimal" in out, out[-3000:]
-    its = [m_.group(1) for m_ in re.finditer(r"^\s+(\d+)\s+[-+]\d\.\d+e[-+]\d+\s+[-+]\d\.\d+e[-+]\d+", out, re.M)]
-    return out, its, re.findall(r"pObj\s+([-+0-9.eE]+)", out), re.findall(r"dObj\s+([-+0-9.eE]+)", out)
 
 
 @pytest.mark.parametrize("inst", sorted(DRIVER_CASES))

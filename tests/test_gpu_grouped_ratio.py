@@ -5,9 +5,9 @@ is the per-cone path of the same library, with the switch off, on a second set o
 kernel forms the per-cone sweep's sums and runs the one-launch Lanczos test's own body, so step, step matrix and what follows
 from them agree bit for bit -- np.array_equal, no tolerance.  An independent yardstick (numpy's eigenvalues in fp64) holds the
 steps to the margins tests/test_gpu_line_search.py uses for the per-cone path."""
+import functools
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -16,32 +16,23 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import line_search_model as lm  # noqa: E402
-from util import RATIO_TOL, check_close, golden_schur_dense, load_golden, lower_mask, y_of  # noqa: E402
+import grouped_cases  # noqa: E402
+from grouped_cases import EXE, INSTANCES, _check_goldens, _cone_of, _destroy, _lp_cone  # noqa: E402
+from util import RATIO_TOL, load_golden, y_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(HERE)
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-EXE = os.path.join(ROOT, "oracle", "_ref", "sdpasolve_mi355x")
-INSTANCES = {"truss1_A": ("truss1.dat-s", 7), "blocks3_A": ("blocks3.dat-s", 3), "chain16_A": ("chain16.dat-s", 16),
-             "arrow128_A": ("arrow128.dat-s", 128)}
+_rule = functools.partial(grouped_cases._rule, "ratio")
+_golden_cones = functools.partial(grouped_cases._golden_cones, _rule)
+instance = grouped_cases.instance_of(_golden_cones)
+_block = functools.partial(grouped_cases._block, "ratio")
+_set = functools.partial(grouped_cases._set, "ratio")
+_two_sets = functools.partial(grouped_cases._two_sets, "ratio")
+
+
+def _drive(inst, grouped):
+    return grouped_cases._drive(inst, ("HDSDP_MI355X_GROUPED_RATIO",) if grouped else ())
 ZERO = {"on": False, "launches": 0, "last_cones": 0, "total_cones": 0, "from_slots": 0, "left_out": 0, "fallbacks": 0}
-
-
-def _rule(n, mloc):
-    """csrc/small_ratio_rule.h for an engine SDP cone on one device with resident data, a one-block factor and the default
-    Lanczos switches: the check rule, n >= 2, and the multipliers fit the packed triangles' region"""
-    n16 = (n + 15) // 16 * 16
-    check = n16 <= 128 and mloc * n16 * n16 <= ((1 << 19) if n16 <= 64 else (1 << 17))
-    return check and n >= 2 and mloc <= n16 * (n16 + 1)
-
-
-def _golden_cones(name, m):
-    from hdsdp_amd import api
-    prob = api.read_sdpa(os.path.join(GOLDEN, INSTANCES[name][0]))
-    cones = [api.SDPCone.from_csc(blk["n"], m, blk["beg"], blk["idx"], blk["val"], iCone=k) for k, blk in enumerate(prob["blocks"])]
-    members = sum(_rule(blk["n"], int(np.count_nonzero(np.diff(np.asarray(blk["beg"])[1:])))) for blk in prob["blocks"])
-    return cones, members
 
 
 def _ratio(c, dtau, dy, ada=0.0):
@@ -83,22 +74,6 @@ def _same_after(a, b, what):
 def _same_steps(got, want, what):
     got, want = np.asarray(got), np.asarray(want)
     assert np.array_equal(got, want, equal_nan=True), f"{what}: steps {got.tolist()} against the loop's {want.tolist()}"
-
-
-@pytest.fixture(scope="module", params=sorted(INSTANCES))
-def instance(request):
-    """two sets of cones of a multi-block golden, made from the same file: `loop` is asked cone by cone with the switch off,
-    `grp` cone by cone under an operator with the switch on"""
-    name = request.param
-    g = load_golden(name)
-    m = int(g["mb_dims"][1])
-    loop, members = _golden_cones(name, m)
-    grp, _ = _golden_cones(name, m)
-    for c in loop + grp:
-        c.set_start(float(g["Rd"][0]))
-    yield name, g, m, loop, grp, members
-    for c in loop + grp:
-        c.destroy()
 
 
 def test_goldens_bit_identity_against_the_per_cone_path(instance):
@@ -145,45 +120,6 @@ def test_goldens_bit_identity_against_the_per_cone_path(instance):
         question(4, *dirs[2])
     finally:
         kkt.destroy()
-
-
-# ---- operators from seeded numpy data ----------------------------------------------------------------------------------
-def _sym(rng, n, density):
-    A = rng.uniform(-1.0, 1.0, (n, n)) * (rng.uniform(0.0, 1.0, (n, n)) < density)
-    A = np.tril(A) + np.tril(A, -1).T
-    if not A.any():
-        A[n - 1, n - 1] = 1.0
-    return A
-
-
-def _cone_of(n, m, C, A):
-    from hdsdp_amd import api
-    beg, idx, val = lm.to_csc([C] + list(A))
-    return api.SDPCone.from_csc(n, m, beg, idx, val)
-
-
-def _block(rng, n, m, rows):
-    """(cone, C, A): a block of dimension n with seeded data on `rows` of the m constraints; A is m x n x n"""
-    C = 0.1 * _sym(rng, n, 1.0) + 4.0 * np.eye(n)
-    A = np.zeros((m, n, n))
-    for k, r in enumerate(rows):
-        A[r] = _sym(rng, n, 1.0 if k % 3 == 0 else 0.3)
-    return _cone_of(n, m, C, A), C, A
-
-
-def _set(seed, m, plan):
-    return [_block(np.random.default_rng([seed, k]), n, m, rows) for k, (n, rows) in enumerate(plan)]
-
-
-def _two_sets(seed, m, plan):
-    """the same seeded blocks twice: (loop blocks, grouped blocks)"""
-    return _set(seed, m, plan), _set(seed, m, plan)
-
-
-def _destroy(*sets):
-    for s in sets:
-        for b in s:
-            b[0].destroy()
 
 
 def _check_step(step, a, S, dS, what):
@@ -255,16 +191,6 @@ def test_seeded_shapes_against_the_loop_and_against_the_exact_step():
         kkt.destroy()
     finally:
         _destroy(loop, grp)
-
-
-def _lp_cone(m, ncol, seed):
-    from hdsdp_amd import api
-    rng = np.random.default_rng(seed)
-    A = rng.uniform(-1.0, 1.0, (m, ncol))
-    c = 4.0 + rng.uniform(0.0, 1.0, ncol)
-    beg = (np.arange(m + 2, dtype=np.int64) * ncol).astype(np.int32)
-    idx = np.tile(np.arange(ncol, dtype=np.int32), m + 1)
-    return api.LPCone.from_csc(m, ncol, beg, idx, np.concatenate([c, A.ravel()]))
 
 
 def test_members_and_others_in_one_operator():
@@ -475,27 +401,6 @@ def test_lifetime():
         _destroy(loop, grp)
 
 
-def _check_goldens(name, g, kkt, ncones):
-    """tests/test_gpu_grouped_build.py's golden comparison, same bars"""
-    from hdsdp_amd import api
-    msk = lower_mask(kkt.m)
-    kkt.build_up(api.KKT_TYPE_HOMOGENEOUS)
-    info = kkt.grouped_build_info()
-    assert info["cones"] == ncones and 1 <= info["launches"] <= 3, info
-    ex = kkt.export()
-    if kkt.diag_target() == 0:
-        check_close(kkt.M[msk], golden_schur_dense(g, "M_hsd")[msk], name + " M_hsd")
-    check_close(ex["ASinv"], g["ASinv_hsd"], name + " ASinv")
-    check_close(ex["ASinvRdSinv"], g["ASinvRdSinv_hsd"], name + " ASinvRdSinv")
-    check_close(ex["ASinvCSinv"], g["ASinvCSinv_hsd"], name + " ASinvCSinv")
-    kkt.build_up(api.KKT_TYPE_INFEASIBLE)
-    if kkt.diag_target() == 0:
-        check_close(kkt.M[msk], golden_schur_dense(g, "M_inf")[msk], name + " M_inf")
-    kkt.factorize()
-    x = kkt.solve(g["b"])
-    assert np.linalg.norm(x - g["sol_b"]) <= 1e-8 * np.linalg.norm(g["sol_b"])
-
-
 @pytest.mark.parametrize("name", ["arrow128_A", "chain16_A"])
 def test_all_three_grouped_switches_together(name):
     """grouped check, grouped ratio test and grouped build on one operator: the check's launch writes the Dinv the ratio kernel
@@ -530,19 +435,6 @@ def test_all_three_grouped_switches_together(name):
 
 # the optimum the driver prints, as tests/test_gpu_reference_driver.py expects it for the same files
 DRIVER_CASES = {"truss1": (8.999996, "6", "7"), "chain16": (74.932288321, "16", "16")}      # (truss1 has one 1 x 1 block)
-
-
-def _drive(inst, grouped):
-    env = dict(os.environ, HDSDP_DROP_ATTACH="1")
-    env.pop("HDSDP_MI355X_GROUPED_RATIO", None)
-    if grouped:
-        env["HDSDP_MI355X_GROUPED_RATIO"] = "1"
-    r = subprocess.run([EXE, os.path.join(GOLDEN, inst + ".dat-s")], capture_output=True, text=True, timeout=600, env=env)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    assert "SDP Status: Primal dual optimal" in out, out[-3000:]
-    its = [m_.group(1) for m_ in re.finditer(r"^\s+(\d+)\s+[-+]\d\.\d+e[-+]\d+\s+[-+]\d\.\d+e[-+]\d+", out, re.M)]
-    return out, its, re.findall(r"pObj\s+([-+0-9.eE]+)", out), re.findall(r"dObj\s+([-+0-9.eE]+)", out)
 
 
 @pytest.mark.parametrize("inst", sorted(DRIVER_CASES))

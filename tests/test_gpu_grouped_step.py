@@ -12,6 +12,7 @@ Two yardsticks from the per-cone path of the same library, both without a tolera
   triangle included, which the grouped kernel reproduces: the rectangle copy's values and the padding's zeros).
 
 An independent yardstick (numpy, fp64) holds the flag to the sign of lambda_min(S + dStep dS) and the barrier to slogdet."""
+import functools
 import os
 import re
 import subprocess
@@ -23,31 +24,19 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import line_search_model as lm  # noqa: E402
-from util import check_close, golden_schur_dense, load_golden, lower_mask, y_of  # noqa: E402
+import grouped_cases  # noqa: E402
+from grouped_cases import EXE, GROUPED, INSTANCES, ROOT, _check_goldens, _destroy, _drive, _lp_cone  # noqa: E402
+from util import load_golden, y_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(HERE)
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-EXE = os.path.join(ROOT, "oracle", "_ref", "sdpasolve_mi355x")
-INSTANCES = {"truss1_A": ("truss1.dat-s", 7), "blocks3_A": ("blocks3.dat-s", 3), "chain16_A": ("chain16.dat-s", 16),
-             "arrow128_A": ("arrow128.dat-s", 128)}
+_rule = functools.partial(grouped_cases._rule, "step")
+_golden_cones = functools.partial(grouped_cases._golden_cones, _rule)
+instance = grouped_cases.instance_of(_golden_cones)
+_block = functools.partial(grouped_cases._block, "step")
+_set = functools.partial(grouped_cases._set, "step")
+_two_sets = functools.partial(grouped_cases._two_sets, "step")
 ZERO = {"on": False, "launches": 0, "last_cones": 0, "total_cones": 0, "from_slots": 0, "left_out": 0}
-
-
-def _rule(n, mloc):
-    """csrc/small_step_rule.h for an engine SDP cone on one device with resident data, one-block factor objects and the default
-    HDM_DIAG_SWEEP: the check rule; n = 1 is a member"""
-    n16 = (n + 15) // 16 * 16
-    return n16 <= 128 and mloc * n16 * n16 <= ((1 << 19) if n16 <= 64 else (1 << 17))
-
-
-def _golden_cones(name, m):
-    from hdsdp_amd import api
-    prob = api.read_sdpa(os.path.join(GOLDEN, INSTANCES[name][0]))
-    cones = [api.SDPCone.from_csc(blk["n"], m, blk["beg"], blk["idx"], blk["val"], iCone=k) for k, blk in enumerate(prob["blocks"])]
-    members = sum(_rule(blk["n"], int(np.count_nonzero(np.diff(np.asarray(blk["beg"])[1:])))) for blk in prob["blocks"])
-    return cones, members
 
 
 def _try(f, *a):
@@ -110,22 +99,6 @@ def _same_cone_every_element(kkt, gc, step, members, what):
     return flags
 
 
-@pytest.fixture(scope="module", params=sorted(INSTANCES))
-def instance(request):
-    """two sets of cones of a multi-block golden, made from the same file: `loop` is asked cone by cone with the switch off,
-    `grp` cone by cone under an operator with the switch on"""
-    name = request.param
-    g = load_golden(name)
-    m = int(g["mb_dims"][1])
-    loop, members = _golden_cones(name, m)
-    grp, _ = _golden_cones(name, m)
-    for c in loop + grp:
-        c.set_start(float(g["Rd"][0]))
-    yield name, g, m, loop, grp, members
-    for c in loop + grp:
-        c.destroy()
-
-
 def test_goldens_bit_identity_against_the_per_cone_path(instance):
     """truss1, blocks3, chain16, arrow128: after a ratio test at the golden's point, the steps 0.5, 0.98 and 1.5 x the smallest
     step (the last puts at least one cone outside): one launch per question with every member in it and members - 1 answers from
@@ -170,50 +143,6 @@ def test_goldens_bit_identity_against_the_per_cone_path(instance):
         _same_cone_every_element(kkt, grp, 0.4 * smin, members, name)
     finally:
         kkt.destroy()
-
-
-# ---- operators from seeded numpy data ----------------------------------------------------------------------------------
-def _sym(rng, n, density):
-    A = rng.uniform(-1.0, 1.0, (n, n)) * (rng.uniform(0.0, 1.0, (n, n)) < density)
-    A = np.tril(A) + np.tril(A, -1).T
-    if not A.any():
-        A[n - 1, n - 1] = 1.0
-    return A
-
-
-def _cone_of(n, m, C, A):
-    from hdsdp_amd import api
-    beg, idx, val = lm.to_csc([C] + list(A))
-    return api.SDPCone.from_csc(n, m, beg, idx, val)
-
-
-def _block(rng, n, m, rows):
-    """(cone, C, A): a block of dimension n with seeded data on `rows` of the m constraints; A is m x n x n.  C is 4 I plus noise of
-    norm below 0.2, with the largest diagonal entry (6) first and the smallest (2) last (n = 1: 2): along dS = -C the first pivot
-    of S + a dS is the first to fail, along dS = -3 I the last one (_pivot_directions)"""
-    C = 0.01 * _sym(rng, n, 1.0) + 4.0 * np.eye(n)
-    if n > 1:
-        C[0, 0] += 2.0
-    C[n - 1, n - 1] -= 2.0
-    A = np.zeros((m, n, n))
-    for k, r in enumerate(rows):
-        A[r] = _sym(rng, n, 1.0 if k % 3 == 0 else 0.3)
-    return _cone_of(n, m, C, A), C, A
-
-
-def _set(seed, m, plan):
-    return [_block(np.random.default_rng([seed, k]), n, m, rows) for k, (n, rows) in enumerate(plan)]
-
-
-def _two_sets(seed, m, plan):
-    """the same seeded blocks twice: (loop blocks, grouped blocks)"""
-    return _set(seed, m, plan), _set(seed, m, plan)
-
-
-def _destroy(*sets):
-    for s in sets:
-        for b in s:
-            b[0].destroy()
 
 
 def _full(c, raw):
@@ -341,16 +270,6 @@ def test_numpy_yardstick_flag_is_the_sign_of_the_smallest_eigenvalue_and_the_bar
         kkt.destroy()
     finally:
         _destroy(grp)
-
-
-def _lp_cone(m, ncol, seed):
-    from hdsdp_amd import api
-    rng = np.random.default_rng(seed)
-    A = rng.uniform(-1.0, 1.0, (m, ncol))
-    c = 4.0 + rng.uniform(0.0, 1.0, ncol)
-    beg = (np.arange(m + 2, dtype=np.int64) * ncol).astype(np.int32)
-    idx = np.tile(np.arange(ncol, dtype=np.int32), m + 1)
-    return api.LPCone.from_csc(m, ncol, beg, idx, np.concatenate([c, A.ravel()]))
 
 
 def test_a_member_that_has_never_had_a_ratio_test_fails_alone():
@@ -565,27 +484,6 @@ def test_lifetime():
         _destroy(loop, grp)
 
 
-def _check_goldens(name, g, kkt, ncones):
-    """tests/test_gpu_grouped_build.py's golden comparison, same bars"""
-    from hdsdp_amd import api
-    msk = lower_mask(kkt.m)
-    kkt.build_up(api.KKT_TYPE_HOMOGENEOUS)
-    info = kkt.grouped_build_info()
-    assert info["cones"] == ncones and 1 <= info["launches"] <= 3, info
-    ex = kkt.export()
-    if kkt.diag_target() == 0:
-        check_close(kkt.M[msk], golden_schur_dense(g, "M_hsd")[msk], name + " M_hsd")
-    check_close(ex["ASinv"], g["ASinv_hsd"], name + " ASinv")
-    check_close(ex["ASinvRdSinv"], g["ASinvRdSinv_hsd"], name + " ASinvRdSinv")
-    check_close(ex["ASinvCSinv"], g["ASinvCSinv_hsd"], name + " ASinvCSinv")
-    kkt.build_up(api.KKT_TYPE_INFEASIBLE)
-    if kkt.diag_target() == 0:
-        check_close(kkt.M[msk], golden_schur_dense(g, "M_inf")[msk], name + " M_inf")
-    kkt.factorize()
-    x = kkt.solve(g["b"])
-    assert np.linalg.norm(x - g["sol_b"]) <= 1e-8 * np.linalg.norm(g["sol_b"])
-
-
 @pytest.mark.parametrize("name", ["arrow128_A", "chain16_A"])
 def test_all_four_grouped_switches_together(name):
     """grouped check, grouped ratio test, grouped step-and-check and grouped build on one operator: the step launch writes the
@@ -663,21 +561,6 @@ def test_untracked_blocks_do_not_serve_a_stale_step_matrix():
 # ---- the unchanged driver ---------------------------------------------------------------------------------------------------
 # the optimum the driver prints, as tests/test_gpu_reference_driver.py expects it for the same files; every block is a member
 DRIVER_CASES = {"truss1": (8.999996, "7", "7"), "chain16": (74.932288321, "16", "16")}
-GROUPED = ("HDSDP_MI355X_GROUPED_BUILD", "HDSDP_MI355X_GROUPED_CHECK", "HDSDP_MI355X_GROUPED_RATIO", "HDSDP_MI355X_GROUPED_STEP")
-
-
-def _drive(inst, on):
-    env = dict(os.environ, HDSDP_DROP_ATTACH="1")
-    for k in GROUPED:
-        env.pop(k, None)
-    for k in on:
-        env[k] = "1"
-    r = subprocess.run([EXE, os.path.join(GOLDEN, inst + ".dat-s")], capture_output=True, text=True, timeout=600, env=env)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-3000:]
-    assert "SDP Status: Primal dual optimal" in out, out[-3000:]
-    its = [m_.group(1) for m_ in re.finditer(r"^\s+(\d+)\s+[-+]\d\.\d+e[-+]\d+\s+[-+]\d\.\d+e[-+]\d+", out, re.M)]
-    return out, its, re.findall(r"pObj\s+([-+0-9.eE]+)", out), re.findall(r"dObj\s+([-+0-9.eE]+)", out)
 
 
 @pytest.mark.parametrize("inst", sorted(DRIVER_CASES))
