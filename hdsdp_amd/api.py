@@ -43,6 +43,7 @@ EXPORTS = [
     "HMiWorkPlanQuery", "HMiConeGetWorkPlan", "HMiKKTSetGroupedBuild", "HMiKKTGetGroupedBuild", "HMiGroupedPlanQuery",
     "HMiKKTSetGroupedCheck", "HMiKKTGetGroupedCheck", "HMiKKTCheckIsInterior",
     "HMiKKTSetGroupedRatio", "HMiKKTGetGroupedRatio", "HMiKKTRatioTest",
+    "HMiKKTSetGroupedRatioChecker", "HMiKKTSetGroupedRatioRest", "HMiKKTGetGroupedRatioDetail",
     "HMiKKTSetGroupedStep", "HMiKKTGetGroupedStep", "HMiKKTAddStepToBufferAndCheck", "HMiConeGetChecker",
     "HMiLinsysSetRefine", "HMiLinsysGetRefine", "HMiLinsysRefineBytes", "HMiKKTSetRefine", "HMiSymResidualProbe",
     "HMiLinsysSetRefineTiles", "HMiLinsysGetRefineTiles", "HMiKKTSetRefineTiles", "HMiTileResidualProbe", "HMiBspRefinedSolve", "HMiBspRefineTimingProbe",
@@ -308,6 +309,9 @@ def load_library():
         "HMiKKTSetGroupedRatio": (C.c_int, [kp, C.c_int]),
         "HMiKKTGetGroupedRatio": (C.c_int, [kp, C.POINTER(C.c_long)]),
         "HMiKKTRatioTest": (C.c_int, [kp, C.c_double, dp, C.c_double, C.c_int, dp, dp]),
+        "HMiKKTSetGroupedRatioChecker": (C.c_int, [kp, C.c_int]),
+        "HMiKKTSetGroupedRatioRest": (C.c_int, [kp, C.c_int]),
+        "HMiKKTGetGroupedRatioDetail": (C.c_int, [kp, C.POINTER(C.c_long)]),
         "HMiKKTSetGroupedStep": (C.c_int, [kp, C.c_int]),
         "HMiKKTGetGroupedStep": (C.c_int, [kp, C.POINTER(C.c_long)]),
         "HMiKKTAddStepToBufferAndCheck": (C.c_int, [kp, C.c_double, C.c_int, ip, ip]),
@@ -1118,6 +1122,24 @@ class KKT:
     def grouped_ratio_info(self):
         """HMiKKTGetGroupedRatio: dict(on, members, launches, last_cones, total_cones, from_slots, left_out, fallbacks)"""
         return self._grouped_info("Ratio", "from_slots", "left_out", "fallbacks")
+
+    def set_grouped_ratio_checker(self, on):
+        """HMiKKTSetGroupedRatioChecker: while the grouped ratio test is on, the set also answers a ratio test on
+        BUFFER_DUALCHECK.  Returns the number of members when the opt-in is on afterwards, else 0"""
+        return int(load_library().HMiKKTSetGroupedRatioChecker(self._k, 1 if on else 0))
+
+    def set_grouped_ratio_rest(self, on):
+        """HMiKKTSetGroupedRatioRest: while the grouped ratio test is on, the rest of the safeguard (fresh-start test and cuts)
+        of a member whose step left the cone runs in the grouped launch, not on the host.  Returns the number of members when
+        the opt-in is on afterwards, else 0"""
+        return int(load_library().HMiKKTSetGroupedRatioRest(self._k, 1 if on else 0))
+
+    def grouped_ratio_detail(self):
+        """HMiKKTGetGroupedRatioDetail: dict(on, checker, rest, checker_launches, device_rests, device_cuts, fallbacks)"""
+        out = (C.c_long * 6)()
+        on = int(load_library().HMiKKTGetGroupedRatioDetail(self._k, out))
+        return dict(on=bool(on), checker=bool(out[0]), rest=bool(out[1]), checker_launches=int(out[2]), device_rests=int(out[3]),
+                    device_cuts=int(out[4]), fallbacks=int(out[5]))
 
     def ratio_test(self, dtau_step, dy, ada_ratio=0.0, buffer=BUFFER_DUALVAR):
         """HMiKKTRatioTest: every cone of the operator along (dtau_step, dy), in order and without early exit; returns

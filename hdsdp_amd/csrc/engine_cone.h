@@ -187,7 +187,10 @@ struct MiCheckSet : HdmQuestionSet<MiCone, MiCheckSet> {
 };
 // The ratio set (engine_ratio_set.h): "how far along (dTauStep, dy)?" on the dual buffer, by one pair of
 // launches.  Members: small_ratio_rule.h.  HMiKKTSetGroupedRatio / HDSDP_MI355X_GROUPED_RATIO.
-struct MiRatioQ { double dTauStep; const double *dy; double dAdaRatio; };
+// Two opt-ins of its own, each only while the set is on, both off again whenever the set is switched, released or populated
+// (DESIGN.md section 26): the set also answers BUFFER_DUALCHECK (HMiKKTSetGroupedRatioChecker / HDSDP_MI355X_GRATIO_CHECKER),
+// and the rest of the safeguard -- fresh-start test and cuts -- runs in the launch (HMiKKTSetGroupedRatioRest / ..._GRATIO_REST).
+struct MiRatioQ { double dTauStep; const double *dy; double dAdaRatio; int whichBuffer; };
 struct MiRatioSet : HdmQuestionSet<MiCone, MiRatioSet> {
     static constexpr const char *NO_MEMORY = "[hdsdp_mi355x] grouped ratio test: no memory for %s; the per-cone tests stay\n";
     std::vector<HdmRatioSlot> slots;       // one per member: the answer of the last launch it was in (small_ratio_rule.h)
@@ -197,9 +200,15 @@ struct MiRatioSet : HdmQuestionSet<MiCone, MiRatioSet> {
     HdmPinned<double> ybuf;                // mapped pinned: the members' gathered multipliers
     // safeguard fallbacks since HKKTInit (members whose step left the cone and took the host's fresh-start test and cuts)
     long fallbacks = 0;
+    bool checker_on = false, rest_on = false;      // the two opt-ins
+    HdmPinned<HdmGroupedRestArgs> rest_table;      // rest_on: mapped pinned, indexed like `table`
+    HdmPinned<double> rest_words;                  // rest_on: mapped pinned, HDM_GROUPED_REST_WORDS per member, by slot
+    // since HKKTInit: launches that asked the checker, members given the rest on the device, cuts made there
+    long checker_launches = 0, device_rests = 0, device_cuts = 0;
     MiRatioSet() : HdmQuestionSet<MiCone, MiRatioSet>(&MiCone::in_ratio) {}
-    void free_launch() { table.reset(); ybuf.reset(); }
-    void reset_counters() { HdmConeSet<MiCone>::reset_counters(); fallbacks = 0; }
+    void free_launch() { table.reset(); ybuf.reset(); rest_table.reset(); rest_words.reset(); checker_on = rest_on = false; }
+    void reset_counters() { HdmConeSet<MiCone>::reset_counters(); fallbacks = checker_launches = device_rests = device_cuts = 0; }
+    int turn_checker(int on_), turn_rest(int on_);   // the opt-ins' switches: 1 if on afterwards
     bool eligible(const MiCone *c) const;
     void empty();
     const char *prepare(size_t k, MiCone *c), *alloc_tables();
@@ -688,9 +697,9 @@ hdsdp_retcode cone_axpy_check(void *cd, double dStep, int whichBuffer, int *isIn
 // engine_ratio_set.h: a member's stored ratio-test answer is dropped (the identity coefficients are part of no dual-state
 // transition, and an answer is served only while nothing at all has changed under it); nothing else happens
 void ratio_set_drop_answer(MiCone *c);
-// c is a member of an active set and is asked (dTauStep, dy, dAdaRatio) on the dual buffer.  Returns true when the set has
-// answered (*rc, *maxStep), false when c's own path must run
-bool ratio_set_answer(MiCone *c, double dTauStep, const double *dy, double dAdaRatio, double *maxStep, hdsdp_retcode *rc);
+// c is a member of an active set and is asked (dTauStep, dy, dAdaRatio) on the dual buffer, or on the checker buffer of a set that
+// answers it.  Returns true when the set has answered (*rc, *maxStep), false when c's own path must run
+bool ratio_set_answer(MiCone *c, double dTauStep, const double *dy, double dAdaRatio, int whichBuffer, double *maxStep, hdsdp_retcode *rc);
 
 void cone_reduce_resi(void *cd, double resiReduction) { ((MiCone *) cd)->Rd = resiReduction; ratio_set_drop_answer((MiCone *) cd); }   // :2224-2228
 void cone_set_perturb(void *cd, double dDualPerturb) { ((MiCone *) cd)->perturb = dDualPerturb; ratio_set_drop_answer((MiCone *) cd); }  // :2236-2241
@@ -794,9 +803,10 @@ hdsdp_retcode cone_ratio_test(void *cd, double dTauStep, double *dy, double dAda
     MiCone *c = (MiCone *) cd;
     HdmChol *fac = (whichBuffer == 0) ? dual_chol(c) : c->checker.get();   // LTarget, :1661-1665
     if (!fac || !fac->factored) return HDSDP_RETCODE_FAILED;
-    if (whichBuffer == 0 && c->in_ratio.active()) {              // (the checker buffer stays per cone, as it does for the check set)
+    // (the checker buffer stays per cone unless the set's opt-in for it is on: DESIGN.md section 26)
+    if (c->in_ratio.active() && (whichBuffer == 0 || set_of<MiRatioSet>(c->in_ratio)->checker_on)) {
         hdsdp_retcode rcs;
-        if (ratio_set_answer(c, dTauStep, dy, dAdaRatio, maxStep, &rcs)) return rcs;
+        if (ratio_set_answer(c, dTauStep, dy, dAdaRatio, whichBuffer, maxStep, &rcs)) return rcs;
     }
     HIP_RC(cone_make_dS(c));
     const double eye = dAdaRatio * c->Rd;

@@ -415,6 +415,20 @@ static void kkt_apply_opt_ins(hdsdp_kkt *HKKT, MiKKTPriv *pv) {
             const int k = t.set(HKKT, 1);
             fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GROUPED_%s=1: %d of %d cone(s) answer %s\n", t.name, k, nCones, t.does);
         }
+    // the ratio set's two opt-ins: each acts only while the grouped ratio test itself is on
+    const struct { bool asked; const char *name; int (*set)(hdsdp_kkt *, int); const char *does; } opts[2] = {
+        {hdm_env_on<ENV_GRATIO_CHECKER>(), "CHECKER", HMiKKTSetGroupedRatioChecker, "a ratio test on the checker buffer from the grouped launch too"},
+        {hdm_env_on<ENV_GRATIO_REST>(), "REST", HMiKKTSetGroupedRatioRest, "with the safeguard's fresh-start test and cuts inside the grouped launch"}};
+    for (const auto &t : opts)
+        if (t.asked) {
+            if (!pv->rat.on)
+                fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GRATIO_%s=1: nothing to do, the grouped ratio test is not on "
+                                "(HDSDP_MI355X_GROUPED_RATIO=1 and at least two members)\n", t.name);
+            else {
+                const int k = t.set(HKKT, 1);
+                fprintf(stderr, "[hdsdp_mi355x] HDSDP_MI355X_GRATIO_%s=1: %d of %d cone(s) answer %s\n", t.name, k, nCones, t.does);
+            }
+        }
     // HDSDP_MI355X_REFINE=k: Schur solves are refined with at most k steps (HMiKKTSetRefine)
     if (const int k = hdm_env_int<ENV_REFINE>().value_or(0); k > 0) {
         (void) HMiKKTSetRefine(HKKT, k);
@@ -813,6 +827,23 @@ int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on) { return priv_of(HKKT)->rat.t
 int HMiKKTGetGroupedRatio(hdsdp_kkt *HKKT, long out[7]) {
     if (out) out[6] = priv_of(HKKT)->rat.fallbacks;
     return kkt_set_get(priv_of(HKKT)->rat, out);
+}
+// the ratio set's two opt-ins: each acts only while the set is on; the number of members when on afterwards
+int HMiKKTSetGroupedRatioChecker(hdsdp_kkt *HKKT, int on) {
+    MiRatioSet &rs = priv_of(HKKT)->rat;
+    return rs.turn_checker(on) ? rs.count() : 0;
+}
+int HMiKKTSetGroupedRatioRest(hdsdp_kkt *HKKT, int on) {
+    MiRatioSet &rs = priv_of(HKKT)->rat;
+    return rs.turn_rest(on) ? rs.count() : 0;
+}
+int HMiKKTGetGroupedRatioDetail(hdsdp_kkt *HKKT, long out[6]) {
+    const MiRatioSet &rs = priv_of(HKKT)->rat;
+    if (out) {
+        out[0] = rs.checker_on ? 1 : 0; out[1] = rs.rest_on ? 1 : 0;
+        out[2] = rs.checker_launches; out[3] = rs.device_rests; out[4] = rs.device_cuts; out[5] = rs.fallbacks;
+    }
+    return rs.on ? 1 : 0;
 }
 hdsdp_retcode HMiKKTRatioTest(hdsdp_kkt *HKKT, double dTauStep, const double *dy, double dAdaRatio, int whichBuffer, double *steps,
                               double *minStep) {

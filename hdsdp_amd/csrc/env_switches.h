@@ -41,6 +41,8 @@ enum class HdmEnvWhen { ONCE, NOW };
     X(GROUPED_BUILD,       "HDSDP_MI355X_GROUPED_BUILD",   OFF_UNLESS_NONZERO, ONCE, "0") \
     X(GROUPED_CHECK,       "HDSDP_MI355X_GROUPED_CHECK",   OFF_UNLESS_NONZERO, ONCE, "0") \
     X(GROUPED_RATIO,       "HDSDP_MI355X_GROUPED_RATIO",   OFF_UNLESS_NONZERO, ONCE, "0") \
+    X(GRATIO_CHECKER,      "HDSDP_MI355X_GRATIO_CHECKER",  OFF_UNLESS_NONZERO, ONCE, "0") \
+    X(GRATIO_REST,         "HDSDP_MI355X_GRATIO_REST",     OFF_UNLESS_NONZERO, ONCE, "0") \
     X(GROUPED_STEP,        "HDSDP_MI355X_GROUPED_STEP",    OFF_UNLESS_NONZERO, ONCE, "0") \
     X(REFINE,              "HDSDP_MI355X_REFINE",          INT,                NOW,  "0") \
     X(REFINE_TILES,        "HDSDP_MI355X_REFINE_TILES",    INT,                NOW,  "0") \

@@ -55,3 +55,23 @@ struct HdmGroupedRatioArgs {
 };
 int hdm_grouped_ratio(const HdmGroupedRatioArgs *table_host, const HdmGroupedRatioArgs *table_dev, int count, hipStream_t s);
 int hdm_grouped_safeguard(const HdmGroupedRatioArgs *table_dev, int count, hipStream_t s);   // small.hip
+
+// ---- the safeguard's rest in the grouped launch ------------------------------------------------------------
+// A second table, indexed like the first (entry b goes with table[b]); the first table's struct, which the two kernels above copy,
+// stays as it is.  Two more launches work on the pair, queued behind the two above; a workgroup whose member's safeguard word
+// (table[b].out[3]) is 0 leaves at once.
+// hdm_grouped_fresh_kernel (lanczos.hip) runs the one-launch Lanczos test's body from the fresh start vector on the member's
+// lanczos_fresh object, with the Linv and dS of table[b]; hdm_grouped_cuts_kernel (small.hip) takes the smaller of the two steps
+// and cuts it by 10 % until S + (1 - 1e-3) step dS factors (engine_cone.h: ratio_safeguard_rest, the same expressions in the same
+// order).
+struct HdmGroupedRestArgs {
+    double *V, *warm;                   // the member's lanczos_fresh object: HdmLanczos::V, ::warm
+    const double *start;                // its ::startd
+    double *fresh_out;                  // its mailbox + LZ_MB_WHOLE: [0] step [1] Lanczos steps [2] status
+    double *rest;                       // the rest's report words: [0] final step [1] a round succeeded (1 / 0; -1: nothing reported)
+                                        // [2] cuts made [3] the fresh-start step (infinite where that test failed)
+};
+constexpr int HDM_GROUPED_REST_WORDS = 4;
+int hdm_grouped_fresh(const HdmGroupedRatioArgs *table_host, const HdmGroupedRatioArgs *table_dev, const HdmGroupedRestArgs *rest_host,
+                      const HdmGroupedRestArgs *rest_dev, int count, hipStream_t s);
+int hdm_grouped_cuts(const HdmGroupedRatioArgs *table_dev, const HdmGroupedRestArgs *rest_dev, int count, hipStream_t s);   // small.hip

@@ -735,6 +735,22 @@ __global__ __launch_bounds__(1024) void hdm_grouped_ratio_kernel(const HdmGroupe
     lz_whole_body<true>(p.Linv, (long) HDM_SMALL_CHECK_P, p.dS, (long) n16, n16, p.V, (long) n16, p.start, p.warm, p.fresh, p.out);
 }
 
+// The safeguard's rest, first half (lanczos.h: HdmGroupedRestArgs), queued behind hdm_grouped_safeguard_kernel
+// on the same stream.  Workgroup b looks at the safeguard word of table[b]: 0 -- the step stands -- and it leaves at once.
+// Otherwise the ratio test again from the FRESH start vector, on the member's lanczos_fresh object (its basis, its warm-start
+// vector, its mailbox: the warm-start state of the member's own Lanczos object stays the reference's), with the same Linv and the
+// dS the first launch wrote: the body as hdm_grouped_ratio_kernel calls it, fresh = 1.  Independent workgroups; the leave is
+// uniform (every thread reads the same word).
+__global__ __launch_bounds__(1024) void hdm_grouped_fresh_kernel(const HdmGroupedRatioArgs *__restrict__ table,
+                                                                 const HdmGroupedRestArgs *__restrict__ rest, int count) {
+    if ((int) blockIdx.x >= count) return;
+    const HdmGroupedRatioArgs p = table[blockIdx.x];
+    if (!(p.out[3] > 0.0)) return;
+    const HdmGroupedRestArgs r = rest[blockIdx.x];
+    const int n16 = p.n16;
+    lz_whole_body<true>(p.Linv, (long) HDM_SMALL_CHECK_P, p.dS, (long) n16, n16, r.V, (long) n16, r.start, r.warm, 1, r.fresh_out);
+}
+
 // z = V[:, 0..kc) * coef   (single workgroup; V column stride ldv)
 __global__ __launch_bounds__(1024) void hdm_lincomb_kernel(const double *__restrict__ V, long ldv, int kc,
                                                            const double *__restrict__ coef, double *__restrict__ z, int n) {
@@ -1131,6 +1147,33 @@ int hdm_grouped_ratio(const HdmGroupedRatioArgs *table_host, const HdmGroupedRat
         configured_dev = dev;
     }
     hipLaunchKernelGGL(hdm_grouped_ratio_kernel, dim3((unsigned) count), dim3(1024), dyn, s, table_dev, count);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The rest's first launch: workgroup b on table[b] and rest[b].  The first table was checked by hdm_grouped_ratio just before (same
+// count, same entries); the second is checked here.  The dynamic LDS is the first launch's: the body packs the same two triangles.
+int hdm_grouped_fresh(const HdmGroupedRatioArgs *table_host, const HdmGroupedRatioArgs *table_dev, const HdmGroupedRestArgs *rest_host,
+                      const HdmGroupedRestArgs *rest_dev, int count, hipStream_t s) {
+    if (!table_host || !table_dev || !rest_host || !rest_dev || count < 1) return 1;
+    int max_n16 = 0;
+    for (int k = 0; k < count; ++k) {
+        const HdmGroupedRatioArgs &a = table_host[k];
+        const HdmGroupedRestArgs &r = rest_host[k];
+        if (a.n < 2 || a.n > a.n16 || a.n16 > LZ_RESIDENT_MAX || (a.n16 & 15) || !a.dS || !a.Linv || !a.out) return 1;
+        if (!r.V || !r.warm || !r.start || !r.fresh_out || !r.rest) return 1;
+        max_n16 = std::max(max_n16, a.n16);
+    }
+    const size_t dyn = sizeof(double) * (size_t) hdm_small_ratio_lds_doubles(max_n16);
+    static thread_local int configured_dev = -1;
+    int dev = 0;
+    HDM_HIP_CHECK(hipGetDevice(&dev));
+    if (configured_dev != dev) {
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_grouped_fresh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int) (sizeof(double) * LZ_RESIDENT_MAX * (LZ_RESIDENT_MAX + 1))));
+        configured_dev = dev;
+    }
+    hipLaunchKernelGGL(hdm_grouped_fresh_kernel, dim3((unsigned) count), dim3(1024), dyn, s, table_dev, rest_dev, count);
     HDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -489,6 +489,84 @@ int hdm_grouped_safeguard(const HdmGroupedRatioArgs *table_dev, int count, hipSt
     return 0;
 }
 
+// ---- the safeguard's rest, second half (lanczos.h: HdmGroupedRestArgs) --------------------------------------
+// Queued behind hdm_grouped_fresh_kernel.  Workgroup b leaves at once where the safeguard word of table[b] is 0.  Otherwise what
+// ratio_safeguard_rest (engine_cone.h) does on the host after its fresh-start test, with the same expressions in the same order on
+// the same doubles: the smaller of the two steps (the fresh one only where that test reported success), then at most 64 rounds of
+// "factor S + (1 - 1e-3) step dS; stop if it factors; step *= 0.9", each round the safeguard kernel's own element expression
+// (hdm_axpy_elem) and sweep.  The sweep's info is the same in every thread; it still goes through LDS and a barrier before the
+// loop branches on it, so that the exit is uniform whatever a later change to the sweep does.  Independent workgroups.
+__global__ __launch_bounds__(SM_T) void hdm_grouped_cuts_kernel(const HdmGroupedRatioArgs *__restrict__ table,
+                                                                const HdmGroupedRestArgs *__restrict__ rest, int count) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    if ((int) blockIdx.x >= count) return;
+    const HdmGroupedRatioArgs p = table[blockIdx.x];
+    if (!(p.out[3] > 0.0)) return;                     // (uniform: every thread read the same word)
+    const HdmGroupedRestArgs q = rest[blockIdx.x];
+    constexpr int ld = SMALL_P + 1;
+    double *Xl = sm;                                   // 128 x 129 (its head: the sweep's block images)
+    double *rsv = sm + (long) SMALL_P * ld;            // 128 deferred scale factors
+    // the round's info, broadcast: the one double hdm_small_check_lds_bytes(0) has behind them (no static LDS: the kernel may ask
+    // for all 160 KB as dynamic)
+    int *sh_info = reinterpret_cast<int *>(rsv + SMALL_P);
+    const int n = p.n, n16 = p.n16;
+    const int tid = threadIdx.x;
+    const int ei = tid & (SMALL_P - 1), ej0 = tid >> 7;
+    double step = p.out[0];
+    const double fresh = (q.fresh_out[2] == 0.0) ? q.fresh_out[0] : INFINITY;
+    if (fresh < step) step = fresh;
+    int cuts = 0, ok = 0;
+#pragma unroll 1
+    for (int it = 0; it < 64; ++it) {
+        // (a round's index arithmetic and bound predicates are redone from these two, not kept in registers across the sweep:
+        // hoisted out of the loop they were 30 spilled VGPRs and 30 spilled SGPRs on top of the safeguard kernel's 233)
+        int ty = tid >> 5, tx = tid & 31;
+        asm volatile("" : "+v"(ty), "+v"(tx));
+        const double st = (1.0 - 1e-3) * step;
+        if (ei < n) {
+            for (int j = ej0; j <= ei; j += SM_T / SMALL_P) {
+                const long e = ei + (long) j * n16;
+                const double v = hdm_axpy_elem(p.S[e], p.dS[e], st);
+                Xl[ei + j * ld] = v;
+                Xl[j + ei * ld] = v;
+            }
+        }
+        __syncthreads();
+        double a[SM_NR][SM_NC], rr[SM_NR][SM_NC];
+#pragma unroll
+        for (int r = 0; r < SM_NR; ++r)
+#pragma unroll
+            for (int c = 0; c < SM_NC; ++c) {
+                const int i = ty + 16 * r, j = tx + 32 * c;
+                a[r][c] = (i < n && j < n) ? Xl[i + j * ld] : ((i == j) ? 1.0 : 0.0);
+            }
+        __syncthreads();
+        double unused;
+        const int info = sm_sweep<false>(n, a, rr, Xl, rsv, ty, tx, &unused);
+        if (tid == 0) *sh_info = info;
+        __syncthreads();                               // (also: every read of this round's images is over before the next round writes)
+        if (*sh_info == 0) { ok = 1; break; }
+        step *= 0.9;
+        cuts += 1;
+    }
+    if (tid == 0) { q.rest[0] = step; q.rest[2] = (double) cuts; q.rest[3] = fresh; q.rest[1] = (double) ok; }
+}
+
+int hdm_grouped_cuts(const HdmGroupedRatioArgs *table_dev, const HdmGroupedRestArgs *rest_dev, int count, hipStream_t s) {
+    if (!table_dev || !rest_dev || count < 1) return 1;
+    const size_t lds = (size_t) hdm_small_check_lds_bytes(0);
+    static thread_local int configured_dev = -1;
+    int dev = 0;
+    HDM_HIP_CHECK(hipGetDevice(&dev));
+    if (configured_dev != dev) {
+        HDM_HIP_CHECK(hipFuncSetAttribute((const void *) hdm_grouped_cuts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) HDM_SMALL_CHECK_LDS_MAX));
+        configured_dev = dev;
+    }
+    hipLaunchKernelGGL(hdm_grouped_cuts_kernel, dim3((unsigned) count), dim3(SM_T), lds, s, table_dev, rest_dev, count);
+    HDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // ---- the grouped step-and-check (small.h: HdmGroupedStepArgs) --------------------------------------------
 // Workgroup b puts table[b]'s checker at S + dStep dS: what cone_axpy_check does for one cone in five launches -- hdm_axpy_mat into
 // Scheck, the rectangle copy into the checker object's L, the identity padding, the cleared info word, the diagonal-block sweep --

@@ -456,6 +456,22 @@ int HMiKKTSetGroupedRatio(hdsdp_kkt *HKKT, int on);
 int HMiKKTGetGroupedRatio(hdsdp_kkt *HKKT, long out[7]);
 hdsdp_retcode HMiKKTRatioTest(hdsdp_kkt *HKKT, double dTauStep, const double *dy, double dAdaRatio, int whichBuffer, double *steps,
                               double *minStep);
+/* Two opt-ins of the grouped ratio test, each off by default and acting only while HMiKKTSetGroupedRatio is
+ * on; switching, releasing or re-initialising the ratio set turns both off again.
+ * HMiKKTSetGroupedRatioChecker: the set also answers a question on BUFFER_DUALCHECK -- the same two launches, reading the checker
+ * buffer and the checker's factor.  A member whose checker object is missing or of another shape takes its own path; one whose
+ * checker holds no factorisation is left out and its own call fails, as it does per cone.  A checker answer is served once, to the
+ * same question on the same buffer, while neither the checker (buffer or factor) nor the member's step matrix has been written.
+ * HMiKKTSetGroupedRatioRest: where a member's step leaves the cone, the rest of the safeguard -- the fresh-start Lanczos test and
+ * the 10 % cuts -- runs in two more launches behind the same synchronisation instead of on the host for that member alone; the
+ * step is the host's, bit for bit.  Turning it on makes each member's fresh-start Lanczos object.
+ * Both return the number of members when the opt-in is on afterwards, else 0.
+ * HMiKKTGetGroupedRatioDetail: out[0] the checker opt-in (1 / 0) [1] the rest opt-in [2] grouped launches that asked the checker,
+ * since HKKTInit [3] members given the rest on the device [4] cuts made on the device [5] host fallbacks (HMiKKTGetGroupedRatio's
+ * [6]); returns 1 if the grouped ratio test is on, else 0. */
+int HMiKKTSetGroupedRatioChecker(hdsdp_kkt *HKKT, int on);
+int HMiKKTSetGroupedRatioRest(hdsdp_kkt *HKKT, int on);
+int HMiKKTGetGroupedRatioDetail(hdsdp_kkt *HKKT, long out[6]);
 /* The grouped step-and-check (csrc/small_step_rule.h, csrc/small.hip, csrc/engine_step_set.h).  Between the
  * ratio test and the barrier the reference's line search asks every cone "is S + dStep dS still inside?" on BUFFER_DUALCHECK, and
  * again with a smaller step until all are; a small SDP cone answers in five launches and one synchronisation of its own.  With the
@@ -664,6 +680,10 @@ void HMiSDPAFree(HMiSDPA **pp);
  *                                           question to one small SDP cone answers all in one launch)
  *  HDSDP_MI355X_GROUPED_RATIO     0         1: HKKTInit turns the grouped ratio test on (a ratio test     test_gpu_grouped_ratio.py
  *                                           asked of one small SDP cone runs all in one launch pair)
+ *  HDSDP_MI355X_GRATIO_CHECKER    0         1: with HDSDP_MI355X_GROUPED_RATIO=1, HKKTInit lets the ratio test_gpu_grouped_ratio_checker.py
+ *                                           set answer BUFFER_DUALCHECK too (HMiKKTSetGroupedRatioChecker)
+ *  HDSDP_MI355X_GRATIO_REST       0         1: with HDSDP_MI355X_GROUPED_RATIO=1, the safeguard's fresh-   test_gpu_grouped_ratio_checker.py
+ *                                           start test and cuts run in the launch (HMiKKTSetGroupedRatioRest)
  *  HDSDP_MI355X_GROUPED_STEP      0         1: HKKTInit turns the grouped step-and-check on (a step asked test_gpu_grouped_step.py
  *                                           of one small SDP cone's checker puts all there in one launch)
  *  HDSDP_MI355X_REFINE            0         k > 0: HKKTInit turns the refined Schur solve on, at most k   test_gpu_refine.py::test_the_environment_switch_turns_refinement_on

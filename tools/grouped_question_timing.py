@@ -6,6 +6,12 @@ few parts in 10^7).  --kind says which:
 
     check   "interior at (tau, y)?" to every cone, then the log barrier at that point from every cone; y moves
     ratio   a ratio test on the dual buffer to every cone; a fixed seeded direction is scaled
+            --buffer checker: on the checker buffer, after one ratio test along the direction and a step-and-check at half its
+            smallest step have put every cone's checker at a trial point; the grouped forms have the ratio set's checker opt-in on
+             -> profiles/grouped_ratio_checker_timing.jsonl
+            --rest 1: the yardstick is not the loop but the grouped form with the safeguard's rest on the host; the other two
+            forms have it in the launch (grouped_host_rest, grouped_device_rest and the two whole-operator forms); the record
+            says how many members left the cone in the timed questions -> profiles/grouped_ratio_rest_timing.jsonl
     step    after one ratio test along a seeded direction, a step-and-check on the checker buffer to every cone; half the smallest
             ratio-test step is scaled
 
@@ -36,6 +42,7 @@ sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 INSTANCES = ("truss1", "chain16", "arrow128")
 FORMS = ("loop", "grouped", "loop_whole", "grouped_whole")
+REST_FORMS = ("grouped_host_rest", "grouped_device_rest", "grouped_host_rest_whole", "grouped_device_rest_whole")
 QUESTION = {"check": "interior at (tau, y) for every cone, then the log barrier at that point for every cone",
             "ratio": "a ratio test on the dual buffer for every cone, along a direction no slot holds",
             "step": "a step-and-check on the checker buffer for every cone, at a step no slot holds, after a ratio test"}
@@ -52,7 +59,7 @@ def pose(kind, asked, y0, dy, smin):
     return y0 * (1.0 - 2e-7 * asked) if kind == "check" else dy * (1.0 + 2e-7 * asked) if kind == "ratio" else 0.5 * smin * (1.0 + 2e-7 * asked)
 
 
-def forms(kind, kkt, cones, tau):
+def forms(kind, kkt, cones, tau, buffer=0):
     """(cone by cone, whole operator): what is timed, x -> check (flags, logdets, all), ratio (steps, smallest), step (flags, all,
     rc).  Chosen once per instance, so that the timed region holds one call and the question itself"""
     if kind == "check":
@@ -62,9 +69,9 @@ def forms(kind, kkt, cones, tau):
         return loop, lambda x: kkt.check_is_interior(tau, x)
     if kind == "ratio":
         def loop(x):
-            steps = [c.ratio_test(0.0, x) for c in cones]
+            steps = [c.ratio_test(0.0, x, 0.0, buffer) for c in cones]
             return steps, min(steps)
-        return loop, lambda x: kkt.ratio_test(0.0, x)
+        return loop, lambda x: kkt.ratio_test(0.0, x, 0.0, buffer)
 
     def loop(x):
         flags = [c.axpy_buffer_and_check(x) for c in cones]
@@ -88,7 +95,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scale", type=float, default=None, help="ratio, step: size of the direction relative to 1 + |y| (0.05)")
     ap.add_argument("--instances", nargs="*", default=list(INSTANCES))
+    ap.add_argument("--buffer", choices=("dual", "checker"), default="dual", help="ratio: the buffer the ratio test is asked on")
+    ap.add_argument("--rest", type=int, choices=(0, 1), default=0, help="ratio: 1 compares the safeguard's rest on the host and in the launch")
     args = ap.parse_args()
+    if args.kind != "ratio" and (args.buffer != "dual" or args.rest):
+        ap.error("--buffer and --rest belong to --kind ratio")
     if args.reps < 31:
         ap.error("--reps must be at least 31")
     kind = args.kind
@@ -96,7 +107,9 @@ def main():
         ap.error("--scale has no meaning for --kind check: its question moves the point, not a direction")
     if args.scale is None:
         args.scale = 0.05
-    out = args.out or os.path.join(ROOT, "profiles", f"grouped_{kind}_timing.jsonl")
+    on_checker, names = args.buffer == "checker", (REST_FORMS if args.rest else FORMS)
+    stem = "ratio_rest" if args.rest else "ratio_checker" if on_checker else kind
+    out = args.out or os.path.join(ROOT, "profiles", f"grouped_{stem}_timing.jsonl")
     from hdsdp_amd import api
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
@@ -117,17 +130,25 @@ def main():
                 if kind != "check":
                     assert all(c.check_is_interior(tau, y0) for c in cones), inst
                     dy = np.random.default_rng(11).uniform(-1.0, 1.0, m) * args.scale * (1.0 + np.abs(y0))
-                if kind == "step":
+                if kind == "step" or on_checker:
                     smin = min(c.ratio_test(0.0, dy) for c in cones)
                     assert 0.0 < smin < 1e6, (inst, smin)
-                loop, whole = forms(kind, kkt, cones, tau)
-                t = {form: [] for form in FORMS}
+                if on_checker:                                     # every cone's checker at a trial point, for good
+                    assert all(c.axpy_buffer_and_check(0.5 * smin) for c in cones), inst
+                loop, whole = forms(kind, kkt, cones, tau, api.BUFFER_DUALCHECK if on_checker else api.BUFFER_DUALVAR)
+                t = {form: [] for form in names}
                 asked = 0
-                launches, fallbacks, smallest = {}, {form: 0 for form in FORMS}, {}
+                launches, fallbacks, smallest = {}, {form: 0 for form in names}, {}
+                device_rests, device_cuts = {form: 0 for form in names}, {form: 0 for form in names}
                 for rep in range(args.warmup + args.reps):
-                    for form in FORMS:
+                    for form in names:
                         on = form.startswith("grouped")
                         assert switch(on) == (members if on and members >= 2 else 0)
+                        if kind == "ratio":                         # (the opt-ins go off with the set's own switch)
+                            assert kkt.set_grouped_ratio_checker(on and on_checker) == (members if on and on_checker else 0)
+                            rest = on and "device_rest" in form
+                            assert kkt.set_grouped_ratio_rest(rest) == (members if rest else 0)
+                            dbefore = kkt.grouped_ratio_detail()
                         asked += 1
                         x, ask = pose(kind, asked, y0, dy, smin), (whole if form.endswith("whole") else loop)
                         before = info()
@@ -141,18 +162,29 @@ def main():
                         if rep >= args.warmup:
                             t[form].append(dt * 1e3)
                             fallbacks[form] += after.get("fallbacks", 0) - before.get("fallbacks", 0)
+                            if kind == "ratio":
+                                dafter = kkt.grouped_ratio_detail()
+                                device_rests[form] += dafter["device_rests"] - dbefore["device_rests"]
+                                device_cuts[form] += dafter["device_cuts"] - dbefore["device_cuts"]
                 rec = {"instance": inst, "cones": len(cones), "members": members, "m": m, "reps": args.reps, "warmup": args.warmup,
-                       "question": QUESTION[kind], "clock": "host perf_counter around the whole question",
+                       "question": QUESTION[kind].replace("the dual buffer", "the checker buffer") if on_checker else QUESTION[kind], "clock": "host perf_counter around the whole question",
                        "grouped_launches_per_question": launches}
                 if kind == "ratio":
                     rec.update({"direction_scale": args.scale, "smallest_step_of_the_last_question": smallest,
-                                "safeguard_fallbacks_in_all_timed_questions": fallbacks})
+                                "safeguard_fallbacks_in_all_timed_questions": fallbacks, "buffer": args.buffer,
+                                "device_rests_in_all_timed_questions": device_rests, "device_cuts_in_all_timed_questions": device_cuts})
+                    if on_checker:
+                        rec["checker_at_step"] = 0.5 * float(smin)
                 if kind == "step":
                     rec.update({"direction_scale": args.scale, "smallest_ratio_test_step": float(smin)})
-                for form in FORMS:
+                for form in names:
                     rec[form] = stats(t[form])
-                rec["ratio_loop_over_grouped"] = rec["loop"]["median_ms"] / rec["grouped"]["median_ms"]
-                rec["ratio_loop_whole_over_grouped_whole"] = rec["loop_whole"]["median_ms"] / rec["grouped_whole"]["median_ms"]
+                # (yardstick, form) pairs: the ratio of the medians, and whether the form's interquartile range lies below the yardstick's
+                for a, b in ((names[0], names[1]), (names[2], names[3])):
+                    rec[f"ratio_{a}_over_{b}"] = rec[a]["median_ms"] / rec[b]["median_ms"]
+                    if kind == "ratio" and (on_checker or args.rest):
+                        rec[f"{b}_iqr_below_{a}_iqr"] = rec[b]["q3_ms"] < rec[a]["q1_ms"]
+                        rec[f"{b}_iqr_overlaps_{a}_iqr"] = not (rec[b]["q3_ms"] < rec[a]["q1_ms"] or rec[a]["q3_ms"] < rec[b]["q1_ms"])
                 if kind == "step":
                     rec["grouped_iqr_below_loop_iqr"] = rec["grouped"]["q3_ms"] < rec["loop"]["q1_ms"]
                     rec["grouped_whole_iqr_below_loop_whole_iqr"] = rec["grouped_whole"]["q3_ms"] < rec["loop_whole"]["q1_ms"]
